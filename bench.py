@@ -445,6 +445,34 @@ def inference_sharded(device, rank, world, nvid=213):
         ops.CONV_PRECISION = saved
 
 
+LOSS_NAMES = ("loss_l", "loss_c", "loss_prop_l", "loss_prop_c", "loss_ct", "loss_start", "loss_end", "loss_act",
+              "loss_prop_act")       # the order DetectorTrainer.step hands the loss terms back in (both recipes)
+DUMP_SAMPLE = 1 << 22                # draws per dumped sample: ~3.8M distinct arena elements (2 x 15 MB of float32)
+
+
+def dump_outputs(out_dir, trainer, last):
+    """What the last timed step computed, as DIR/<name>.npy (float32): the cost and loss terms it returned, and a fixed
+    sample of the parameters it updated and of the gradient arena it filled.  The sample indices are drawn from a fixed
+    seed (the arena holds ~45M parameters, 180 MB per array), so two builds of the project can be compared file by file."""
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    cost, losses = last
+    arrays = {"cost": cost}
+    for name, t in zip(LOSS_NAMES, losses):
+        if t is not None:
+            arrays[name] = t
+    a = trainer.arena
+    if a.numel <= DUMP_SAMPLE:
+        idx = None
+    else:
+        idx = np.unique(np.random.RandomState(0).randint(0, a.numel, size=DUMP_SAMPLE))
+        idx = torch.from_numpy(idx).to(a.flat.device)
+    arrays["param_sample"] = a.flat if idx is None else a.flat[idx]
+    arrays["grad_sample"] = a.grad if idx is None else a.grad[idx]
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def _flush_c_stdio():
     import ctypes
     try:
@@ -482,7 +510,12 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-hbm-kernels", action="store_true",
                     help="skip the achieved-GB/s table of the HBM-bound kernel classes (tools/bench_hbm_kernels.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32): cost, loss "
+                         "terms, a fixed sample of the updated parameters and of the gradients (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     anet = args.recipe == "anet"
     if args.batch is None:
         args.batch = 2 if anet else 8
@@ -693,10 +726,13 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
     trainer.measure_exposed = False
+    if args.dump_outputs and rank == 0:
+        # before anything else steps the trainer: a replayed graph hands back the same output buffers every step
+        dump_outputs(args.dump_outputs, trainer, last)
     exposed_ms = None
     if trainer.exposed_events:
         exposed_ms = sum(a.elapsed_time(b) for a, b in trainer.exposed_events) / len(trainer.exposed_events)

@@ -9,6 +9,42 @@ import torch
 from oracle import afsd_oracle as O
 from oracle import arch
 
+# The forward vectors of thumos_b1.npz hold the bits of the CPU arithmetic they were written with:
+# oracle/pin_against_reference.py ran with 8 intra-op threads (the build container's os.cpu_count()) on the AVX-512
+# oneDNN / MKL kernels of an Intel CPU.  The thread count decides how the convolutions split their sums, so it is pinned
+# here rather than taken from the host.  On that arithmetic the comparison is bitwise (atol 1e-6 is below one fp32 ulp of
+# |loc| > 16).  Other CPUs run other kernels and add up in another order; there the outputs are compared within the
+# spread that re-association causes, measured with tools/oracle_spread.py (other thread counts on the Intel host; 8 and
+# 16 threads on an AMD EPYC 9575F): `loc` (|x| up to ~55) moves by at most 3.7e-4, every other output and the ssl
+# features by at most 5.7e-6.  The proposal segments derived from `loc` stay exact on every host (the fixture's clip seed
+# keeps them 9.5e-4 away from a rounding tie, tests/golden/PIN_REPORT.txt).
+PIN_THREADS = 8
+
+
+def _cpu_vendor():
+    try:
+        with open("/proc/cpuinfo") as f:
+            for line in f:
+                if line.startswith("vendor_id"):
+                    return line.split(":", 1)[1].strip()
+    except OSError:
+        pass
+    return "unknown"
+
+
+PIN_ARITHMETIC = _cpu_vendor() == "GenuineIntel" and torch.backends.cpu.get_cpu_capability() == "AVX512"
+FWD_ATOL = {k: 1e-6 if PIN_ARITHMETIC else (1e-3 if k == "loc" else 1e-5)
+            for k in ("loc", "conf", "prop_loc", "prop_conf", "center", "act", "prop_act", "unct", "prop_unct")}
+SSL_ATOL = 1e-6 if PIN_ARITHMETIC else 1e-5
+
+
+@pytest.fixture
+def pin_threads():
+    saved = torch.get_num_threads()
+    torch.set_num_threads(PIN_THREADS)
+    yield
+    torch.set_num_threads(saved)
+
 
 @pytest.fixture(scope="module")
 def b1(golden_dir):
@@ -16,9 +52,13 @@ def b1(golden_dir):
     P = O.to_torch(arch.make_params(int(fx["param_seed"])))
     x = torch.from_numpy(arch.make_clip(int(fx["clip_seed"]), 1))
     keep = {}
-    torch.set_num_threads(os.cpu_count())
-    with torch.no_grad():
-        out = O.bdnet_forward(P, x, keep=keep)
+    saved = torch.get_num_threads()
+    torch.set_num_threads(PIN_THREADS)
+    try:
+        with torch.no_grad():
+            out = O.bdnet_forward(P, x, keep=keep)
+    finally:
+        torch.set_num_threads(saved)
     return fx, out, keep
 
 
@@ -31,8 +71,8 @@ def test_spec_counts():
 
 def test_forward_matches_reference_vectors(b1):
     fx, out, keep = b1
-    for k in ("loc", "conf", "prop_loc", "prop_conf", "center", "act", "prop_act", "unct", "prop_unct"):
-        np.testing.assert_allclose(out[k].numpy(), fx["out_" + k], rtol=0, atol=1e-6, err_msg=k)
+    for k, atol in FWD_ATOL.items():
+        np.testing.assert_allclose(out[k].numpy(), fx["out_" + k], rtol=0, atol=atol, err_msg=k)
     for i in range(6):
         assert np.array_equal(keep["segments"][i].numpy(), fx[f"segments_{i}"])
         assert np.array_equal(keep["frame_segments"][i].numpy(), fx[f"frame_segments_{i}"])
@@ -74,13 +114,12 @@ def test_softnms_quirks():
     assert cnt == 2 and mask.tolist() == [False, True, True] and rows[0, 2] == 0.9 and rows[1, 2] == 0.5
 
 
-def test_ssl_triplet_branch_matches_reference_vectors(golden_dir):
+def test_ssl_triplet_branch_matches_reference_vectors(golden_dir, pin_threads):
     """a14: O.ssl_triplets / O.triplet_cost regenerate what the reference's BDNet.forward(ssl=True) and its three
     TripletMarginLoss terms gave in the build container (fixture entries ssl{set}_*, oracle/pin_against_reference.py)."""
     fx = np.load(os.path.join(golden_dir, "thumos_b1.npz"))
     P = O.to_torch(arch.make_params(int(fx["param_seed"])))
     x = torch.from_numpy(arch.make_clip(int(fx["ssl_clip_seed"]), 1))
-    torch.set_num_threads(os.cpu_count())
     for si in range(fx["ssl_proposals"].shape[0]):
         props = [torch.from_numpy(fx["ssl_proposals"][si])]
         with torch.no_grad():
@@ -88,7 +127,7 @@ def test_ssl_triplet_branch_matches_reference_vectors(golden_dir):
             cost = float(O.triplet_cost(a, p, n, 1.0))
         for nm, got in (("anchor", a), ("positive", p), ("negative", n)):
             for i in range(3):
-                np.testing.assert_allclose(got[i].numpy(), fx[f"ssl{si}_{nm}_{i}"], rtol=0, atol=1e-6)
+                np.testing.assert_allclose(got[i].numpy(), fx[f"ssl{si}_{nm}_{i}"], rtol=0, atol=SSL_ATOL)
         assert abs(cost - float(fx[f"ssl{si}_cost"])) < 1e-5
         assert abs(cost - float(fx[f"ssl{si}_terms"].sum())) < 1e-5
 
