@@ -53,9 +53,15 @@ extern "C" {
 
 int otal_abi_version(void);
 const char* otal_error_string(int code);
-/* Named integer switches that select kernel variants (A/B tests, micro-benchmarks; e.g. "OTAL_CONV_NO1A").  A switch
- * starts from the environment variable of the same name, read once at its first use -- the launch path itself never
- * calls getenv; otal_set_option changes it at run time, otal_get_option reads it (dflt when it was never set). */
+/* Named integer switches that select kernel variants -- the references of the A/B tests:
+ *   OTAL_CONV_NO1A OTAL_CONV_NO1AW OTAL_CONV_1A_NOTILE OTAL_CONV_1A_WGS OTAL_W1A_SPLITS  (Conv3d_1a)
+ *   OTAL_CONV_NODIRECT OTAL_CONV_DIRECT_MINTILES OTAL_CONV_DIRECT_MINTILES512 OTAL_CONV_DIRECT_XPF2  (direct 3x3x3)
+ *   OTAL_CONV_NOWDIRECT OTAL_WDIRECT_BLOCKS  (direct 3x3x3 weight gradient)
+ *   OTAL_CONV_NO1X1STREAM OTAL_CONV_NOW1X1 OTAL_CONV_NOPROJ OTAL_CONV_NOPROJW OTAL_CONV_NO1DTILE OTAL_CONV_NOW1D
+ *   OTAL_POOL_NO133 OTAL_POOL_NOROWS OTAL_LOSS_NOSTAGE
+ * A switch starts from the environment variable of the same name, read once at its first use -- the launch path itself
+ * never calls getenv; otal_set_option changes it at run time (OTAL_E_UNSUPPORTED for a name not listed here),
+ * otal_get_option reads it (dflt for a name not listed here). */
 int otal_set_option(const char* name, int value);
 int otal_get_option(const char* name, int dflt);
 /* Stream fork / join for callers that spread independent launches of this library over several HIP streams (the host

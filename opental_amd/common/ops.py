@@ -144,7 +144,6 @@ WGRAD_STREAM = os.environ.get("OTAL_WGRAD_STREAM", "1") != "0"
 # into their arena slots are joined by the trainer (bucket flushes of a data-parallel run, end_backward), not at the end
 # of each autograd node.
 SIDE_DEFER_JOIN = False
-SIDE_IN_GRAPH = os.environ.get("OTAL_WGRAD_STREAM_IN_GRAPH", "0") != "0"      # experiments only
 _SIDES = {}
 
 
@@ -234,11 +233,10 @@ class SideWgrads:
     dy are kept alive until join(): the caching allocator would otherwise hand their blocks to later main-stream launches
     while the side stream still reads them.  Nothing on the main stream may modify a recorded dy before join() -- the
     backward passes below never write to a gradient tensor after its producer."""
-    CHUNK = int(os.environ.get("OTAL_WGRAD_CHUNK", "4"))
+    CHUNK = 4
 
     def __init__(self, device):
-        prio = int(os.environ.get("OTAL_WGRAD_STREAM_PRIORITY", "0"))
-        self.side = torch.cuda.Stream(device=device, priority=prio)
+        self.side = torch.cuda.Stream(device=device)
         self._raw = ctypes.c_void_p(self.side.cuda_stream)
         self.pending = []
         self.keep = []
@@ -247,8 +245,7 @@ class SideWgrads:
     def on(self):
         # not inside a graph capture: a replayed hipGraph runs its branches one after the other (measured at b = 1, 2, 8:
         # 0.06-0.2 ms per step SLOWER with the fork than without), so only eager launches gain from the second stream
-        return WGRAD_STREAM and CONV_PROFILE is None and (LANES is not None or SIDE_IN_GRAPH
-                                                          or not torch.cuda.is_current_stream_capturing())
+        return WGRAD_STREAM and CONV_PROFILE is None and (LANES is not None or not torch.cuda.is_current_stream_capturing())
 
     def wgrad(self, x, dy, w_shape, k, s, spatial_valid=False, levels=None, out=None):
         if not self.on:
@@ -567,7 +564,6 @@ class PrologueCache:
         self.dev_starts = None
         self.dev_descs = None
         self.dirty = False
-        self.pending_join = False    # the refresh runs on the side lane and nobody has waited for it yet
 
     def region(self, mode, ga, sa, key, w, prec):
         if key in self.entries:
@@ -607,23 +603,11 @@ class PrologueCache:
             self.dev_starts = torch.tensor(starts, dtype=torch.int32).to(dev)
             self.total_blocks = starts[-1]
             self.dirty = False
-        def launch():
-            L.check(L.lib().otal_conv_prologue_batch(len(self.descs), L.ptr(self.dev_descs), L.ptr(self.dev_starts),
-                                                     int(self.total_blocks), L.stream()), "otal_conv_prologue_batch")
-        if LANES is not None and PREP_LANE:
-            # lane-graph step: the re-pack (0.54 GB of traffic, ~140 us) goes to the SIDE lane and the main lane starts with the
-            # first convolution, which packs its own weights (Conv3d_1a's tile kernel, matrix-bound: 380 us + the pool behind
-            # it); the main lane waits for the side lane in front of the first launch that reads a region (_prologue)
-            LANES.side_chunk(launch)
-            self.pending_join = True
-        else:
-            launch()
+        L.check(L.lib().otal_conv_prologue_batch(len(self.descs), L.ptr(self.dev_descs), L.ptr(self.dev_starts),
+                                                 int(self.total_blocks), L.stream()), "otal_conv_prologue_batch")
 
 
 PROLOGUES = None        # the active PrologueCache, or None (every launch builds its own prologue)
-# OTAL_PREP_LANE=1: in lane graphs the step's weight re-pack runs on the side lane beside Conv3d_1a's forward.  Measured +-0
-# (r05f timeline: the pack's 142 us disappear from the main lane and conv1a_tile_fwd_kernel stretches by 110 us): off.
-PREP_LANE = os.environ.get("OTAL_PREP_LANE", "0") == "1"
 
 
 def activate_prologues(cache):
@@ -635,11 +619,6 @@ def activate_prologues(cache):
 
 def deactivate_prologues():
     global PROLOGUES
-    c = PROLOGUES
-    if c is not None and c.pending_join:         # nobody consumed a region: the side lane is joined all the same
-        if LANES is not None:
-            LANES.cut(("join",))
-        c.pending_join = False
     PROLOGUES = None
 
 
@@ -657,9 +636,6 @@ def _prologue(mode, ga, sa, pkey, w, prec):
     reg = c.region(mode, ga, sa, (wp, pkey, prec), w, prec)
     if reg is None:
         return None
-    if c.pending_join and LANES is not None:
-        LANES.cut(("join",))
-        c.pending_join = False
     return L.ptr(reg)
 
 
@@ -1236,11 +1212,6 @@ def _pool_geom(x5, k, s):
     return [B, C, Ti, Hi, Wi, *outs, *k, *s, *pads], tuple(outs)
 
 
-# OTAL_POOL_KEYS=1: the strided pools behind a conv + ReLU take the ordered-key (v_max3_u32) forward kernel.  Bit-identical
-# to the scanning kernel and within +-5 % of it either way once both were freed of their serialized loads: off.
-POOL_KEYS = os.environ.get("OTAL_POOL_KEYS", "0") == "1"
-
-
 def maxpool3d_forward(x, k, s, out=None, signbits=False, half_out=False, nonneg=False):
     """(y, winner bytes) -- with signbits=True (y, winner bytes, sign bits of x or None): the strided 3x3 pools can hand
     the ReLU mask of their input to the backward pass as one bit per element (maxpool3d_backward(out_signbits=...)).
@@ -1502,10 +1473,6 @@ class AnetDetectionLossFunction(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------- head output tails
-HEAD_WGRAD_SIDE = os.environ.get("OTAL_HEAD_WGRAD_SIDE", "1") != "0"     # the fused heads' weight gradients on the weight-gradient lane
-HEAD_GRAD_SLOTS = "OTAL_NO_GRAD_SLOTS_HEADS" not in os.environ      # (A/B switch of the head bias / ScaleExp gradient slots)
-
-
 _SLOT_INDEX = {}        # arena offsets of a group of one-element gradient slots, as a device index tensor
 
 
@@ -1574,7 +1541,7 @@ class HeadOutputsFunction(torch.autograd.Function):
                     "otal_head_outputs_bwd")
         # the nlev one-element gradients: written in place when the parameters' arena slots are adjacent (no packing, no copies:
         # they were 6 of the 13 tiny gradient copies -- a hipMemcpyAsync node each -- of every step's bucket flushes)
-        want = HEAD_GRAD_SLOTS and all(ctx.needs_input_grad[3:3 + nlev])     # (the refined stage passes the scales detached)
+        want = all(ctx.needs_input_grad[3:3 + nlev])     # (the refined stage passes the scales detached)
         slots = [grad_slot(p) if want else None for p in ctx.scale_params]
         direct = _adjacent_view(slots) if all(sl is not None for sl in slots) else None
         if direct is not None:
@@ -1662,13 +1629,13 @@ class HeadConvsFunction(torch.autograd.Function):
         # a hipMemcpyAsync node each -- that every step's bucket flushes issued)
         dbs = []
         for w, b in zip(ws, ctx.bias_params):
-            slot = grad_slot(b) if (b is not None and HEAD_GRAD_SLOTS) else None
+            slot = grad_slot(b) if b is not None else None
             slots_b.append(slot)
             dbs.append(slot if slot is not None else (torch.empty(w.shape[0], dtype=torch.float32, device=w.device) if b is not None else None))
         VP = lambda ts: (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
         in_slots = all(s_ is not None for s_ in slots_w) and all(s_ is not None for s_, b in zip(slots_b, ctx.bias_params) if b is not None)
         side = side_wgrads(xs[0].device)
-        if HEAD_WGRAD_SIDE and side.on and in_slots and SIDE_DEFER_JOIN:
+        if side.on and in_slots and SIDE_DEFER_JOIN:
             # the data gradients on the chain that waits for them, the weight / bias gradients on the weight-gradient lane (they
             # land in arena slots nobody reads before the trainer's join): 29 + 39 us off the serial middle of the step
             L.check(L.lib().otal_head_convs_bwd_parts(*meta, VP(xs), VP(ws), VP(dys), VP(dxs), VP(dws), VP(dbs), B, C, N, nlev, lev, 1,

@@ -15,7 +15,7 @@ struct Conv1aTileArgs {
     int64_t x_bs, x_cs, y_bs, y_cs;
     int B, Ti, Hi, To, Ho, M;
     int relu, half;
-    int flags;                  // ablation builds only
+    int flags;                  // unused: kept so that the kernel argument offsets (and the kernel code) stay as they are
 };
 
 // 1 when the geometry is the tiled kernel's (To % 4 == 0, Ho % 4 == 0; everything else is checked by the caller)

@@ -114,11 +114,7 @@ __global__ __launch_bounds__(256, 2) void conv1a_wgrad_direct_kernel(const W1aAr
         const int b = bid / tiles_t;
         const int to0 = tt0 * 2, ho0 = th * 2;
         const int ti0 = 2 * to0 - g.pt + dt, hi0 = 2 * ho0 - g.ph;
-#if defined(OTAL_W1A_FAKE) && (OTAL_W1A_FAKE & 2)      // traffic experiment (tools/fake_traffic_1a_wgrad.sh): every block reads the FIRST block's x
-        const int64_t xb0 = ((int64_t)(dt - g.pt) * g.Hi - g.ph) * g.Wi + 0 * (b + ti0 + hi0);
-#else
         const int64_t xb0 = (int64_t)b * g.x_bs + ((int64_t)ti0 * g.Hi + hi0) * g.Wi;
-#endif
 #pragma unroll
         for (int i = 0; i < X_ITERS; ++i) {
             const int pl = xpr[i] >> 8, rr = xpr[i] & 255;
@@ -130,11 +126,7 @@ __global__ __launch_bounds__(256, 2) void conv1a_wgrad_direct_kernel(const W1aAr
                 xv[i][ci] = make_float4(__uint_as_float(v.a), __uint_as_float(v.b), __uint_as_float(v.c), __uint_as_float(v.d));
             }
         }
-#if defined(OTAL_W1A_FAKE) && (OTAL_W1A_FAKE & 1)      // ... and the first block's dy
-        const int ybase = 0 * (b + to0 + ho0);
-#else
         const int ybase = (int)(((int64_t)b * g.y_bs + (int64_t)to0 * HWo + ho0 * g.Wo) * (DYH ? 2 : 4));
-#endif
 #pragma unroll
         for (int j = 0; j < A_ITERS; ++j)
             ra[j] = __builtin_bit_cast(Words4, __builtin_amdgcn_raw_buffer_load_b128(rdy, avo[j], ybase, 0));
@@ -229,7 +221,7 @@ __global__ __launch_bounds__(256, 2) void conv1a_wgrad_direct_kernel(const W1aAr
 }
 
 static inline bool conv1a_wgrad_eligible(const ConvGeom& g, int prec, const void* x, const void* dy) {
-    if (!prec || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NO1AW", 0)) return false;
+    if (!prec || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NO1AW")) return false;
     if (g.Cin != 3 || g.Cout > 64 || g.kt != 7 || g.kh != 7 || g.kw != 7 || g.st != 2 || g.sh != 2 || g.sw != 2) return false;
     if (g.pt != 2 || g.ph != 2 || g.pw != 2 || g.Wi != 96 || g.Wo != C1_WO || g.Hi != 2 * g.Ho || g.Ti != 2 * g.To) return false;
     if (g.To % 2 || g.Ho % 2 || g.x_bs % 4 || g.x_cs % 4 || g.y_bs % 4 || g.y_cs % 4) return false;
@@ -244,7 +236,7 @@ int launch_conv1a_wgrad(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) 
     d.nblocks = g.B * (g.To / 2) * (g.Ho / 2);
     // 7 taps x S splits workgroups, two resident per CU (registers): 7 x 73 = 511 of 512 slots
     // (measured on the b = 8 layer: 36 splits 0.87 ms, 73: 0.81, 109: 0.93, 146: 0.89; the pair-mode kernel: 1.05)
-    int splits = OTAL_OPT("OTAL_W1A_SPLITS", 0) > 0 ? OTAL_OPT("OTAL_W1A_SPLITS", 0) : 73;
+    int splits = OTAL_OPT("OTAL_W1A_SPLITS") > 0 ? OTAL_OPT("OTAL_W1A_SPLITS") : 73;
     if (splits > d.nblocks) splits = d.nblocks;
     const size_t slab1 = (size_t)a.M * a.N * sizeof(float);
     if (splits > 1 && (!ws || ws_bytes < (size_t)splits * slab1)) {

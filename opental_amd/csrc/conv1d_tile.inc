@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void conv1d_tile_kernel(const ConvArgs a) {
     // owns a (half of the row blocks) x (quarter of the position blocks) rectangle: half of the weight pack + a quarter of
     // the map per L2 (counter 19.8 -> ~12 MB).  A bijection whenever the grid divides (2, 4); the plain map otherwise.
     int bx = blockIdx.x, by = blockIdx.y;
-    if ((gridDim.x & 1) == 0 && (gridDim.y & 3) == 0 && !(a.flags & EPI_PLAIN_GRID)) {
+    if ((gridDim.x & 1) == 0 && (gridDim.y & 3) == 0) {
         const int lin = blockIdx.x + gridDim.x * blockIdx.y, xcd = lin & 7, idx = lin >> 3;
         const int hx = gridDim.x >> 1, qy = gridDim.y >> 2;
         bx = (xcd & 1) * hx + idx % hx;
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void conv1d_tile_kernel(const ConvArgs a) {
 }
 
 static inline bool conv1d_tile_eligible(const ConvGeom& g, int mode, int prec, const void* src, const ConvArgs& a) {
-    if (!prec || mode == MODE_WGRAD || OTAL_OPT("OTAL_CONV_NO1DTILE", 0)) return false;
+    if (!prec || mode == MODE_WGRAD || OTAL_OPT("OTAL_CONV_NO1DTILE")) return false;
     if (g.Hi != 1 || g.Wi != 1 || g.Ho != 1 || g.Wo != 1 || g.kh != 1 || g.kw != 1 || g.st != 1 || g.To != g.Ti) return false;
     if (!((g.kt == 1 && g.pt == 0) || (g.kt == 3 && g.pt == 1))) return false;
     if (g.Ti > 4096) return false;
@@ -242,7 +242,7 @@ static int launch_c1t(const ConvArgs& a, dim3 grid, hipStream_t st) {
 template <int MODE>
 int launch_conv1d_tile(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     // tables + packed weights: the persistent region of the chunked path (same layout), or built here in the workspace
-    const int BMsel = choose_bm(a.M, 1);
+    const int BMsel = choose_bm(a.M, true);
     a.Kp = chunk_kp(a.K);
     const size_t tb = chunk_tab_bytes(a.K), wb = chunk_wp_bytes(a.M, BMsel, a.K);
     unsigned short* wp;
@@ -279,7 +279,6 @@ int launch_conv1d_tile(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     a.splits = 1; a.k_per_split = 0; a.slab = nullptr;
     set_epilogue_extents<MODE>(a);
     if (a.out_bytes == 0u) return OTAL_E_UNSUPPORTED;
-    if (OTAL_OPT("OTAL_C1T_PLAINGRID", 0)) a.flags |= EPI_PLAIN_GRID;      // (A/B switch of the XCD-aware tile map)
     const dim3 grid((a.M + 31) / 32, a.g.B * ((a.g.Ti + 63) / 64), a.pair ? 2 : 1);
     return a.g.kt == 3 ? launch_c1t<3, MODE>(a, grid, st) : launch_c1t<1, MODE>(a, grid, st);
 }

@@ -45,7 +45,6 @@ struct S1Args {
     int tps, tiles;                 // position tiles per sample, in all
     int wgs;                        // persistent workgroups per row group (a multiple of 8)
     int relu;
-    int dbg;                        // timing experiments only (OTAL_1X1S_DBG): 1 no weight DMA, 2 no src DMA, 4 no epilogue
 };
 
 // one LDS-DMA instruction: lane l's 16 bytes at `gsrc` land at LDS byte lds_dst + 16 l.  Not a load hipcc knows about: no
@@ -164,19 +163,15 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const S1Args a) 
         const int k0 = l_chunk * KC;
         const long long xo = l_org + (long long)k0 * a.src_cs;
         const unsigned st = __builtin_amdgcn_readfirstlane(smem_lds + stage * STAGE);
-        if (!(a.dbg & 2)) {
 #pragma unroll
         for (int j = 0; j < XB; ++j) {
             const void* g = k0 + xrow[j] < a.K ? (const void*)(a.src + xo + xoff[j]) : (const void*)a.zero;
             dma16(g, st + xdst[j]);
         }
-        }
-        if (!(a.dbg & 1)) {
 #pragma unroll
         for (int j = 0; j < WB; ++j) {
             const void* g = wok[j] ? (const void*)(a.wp + woff[j] + k0) : (const void*)a.zero;
             dma16(g, st + wdst[j]);
-        }
         }
         if (++l_chunk == NC) {
             l_chunk = 0;
@@ -304,7 +299,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const S1Args a) 
         if (it + 2 < items) dma_wait<L>(); else dma_wait<0>();
         __builtin_amdgcn_s_barrier();
         if (++c_chunk == NC) {
-            if (!(a.dbg & 4)) finish(c_tile);
+            finish(c_tile);
             clear();
             c_chunk = 0;
             c_tile += a.wgs;
@@ -315,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const S1Args a) 
 
 // the launch: eligibility, tile shape, grid
 static inline bool conv1x1_stream_eligible(const ConvGeom& g, int mode) {
-    if (OTAL_OPT("OTAL_CONV_NO1X1STREAM", 0)) return false;
+    if (OTAL_OPT("OTAL_CONV_NO1X1STREAM")) return false;
     if (g.kt != 1 || g.kh != 1 || g.kw != 1 || g.st != 1 || g.sh != 1 || g.sw != 1 || g.nlev > 1) return false;
     const int64_t P = conv_out_positions(g);
     if (P != conv_in_positions(g) || P % 128) return false;
@@ -350,13 +345,12 @@ static int launch_conv1x1_stream(const ConvArgs& a, const unsigned short* wp, si
     if (!s.zero) return OTAL_E_UNSUPPORTED;
     s.M = a.M; s.Mpad = Mpad; s.K = a.K; s.Kp = chunk_kp(a.K); s.P = P;
     s.relu = (a.flags & EPI_RELU) ? 1 : 0;
-    s.dbg = OTAL_OPT("OTAL_1X1S_DBG", 0);
     // tile shape: up to 6 row tiles per wave at 128 positions, up to 4 at 256 (only where the grid stays full)
     const int mt_all = (a.M + 31) / 32;
     int nw = 1;
     // (256-position tiles only with up to two row tiles per wave: the <4, 2> form needed 92 KB of LDS -- one workgroup per CU
     //  under a grid sized for two, DMA destinations past M0's 64 KB -- and no layer of the model selected it: removed)
-    if (mt_all <= 2 && P % 256 == 0 && (int64_t)g.B * (P / 256) >= 1024 && !OTAL_OPT("OTAL_1X1S_NW1", 0)) nw = 2;
+    if (mt_all <= 2 && P % 256 == 0 && (int64_t)g.B * (P / 256) >= 1024) nw = 2;
     const int cap = nw == 2 ? 2 : 6;
     const int msplit = (mt_all + cap - 1) / cap;
     int mt = (mt_all + msplit - 1) / msplit;
@@ -364,7 +358,7 @@ static int launch_conv1x1_stream(const ConvArgs& a, const unsigned short* wp, si
     const int BN = 128 * nw;
     s.tps = P / BN;
     s.tiles = g.B * s.tps;
-    int wgs = OTAL_OPT("OTAL_1X1S_WGS", 512) / msplit;       // two workgroups per CU in all
+    int wgs = 512 / msplit;                                   // two workgroups per CU in all
     if (wgs > s.tiles) wgs = s.tiles;
     wgs = (wgs + 7) & ~7;                                     // sibling row groups of a tile on one XCD
     s.wgs = wgs;

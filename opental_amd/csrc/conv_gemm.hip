@@ -45,7 +45,9 @@ namespace {
 
 constexpr int NT = 256;
 enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_WGRAD = 2 };
-enum { EPI_RELU = 1, EPI_ACCUM = 2, DBG_NOLOAD = 4, DBG_NOSTORE = 8, DBG_NOBARRIER = 16, EPI_NPAD8 = 32, EPI_PLAIN_GRID = 256 };   // DBG_*: ablation only (OTAL_CONV_DEBUG)
+// (NO_STORE / NO_BARRIER: never set.  conv_gemm_kernel still tests them: without the two run-time branches the compiler
+//  lays its loop out differently -- more SGPRs in some instantiations, a 20-byte private segment in two)
+enum { EPI_RELU = 1, EPI_ACCUM = 2, NO_STORE = 8, NO_BARRIER = 16, EPI_NPAD8 = 32 };
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -724,7 +726,6 @@ __global__ __launch_bounds__(NT) void conv_gemm_kernel(const ConvArgs a) {
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     const int nk = (k_end - k_begin + BK - 1) / BK;
-    const bool dbg_load = !(a.flags & DBG_NOLOAD);
     prep(k_begin, nk > 0);
 #pragma unroll
     for (int q = 0; q < A_LOADS; ++q) loadA(q, k_begin, nk > 0);
@@ -739,7 +740,7 @@ __global__ __launch_bounds__(NT) void conv_gemm_kernel(const ConvArgs a) {
     constexpr int A_PER_CH = (A_LOADS + NCH - 1) / NCH, B_PER_CH = (B_LOADS + NCH - 1) / NCH;
     for (int it = 0; it < nk; ++it) {
         const int buf = it & 1;
-        const bool has_next = (it + 1 < nk) && dbg_load;
+        const bool has_next = it + 1 < nk;
         const int kn = k_begin + (it + 1) * BK;
         prep(kn, has_next);
 #pragma unroll
@@ -783,8 +784,8 @@ __global__ __launch_bounds__(NT) void conv_gemm_kernel(const ConvArgs a) {
             }
             __builtin_amdgcn_sched_barrier(0);      // keep the slices where they are
         }
-        if (!(a.flags & DBG_NOSTORE)) store_tiles(buf ^ 1);   // harmless on the last step (buffer is never read)
-        if (!(a.flags & DBG_NOBARRIER)) __syncthreads();
+        if (!(a.flags & NO_STORE)) store_tiles(buf ^ 1);   // harmless on the last step (buffer is never read)
+        if (!(a.flags & NO_BARRIER)) __syncthreads();
     }
 
     store_acc<MODE, WM, WN, BM>(a, acc, m0, n0, wm0, wn0, lane, split, reinterpret_cast<float*>(smemA[0]));
@@ -1170,11 +1171,7 @@ __global__ __launch_bounds__(NT, KWV ? 1 : (BM == 96 ? 4 : (BM == 192 ? 3 : 1)))
         const unsigned short* bs = smB[buf];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-#ifdef OTAL_DIRECT_ABLATE
-            if (c == 0) { if (!(a.flags & 128)) loadA(kn); if (!(a.flags & DBG_NOLOAD)) loadB(0); } else if (!(a.flags & DBG_NOLOAD)) loadB(1);
-#else
             if (c == 0) { loadA(kn); loadB(0); } else loadB(1);
-#endif
             bf16x8 av[WM], bv[WN];
 #pragma unroll
             for (int i = 0; i < WM; ++i)
@@ -1192,19 +1189,6 @@ __global__ __launch_bounds__(NT, KWV ? 1 : (BM == 96 ? 4 : (BM == 192 ? 3 : 1)))
         store_tiles(buf ^ 1);
         __syncthreads();
     }
-#ifdef OTAL_DIRECT_ABLATE
-    if (a.flags & 64) {
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) t += acc[i][j][r];
-        if (t == 1.2345678e30f) a.out[0] = t;
-        return;
-    }
-#endif
     if constexpr (H) {
         if (a.splits == 1) {
             store_acc_h<MODE, WM, WN, BM, BN>(a, acc, m0, n0, wm0, wn0, lane, smem_, NT);
@@ -2076,7 +2060,7 @@ static int launch_splitk_reduce(const ConvArgs& a, hipStream_t st) {
             return 0;
         }
     }
-    if (v4 && a.splits >= 16 && total <= (1 << 21) && !OTAL_OPT("OTAL_CONV_NOTALLREDUCE", 0)) {
+    if (v4 && a.splits >= 16 && total <= (1 << 21)) {
         const int blocks = (int)((total / 4 + 63) / 64);
         hipLaunchKernelGGL((splitk_reduce_tall_kernel<MODE, H>), dim3(blocks), dim3(256), 0, st, a);
         return otal_launch_status();
@@ -2128,9 +2112,9 @@ int fill_geom(ConvGeom& g, const int* d) {
 }
 
 // tile height: least padded M, with a small penalty for the lower arithmetic intensity of short tiles
-int choose_bm(int M, int tall = 0) {
-    const int tall_env = OTAL_OPT("OTAL_CONV_TALL", 1);    // bit0: fwd/dgrad (on: 2c fwd +16 %), bit1: wgrad (off: -9 %)
-    if ((tall & tall_env) && M % 192 == 0) return 192;     // one 192-row tile re-fetches the gathered operand half as often
+// (192-row tiles for the chunked forward / data gradient: 2c forward +16 %; the weight gradient's measured -9 %)
+int choose_bm(int M, bool tall = false) {
+    if (tall && M % 192 == 0) return 192;                  // one 192-row tile re-fetches the gathered operand half as often
     const int cand[4] = {128, 96, 64, 32};
     const double pen[4] = {1.00, 1.03, 1.10, 1.30};
     int best = 128;
@@ -2144,21 +2128,17 @@ int choose_bm(int M, int tall = 0) {
 
 // choose split-K so that the grid fills the chip (256 CUs) without shredding K
 int choose_splits(int tiles, int K, int prec = 1, bool wgrad = false) {
-    const int target_env = OTAL_OPT("OTAL_CONV_SPLIT_BLOCKS", 0);
     // bf16: >= 8 K steps of 32 per split (fewer, larger slabs: measured +4 % step throughput over 4);
     // fp32 parity path: 128 k per split as in the version the gradient-parity fixtures were validated with
-    const int minsteps_env = OTAL_OPT("OTAL_CONV_SPLIT_MINSTEPS", 0);
-    const int cap_env = OTAL_OPT("OTAL_CONV_MAXSPLIT", 0);
     // The vector weight-gradient kernel keeps 4 workgroups per CU resident and its K is huge (all positions): it wants two
     // full waves of workgroups (2048; 512 left it at 2 waves per SIMD, 61 % of wave time parked).  Splits of >= 16 K steps:
     // a K step is latency-bound (~1 us) when few workgroups are resident, so the small 1x1 / 1-D layers (18 k or 1 k
     // positions, a handful of tiles) finish sooner as many short splits than as a few long ones (measured per step:
     // 48 steps 407.6 clips/s, 24: 419.0, 12: 420.1, 6: 416.2).  Forward / data gradient keep the 512-workgroup target.
     const bool wv = wgrad && prec;
-    const int target = target_env ? target_env : (wv ? 2048 : 512);
-    const int wg_minsteps_env = OTAL_OPT("OTAL_WGRAD_MINSTEPS", 0);
-    const int minsteps = (wv && wg_minsteps_env) ? wg_minsteps_env : minsteps_env ? minsteps_env : (wv ? 16 : (prec ? 8 : 4));
-    const int cap = cap_env ? cap_env : (wv ? 1024 : 384);
+    const int target = wv ? 2048 : 512;
+    const int minsteps = wv ? 16 : (prec ? 8 : 4);
+    const int cap = wv ? 1024 : 384;
     if (tiles >= target * 3 / 4) return 1;
     int want = (target + tiles - 1) / tiles;
     int maxs = K / (minsteps * 32);
@@ -2184,9 +2164,9 @@ static void set_epilogue_extents(ConvArgs& a) {
     if (MODE == MODE_FWD) out = 4 * ((int64_t)(g.B - 1) * g.y_bs + (int64_t)(g.Cout - 1) * g.y_cs + conv_out_positions(g));
     else if (MODE == MODE_DGRAD) out = 4 * ((int64_t)(g.B - 1) * g.x_bs + (int64_t)(g.Cin - 1) * g.x_cs + conv_in_positions(g));
     else out = 4 * (int64_t)g.Cout * g.Cin * conv_kvol(g);
-    a.out_bytes = (out > 0 && out < (int64_t)0xfffffff0u && !OTAL_OPT("OTAL_CONV_SLOW_EPILOGUE", 0)) ? (unsigned)out : 0u;
+    a.out_bytes = (out > 0 && out < (int64_t)0xfffffff0u) ? (unsigned)out : 0u;
     const int64_t slab = 4 * (int64_t)a.splits * a.M * a.N;
-    a.slab_bytes = (a.splits > 1 && slab < (int64_t)0xfffffff0u && !OTAL_OPT("OTAL_CONV_SLOW_EPILOGUE", 0)) ? (unsigned)slab : 0u;
+    a.slab_bytes = (a.splits > 1 && slab < (int64_t)0xfffffff0u) ? (unsigned)slab : 0u;
 }
 
 // =================================================================================================
@@ -2423,13 +2403,8 @@ __global__ __launch_bounds__(BNP * 2 / WN, MINW) void conv3_direct_kernel(const 
         for (int j = 0; j < WN; ++j) bvA[j] = frag_b(buf, dt, 0, j);
 #pragma unroll
         for (int g9 = 0; g9 < 9; ++g9) {
-#ifdef OTAL_DIRECT_ABLATE       // timing experiments only (tools/ablate_direct.sh): results are wrong under these flags
-            if (g9 == 0 && !(a.flags & DBG_NOLOAD)) load_x(sx, OTHER);
-            if (g9 == 1 && !(a.flags & 128)) load_a(sn);
-#else
             if (g9 == 0) load_x(sx, OTHER);
             if (g9 == 1) load_a(sn);
-#endif
             bf16x8 (&av)[WM] = (g9 & 1) ? avB : avA;
             bf16x8 (&bv)[WN] = (g9 & 1) ? bvB : bvA;
             bf16x8 (&avn)[WM] = (g9 & 1) ? avA : avB;
@@ -2455,13 +2430,8 @@ __global__ __launch_bounds__(BNP * 2 / WN, MINW) void conv3_direct_kernel(const 
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-#ifdef OTAL_DIRECT_ABLATE
-        if (!(a.flags & DBG_NOSTORE)) store(buf ^ 1, sn, CUR);
-        if (!(a.flags & DBG_NOBARRIER)) __syncthreads();
-#else
         store(buf ^ 1, sn, CUR);
         __syncthreads();
-#endif
     };
     if constexpr (XPF2) {
         for (int s = 0; s < nsteps; s += 2) {
@@ -2539,19 +2509,6 @@ __global__ __launch_bounds__(BNP * 2 / WN, MINW) void conv3_direct_kernel(const 
         }
         return;
     }
-#ifdef OTAL_DIRECT_ABLATE
-    if (a.flags & 64) {         // no epilogue (the accumulators stay live through an impossible store)
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) t += acc[i][j][r];
-        if (t == 1.2345678e30f) a.out[0] = t;
-        return;
-    }
-#endif
     store_acc<MODE, WM, WN, BM>(a, acc, m0, n0, 0, wave * WN * 32, lane, 0, reinterpret_cast<float*>(smA(0)));
 }
 
@@ -2631,13 +2588,8 @@ __global__ __launch_bounds__(C1_NT) void conv1a_direct_fwd_kernel(const Conv1aAr
             const int item = tid + C1_NT * (it0 + u);
             const int pl = item / (C1_NR * 24), rem = item - pl * (C1_NR * 24), rr = rem / 24, q = rem - rr * 24;
             const int ti = 2 * to0 - g.pt + pl, hi = 2 * ho0 - g.ph + rr;
-#ifdef OTAL_DIRECT_ABLATE
-            const bool ok = !(a.flags & 4) && it0 + u < ITERS && item < ITEMS && (unsigned)ti < (unsigned)g.Ti && (unsigned)hi < (unsigned)g.Hi;
-            lds_off[u] = !(a.flags & 8) && item < ITEMS && it0 + u < ITERS ? (pl * C1_NR + rr) * C1_PITCH + (4 * q + 2) * 8 : -1;
-#else
             const bool ok = it0 + u < ITERS && item < ITEMS && (unsigned)ti < (unsigned)g.Ti && (unsigned)hi < (unsigned)g.Hi;
             lds_off[u] = item < ITEMS && it0 + u < ITERS ? (pl * C1_NR + rr) * C1_PITCH + (4 * q + 2) * 8 : -1;
-#endif
             const float* src = xb + ((int64_t)(ok ? ti : 0) * g.Hi + (ok ? hi : 0)) * g.Wi + 4 * q;
 #pragma unroll
             for (int ci = 0; ci < 3; ++ci)
@@ -2666,14 +2618,8 @@ __global__ __launch_bounds__(C1_NT) void conv1a_direct_fwd_kernel(const Conv1aAr
     // only ~130 MFMA cycles long, so a load issued two steps ahead (first version) stalled EVERY step on the L2 latency:
     // the registers form a FIFO of seven slices (slice s lives in rq[s % 7]) -- loads run nine steps ahead of their use.
     Words4 rq[7];
-#ifdef OTAL_DIRECT_ABLATE
-    const bool abl_w = (a.flags & 128) != 0;
-    auto load_a = [&](int s) { if (tid < 256 && !abl_w) rq[s % 7] = __builtin_bit_cast(Words4, __builtin_amdgcn_raw_buffer_load_b128(rw, avo, s * 64, 0)); };
-    auto store_a = [&](int s) { if (tid < 256 && !abl_w) *reinterpret_cast<Words4*>(smA[s & 1] + (tid >> 2) * C1_PA + (tid & 3) * 16) = rq[s % 7]; };
-#else
     auto load_a = [&](int s) { if (tid < 256) rq[s % 7] = __builtin_bit_cast(Words4, __builtin_amdgcn_raw_buffer_load_b128(rw, avo, s * 64, 0)); };
     auto store_a = [&](int s) { if (tid < 256) *reinterpret_cast<Words4*>(smA[s & 1] + (tid >> 2) * C1_PA + (tid & 3) * 16) = rq[s % 7]; };
-#endif
     load_a(0);
     load_a(1);
 #pragma unroll
@@ -2715,12 +2661,7 @@ __global__ __launch_bounds__(C1_NT) void conv1a_direct_fwd_kernel(const Conv1aAr
 #pragma unroll
     for (int s = 0; s < C1_STEPS; ++s) {    // fully unrolled: `set` and the FIFO slot index register arrays
         const int set = s & 1;
-#ifdef OTAL_DIRECT_ABLATE       // timing experiments only (tools/ablate_direct.sh): results are wrong under these flags
-        if (s + 1 < C1_STEPS && !(a.flags & 256)) read_ops(set ^ 1, s + 1);
-        if (!(a.flags & 512))
-#else
         if (s + 1 < C1_STEPS) read_ops(set ^ 1, s + 1);
-#endif
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -2728,22 +2669,8 @@ __global__ __launch_bounds__(C1_NT) void conv1a_direct_fwd_kernel(const Conv1aAr
                 acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[set][kk][i], bv[set][kk], acc[i][0], 0, 0, 0);
         if (s + 2 < C1_STEPS) store_a(s + 2);              // into the slot of slice s (its operands were read during step s-1)
         if (s + 9 < C1_STEPS) load_a(s + 9);                // refills the register just stored
-#ifdef OTAL_DIRECT_ABLATE
-        if (!(a.flags & DBG_NOBARRIER))
-#endif
         __syncthreads();
     }
-#ifdef OTAL_DIRECT_ABLATE
-    if (a.flags & 64) {
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) t += acc[i][0][r];
-        if (t == 1.2345678e30f) a.out[0] = t;
-        return;
-    }
-#endif
     if (a.half) {
         // bf16 output (the layer's 604 MB of fp32 activations are only ever read back through bf16 roundings: MaxPool3d_2a
         // commutes with the monotonic rounding and Conv3d_2b rounds its operand anyway -- the forward values are unchanged):
@@ -2785,7 +2712,7 @@ static inline bool conv1a_half_out_ok(const ConvGeom& g, const void* y) {
     return g.y_bs % 8 == 0 && g.y_cs % 8 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
 }
 static inline bool conv1a_direct_eligible(const ConvGeom& g, int mode, int prec, const void* x) {
-    if (!prec || mode != MODE_FWD || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NO1A", 0)) return false;
+    if (!prec || mode != MODE_FWD || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NO1A")) return false;
     if (g.Cin != 3 || g.kt != 7 || g.kh != 7 || g.kw != 7 || g.st != 2 || g.sh != 2 || g.sw != 2) return false;
     if (g.pt != 2 || g.ph != 2 || g.pw != 2 || g.Wi != 96 || g.Wo != C1_WO || g.Hi != 2 * g.Ho || g.Ti != 2 * g.To) return false;
     if (g.To % C1_TT || g.Ho % C1_TR || g.x_bs % 4 || g.x_cs % 4 || (reinterpret_cast<uintptr_t>(x) & 15)) return false;
@@ -2794,9 +2721,6 @@ static inline bool conv1a_direct_eligible(const ConvGeom& g, int mode, int prec,
 static inline size_t conv1a_wp_bytes(int M) { return (((size_t)((M + 63) / 64 * 64) * C1_STEPS * 64) + 255) & ~(size_t)255; }
 
 int launch_conv1a_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
-#ifdef OTAL_DIRECT_ABLATE
-    a.flags |= (OTAL_OPT("OTAL_CONV_DEBUG", 0) & (4 | 8 | 16 | 64 | 128 | 256 | 512));
-#endif
     if (otal_conv::conv1a_tile_eligible(a.g.To, a.g.Ho) && !(a.flags & EPI_ACCUM)) {      // 4 x 4 x 48 tiles (conv1a_tile.hip)
         otal_conv::Conv1aTileArgs t;
         t.x = a.x; t.w = a.w; t.wp = nullptr; t.out = a.out; t.scale = a.scale; t.shift = a.shift;
@@ -2963,7 +2887,7 @@ __global__ __launch_bounds__(256) void conv_wgrad1d_kernel(const ConvArgs a, int
 
 static inline int wgrad1d_chunks(const ConvGeom& g) { return (g.Ti + W1_TC - 1) / W1_TC; }
 static inline bool wgrad1d_eligible(const ConvGeom& g, int prec, const void* x, const void* dy) {
-    if (!prec || OTAL_OPT("OTAL_CONV_NOW1D", 0)) return false;
+    if (!prec || OTAL_OPT("OTAL_CONV_NOW1D")) return false;
     if (g.Hi != 1 || g.Wi != 1 || g.Ho != 1 || g.Wo != 1 || g.kh != 1 || g.kw != 1 || g.st != 1 || g.To != g.Ti) return false;
     if (!((g.kt == 1 && g.pt == 0) || (g.kt == 3 && g.pt == 1))) return false;
     if (g.Cin % 64 || (g.x_bs | g.x_cs | g.y_bs | g.y_cs) & 1) return false;
@@ -2972,15 +2896,12 @@ static inline bool wgrad1d_eligible(const ConvGeom& g, int prec, const void* x, 
 }
 
 int launch_wgrad1d(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int upw_env = OTAL_OPT("OTAL_W1D_UPW", 0);
     const int nchunks = wgrad1d_chunks(a.g), units = a.g.B * nchunks;
-    const int tiles = ((a.g.Cout + 63) / 64) * (a.g.Cin / 64);
     // units per workgroup = (sample, chunk) units folded into one split-K slab.  Round 2 (every reduction its own launch behind
     // its GEMM, one lane): 1 -> 478.4, 2 -> 475.8, 4 -> 465.7 clips/s.  Round 6 (reductions batched on the weight-gradient lane, whose
     // slab traffic is what these eight launches cost -- 328 MB written, 328 MB read back per step): 1 / 2 / 4 / 8 -> 8.09 / 8.03 /
     // 8.02 / 8.02 ms.  Four where there are eight units or more (two slabs at b = 8), two from four units on.
-    const int upw = upw_env > 0 ? upw_env : (units >= 8 ? 4 : units >= 4 ? 2 : 1);
-    (void)tiles;
+    const int upw = units >= 8 ? 4 : units >= 4 ? 2 : 1;
     const int splits = (units + upw - 1) / upw;
     const size_t need = ((size_t)splits * a.M * a.N * sizeof(float) + 255) & ~(size_t)255;
     if (!ws || ws_bytes < need * (a.pair ? 2 : 1)) return OTAL_E_UNSUPPORTED;
@@ -3019,21 +2940,19 @@ static inline bool half_layout_ok(const ConvGeom& g, const void* x, const void* 
 }
 static inline bool chunk_eligible(const ConvGeom& g, int mode, int prec) {
     if (!prec || mode == MODE_WGRAD) return false;
-    if (OTAL_OPT("OTAL_CONV_NOCHUNK", 0)) return false;
     const int C = mode == MODE_FWD ? g.Cin : g.Cout;
-    if (C % 8 && !(mode == MODE_FWD && g.kw >= 3 && !OTAL_OPT("OTAL_CONV_NOKWV", 0))) return false;    // forward has the kw-vector mode
+    if (C % 8 && !(mode == MODE_FWD && g.kw >= 3)) return false;    // forward has the kw-vector mode
     const int64_t ext = gather_extent_bytes(g, mode);
     return ext > 0 && ext < (int64_t)0xfffffff0u;       // 32-bit buffer offsets
 }
 
 // positions one thread may fetch with a single vector load (see conv_gemm_bf16c_kernel)
 static inline int chunk_vector_width(const ConvGeom& g) {
-    if (OTAL_OPT("OTAL_CONV_CW", 0) == 1) return 1;
     if (g.st != 1 || g.sh != 1 || g.sw != 1 || g.nlev > 1) return 1;
     if (g.Wo != g.Wi || (g.kw != 1 && g.kw != 3) || g.pw != (g.kw - 1) / 2) return 1;
     // 1x1x1: no shifted tap, so 4 consecutive positions of a sample are contiguous across row ends as well
-    if (g.kt == 1 && g.kh == 1 && g.kw == 1 && g.To == g.Ti && g.Ho == g.Hi && conv_out_positions(g) % 4 == 0 &&
-        !OTAL_OPT("OTAL_CONV_NO1X1V4", 0)) return 4;
+    if (g.kt == 1 && g.kh == 1 && g.kw == 1 && g.To == g.Ti && g.Ho == g.Hi && conv_out_positions(g) % 4 == 0)
+        return 4;
     if (g.Wi % 4 == 0) return 4;
     if (g.Wi % 2 == 0) return 2;
     return 1;
@@ -3044,7 +2963,7 @@ template <int MODE>
 static void fill_prep_desc(PrepDesc& d, const ConvArgs& a, int2* ctab, unsigned short* wp) {
     const int C = MODE == MODE_FWD ? a.g.Cin : a.g.Cout;
     const bool kwv = MODE == MODE_FWD && (C % 8) != 0;
-    const int BMsel = choose_bm(a.M, kwv ? 0 : 1);
+    const int BMsel = choose_bm(a.M, !kwv);
     d.ctab = ctab; d.wp = reinterpret_cast<unsigned*>(wp); d.wsrc = a.w; d.g = a.g;
     d.M = a.M; d.Mpad = (a.M + BMsel - 1) / BMsel * BMsel; d.C = C; d.kvol = conv_kvol(a.g);
     d.K = a.K; d.Kp = chunk_kp(a.K); d.nchunk = d.Kp / 8 + CHUNK_PAD; d.kwv = kwv ? 1 : 0; d.natural = a.w_natural; d.mode = MODE;
@@ -3088,11 +3007,11 @@ int launch_chunked(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     const bool kwv = MODE == MODE_FWD && (C % 8) != 0;
     if (H && (kwv || (a.flags & EPI_ACCUM) || conv_in_positions(a.g) != conv_out_positions(a.g))) return OTAL_E_UNSUPPORTED;
     if (kwv) a.K = a.g.Cin * a.g.kt * a.g.kh * 8;          // kw padded to 8 taps per (ci, dt, dh) row
-    const int BMpack = choose_bm(a.M, kwv ? 0 : 1);           // the weight pack's row padding (persistent regions are sized by it)
+    const int BMpack = choose_bm(a.M, !kwv);           // the weight pack's row padding (persistent regions are sized by it)
     int BMsel = BMpack;
     // bf16 tensors: the 128-row variant needs 247 registers (two workgroups per CU), the 96-row one 105 (four); rows past the
     // pack's padding read zeros through the buffer bounds check, so a different tile height may run on the same pack
-    if (H && BMsel == 128 && OTAL_OPT("OTAL_CHUNK_H_NO128", 1)) BMsel = 96;
+    if (H && BMsel == 128) BMsel = 96;
     const int tm = (a.M + BMsel - 1) / BMsel, tn = (a.N + 127) / 128;
     a.Kp = chunk_kp(a.K);
     const size_t tb = chunk_tab_bytes(a.K), wb = chunk_wp_bytes(a.M, BMpack, a.K);
@@ -3139,9 +3058,6 @@ int launch_chunked(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     a.k_per_split = kps;
     a.slab = splits > 1 ? (float*)ws : nullptr;
     set_epilogue_extents<MODE>(a);
-#ifdef OTAL_DIRECT_ABLATE
-    a.flags |= (OTAL_OPT("OTAL_CONV_DEBUG", 0) & (DBG_NOLOAD | 64 | 128));
-#endif
     const dim3 grid(tn, tm, splits);
     const int cw = chunk_vector_width(a.g);
 #define OTAL_LAUNCH_C(BM_, WM_, WN_)                                                                                   \
@@ -3160,7 +3076,7 @@ int launch_chunked(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     }
     if (kwv) {
     } else if (BMsel == 192) OTAL_LAUNCH_C(192, 6, 1);
-    else if (BMsel == 128) OTAL_LAUNCH_C(128, 2, 2);
+    else if (BMsel == 128) { if constexpr (!H) OTAL_LAUNCH_C(128, 2, 2); }     // (bf16 tensors: 96 rows, above)
     else if (BMsel == 96) OTAL_LAUNCH_C(96, 3, 1);
     else if (BMsel == 64) OTAL_LAUNCH_C(64, 2, 1);
     else OTAL_LAUNCH_C(32, 1, 1);
@@ -3176,7 +3092,7 @@ int launch_chunked(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
 constexpr int PTAB_PAD = 64;        // entries readable past the last group (two K steps of prefetch at CW = 2 -> 32)
 // stride-2 pair mode of the vector WGRAD (Conv3d_1a): window ends must stay within 4 elements of the row
 static inline bool wgrad_pair_mode(const ConvGeom& g, int prec) {
-    if (!prec || OTAL_OPT("OTAL_CONV_NOVEC_WGRAD", 0) || g.nlev > 1) return false;
+    if (!prec || g.nlev > 1) return false;
     if (g.sw != 2 || g.st > 2 || g.sh > 2 || g.kw > 7 || g.pw > 3 || g.Wo % 8 || conv_out_positions(g) % 32) return false;
     if (g.Wi - (2 * (g.Wo - 8) - g.pw + 6) < 12) return false;      // last window: elements 0..11 inside the row
     const int64_t ex = 4 * ((int64_t)(g.B - 1) * g.x_bs + (int64_t)(g.Cin - 1) * g.x_cs + conv_in_positions(g));
@@ -3184,7 +3100,7 @@ static inline bool wgrad_pair_mode(const ConvGeom& g, int prec) {
     return ex > 0 && ey > 0 && ex < (int64_t)0xffffff00u && ey < (int64_t)0xfffffff0u;
 }
 static inline int wgrad_vector_width(const ConvGeom& g, int prec) {
-    if (!prec || OTAL_OPT("OTAL_CONV_NOVEC_WGRAD", 0)) return 0;
+    if (!prec) return 0;
     if (g.st != 1 || g.sh != 1 || g.sw != 1 || g.nlev > 1) return 0;
     if (g.To != g.Ti || g.Ho != g.Hi || g.Wo != g.Wi) return 0;
     if ((g.kw != 1 && g.kw != 3) || g.pw != (g.kw - 1) / 2) return 0;
@@ -3194,7 +3110,7 @@ static inline int wgrad_vector_width(const ConvGeom& g, int prec) {
     if (ex <= 0 || ey <= 0 || ex >= (int64_t)0xfffffff0u || ey >= (int64_t)0xfffffff0u) return 0;
     // a 1x1x1 kernel has no shifted tap: any 8 consecutive positions of a sample are one contiguous vector, whatever the row
     // length (6x6 planes were on 2-element vectors, 3x3 planes on the generic kernel)
-    if (g.kt == 1 && g.kh == 1 && g.kw == 1 && !OTAL_OPT("OTAL_CONV_NO1X1V8", 0)) return 8;
+    if (g.kt == 1 && g.kh == 1 && g.kw == 1) return 8;
     if (g.Wi % 8 == 0) return 8;
     if (g.Wi % 4 == 0) return 4;
     if (g.Wi % 2 == 0) return 2;
@@ -3212,11 +3128,7 @@ int launch_wgrad_vector(ConvArgs& a, int cw, void* ws, size_t ws_bytes, hipStrea
         a.N = a.g.Cin * a.g.kt * a.g.kh * 8;
         a.flags |= EPI_NPAD8;
     }
-    int BMsel = choose_bm(a.M, pair ? 0 : 2);
-    {   // (experiment knob: a smaller row block = a smaller register / LDS footprint per workgroup beside the main lane's kernels)
-        const int cap = OTAL_OPT("OTAL_WGRADV_MAXBM", 192);
-        while (BMsel > cap && BMsel > 32) BMsel = BMsel == 192 ? 128 : (BMsel == 128 ? 96 : (BMsel == 96 ? 64 : 32));
-    }
+    const int BMsel = choose_bm(a.M);
     const int tm = (a.M + BMsel - 1) / BMsel, tn = (a.N + 127) / 128;
     const size_t tb = ptab_bytes(a.g, cw);
     a.fd = make_conv_fastdiv(a.g);
@@ -3285,7 +3197,7 @@ static inline int direct_bm(const ConvGeom& g, int M) {
     // one workgroup per CU and launch round: where 64-row tiles of 256 positions need a second, nearly empty round (the 6x6
     // planes of Mixed_4b..4d b1b forward: 4 x 72 = 288 workgroups) and 96-row tiles do not (3 x 72 = 216), the padded rows
     // are cheaper than the round -- forward 43 / 68 / 76 us on 64-row tiles against 56 us for Mixed_4e's 216 tiles of 96
-    if (M > 96 && !OTAL_OPT("OTAL_CONV_DIRECT_NOROUNDS", 0)) {
+    if (M > 96) {
         const int64_t nt = (int64_t)g.B * conv_out_positions(g) / 256;
         const int64_t w64 = (M + 63) / 64 * nt, w96 = (M + 95) / 96 * nt;
         if (w64 <= 512 && (w96 + 255) / 256 * 96 < (w64 + 255) / 256 * 64) return 96;
@@ -3294,9 +3206,9 @@ static inline int direct_bm(const ConvGeom& g, int M) {
     // 16 .. 32 rows (data gradient of the Inception b2b layers: M = Cin = 16 / 24 / 32; forward of Mixed_3b.b2b): one 32-row
     // MFMA tile per wave.  LDS-read-bound (9 weight + 9 position fragments per 9 MFMAs), but these layers are tiny and ran
     // on the gather kernel at 25 .. 90 us for 0.1 .. 1 GFLOP of work per sample
-    if (M <= 32 && !OTAL_OPT("OTAL_CONV_DIRECT_NO32", 0)) return 32;
+    if (M <= 32) return 32;
     const int pad64 = (M + 63) / 64 * 64;
-    return (pad64 - M) * 100 <= M * OTAL_OPT("OTAL_CONV_DIRECT_PAD", 34) ? 64 : 0;     // accept <= 34 % padded rows (Mixed_4e: 144 -> 192)
+    return (pad64 - M) * 100 <= M * 34 ? 64 : 0;     // accept <= 34 % padded rows (Mixed_4e: 144 -> 192)
 }
 // positions per workgroup: 256 (8 waves), or 128 (4 waves) when 256 would leave the chip half empty (the 6x6 planes of
 // Mixed_4x: 72 position tiles); 0 = too few tiles either way (no split-K on this path)
@@ -3306,19 +3218,17 @@ static inline int direct_bnp(const ConvGeom& g, int M) {
     const int64_t tm = (M + BM - 1) / BM, NP = (int64_t)g.B * conv_out_positions(g);
     // (140: the 144 tiles of a one-M-tile layer on the 6x6 planes still take the 128-position form -- Mixed_4b / 4e b2b forward
     //  17.5 -> 10.1 us, 27.6 -> 12.9 us, Mixed_4b b1b data gradient 71 -> 54 us against the gather kernel; tools/micro_planes6.py)
-    const int min_tiles = OTAL_OPT("OTAL_CONV_DIRECT_MINTILES", 140);
+    const int min_tiles = OTAL_OPT("OTAL_CONV_DIRECT_MINTILES");
     // 512 positions (two tiles per wave: the weight fragments are shared, the kernel turns MFMA-bound) when that still gives
     // every CU two rounds of workgroups and the tile stays inside one sample
     // (96-row tiles only: a 64-row tile of 256 positions fits TWICE per CU -- 16 waves -- and measured faster than one 512 tile)
-    if (BM == 96 && !OTAL_OPT("OTAL_CONV_DIRECT_NO512", 0) && conv_out_positions(g) % 512 == 0 &&
-        tm * (NP / 512) >= OTAL_OPT("OTAL_CONV_DIRECT_MINTILES512", 512)) return 512;
+    if (BM == 96 && conv_out_positions(g) % 512 == 0 && tm * (NP / 512) >= OTAL_OPT("OTAL_CONV_DIRECT_MINTILES512")) return 512;
     if (tm * (NP / 256) >= min_tiles) return 256;
-    if (!OTAL_OPT("OTAL_CONV_DIRECT_NO128", 0) && tm * (NP / 128) >= min_tiles) return 128;
+    if (tm * (NP / 128) >= min_tiles) return 128;
     return 0;
 }
 static inline bool direct_eligible(const ConvGeom& g, int mode, int prec, int M) {
-    const bool off = OTAL_OPT("OTAL_CONV_NODIRECT", 0) != 0;
-    if (off || !prec || mode == MODE_WGRAD || g.nlev > 1) return false;
+    if (OTAL_OPT("OTAL_CONV_NODIRECT") || !prec || mode == MODE_WGRAD || g.nlev > 1) return false;
     if (g.kt != 3 || g.kh != 3 || g.kw != 3 || g.st != 1 || g.sh != 1 || g.sw != 1 || g.pt != 1 || g.ph != 1 || g.pw != 1) return false;
     if (g.To != g.Ti || g.Ho != g.Hi || g.Wo != g.Wi || g.Wi > 24) return false;
     const int P = conv_out_positions(g);
@@ -3334,34 +3244,6 @@ static inline size_t direct_wp_bytes(const ConvGeom& g, int M, int C) {
 
 template <int BM, int BNP, int PX = 48, bool H = false>
 constexpr int direct_lds_bytes() { return 2 * BM * 304 + 2 * (BNP + (H ? 56 : 52)) * PX + 16; }
-// four waves x two position tiles, dense LDS pitch: 78 KB (BM = 96) / 59 KB (BM = 64) -> two workgroups per CU
-template <int BM, int MODE>
-static int launch_direct256x2(const DirectArgs& d, dim3 grid, hipStream_t st) {
-    constexpr int lds = direct_lds_bytes<BM, 256, 32>();
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_direct_kernel<BM, MODE, 256, 2, 32, 2>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
-    hipLaunchKernelGGL((conv3_direct_kernel<BM, MODE, 256, 2, 32, 2>), grid, dim3(256), lds, st, d);
-    return otal_launch_status();
-}
-// eight waves x one position tile, dense pitch, <= 128 registers: two 8-wave workgroups (16 waves) per CU
-template <int BM, int MODE>
-static int launch_direct256d(const DirectArgs& d, dim3 grid, hipStream_t st) {
-    constexpr int lds = direct_lds_bytes<BM, 256, 32>();
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_direct_kernel<BM, MODE, 256, 1, 32, 4>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
-    hipLaunchKernelGGL((conv3_direct_kernel<BM, MODE, 256, 1, 32, 4>), grid, dim3(512), lds, st, d);
-    return otal_launch_status();
-}
 template <int BM, int MODE, bool XPF2 = false, bool H = false>
 static int launch_direct512(const DirectArgs& d, dim3 grid, hipStream_t st) {
     constexpr int lds = direct_lds_bytes<BM, 512, 48, H>();
@@ -3398,9 +3280,6 @@ int launch_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     a.src_bytes = (unsigned)gather_extent_bytes(a.g, MODE, H ? 2 : 4);
     a.splits = 1; a.k_per_split = 0; a.slab = nullptr;
     set_epilogue_extents<MODE>(a);
-#ifdef OTAL_DIRECT_ABLATE
-    a.flags |= (OTAL_OPT("OTAL_CONV_DEBUG", 0) & (DBG_NOLOAD | DBG_NOSTORE | DBG_NOBARRIER | 64 | 128));
-#endif
     d.c = a;
     d.wp = reinterpret_cast<const unsigned short*>(ws);
     d.C = C; d.Ktot = C * 27; d.wp_bytes = (unsigned)wb;
@@ -3417,7 +3296,7 @@ int launch_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     // bit 1 -- 96 x 512 (forward); bit 2 -- every 64 x 256 launch.  Measured (tools/xpf_sweep.sh): Conv3d_2c fwd 505 -> 499 us,
     // Mixed_3c.b1b fwd 239 -> 232, Mixed_3b.b1b dgrad 158 -> 150, Mixed_4c .. 4f b1b dgrad 309 -> 285 (sum); with bit 2
     // Conv3d_2c dgrad 476 -> 558 and the 64-row forward launches +15 %: the load latency was NOT what these tiles wait for
-    const int xpf2 = OTAL_OPT("OTAL_CONV_DIRECT_XPF2", 3);
+    const int xpf2 = OTAL_OPT("OTAL_CONV_DIRECT_XPF2");
     if (bnp == 512) {           // two position tiles per wave (dynamic LDS: 112 KB)
         const dim3 grid(a.N / 512, tm, 1);
         if constexpr (MODE == MODE_FWD) {
@@ -3427,13 +3306,6 @@ int launch_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
         return launch_direct512<64, MODE, false, H>(d, grid, st);
     }
     const dim3 grid(a.N / 256, tm, 1);
-    if constexpr (!H) {         // experiments: fp32 tensors only
-        if (OTAL_OPT("OTAL_CONV_DIRECT_256X2", 0) == 1 && BM != 32) {
-            if (BM == 96) return launch_direct256x2<96, MODE>(d, grid, st);
-            return launch_direct256x2<64, MODE>(d, grid, st);
-        }
-        if (OTAL_OPT("OTAL_CONV_DIRECT_256X2", 0) == 2 && BM == 96) return launch_direct256d<96, MODE>(d, grid, st);
-    }
     if (BM == 96 && (xpf2 & 1)) hipLaunchKernelGGL((conv3_direct_kernel<96, MODE, 256, 1, 48, 1, true, H>), grid, dim3(512), (direct_lds_bytes<96, 256, 48, H>()), st, d);
     else if (BM == 64 && ((xpf2 & 4) || ((xpf2 & 1) && (int64_t)grid.x * grid.y <= 256))) hipLaunchKernelGGL((conv3_direct_kernel<64, MODE, 256, 1, 48, 1, true, H>), grid, dim3(512), (direct_lds_bytes<64, 256, 48, H>()), st, d);
     else if (BM == 96) hipLaunchKernelGGL((conv3_direct_kernel<96, MODE, 256, 1, 48, 1, false, H>), grid, dim3(512), (direct_lds_bytes<96, 256, 48, H>()), st, d);
@@ -3452,7 +3324,7 @@ int launch_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
 // wgrad: 3 direct, 4 wide 1x1, 5 vector (the number is the vector width + 16).  Shared by part 1's dispatcher and part 0's
 // otal_conv_half_storage() query; x / dy may be null (the query has no tensors: alignment is then the caller's contract).
 static inline int half_kernel_kind(const ConvGeom& g, int mode, const void* x, const void* dy) {
-    if (g.nlev > 1 || OTAL_OPT("OTAL_CONV_NOHALF", 0)) return 0;
+    if (g.nlev > 1) return 0;
     if (conv_out_positions(g) % 8 || conv_in_positions(g) % 8 || g.x_bs % 8 || g.x_cs % 8 || g.y_bs % 8 || g.y_cs % 8) return 0;
     if (mode == MODE_FWD || mode == MODE_DGRAD) {
         const int M = mode == MODE_FWD ? g.Cout : g.Cin, C = mode == MODE_FWD ? g.Cin : g.Cout;
@@ -3544,7 +3416,7 @@ int launch_mode(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
             if (e != OTAL_E_UNSUPPORTED) return e;
         }
         if (a.half) {       // bf16-stored y: Conv3d_1a's direct kernel and the direct 3x3x3 kernel
-            if (!OTAL_OPT("OTAL_CONV_NO1A", 0) && conv1a_direct_eligible(a.g, MODE, a.prec, a.x) && conv1a_half_out_ok(a.g, a.out))
+            if (!OTAL_OPT("OTAL_CONV_NO1A") && conv1a_direct_eligible(a.g, MODE, a.prec, a.x) && conv1a_half_out_ok(a.g, a.out))
                 return launch_conv1a_direct(a, ws, ws_bytes, st);
             if (direct_eligible(a.g, MODE, a.prec, a.M) && conv1a_half_out_ok(a.g, a.out)) return launch_direct<MODE>(a, ws, ws_bytes, st);
             return OTAL_E_UNSUPPORTED;
@@ -3577,7 +3449,6 @@ int launch_mode(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     }
     a.zero = zero_word_address();
     if (!a.zero) return OTAL_E_UNSUPPORTED;
-    a.flags |= (OTAL_OPT("OTAL_CONV_DEBUG", 0) & (DBG_NOLOAD | DBG_NOSTORE | DBG_NOBARRIER));
     if (MODE != MODE_WGRAD) {       // carve the tap table off the front of the workspace and build it
         const size_t tb = tab_bytes(a.K);
         if (!ws || ws_bytes < tb) return OTAL_E_UNSUPPORTED;
@@ -3602,9 +3473,9 @@ int launch_mode(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     int splits = choose_splits(tm * tn, a.K, a.prec);
     if (MODE == MODE_WGRAD && a.prec) {
         // the generic kernel gets the weight gradients of the 1-D pyramid / head layers (126 positions per sample: no vector
-        // path): K = B * 126 positions, a few dozen tiles -- latency-bound K steps, so split down to OTAL_GWGRAD_MINSTEPS
-        const int ms = OTAL_OPT("OTAL_GWGRAD_MINSTEPS", 4);      // measured: 8 -> 474.6, 4 -> 478.3, 2 -> 478.0, 1 -> 476.3 clips/s
-        const int tg = OTAL_OPT("OTAL_GWGRAD_TARGET", 512);
+        // path): K = B * 126 positions, a few dozen tiles -- latency-bound K steps, so split down to 4 K steps per split
+        const int ms = 4;      // measured: 8 -> 474.6, 4 -> 478.3, 2 -> 478.0, 1 -> 476.3 clips/s
+        const int tg = 512;
         const int tiles = tm * tn;
         int want = (tg + tiles - 1) / tiles, maxs = a.K / (ms * 32);
         if (maxs < 1) maxs = 1;
@@ -3748,7 +3619,7 @@ int pair_geom(ConvArgs& a, const int* geom, const int64_t* strides) {
     if (int e = fill_geom(a.g, geom)) return e;
     a.g.x_bs = strides[0]; a.g.x_cs = strides[1]; a.g.y_bs = strides[2]; a.g.y_cs = strides[3];
     a.pair = 1;
-    return OTAL_OPT("OTAL_CONV_NOPAIR", 0) ? OTAL_E_UNSUPPORTED : 0;
+    return 0;
 }
 }  // namespace
 
@@ -3807,8 +3678,8 @@ extern "C" int otal_conv_half_storage(const int* geom, const int64_t* strides, i
     if (a.g.y_bs % 8 || a.g.y_cs % 8) return 0;
     if (precision & 8) return half_kernel_kind(a.g, mode, nullptr, nullptr) ? 1 : 0;      // bf16 on both sides of the layer
     if (mode == MODE_FWD) {
-        if (conv1a_direct_eligible(a.g, MODE_FWD, 1, nullptr) && !OTAL_OPT("OTAL_CONV_NO1A", 0)) return 1;
-        return direct_eligible(a.g, MODE_FWD, 1, a.g.Cout) && !OTAL_OPT("OTAL_CONV_NODIRECT_HALF", 0) ? 1 : 0;
+        if (conv1a_direct_eligible(a.g, MODE_FWD, 1, nullptr) && !OTAL_OPT("OTAL_CONV_NO1A")) return 1;
+        return direct_eligible(a.g, MODE_FWD, 1, a.g.Cout) ? 1 : 0;
     }
     if (mode == MODE_WGRAD) return conv1a_wgrad_eligible(a.g, 1, nullptr, nullptr) ? 1 : 0;
     return 0;
@@ -3834,9 +3705,9 @@ int prologue_kind(const ConvGeom& g, int mode, int precision) {
     }
     const int M = mode == MODE_FWD ? g.Cout : g.Cin;
     if (mode == MODE_FWD && g.kt == 1 && g.kh == g.Hi && g.kw == g.Wi && g.Hi * g.Wi == 36 && g.Ho == 1 && g.Wo == 1 &&
-        g.Cin % 4 == 0 && !OTAL_OPT("OTAL_CONV_NOPROJ", 0)) return 0;       // the projection GEMM reads the fp32 weights in place
+        g.Cin % 4 == 0 && !OTAL_OPT("OTAL_CONV_NOPROJ")) return 0;       // the projection GEMM reads the fp32 weights in place
     if (conv1a_direct_eligible(g, mode, prec, nullptr)) return 0;
-    if (direct_eligible(g, mode, prec, M)) return OTAL_OPT("OTAL_CONV_NODIRECTPRE", 0) ? 0 : 3;      // the direct kernel's weight pack
+    if (direct_eligible(g, mode, prec, M)) return 3;      // the direct kernel's weight pack
     return chunk_eligible(g, mode, prec) ? 1 : 0;
 }
 int fill_args_for_prologue(ConvArgs& a, const int* geom, const int64_t* strides, int mode, const float* w, int precision) {
@@ -3859,7 +3730,7 @@ extern "C" size_t otal_conv_prologue_bytes(const int* geom, const int64_t* strid
     const int kind = prologue_kind(a.g, mode, precision);
     if (kind == 1) {
         const bool kwv = mode == MODE_FWD && (a.g.Cin % 8) != 0;
-        return chunk_tab_bytes(a.K) + chunk_wp_bytes(a.M, choose_bm(a.M, kwv ? 0 : 1), a.K);
+        return chunk_tab_bytes(a.K) + chunk_wp_bytes(a.M, choose_bm(a.M, !kwv), a.K);
     }
     if (kind == 2) return ptab_bytes(a.g, a.g.sw == 2 ? 8 : wgrad_vector_width(a.g, a.prec));
     if (kind == 3) return direct_wp_bytes(a.g, a.M, mode == MODE_FWD ? a.g.Cin : a.g.Cout);

@@ -696,13 +696,13 @@ __global__ __launch_bounds__(512) void conv3_wgrad_planes3_kernel(const WD3Args 
 }
 
 static inline bool wgrad_direct_eligible(const ConvGeom& g, int prec, const void* x, const void* dy) {
-    if (!prec || OTAL_OPT("OTAL_CONV_NOWDIRECT", 0) || g.nlev > 1) return false;
+    if (!prec || OTAL_OPT("OTAL_CONV_NOWDIRECT") || g.nlev > 1) return false;
     if (g.kt != 3 || g.kh != 3 || g.kw != 3 || g.st != 1 || g.sh != 1 || g.sw != 1 || g.pt != 1 || g.ph != 1 || g.pw != 1) return false;
     if (g.To != g.Ti || g.Ho != g.Hi || g.Wo != g.Wi) return false;
-    const bool planes6 = g.Wi == 6 && g.Hi == 6 && g.Ti % 4 == 0 && !OTAL_OPT("OTAL_CONV_NOWDIRECT6", 0);
-    const bool planes3 = g.Wi == 3 && g.Hi == 3 && g.Ti % 16 == 0 && !OTAL_OPT("OTAL_CONV_NOWDIRECT3", 0);
+    const bool planes6 = g.Wi == 6 && g.Hi == 6 && g.Ti % 4 == 0;
+    const bool planes3 = g.Wi == 3 && g.Hi == 3 && g.Ti % 16 == 0;
     if (!((g.Wi == 24 && g.Hi % 4 == 0) || (g.Wi == 12 && g.Hi == 12) || planes6 || planes3) || g.Cin % 2) return false;
-    if (g.Cin < (planes3 ? OTAL_OPT("OTAL_WDIRECT3_MINC", 32) : planes6 ? OTAL_OPT("OTAL_WDIRECT6_MINC", 64) : OTAL_OPT("OTAL_WDIRECT_MINC", 64)) || g.Cout < OTAL_OPT("OTAL_WDIRECT_MINM", 64)) return false;
+    if (g.Cin < (planes3 ? 32 : 64) || g.Cout < 64) return false;
     if (((uintptr_t)x & 15) || ((uintptr_t)dy & 15) || g.x_cs % 4 || g.x_bs % 4 || g.y_cs % 4 || g.y_bs % 4) return false;
     const int64_t ex = gather_extent_bytes(g, MODE_FWD), ey = gather_extent_bytes(g, MODE_DGRAD);
     return ex > 0 && ey > 0 && ex < (1LL << 31) && ey < (1LL << 31);
@@ -756,25 +756,24 @@ int launch_wgrad_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) 
     const ConvGeom& g = a.g;
     // 64-row tiles: a 96-row tile (192 accumulator registers) spills 19 registers on 24-wide planes, and where it fits
     // (12-wide planes) it measured slower (Mixed_3c b1b: 0.505 vs 0.443 ms)
-    // OTAL_WDIRECT_BM32: bit 0 -- 6x6 planes, bit 1 -- 12x12, bit 2 -- 24x24 take 32-row tiles: half the accumulators (116-146
-    // VGPRs instead of ~200: a workgroup that fits beside the other lane's, see wgrad1x1.inc) for twice the workgroups re-reading
-    // x.  Step, one box: 0 / 1 / 2 / 3 = 942 / 949 / 941 / 938 clips/s -- the five 6x6 layers (Mixed_4b..4f, issued beside the
-    // module's data gradients) gain, the 12x12 ones lose more alone than the fit returns, Conv3d_2c's runs in the one-lane tail.
-    const int bm32 = OTAL_OPT("OTAL_WDIRECT_BM32", 1);
-    const int BM = ((g.Wi == 6 && (bm32 & 1)) || (g.Wi == 12 && (bm32 & 2)) || (g.Wi == 24 && (bm32 & 4)) || (g.Wi == 3 && OTAL_OPT("OTAL_WDIRECT3_BM32", 1))) ? 32 : 64;
+    // The 6x6 and 3x3 planes take 32-row tiles: half the accumulators (116-146 VGPRs instead of ~200: a workgroup that fits
+    // beside the other lane's, see wgrad1x1.inc) for twice the workgroups re-reading x.  Step, one box, 32-row tiles on none /
+    // 6x6 / 12x12 / both = 942 / 949 / 941 / 938 clips/s -- the five 6x6 layers (Mixed_4b..4f, issued beside the module's data
+    // gradients) gain, the 12x12 ones lose more alone than the fit returns, Conv3d_2c's runs in the one-lane tail.
+    const bool planes6 = g.Wi == 6, planes3 = g.Wi == 3;
+    const int BM = planes6 || planes3 ? 32 : 64;
     const int tm = (a.M + BM - 1) / BM, tc = (g.Cin + 31) / 32;
     WD3Args d;
-    const bool planes6 = g.Wi == 6, planes3 = g.Wi == 3;
-    const int PRr = g.Wi == 24 ? (OTAL_OPT("OTAL_WDIRECT_PR8", 1) && g.Hi % 8 == 0 ? 8 : 4) : g.Wi;     // rows per K step
+    const int PRr = g.Wi == 24 ? (g.Hi % 8 == 0 ? 8 : 4) : g.Wi;     // rows per K step
     d.HB = g.Hi / PRr;
     d.steps = planes3 ? g.B * (g.Ti / 16) : planes6 ? g.B * (g.Ti / 4) : g.B * g.Ti * d.HB;       // ordered (sample, row block, t), t fastest; 6x6: four planes a step, 3x3: sixteen
     // one 512-thread workgroup per CU is resident (its registers fill the CU): aim at one full round of 256 workgroups,
     // >= 8 K steps per split, slabs <= the workspace
     const int tiles = tm * tc;
     int splits = tiles >= 256 ? 1 : 256 / tiles;            // never 257 workgroups: the 257th would wait for a whole round
-    const int target = OTAL_OPT("OTAL_WDIRECT_BLOCKS", 0);
+    const int target = OTAL_OPT("OTAL_WDIRECT_BLOCKS");
     if (target > 0) splits = target / tiles > 0 ? target / tiles : 1;
-    const int min_steps = planes3 ? OTAL_OPT("OTAL_WDIRECT3_MINSTEPS", 4) : planes6 ? 4 : 8;
+    const int min_steps = planes3 || planes6 ? 4 : 8;
     if (splits > d.steps / min_steps) splits = d.steps / min_steps > 0 ? d.steps / min_steps : 1;
     const size_t slab1 = (size_t)a.M * a.N * sizeof(float);
     if (splits > 1 && (!ws || ws_bytes < (size_t)splits * slab1)) {
@@ -794,13 +793,8 @@ int launch_wgrad_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) 
     d.c = a;
     const dim3 grid(tc, tm, splits);
     int e;
-    if (planes3) e = BM == 32 ? launch_wd3p<32, H>(d, grid, st) : launch_wd3p<64, H>(d, grid, st);
-    else if (BM == 32) {
-        if (planes6) e = launch_wd6<32, H>(d, grid, st);
-        else if (g.Wi == 24) e = PRr == 8 ? launch_wd3<32, 24, 8, H>(d, grid, st) : launch_wd3<32, 24, 4, H>(d, grid, st);
-        else e = launch_wd3<32, 12, 12, H>(d, grid, st);
-    } else
-    if (planes6) e = launch_wd6<64, H>(d, grid, st);
+    if (planes3) e = launch_wd3p<32, H>(d, grid, st);
+    else if (planes6) e = launch_wd6<32, H>(d, grid, st);
     else if (g.Wi == 24) e = PRr == 8 ? launch_wd3<64, 24, 8, H>(d, grid, st) : launch_wd3<64, 24, 4, H>(d, grid, st);
     else e = launch_wd3<64, 12, 12, H>(d, grid, st);    // whole 12x12 planes: 9 k16 steps per barrier (4 rows: 3 steps, 0.44 -> ms)
     if (e) return e;

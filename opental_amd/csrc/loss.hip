@@ -829,7 +829,7 @@ extern "C" int otal_detection_loss(const float* loc, const float* conf, const fl
     const size_t stage = (size_t)B * K * C * sizeof(float);
     constexpr size_t STAGE_MAX = 96 * 1024;
     static int staged_ok = -1;          // -1: not asked yet; the attribute is set once per process
-    if (cls_mode == 0 && stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE", 0)) {
+    if (cls_mode == 0 && stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE")) {
         if (staged_ok < 0)
             staged_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(detection_loss_kernel<true>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAGE_MAX) == hipSuccess ? 1 : 0;

@@ -1350,7 +1350,7 @@ static inline int strided_k33_kind(const PoolGeom& g, const void* x, const void*
     if (!(g.kh == 3 && g.kw == 3 && g.sh == 2 && g.sw == 2 && g.pt == 0 && g.ph == 0 && g.pw == 0 && g.Hi % 2 == 0 &&
           g.Wi % 4 == 0 && g.Ho == g.Hi / 2 && g.Wo == g.Wi / 2 && g.x_bs % 4 == 0 && g.x_cs % 4 == 0 && g.y_bs % 2 == 0 &&
           g.y_cs % 2 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0) ||
-        OTAL_OPT("OTAL_POOL_NO133", 0))
+        OTAL_OPT("OTAL_POOL_NO133"))
         return 0;
     if (g.kt == 1 && g.st == 1 && g.To == g.Ti) return 1;
     if (g.kt == 3 && g.st == 2 && g.Ti % 2 == 0 && g.To == g.Ti / 2) return 3;
@@ -1377,8 +1377,7 @@ int fwd_planes(const PoolGeom& g, size_t& lds) {
 }
 // input planes per block (backward) + the largest number of output planes a block stages
 int bwd_planes(const PoolGeom& g, int& tlo_max, size_t& lds) {
-    const int tile_elems = OTAL_OPT("OTAL_POOL_TILE_G", 4096);
-    int ti = tile_elems / (g.Hi * g.Wi);
+    int ti = 4096 / (g.Hi * g.Wi);
     if (ti < 1) ti = 1;
     if (ti > g.Ti) ti = g.Ti;
     const int ct = (g.kt + g.st - 1) / g.st;
@@ -1418,10 +1417,9 @@ static int pool_fwd(const int* geom, const int64_t* strides, const float* x, flo
         const dim3 grid((n2 + 255) / 256, g.B * g.C);
         const FastDiv fW2 = make_fastdiv((uint32_t)(g.Wo / 2));
         if (io == 3 && kind == 1 && g.Wi % 8 == 0 && g.x_bs % 8 == 0 && g.x_cs % 8 == 0 && g.y_bs % 4 == 0 && g.y_cs % 4 == 0 &&
-            (reinterpret_cast<uintptr_t>(argtap) & 3) == 0 && (!signbits || (reinterpret_cast<uintptr_t>(signbits) & 1) == 0) &&
-            !OTAL_OPT("OTAL_POOL_NOW8", 0)) {           // eight input columns per thread
+            (reinterpret_cast<uintptr_t>(argtap) & 3) == 0 && (!signbits || (reinterpret_cast<uintptr_t>(signbits) & 1) == 0)) {           // eight input columns per thread
             const int n4 = g.To * g.Ho * (g.Wo / 4);
-            if (nonneg && !OTAL_OPT("OTAL_POOL_NOKEYS", 0))
+            if (nonneg)
                 hipLaunchKernelGGL(maxpool133_s2_w8_nn_fwd_kernel, dim3((n4 + 255) / 256, g.B * g.C), dim3(256), 0, st_, x, y, argtap, g,
                                    make_fastdiv((uint32_t)(g.Wo / 4)), signbits);
             else
@@ -1437,10 +1435,9 @@ static int pool_fwd(const int* geom, const int64_t* strides, const float* x, flo
         else hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<3, false>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
         return otal_launch_status();
     }
-    if (is_333_s1(g) && !OTAL_OPT("OTAL_POOL_NOLDS", 0)) {
-        const int tile_elems = OTAL_OPT("OTAL_POOL_TILE", 1152);
+    if (is_333_s1(g)) {
         const int P = g.Hi, Q = P + 2;
-        int tt = tile_elems / (P * P);
+        int tt = 1152 / (P * P);
         tt = tt < 1 ? 1 : (tt > g.To ? g.To : tt);
         auto need = [&](int t) { return (size_t)(t + 2) * (Q * Q + Q * P) * sizeof(float) + (size_t)(t + 2) * (Q * P + P * P); };
         while (tt > 1 && need(tt) > POOL_LDS_BUDGET) --tt;
@@ -1460,7 +1457,7 @@ static int pool_fwd(const int* geom, const int64_t* strides, const float* x, flo
             else hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<6, true>), rgrid, dim3(256), lds, st_, x, y, argtap, g, TT);
             return otal_launch_status();
         }
-        if (vec && vy && (P == 12 || P == 6) && !OTAL_OPT("OTAL_POOL_NOROWS", 0)) {     // one row per thread
+        if (vec && vy && (P == 12 || P == 6) && !OTAL_OPT("OTAL_POOL_NOROWS")) {     // one row per thread
             const int TT = 256 / P - 2;
             const dim3 rgrid((g.To + TT - 1) / TT, g.B * g.C);
             const size_t lds = (size_t)2 * (TT + 2) * P * P * sizeof(float);
@@ -1478,7 +1475,7 @@ static int pool_fwd(const int* geom, const int64_t* strides, const float* x, flo
     // staging pays when the taps overlap (stride 1: every input is read kvol times); the strided pools read each input
     // ~2 times and were measured faster with direct loads (r01: 230 vs 514 us for the 1x3x3 / (1,2,2) pool)
     const bool overlap = g.st == 1 && g.sh == 1 && g.sw == 1;
-    const int tt = (OTAL_OPT("OTAL_POOL_NOLDS", 0) || !overlap) ? 0 : fwd_planes(g, lds);
+    const int tt = overlap ? fwd_planes(g, lds) : 0;
     if (tt > 0) {
         const dim3 grid((g.To + tt - 1) / tt, g.B * g.C);
         OTAL_POOL_DISPATCH(maxpool3d_fwd_lds_kernel, grid, lds, x, y, argtap, g, tt);
@@ -1510,13 +1507,12 @@ static int pool_bwd(const int* geom, const int64_t* strides, const float* dy, co
         const dim3 grid((n4 + 255) / 256, g.B * g.C);
         const FastDiv fW4 = make_fastdiv((uint32_t)(g.Wi / 4)), fH2 = make_fastdiv((uint32_t)(g.Hi / 2));
         if (all_half && kind == 1 && g.Wi % 8 == 0 && g.x_bs % 8 == 0 && g.x_cs % 8 == 0 && g.y_bs % 4 == 0 && g.y_cs % 4 == 0 &&
-            (reinterpret_cast<uintptr_t>(argtap) & 3) == 0 && (!signbits || (reinterpret_cast<uintptr_t>(signbits) & 1) == 0) &&
-            !OTAL_OPT("OTAL_POOL_NOW8", 0)) {
+            (reinterpret_cast<uintptr_t>(argtap) & 3) == 0 && (!signbits || (reinterpret_cast<uintptr_t>(signbits) & 1) == 0)) {
             const int n8 = g.Ti * (g.Hi / 2) * (g.Wi / 8);
             hipLaunchKernelGGL(maxpool133_s2_w8_bwd_kernel, dim3((n8 + 255) / 256, g.B * g.C), dim3(256), 0, st_, dy, argtap, dx, g, out_scale,
                                make_fastdiv((uint32_t)(g.Wi / 8)), fH2, signbits);
         } else if (all_half && kind == 1) hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, true, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        else if (all_half && g.Wi == 12 && g.x_bs % 4 == 0 && g.x_cs % 4 == 0 && g.y_bs % 2 == 0 && g.y_cs % 2 == 0 && !OTAL_OPT("OTAL_POOL_NOW12", 0))
+        else if (all_half && g.Wi == 12 && g.x_bs % 4 == 0 && g.x_cs % 4 == 0 && g.y_bs % 2 == 0 && g.y_cs % 2 == 0)
             hipLaunchKernelGGL(maxpool333_s2_w12_bwd_kernel, dim3((g.To * (g.Hi / 2) + 255) / 256, g.B * g.C), dim3(256), 0, st_, dy, argtap, dx, g, out_scale, signbits);
         else if (all_half) hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<3, true, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
         else if (io == 1) hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
@@ -1524,7 +1520,7 @@ static int pool_bwd(const int* geom, const int64_t* strides, const float* dy, co
         else hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<3, false>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
         return otal_launch_status();
     }
-    if (is_333_s1(g) && !OTAL_OPT("OTAL_POOL_NOLDS", 0)) {
+    if (is_333_s1(g)) {
         const int PP = g.Hi * g.Wi, ti = POOL_SEP_ELEMS / PP;
         const size_t l3 = (size_t)((ti + 2) * PP + 2 * ti * PP) * sizeof(float) + (size_t)(ti + 2) * PP;
         const dim3 grid((g.Ti + ti - 1) / ti, g.B * g.C);
@@ -1546,7 +1542,7 @@ static int pool_bwd(const int* geom, const int64_t* strides, const float* dy, co
             else hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<6, true>), rgrid, dim3(256), lds, st_, dy, argtap, dx, g, TIr, accumulate, out_mask, out_scale);
             return otal_launch_status();
         }
-        if (v2 && (g.Hi == 12 || g.Hi == 6) && !OTAL_OPT("OTAL_POOL_NOROWS", 0)) {      // one input row per thread
+        if (v2 && (g.Hi == 12 || g.Hi == 6) && !OTAL_OPT("OTAL_POOL_NOROWS")) {      // one input row per thread
             const int P = g.Hi, TIr = 256 / P - 2, TB = P == 12 ? 12 : 8;
             const dim3 rgrid((g.Ti + TIr - 1) / TIr, g.B * g.C);
             const size_t lds = (size_t)2 * (TIr + 2) * P * P * sizeof(float) + (size_t)(TIr + 2) * P * TB;
@@ -1564,7 +1560,7 @@ static int pool_bwd(const int* geom, const int64_t* strides, const float* dy, co
     if (io) return OTAL_E_UNSUPPORTED;
     size_t lds = 0;
     int tlo_max = 0;
-    const int ti = OTAL_OPT("OTAL_POOL_NOLDS", 0) ? 0 : bwd_planes(g, tlo_max, lds);
+    const int ti = bwd_planes(g, tlo_max, lds);
     if (ti > 0) {
         const dim3 grid((g.Ti + ti - 1) / ti, g.B * g.C);
         OTAL_POOL_DISPATCH(maxpool3d_bwd_lds_kernel, grid, lds, dy, argtap, dx, g, accumulate, out_mask, out_scale, ti, tlo_max);

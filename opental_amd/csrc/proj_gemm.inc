@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void proj_fwd_kernel(const ConvArgs a, int ci_
 }
 
 static inline bool proj_fwd_eligible(const ConvGeom& g, int mode, int prec, const void* x, const void* w) {
-    if (!prec || mode != MODE_FWD || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NOPROJ", 0)) return false;
+    if (!prec || mode != MODE_FWD || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NOPROJ")) return false;
     if (g.kt != 1 || g.st != 1 || g.kh != g.Hi || g.kw != g.Wi || g.Ho != 1 || g.Wo != 1 || g.To != g.Ti) return false;
     if (g.Hi * g.Wi != PJ_HW || g.ph != 0 || g.pw != 0 || g.pt != 0 || g.Cin % 4) return false;
     // (16-byte loads at 4-byte aligned addresses are legal on gfx950 -- tools/ubench/alignprobe.hip; a weight inside the
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256) void proj_wgrad_kernel(const ConvArgs a, int H
 }
 
 static inline bool proj_wgrad_eligible(const ConvGeom& g, int prec, const void* x, const void* dy) {
-    if (!prec || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NOPROJW", 0)) return false;
+    if (!prec || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NOPROJW")) return false;
     if (g.kt != 1 || g.st != 1 || g.kh != g.Hi || g.kw != g.Wi || g.Ho != 1 || g.Wo != 1 || g.To != g.Ti) return false;
     if (g.ph != 0 || g.pw != 0 || g.pt != 0 || g.Hi * g.Wi < 2) return false;          // (a 1 x 1 plane is a 1 x 1 x 1 layer: other kernels)
     if (g.To % PW_KS || g.y_cs < g.To || (g.y_cs & 3) || (g.y_bs & 3)) return false;    // whole K steps; 16-byte dc loads

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(512) void wgrad1x1_wide_kernel(const ConvArgs a) {
 }
 
 static inline bool wgrad1x1_wide_eligible(const ConvGeom& g, int prec, const void* x, const void* dy) {
-    if (!prec || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NOW1X1", 0)) return false;
+    if (!prec || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NOW1X1")) return false;
     if (g.kt != 1 || g.kh != 1 || g.kw != 1 || g.st != 1 || g.sh != 1 || g.sw != 1) return false;
     if (g.To != g.Ti || g.Ho != g.Hi || g.Wo != g.Wi) return false;
     if (g.Hi == 1 && g.Wi == 1) return false;               // the 1-D layers have their own weight-gradient kernel
@@ -138,18 +138,16 @@ template <bool H = false>
 int launch_wgrad1x1_wide(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     const ConvGeom& g = a.g;
     // row-block height: few row blocks first (each re-reads x), then little padding
-    const int cand[7] = {9, 7, 6, 5, 4, 3, 2};
-    int mt = 2, best = 1 << 30;
-    // Row blocks of at most 4 x 32 (OTAL_W1X1_MAXMT, 2 .. 9).  Alone, the tallest block that covers M is the fastest (Mixed_3c:
+    // Row blocks of at most 4 x 32.  Alone, the tallest block that covers M is the fastest (Mixed_3c:
     // <9> 35 us against ~45 for <4>) -- but these launches run on the weight-gradient lane BESIDE the data-gradient lane's
     // kernels, and a 512-thread workgroup at 234 VGPRs (<9>) needs an EMPTY compute unit: it only got one when the main
     // lane's kernel ran out of workgroups (35 us alone, 370 us beside Conv3d_2c's data gradient in the lane timeline), and the
     // backlog surfaced as the step's one-lane tail.  <4> (118 VGPRs, 61 KB of LDS) fits the slot one retiring workgroup of
     // the direct 3x3x3 kernel leaves (8 waves x 104-120 VGPRs, 70 KB).  Step, one box: cap 9 / 5 / 4 / 3 / 2 =
     // 928 / 935 / 939 / 926 / 931 clips/s.
-    const int mt_cap = OTAL_OPT("OTAL_W1X1_MAXMT", 4);
-    for (int i = 0; i < 7; ++i) {
-        if (cand[i] > mt_cap && cand[i] != 2) continue;
+    const int cand[3] = {4, 3, 2};
+    int mt = 2, best = 1 << 30;
+    for (int i = 0; i < 3; ++i) {
         const int rb = cand[i] * 32, blocks = (a.M + rb - 1) / rb;
         const int cost = blocks * 256 + blocks * rb;
         if (cost < best) { best = cost; mt = cand[i]; }
@@ -160,7 +158,7 @@ int launch_wgrad1x1_wide(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st)
     a.src_bytes = (unsigned)gather_extent_bytes(g, MODE_FWD, H ? 2 : 4);
     a.dy_bytes = (unsigned)gather_extent_bytes(g, MODE_DGRAD, H ? 2 : 4);
     // one round of workgroups, >= 8 K steps per split
-    const int wgs = (mt <= 2 ? 2 : 1) * OTAL_OPT("OTAL_W1X1_WGS", 256);              // the 64-row variant fits twice per CU: twice the loads in flight
+    const int wgs = (mt <= 2 ? 2 : 1) * 256;              // the 64-row variant fits twice per CU: twice the loads in flight
     int splits = tm * tn >= wgs ? 1 : wgs / (tm * tn);
     if (splits > a.K / (8 * 32)) splits = a.K / (8 * 32) > 0 ? a.K / (8 * 32) : 1;
     const size_t slab1 = (size_t)a.M * a.N * sizeof(float);
@@ -178,10 +176,6 @@ int launch_wgrad1x1_wide(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st)
     const dim3 grid(tn, tm, splits);
     int e;
     switch (mt) {
-        case 9: e = launch_w1x1<9, H>(a, grid, st); break;
-        case 7: e = launch_w1x1<7, H>(a, grid, st); break;
-        case 6: e = launch_w1x1<6, H>(a, grid, st); break;
-        case 5: e = launch_w1x1<5, H>(a, grid, st); break;
         case 4: e = launch_w1x1<4, H>(a, grid, st); break;
         case 3: e = launch_w1x1<3, H>(a, grid, st); break;
         default: e = launch_w1x1<2, H>(a, grid, st); break;

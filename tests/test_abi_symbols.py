@@ -53,6 +53,27 @@ def test_argument_errors_do_not_launch(lib):
     assert lib.otal_bmp_bwd(one, one, f, one, 1, 4, 8, 16, 1, 1, 0, None) == -2  # compat with N > T
 
 
+def test_set_option_accepts_only_the_listed_switches(lib):
+    lib.otal_get_option.restype = ctypes.c_int
+    assert lib.otal_get_option(b"OTAL_LOSS_NOSTAGE", 7) == int(os.environ.get("OTAL_LOSS_NOSTAGE", "0"))
+    assert lib.otal_set_option(b"OTAL_LOSS_NOSTAGE", 1) == 0
+    try:
+        assert lib.otal_get_option(b"OTAL_LOSS_NOSTAGE", 0) == 1
+    finally:
+        assert lib.otal_set_option(b"OTAL_LOSS_NOSTAGE", 0) == 0
+    assert lib.otal_get_option(b"OTAL_LOSS_NOSTAGE", 1) == 0
+    assert lib.otal_set_option(b"OTAL_CONV_DIRECT_MINTILES512", 256) == 0
+    try:
+        assert lib.otal_get_option(b"OTAL_CONV_DIRECT_MINTILES512", 0) == 256
+    finally:
+        assert lib.otal_set_option(b"OTAL_CONV_DIRECT_MINTILES512", 512) == 0
+    unsupported = -7        # OTAL_E_UNSUPPORTED
+    for name in (b"OTAL_CONV_DEBUG", b"OTAL_POOL_NOKEYS", b"OTAL_CONV_NOCHUK", b""):     # retired, retired, a typo, empty
+        assert lib.otal_set_option(name, 1) == unsupported, name
+        assert lib.otal_get_option(name, 5) == 5, name
+    assert lib.otal_set_option(None, 1) == -1
+
+
 def test_product_does_not_import_oracle():
     bad = []
     for root, _, files in os.walk(os.path.join(REPO, "opental_amd")):

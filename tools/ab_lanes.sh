@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of the lane-graph step on ONE box (boxes differ by a few per cent): each configuration = env assignments, "-" = none
-# usage: tools/ab_lanes.sh "-" "OTAL_CONV_DIRECT_NO32=1" "OTAL_CONV_DIRECT_NO32=1 OTAL_CONV_DIRECT_MINTILES=192"
+# usage: tools/ab_lanes.sh "-" "OTAL_CONV_DIRECT_XPF2=0" "OTAL_CONV_DIRECT_XPF2=0 OTAL_CONV_DIRECT_MINTILES=192"
 for cfg in "$@"; do
   [ "$cfg" = "-" ] && cfg=""
   for rep in 1 2; do

@@ -1,5 +1,5 @@
 """The 3x3x3 weight gradient on 3x3 planes (Mixed_5b / 5c b1b, b2b at b = 8): conv3_wgrad_planes3_kernel against the
-generic gather kernel (OTAL_CONV_NOWDIRECT3=1 in a second process) and an fp64 reference on the bf16-rounded operands.
+generic gather kernel (OTAL_CONV_NOWDIRECT=1 in a second process) and an fp64 reference on the bf16-rounded operands.
 usage: python tools/micro_planes3.py [half]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
