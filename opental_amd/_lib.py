@@ -48,7 +48,7 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-STREAM_OVERRIDE = None      # a raw stream handle: launches go there instead of torch's current stream (ops.SideWgrads)
+STREAM_OVERRIDE = None      # a raw stream handle: launches go there instead of torch's current stream (ops.issue_on)
 
 
 def stream():

@@ -463,7 +463,8 @@ class I3DFeaturesFunction(Function):
                         found[name] = (ops.convert_storage(cur, torch.float32), len(tape))
                 else:
                     found[name] = (cur, len(tape))
-                hook = ops.ENDPOINT_HOOKS.get(name) if ops.ENDPOINT_HOOKS else None
+                hooks = ops.STEP.endpoint_hooks
+                hook = hooks.get(name) if hooks else None
                 if hook is not None:                        # a consumer that can start on this endpoint now (ops.early_lane)
                     hook(found[name][0])
         missing = [e for e in endpoints if e not in found]
@@ -550,9 +551,10 @@ class I3DFeaturesFunction(Function):
                 _, wi, k, s, xin, y, in_scale, _ = step
                 slot = ops.grad_slot(weights[wi])
                 in_slots = in_slots and slot is not None
-                if first and not need_dx and ops.LAST_WGRAD_MAIN:
+                if first and not need_dx:
                     # the walk's LAST weight gradient (Conv3d_1a: its input needs no gradient, nothing follows on this lane) runs
-                    # HERE, beside what the weight-gradient lane still holds (the Mixed_3 backlog, Conv3d_2c, 2b) -- ops.LAST_WGRAD_MAIN
+                    # HERE, beside what the weight-gradient lane still holds (the Mixed_3 backlog, Conv3d_2c, 2b): 8.07 -> 7.99 ms
+                    # per step when measured; moving Conv3d_2b's or 2c's here as well gained nothing more
                     side.issue()
                     dws[wi] = ops.conv_wgrad(xin, dcur, weights[wi].shape, k, s, out=slot)
                 else:

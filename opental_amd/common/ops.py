@@ -69,33 +69,114 @@ def workspace(device, side=False):
     return ws
 
 
-# ---- deferred weight-gradient reductions (include/opental_hip.h: otal_conv_defer_reduces).  While a trainer's backward
-# runs, the split-K reduce of a weight gradient is recorded instead of launched; its slabs stay in the workspace and every
-# later launch on that stream works BEHIND them (_WS_CURSOR); flush_reduces() runs all recorded reductions as one launch --
-# called when the backbone announces a module's gradients (grads_ready), at the trainer's bucket flushes, and when the
-# slabs fill up.  The library keeps ONE list of recorded reductions, so all of them sit on one stream at a time
-# (_DEFER_OWNER: (side workspace?, torch stream or None = the current one)); a weight gradient issued on the other stream
-# flushes them first.
-_DEFER = False
-_WS_CURSOR = [0, 0, 0, 0]   # main / weight-gradient side / branch lane / early lane workspace
-_WS_SIDE = 0                # 1 while SideWgrads issues a launch on its stream, 2 inside a BranchLane block
-_SIDE_NOW = None            # ... and that torch stream
-_DEFER_OWNER = None
+# ---- the launch path's per-step state: ONE instance per process (STEP).  A trainer opens a backward session
+# (begin_backward), closes it after its last join (end_backward), and every way out of a step -- normal, exception, failed
+# capture -- ends in reset().  Only one trainer may run a backward in a process at a time: begin_backward checks it.
+class StepState:
+    def __init__(self):
+        self.lanes = None               # the LanePlan being captured (DetectorTrainer.capture_step(lanes=True)), or None
+        self.slots = None               # the running trainer's GradSlots: weight gradients go straight into its arena
+        self.ready = None               # ... and its callback for weight gradients that are final before their node returns
+        self.defer_join = False         # weight gradients in arena slots are joined by the trainer, not per node (SideWgrads)
+        self.pending_sums = None        # deferred GroupNorm batch sums (gn_relu_backward), or None: summed at once
+        self.prologues = None           # the active PrologueCache, or None (every launch builds its own prologue)
+        self.late_weights = None        # the stem tail's weights once the late mark is down (late_mark)
+        self.endpoint_hooks = None      # {backbone endpoint: hook} while a forward pass runs (the early lane), or None
+        self.early_results = {}         # Mixed_4f address -> its projection, run on the early lane (TrunkFunction.forward)
+        self.pending_joins = {}         # gradient address -> the lane that still writes it (join_pending)
+        # deferred weight-gradient reductions (include/opental_hip.h: otal_conv_defer_reduces).  While a trainer's backward
+        # runs, the split-K reduce of a weight gradient is recorded instead of launched; its slabs stay in the workspace and
+        # every later launch on that stream works BEHIND them (ws_cursor); flush_reduces() runs all recorded reductions as
+        # one launch -- called when the backbone announces a module's gradients (grads_ready), at the trainer's bucket
+        # flushes, and when the slabs fill up.  The library keeps ONE list of recorded reductions, so all of them sit on
+        # one stream at a time (defer_owner: (workspace index, torch stream or None = the current one)); a weight gradient
+        # issued on another stream flushes them first.
+        self.defer = False
+        self.defer_owner = None
+        self.ws_cursor = [0, 0, 0, 0]   # main / weight-gradient side / branch lane / early lane workspace
+        # the lane now being issued on (issue_on): its workspace index and torch stream (None: torch's current stream)
+        self.ws_index = 0
+        self.stream = None
+
+    def begin_backward(self, slots, ready, early):
+        """Open a trainer's backward session.  early=False (a step that runs the backbone twice): weight gradients are
+        joined per node and GroupNorm's batch sums are not deferred -- a parameter may receive a second gradient, which
+        would be accumulated into its arena slice before the deferred sum is written there."""
+        if self.slots is not None:
+            raise RuntimeError("a trainer's backward is already running in this process (one at a time)")
+        self.slots, self.ready = slots, ready
+        self.defer_join = early
+        self.pending_sums = [] if early else None
+        defer_reduces(early and CONV_PROFILE is None)     # split-K reduces batched (per-op timing: at once)
+
+    def end_backward(self):
+        """Close the session normally, after the trainer has joined the weight-gradient lane: what is still recorded
+        runs, the deferred batch sums land in the arena, and the trainer's slots are handed back."""
+        self.defer_join = False
+        defer_reduces(False)
+        flush_pending_sums()
+        self.pending_sums = self.slots = self.ready = None
+
+    def reset(self, failed_capture=False):
+        """The one teardown of a step, idempotent; after a normal end_backward it issues no launch.  failed_capture: the
+        cleanup of an aborted capture, which ignores the library's error when switching deferral off."""
+        self.prologues = None
+        self.slots = self.ready = self.pending_sums = None
+        self.defer_join = False
+        self.late_weights = None
+        self.lanes = None
+        for sd in _SIDES.values():      # launches an aborted step recorded for the weight-gradient lane: never issued
+            sd.pending.clear()
+            sd.keep.clear()
+        self.early_results.clear()
+        self.pending_joins.clear()
+        try:                            # last: a library error leaves nothing above undone
+            defer_reduces(False)
+        except RuntimeError:
+            if not failed_capture:
+                raise
+
+
+STEP = StepState()
+
+
+class issue_on:
+    """with issue_on(ws_index, stream): this library's launches go to `stream` (a torch stream), with the split-K
+    workspace `ws_index`; current=True also makes it torch's current stream.  The lane issued on before is restored."""
+    __slots__ = ("ws", "stream", "ctx", "saved")
+
+    def __init__(self, ws_index, stream, current=False):
+        self.ws, self.stream = ws_index, stream
+        self.ctx = torch.cuda.stream(stream) if current else None
+
+    def __enter__(self):
+        s = STEP
+        self.saved = (s.ws_index, s.stream, L.STREAM_OVERRIDE)
+        s.ws_index, s.stream, L.STREAM_OVERRIDE = self.ws, self.stream, self.stream.cuda_stream
+        if self.ctx is not None:
+            self.ctx.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        if self.ctx is not None:
+            self.ctx.__exit__(*exc)
+        STEP.ws_index, STEP.stream, L.STREAM_OVERRIDE = self.saved
+        return False
 
 
 def _ws_args(device):
     """(pointer, size) of the workspace a launch may use now."""
-    ws = workspace(device, _WS_SIDE)
-    cur = _WS_CURSOR[_WS_SIDE]
+    s = STEP
+    ws = workspace(device, s.ws_index)
+    cur = s.ws_cursor[s.ws_index]
     return ctypes.c_void_p(ws.data_ptr() + cur), ctypes.c_size_t(min(ws.numel() - cur, WORKSPACE_BYTES))
 
 
 def defer_reduces(on):
-    global _DEFER
     if not on:
         flush_reduces()
     L.check(L.lib().otal_conv_defer_reduces(int(bool(on))), "otal_conv_defer_reduces")
-    _DEFER = bool(on)
+    STEP.defer = bool(on)
 
 
 def _stream_wait(stream):
@@ -106,9 +187,9 @@ def _stream_wait(stream):
 def flush_reduces(wait=True):
     """Run the recorded reductions on the stream their slabs were written on; when that is not the stream the caller
     launches on, the caller's stream waits for them (unless wait=False: the caller joins the side stream later)."""
-    global _DEFER_OWNER
-    own = _DEFER_OWNER
-    if _DEFER and own is not None:
+    s = STEP
+    own = s.defer_owner
+    if s.defer and own is not None:
         stream = own[1]
         if stream is None:
             L.check(L.lib().otal_conv_flush_reduces(L.stream()), "otal_conv_flush_reduces")
@@ -116,20 +197,21 @@ def flush_reduces(wait=True):
             L.check(L.lib().otal_conv_flush_reduces(ctypes.c_void_p(stream.cuda_stream)), "otal_conv_flush_reduces")
             if wait and L.STREAM_OVERRIDE != stream.cuda_stream:
                 _stream_wait(stream)
-    _DEFER_OWNER = None
-    _WS_CURSOR[0] = _WS_CURSOR[1] = 0           # (the branch lane never holds recorded reductions: its cursor stays 0)
+    s.defer_owner = None
+    s.ws_cursor[0] = s.ws_cursor[1] = 0         # (the branch lane never holds recorded reductions: its cursor stays 0)
 
 
 def _after_wgrad(device):
     """Advance the workspace cursor past the slabs a deferred reduction still needs; flush when they pile up."""
-    global _DEFER_OWNER
+    s = STEP
     lib = L.lib()
     lib.otal_conv_deferred_end.restype = ctypes.c_size_t
     end = int(lib.otal_conv_deferred_end())
     if end:
-        _DEFER_OWNER = (_WS_SIDE, _SIDE_NOW)
-        _WS_CURSOR[_WS_SIDE] = (end - workspace(device, _WS_SIDE).data_ptr() + 255) & ~255
-        if _WS_CURSOR[_WS_SIDE] > WORKSPACE_TOTAL - WORKSPACE_BYTES:
+        i = s.ws_index
+        s.defer_owner = (i, s.stream)
+        s.ws_cursor[i] = (end - workspace(device, i).data_ptr() + 255) & ~255
+        if s.ws_cursor[i] > WORKSPACE_TOTAL - WORKSPACE_BYTES:
             flush_reduces()
 
 
@@ -140,10 +222,6 @@ def _after_wgrad(device):
 # two families run on two streams and share the chip.  Results are bit-identical: same kernels, same order within each
 # family.
 WGRAD_STREAM = os.environ.get("OTAL_WGRAD_STREAM", "1") != "0"
-# True while a trainer's single-use backward runs (DetectorTrainer.begin_backward(early=True)): weight gradients written
-# into their arena slots are joined by the trainer (bucket flushes of a data-parallel run, end_backward), not at the end
-# of each autograd node.
-SIDE_DEFER_JOIN = False
 _SIDES = {}
 
 
@@ -222,9 +300,6 @@ class LanePlan:
                 e[1]()
 
 
-LANES = None        # the LanePlan being captured (DetectorTrainer.capture_step(lanes=True)), or None
-
-
 class SideWgrads:
     """wgrad(...) RECORDS conv_wgrad(...) and returns its destination; issue() launches what has been recorded on the side
     stream, behind everything the main stream has been given so far (one fork per chunk of layers: a fork is two HIP calls,
@@ -245,7 +320,7 @@ class SideWgrads:
     def on(self):
         # not inside a graph capture: a replayed hipGraph runs its branches one after the other (measured at b = 1, 2, 8:
         # 0.06-0.2 ms per step SLOWER with the fork than without), so only eager launches gain from the second stream
-        return WGRAD_STREAM and CONV_PROFILE is None and (LANES is not None or not torch.cuda.is_current_stream_capturing())
+        return WGRAD_STREAM and CONV_PROFILE is None and (STEP.lanes is not None or not torch.cuda.is_current_stream_capturing())
 
     def wgrad(self, x, dy, w_shape, k, s, spatial_valid=False, levels=None, out=None):
         if not self.on:
@@ -279,25 +354,22 @@ class SideWgrads:
     def issue(self):
         if not self.pending:
             return
-        if _DEFER_OWNER is not None and not _DEFER_OWNER[0]:
+        if STEP.defer_owner is not None and not STEP.defer_owner[0]:
             flush_reduces()                 # reductions recorded on the main stream: run them there first
-        raw = self._raw
 
         def run():
-            global _WS_SIDE, _SIDE_NOW
-            _WS_SIDE, _SIDE_NOW, L.STREAM_OVERRIDE = 1, self.side, raw.value
             try:
-                for fn in self.pending:
-                    fn()
-                if _DEFER and _DEFER_OWNER is not None:
-                    flush_reduces(wait=False)   # this chunk's reductions: one launch, on the side stream
+                with issue_on(1, self.side):
+                    for fn in self.pending:
+                        fn()
+                    if STEP.defer and STEP.defer_owner is not None:
+                        flush_reduces(wait=False)   # this chunk's reductions: one launch, on the side stream
             finally:
-                _WS_SIDE, _SIDE_NOW, L.STREAM_OVERRIDE = 0, None, None
                 self.pending.clear()
-        if LANES is not None:               # capture: the chunk becomes a graph of its own (LanePlan)
-            LANES.side_chunk(run)
+        if STEP.lanes is not None:          # capture: the chunk becomes a graph of its own (LanePlan)
+            STEP.lanes.side_chunk(run)
             return
-        L.check(L.lib().otal_stream_wait(raw, L.stream()), "otal_stream_wait")      # torch's current stream: the dy producers are on it
+        L.check(L.lib().otal_stream_wait(self._raw, L.stream()), "otal_stream_wait")    # torch's current stream: the dy producers are on it
         run()
 
     def flush(self):
@@ -308,17 +380,17 @@ class SideWgrads:
     def join(self):
         if self.keep:
             self.issue()
-            if LANES is not None:
-                LANES.cut(("join",))
-                LANES.keep.extend(self.keep)
+            if STEP.lanes is not None:
+                STEP.lanes.cut(("join",))
+                STEP.lanes.keep.extend(self.keep)
             else:
                 _stream_wait(self.side)
             self.keep.clear()
 
     def node_end(self, in_slots):
         """End of an autograd node: its weight gradients are handed to autograd, which may add them to earlier ones on the
-        main stream -- unless they sit in the trainer's arena slots and the trainer joins (SIDE_DEFER_JOIN)."""
-        if not (SIDE_DEFER_JOIN and in_slots):
+        main stream -- unless they sit in the trainer's arena slots and the trainer joins (STEP.defer_join)."""
+        if not (STEP.defer_join and in_slots):
             self.join()
         else:
             self.flush()
@@ -328,9 +400,9 @@ class SideWgrads:
 # one: common/i3d_backbone.py).  with lane: ... issues this library's launches on the lane's stream, with the lane's own
 # workspace; fork() / join() are one event each.
 BRANCH_LANE = os.environ.get("OTAL_BRANCH_LANE", "1") != "0"
-# the pyramid as two hand-scheduled autograd nodes (thumos14/pyramid_fused.py) instead of one node per block
+# the pyramid as two hand-scheduled autograd nodes (thumos14/pyramid_fused.py) instead of one node per block, with their
+# independent chains on the branch lane
 FUSED_PYRAMID = os.environ.get("OTAL_FUSED_PYRAMID", "1") != "0"
-PYRAMID_LANE = os.environ.get("OTAL_PYRAMID_LANE", "1") != "0"        # ... with their independent chains on the branch lane
 _BRANCHES = {}
 
 
@@ -338,8 +410,8 @@ class BranchLane:
     def __init__(self, device, ws_index=2):
         self.stream = torch.cuda.Stream(device=device)
         self._raw = ctypes.c_void_p(self.stream.cuda_stream)
-        self._saved = None
         self._ws = ws_index         # the lane's own split-K workspace (launches of two lanes run side by side)
+        self._on = None
 
     @property
     def on(self):
@@ -353,22 +425,16 @@ class BranchLane:
         L.check(L.lib().otal_stream_wait(L.stream(), self._raw), "otal_stream_wait")
 
     def __enter__(self):
-        global _WS_SIDE
-        self._saved = (_WS_SIDE, L.STREAM_OVERRIDE)
-        _WS_SIDE, L.STREAM_OVERRIDE = self._ws, self._raw.value
         # the lane is also torch's current stream inside the block: tensors allocated here come from the LANE's pool of the
         # caching allocator.  With the main stream current, a block the main lane had just freed (its last reader still
         # queued there) could be handed to a lane tensor and overwritten by a lane kernel first -- two lanes, one pool
-        self._ctx = torch.cuda.stream(self.stream)
-        self._ctx.__enter__()
+        self._on = issue_on(self._ws, self.stream, current=True)
+        self._on.__enter__()
         return self
 
     def __exit__(self, *exc):
-        global _WS_SIDE
-        self._ctx.__exit__(*exc)
-        self._ctx = None
-        _WS_SIDE, L.STREAM_OVERRIDE = self._saved
-        return False
+        on, self._on = self._on, None
+        return on.__exit__(*exc)
 
 
 def branch_lane(device):
@@ -381,15 +447,11 @@ def branch_lane(device):
 
 # ---- the early lane: the Mixed_4f projection of the pyramid (Unit3D [1,6,6], AFSD/thumos14/BDNet.py:129-139,:310-313) needs
 # only Mixed_4f, which the backbone finishes ~280 us before Mixed_5c -- five small-plane launches that leave most of the chip
-# idle.  The backbone calls ENDPOINT_HOOKS[name](tensor) where an endpoint is final; the pyramid's hook runs the projection
-# on this lane (its own stream and split-K workspace: the branch lane forks and joins inside Mixed_5b / 5c meanwhile) and
-# parks the result in EARLY_RESULTS for TrunkFunction.forward (thumos14/pyramid_fused.py), which joins the lane.  Backward,
-# mirrored: the projection's data gradient (the gradient of Mixed_4f) runs on the lane while the main lane already walks
-# Mixed_5c / 5b; the backbone joins (join_pending) where it picks that gradient up.
-EARLY_PROJ = os.environ.get("OTAL_EARLY_PROJ", "1") != "0"
-ENDPOINT_HOOKS = None
-EARLY_RESULTS = {}
-PENDING_JOINS = {}
+# idle.  The backbone calls STEP.endpoint_hooks[name](tensor) where an endpoint is final; the pyramid's hook runs the
+# projection on this lane (its own stream and split-K workspace: the branch lane forks and joins inside Mixed_5b / 5c
+# meanwhile) and parks the result in STEP.early_results for TrunkFunction.forward (thumos14/pyramid_fused.py), which joins
+# the lane.  Backward, mirrored: the projection's data gradient (the gradient of Mixed_4f) runs on the lane while the main
+# lane already walks Mixed_5c / 5b; the backbone joins (join_pending) where it picks that gradient up.
 _EARLY = {}
 
 
@@ -403,7 +465,8 @@ def early_lane(device):
 
 def join_pending(t):
     """The main lane waits for the lane that still writes `t` (a gradient handed over without a join)."""
-    lane = PENDING_JOINS.pop(t.data_ptr(), None) if PENDING_JOINS else None
+    joins = STEP.pending_joins
+    lane = joins.pop(t.data_ptr(), None) if joins else None
     if lane is not None:
         lane.join()
 
@@ -435,30 +498,19 @@ def side_wgrads(device):
 # side lane) are the step's tail: the main lane has nothing left but Adam, which needs every gradient -- except that an
 # elementwise optimizer can update all OTHER parameters as soon as THEIR gradients are final.  The backbone's backward
 # calls late_mark() where only its stem tail is left; in a lane-graph capture that closes the side lane's chunk and records a
-# ("mark",) entry, and the trainer (DetectorTrainer.end_backward) runs Adam over everything but LATE_WEIGHTS behind the mark,
-# beside the tail's weight gradients, and Adam over the tail's few parameters after the final join.
-EARLY_ADAM = os.environ.get("OTAL_EARLY_ADAM", "1") != "0"
-# The backbone's last weight gradient (Conv3d_1a, 0.44 ms) on the MAIN lane, which has nothing left when it reaches it, while
-# the weight-gradient lane works off what it still holds (~0.5 ms: the end of Mixed_3, Conv3d_2c, 2b).  Measured +-0 in the
-# first session of round 6 (8.217 vs 8.228 ms: the kernel then kept three workgroups per CU resident and the two lanes'
-# kernels took turns); with the second session's kernel (two per CU, 220 registers) 8.07 -> 7.99 ms, 8.25 -> 8.13 on a slower box.
-# Also moving Conv3d_2b's or 2c's behind it: no further gain (8.02-8.07).
-LAST_WGRAD_MAIN = os.environ.get("OTAL_LAST_WGRAD_MAIN", "1") != "0"
-LATE_WEIGHTS = None
-
-
+# ("mark",) entry, and the trainer (DetectorTrainer.end_backward) runs Adam over everything but STEP.late_weights behind the
+# mark, beside the tail's weight gradients, and Adam over the tail's few parameters after the final join.
 def late_mark(weights):
-    global LATE_WEIGHTS
-    if LANES is None or not EARLY_ADAM or LATE_WEIGHTS is not None:
+    s = STEP
+    if s.lanes is None or s.late_weights is not None:
         return
     side_issue()
-    LANES.cut(("mark",))
-    LATE_WEIGHTS = list(weights)
+    s.lanes.cut(("mark",))
+    s.late_weights = list(weights)
 
 
 def take_late_weights():
-    global LATE_WEIGHTS
-    w, LATE_WEIGHTS = LATE_WEIGHTS, None
+    w, STEP.late_weights = STEP.late_weights, None
     return w
 
 
@@ -607,24 +659,19 @@ class PrologueCache:
                                                  int(self.total_blocks), L.stream()), "otal_conv_prologue_batch")
 
 
-PROLOGUES = None        # the active PrologueCache, or None (every launch builds its own prologue)
-
-
 def activate_prologues(cache):
-    global PROLOGUES
-    PROLOGUES = cache
+    STEP.prologues = cache
     if cache is not None:
         cache.refresh()
 
 
 def deactivate_prologues():
-    global PROLOGUES
-    PROLOGUES = None
+    STEP.prologues = None
 
 
 def _prologue(mode, ga, sa, pkey, w, prec):
     """pkey: the launch's static identity (mode, geometry, strides) from its plan."""
-    c = PROLOGUES
+    c = STEP.prologues
     if c is None or not (prec & 1):
         return None
     wp = 0
@@ -884,22 +931,19 @@ class GradSlots:
             j += 1
 
 
-GRAD_SLOTS = None       # the running trainer's GradSlots (DetectorTrainer.begin_backward / end_backward)
-GRAD_READY = None       # the running trainer's callback for weight gradients that are final before their node returns
-
-
 def grads_ready(pairs):
     """A multi-layer autograd node (the I3D backbone) announces (weight, gradient) pairs as soon as they are final, so a
     data-parallel trainer can hand the finished arena range to RCCL while the node's remaining layers still run."""
     flush_reduces()                 # the announced gradients are final: their recorded reductions run now, as one launch
-    cb = GRAD_READY
+    cb = STEP.ready
     if cb is not None:
         cb(pairs)
 
 
 def grad_slot(w):
     """Destination of `w`'s gradient in the running trainer's arena, or None (no trainer, foreign weight, slot taken)."""
-    return GRAD_SLOTS.take(w) if GRAD_SLOTS is not None and "OTAL_NO_GRAD_SLOTS" not in os.environ else None
+    slots = STEP.slots
+    return slots.take(w) if slots is not None and "OTAL_NO_GRAD_SLOTS" not in os.environ else None
 
 
 def conv_wgrad(x, dy, w_shape, k, s, spatial_valid=False, levels=None, out=None, accumulate=False):
@@ -919,7 +963,8 @@ def conv_wgrad(x, dy, w_shape, k, s, spatial_valid=False, levels=None, out=None,
         out = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
     if not out.is_contiguous():
         raise RuntimeError("dw must be contiguous")
-    if _DEFER and (accumulate or (_DEFER_OWNER is not None and _DEFER_OWNER[0] != _WS_SIDE)):
+    st = STEP
+    if st.defer and (accumulate or (st.defer_owner is not None and st.defer_owner[0] != st.ws_index)):
         flush_reduces()             # a recorded reduction may still be on its way to this very buffer / sits on the other stream
     wsp, wsn = _ws_args(x.device)
     ev = _prof_begin()
@@ -928,7 +973,7 @@ def conv_wgrad(x, dy, w_shape, k, s, spatial_valid=False, levels=None, out=None,
     L.check(L.lib().otal_conv_wgrad(ga, sa, L.ptr(x), L.ptr(dy), L.ptr(out),
                                     int(accumulate), prec | (4 if half_dy else 0) | (8 if half_x else 0), pre, wsp, wsn, L.stream()),
             "otal_conv_wgrad")
-    if _DEFER:
+    if st.defer:
         _after_wgrad(x.device)
     _prof_end(ev, "wgrad", g)
     return out
@@ -1016,7 +1061,8 @@ def conv_wgrad_pair(xs, dys, w_shape, k, s, levels=None, outs=(None, None)):
     outs = [o if o is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=xs[0].device) for o in outs]
     if not (outs[0].is_contiguous() and outs[1].is_contiguous()):
         return None
-    if _DEFER and _DEFER_OWNER is not None and _DEFER_OWNER[0] != _WS_SIDE:
+    st = STEP
+    if st.defer and st.defer_owner is not None and st.defer_owner[0] != st.ws_index:
         flush_reduces()
     wsp, wsn = _ws_args(xs[0].device)
     ev = _prof_begin()
@@ -1024,7 +1070,7 @@ def conv_wgrad_pair(xs, dys, w_shape, k, s, levels=None, outs=(None, None)):
     if rc == L.E_UNSUPPORTED:
         return None
     L.check(rc, "otal_conv_wgrad_pair")
-    if _DEFER:
+    if st.defer:
         _after_wgrad(xs[0].device)
     _prof_end(ev, "wgrad", g, 2)
     return outs
@@ -1121,12 +1167,9 @@ def pyramid_merge_backward(da, db, dframe, dnext, t0, up):
     return dp0, dp1
 
 
-PENDING_SUMS = None     # the running trainer's list of deferred batch sums (DetectorTrainer.begin_backward), or None
-
-
 def gn_relu_backward(dy, x, gamma, beta, stats, groups=32, relu=True, levels=None, bias=None):
     """(dx, d_gamma, d_beta, d_conv_bias).  dy may be a channel slice of a wider (B, Ctot, T) map (read in place).
-    With a running trainer (PENDING_SUMS) whose gradient arena has free slots for gamma, beta and `bias` (the preceding
+    With a running trainer (STEP.pending_sums) whose gradient arena has free slots for gamma, beta and `bias` (the preceding
     convolution's bias parameter), the three batch sums are DEFERRED: the returned gradients are the arena slices and
     flush_pending_sums() fills them -- one launch for all layers pending at the next bucket flush."""
     B, C, T = x.shape
@@ -1147,17 +1190,18 @@ def gn_relu_backward(dy, x, gamma, beta, stats, groups=32, relu=True, levels=Non
 def _gn_sums(partial, gamma, beta, bias, C, B):
     """(d_gamma, d_beta, d_conv_bias) from the backward kernel's per-sample partials: deferred into the gradient arena when
     a trainer is running (see gn_relu_backward), else summed now."""
-    if PENDING_SUMS is not None and bias is not None and GRAD_SLOTS is not None:
-        slots = [GRAD_SLOTS.take(t) for t in (gamma, beta, bias)]
+    s = STEP
+    if s.pending_sums is not None and bias is not None and s.slots is not None:
+        slots = [s.slots.take(t) for t in (gamma, beta, bias)]
         if all(sl is not None for sl in slots):
             # only ADDRESSES are kept: a second reference to a slot tensor would make autograd clone it instead of
             # adopting it as .grad (AccumulateGrad steals a gradient only while it holds the sole reference), and the
             # clone -- taken before the deferred sum has run -- would later be copied over the sum
-            PENDING_SUMS.append((partial, tuple(sl.data_ptr() for sl in slots), C, B))
+            s.pending_sums.append((partial, tuple(sl.data_ptr() for sl in slots), C, B))
             return slots[0], slots[1], slots[2]
         for t, sl in zip((gamma, beta, bias), slots):       # hand back what was taken: the plain path returns fresh tensors
             if sl is not None:
-                GRAD_SLOTS.release(t)
+                s.slots.release(t)
     red = partial.sum(0)            # (3,C): d_gamma, d_beta, d_conv_bias -- three contiguous rows, no copies
     return red[0], red[1], red[2]
 
@@ -1189,7 +1233,7 @@ def gn_relu_backward_pair(dys, xs, gammas, betas, stats, groups=32, relu=True, l
 
 def flush_pending_sums():
     """Run the deferred batch sums of gn_relu_backward: one launch for every layer pending (otal_sum_partials)."""
-    items = PENDING_SUMS
+    items = STEP.pending_sums
     if not items:
         return
     n = len(items)
@@ -1554,16 +1598,16 @@ class HeadOutputsFunction(torch.autograd.Function):
             key = tuple(sl.data_ptr() for sl in slots)
             idx = _SLOT_INDEX.get(key)
             if idx is None:
-                flat = GRAD_SLOTS.grad
+                flat = STEP.slots.grad
                 idx = torch.tensor([(sl.data_ptr() - flat.data_ptr()) // 4 for sl in slots], dtype=torch.int64).to(flat.device)
                 if len(_SLOT_INDEX) > 64:
                     _SLOT_INDEX.clear()
                 _SLOT_INDEX[key] = idx
-            GRAD_SLOTS.grad.index_copy_(0, idx, dscales)
+            STEP.slots.grad.index_copy_(0, idx, dscales)
             return (None, None, None) + tuple(slots) + tuple(draws)
         for p, sl in zip(ctx.scale_params, slots):
             if sl is not None:
-                GRAD_SLOTS.release(p)
+                STEP.slots.release(p)
         aligned = torch.zeros((nlev, 4), dtype=dscales.dtype, device=dscales.device)
         aligned[:, 0] = dscales
         return (None, None, None) + tuple(aligned[l, :1] for l in range(nlev)) + tuple(draws)
@@ -1635,7 +1679,7 @@ class HeadConvsFunction(torch.autograd.Function):
         VP = lambda ts: (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
         in_slots = all(s_ is not None for s_ in slots_w) and all(s_ is not None for s_, b in zip(slots_b, ctx.bias_params) if b is not None)
         side = side_wgrads(xs[0].device)
-        if side.on and in_slots and SIDE_DEFER_JOIN:
+        if side.on and in_slots and STEP.defer_join:
             # the data gradients on the chain that waits for them, the weight / bias gradients on the weight-gradient lane (they
             # land in arena slots nobody reads before the trainer's join): 29 + 39 us off the serial middle of the step
             L.check(L.lib().otal_head_convs_bwd_parts(*meta, VP(xs), VP(ws), VP(dys), VP(dxs), VP(dws), VP(dbs), B, C, N, nlev, lev, 1,

@@ -25,6 +25,7 @@ from torch.autograd import Function
 
 from .. import _lib as L
 from ..common import ops
+from ..common.i3d_backbone import I3DFeaturesFunction
 from ..prop_pooling import boundary_pooling_op as bp
 
 ONE = (1, 1, 1)
@@ -143,7 +144,7 @@ class TrunkFunction(Function):
         t0, total = lev[1], lev[-1]
         tape = {}
         # projections (BDNet.py:310-319); the Mixed_4f one may already be running on the early lane (ops.early_lane)
-        early = ops.EARLY_RESULTS.pop(x1.data_ptr(), None)
+        early = ops.STEP.early_results.pop(x1.data_ptr(), None)
         if early is None:
             c0 = ops.conv_forward(x1, pyr[0][0], cfg["k0"], ONE, shift=pyr[0][1], spatial_valid=True).view(B, C, t0)
             p0, st0 = ops.gn_relu_forward(c0, pyr[0][2], pyr[0][3], G, eps, True, None)
@@ -156,7 +157,7 @@ class TrunkFunction(Function):
         tape["proj"] = (c0, st0, c1, st1)
         # the frame-level deconv (BDNet.py:324-326) on the branch lane, beside the stride-2 levels and the towers
         lane = ops.branch_lane(x1.device)
-        use_lane = lane.on and ops.PYRAMID_LANE
+        use_lane = lane.on
         dtape = []
 
         def deconv():
@@ -187,6 +188,9 @@ class TrunkFunction(Function):
             frame = deconv()
         loc_feat, conf_feat = s2[0][1], s2[1][1]
         ctx.cfg = cfg
+        # backward may hand the gradient of Mixed_4f over while the early lane still writes it only when x1 comes straight
+        # from the backbone's node, which joins that lane where it picks the gradient up (ops.join_pending)
+        ctx.backbone_joins = getattr(x1.grad_fn, "_forward_cls", None) is I3DFeaturesFunction
         ctx.tape = (tape["proj"], packed, frame_in, dtape, ptape,
                     ((s1[0][0], s1[0][2]), (s1[1][0], s1[1][2]), (s2[0][0], s2[0][2]), (s2[1][0], s2[1][2])),
                     (s1[0][1], s1[1][1]))
@@ -211,7 +215,7 @@ class TrunkFunction(Function):
         def put(i, dw):
             grads[4 * i] = dw
         lane = ops.branch_lane(dev)
-        use_lane = lane.on and ops.PYRAMID_LANE and d_frame is not None
+        use_lane = lane.on and d_frame is not None
         d_loc, d_conf = d_loc.contiguous(), d_conf.contiguous()
         if d_frame is not None:
             d_frame = d_frame.contiguous()
@@ -283,7 +287,7 @@ class TrunkFunction(Function):
             if ctx.needs_input_grad[1 + i]:
                 dgrad = lambda: (ops.conv_dgrad_collapse(dc5, pyr[i][0], x.shape) if ops.is_full_collapse(x.shape, k, ONE, True)
                                  else ops.conv_dgrad(dc5, pyr[i][0], x.shape, k, ONE, spatial_valid=True))
-                if i == 0 and ops.EARLY_PROJ and elane.on and ops.PYRAMID_LANE and ctx.needs_input_grad[2] and ops.LANES is None:
+                if i == 0 and ctx.backbone_joins and elane.on and ctx.needs_input_grad[2] and ops.STEP.lanes is None:
                     # the gradient of Mixed_4f is needed only after Mixed_5c / 5b / MaxPool3d_5a have been walked back:
                     # its GEMM runs on the early lane beside them, the backbone joins where it picks the gradient up.
                     # (Eager launches only: a lane-graph capture is CUT where the weight-gradient lane takes a chunk, and a
@@ -291,7 +295,7 @@ class TrunkFunction(Function):
                     elane.fork()
                     with elane:
                         dxs[0] = dgrad()
-                    ops.PENDING_JOINS[dxs[0].data_ptr()] = elane
+                    ops.STEP.pending_joins[dxs[0].data_ptr()] = elane
                     ctx.early_keep = (dc5, dxs[0])
                 else:
                     dxs[i] = dgrad()
@@ -320,7 +324,7 @@ class BranchesFunction(Function):
         dev = loc_feat.device
         cat = [torch.empty((B, 4 * Cp, T), dtype=torch.float32, device=dev) for _ in range(2)]      # [roi | pooled | short]
         lane = ops.branch_lane(dev)
-        use_lane = lane.on and ops.PYRAMID_LANE
+        use_lane = lane.on
 
         def roi_path():
             pooled = bp.bmp_forward(frame, frame_segments)                                          # BDNet.py:109 (shared)
@@ -374,7 +378,7 @@ class BranchesFunction(Function):
         put(3, WG.pair(cat, (r[0][0], r[1][0]), (prop[0][0], prop[1][0]), K1, ONE, lev))
         dcat = _dgrad_pair((r[0][0], r[1][0]), (prop[0][0], prop[1][0]), cat[0].shape, K1, lev)
         lane = ops.branch_lane(dev)
-        use_lane = lane.on and ops.PYRAMID_LANE
+        use_lane = lane.on
         d_frame = None
         hold = []
 
@@ -481,10 +485,10 @@ def eligible_static(pyramid):
 
 
 def early_projection_hooks(pyramid):
-    """{endpoint: hook} for ops.ENDPOINT_HOOKS: the Mixed_4f projection starts on the early lane the moment the backbone has
+    """{endpoint: hook} for ops.STEP.endpoint_hooks: the Mixed_4f projection starts on the early lane the moment the backbone has
     the endpoint (TrunkFunction.forward picks the result up)."""
     p = pyramid
-    if not (ops.FUSED_PYRAMID and ops.EARLY_PROJ and ops.PYRAMID_LANE and eligible_static(p)):
+    if not (ops.FUSED_PYRAMID and eligible_static(p)):
         return None
     w, b, gamma, beta = _block_params(p.pyramids[0])
     k0, eps = tuple(p.pyramids[0][0]._kernel_shape), p.pyramids[0][1].eps
@@ -494,11 +498,11 @@ def early_projection_hooks(pyramid):
         lane = ops.early_lane(x1.device)
         if not lane.on or not x1.is_cuda or x1.dtype != torch.float32:
             return
-        ops.EARLY_RESULTS.clear()                       # (a forward pass whose pyramid never ran leaves nothing behind)
+        ops.STEP.early_results.clear()                  # (a forward pass whose pyramid never ran leaves nothing behind)
         lane.fork()
         with lane, torch.no_grad():
             B = x1.shape[0]
             c0 = ops.conv_forward(x1, w, k0, ONE, shift=b, spatial_valid=True).view(B, w.shape[0], t0)
             p0, st0 = ops.gn_relu_forward(c0, gamma, beta, 32, eps, True, None)
-        ops.EARLY_RESULTS[x1.data_ptr()] = (c0, p0, st0, lane)
+        ops.STEP.early_results[x1.data_ptr()] = (c0, p0, st0, lane)
     return {p.projection_inputs[0]: hook}

@@ -213,7 +213,7 @@ class DetectorTrainer:
         self.forward_fn = forward_one_epoch if forward_fn is None else forward_fn
         adjacent = [m.fused_1x1_weights() for m in net.modules() if hasattr(m, 'fused_1x1_weights')]
         # The backbone is ONE autograd node that finishes last; it announces its weight gradients layer by layer while it
-        # runs (ops.GRAD_READY), so its buckets are kept apart from the pyramid's and go to RCCL from inside its backward.
+        # runs (ops.STEP.ready), so its buckets are kept apart from the pyramid's and go to RCCL from inside its backward.
         backbone = getattr(net, 'backbone', None)
         late = {id(p) for p in backbone.parameters()} if isinstance(backbone, nn.Module) else set()
         # ... and the weight whose gradient is computed LAST (the first trainable backbone parameter: Conv3d_1a) gets a
@@ -288,7 +288,7 @@ class DetectorTrainer:
     # launching `arena_view += grad` per parameter (~190 tiny kernels per step + a 179 MB zero fill).  A gradient is
     # "done" either when autograd has accumulated it (post-accumulate hook) or -- backbone weights, whose gradients the
     # weight-gradient launches write straight into the arena -- when the backbone's backward announces it
-    # (ops.GRAD_READY), long before that node returns.  When the last gradient of a bucket is done, one multi-tensor copy
+    # (ops.STEP.ready), long before that node returns.  When the last gradient of a bucket is done, one multi-tensor copy
     # moves the stragglers into the arena and, in data-parallel runs, the bucket's all-reduce is issued (in
     # self._flush_order).
     def _make_hook(self, i):
@@ -354,10 +354,10 @@ class DetectorTrainer:
             torch._foreach_copy_(dst, src)
         if self.collectives and not self._capturing:
             self._issue_allreduce(b, side=ops.side_busy())
-        elif self.collectives and ops.LANES is not None:
+        elif self.collectives and ops.STEP.lanes is not None:
             # lane capture: the bucket's weight gradients became a side graph above, and the replay issues the all-reduce
             # right behind it, from the side stream
-            ops.LANES.cut(("call", lambda b=b: self._issue_allreduce(b, side=True)))
+            ops.STEP.lanes.cut(("call", lambda b=b: self._issue_allreduce(b, side=True)))
 
     def _trace(self, kind, b=None, stream=None):
         """bench.py --gpus N: where on the lane timeline a bucket's all-reduce is issued and where the step waits for them --
@@ -385,6 +385,9 @@ class DetectorTrainer:
     def begin_backward(self, early=True):
         """Call before cost.backward(): gradients start undefined, buckets open.  `early=False` (a step that runs the
         backbone twice, i.e. the ssl branch): gradients are only final when autograd has accumulated them."""
+        # weight gradients are written straight into the arena, on a second stream that end_backward / the bucket flushes
+        # join; GroupNorm's batch sums and split-K reductions are deferred to the bucket flushes
+        ops.STEP.begin_backward(self._slots, self._grads_ready, early)
         a = self.arena
         for p in a.params:
             p.grad = None
@@ -397,19 +400,12 @@ class DetectorTrainer:
         self._cursor = 0
         self._early = early
         self._slots.reset()
-        ops.GRAD_SLOTS = self._slots                # weight gradients are written straight into the arena
-        ops.GRAD_READY = self._grads_ready
-        ops.SIDE_DEFER_JOIN = early                 # ... on a second stream that end_backward / the bucket flushes join
-        # GroupNorm's batch sums are deferred to the bucket flushes -- unless a parameter may be used twice in this backward
-        # (ssl step): a second gradient would be accumulated into the arena slice before the deferred sum is written there
-        ops.PENDING_SUMS = [] if early else None
-        ops.defer_reduces(early and ops.CONV_PROFILE is None)     # split-K reduces of weight gradients: batched (per-op timing: at once)
         if self.collectives and self._ibm_state() is not None:
             # the loss kernel updated the IBM EMA in the forward pass: its 50-float average travels under the backward
             if not self._capturing:
                 self._issue_ibm()
-            elif ops.LANES is not None:
-                ops.LANES.cut(("call", self._issue_ibm))
+            elif ops.STEP.lanes is not None:
+                ops.STEP.lanes.cut(("call", self._issue_ibm))
 
     def _issue_ibm(self):
         self._ibm_work = dist.all_reduce(self._ibm_state(), op=dist.ReduceOp.SUM, group=self.group, async_op=True)
@@ -426,7 +422,7 @@ class DetectorTrainer:
         self._drain(force=True)
         self._adam_left = None
         late = ops.take_late_weights()
-        if late and ops.LANES is not None and self._capturing and not self.collectives and not self._skipped:
+        if late and ops.STEP.lanes is not None and self._capturing and not self.collectives and not self._skipped:
             # lane capture, one process: Adam for everything but the stem tail's weights runs NOW on the main lane -- behind the
             # mark the backbone left on the side lane (ops.late_mark), beside the tail's weight gradients -- and only the
             # tail's parameters wait for the final join (_graph_body)
@@ -434,22 +430,17 @@ class DetectorTrainer:
             if span is not None:
                 ops.side_issue()                        # the tail's chunk (its fork sits in front of the optimizer launches)
                 ops.flush_pending_sums()                # GroupNorm batch sums: main-lane launches into the arena
-                ops.LANES.cut(("wait_mark",))
+                ops.STEP.lanes.cut(("wait_mark",))
                 self._adam_captured(0, span[0])
                 self._adam_captured(span[1], self.arena.numel)
                 self._adam_left = span
         ops.side_join()                                 # the weight gradients' stream: everything after this reads them
-        ops.SIDE_DEFER_JOIN = False
-        ops.defer_reduces(False)                        # flushes what is still recorded
-        ops.flush_pending_sums()
-        ops.PENDING_SUMS = None
-        ops.GRAD_SLOTS = None
-        ops.GRAD_READY = None
+        ops.STEP.end_backward()                         # flushes the recorded reductions and the deferred batch sums
         self._pending = None
         for p, v in zip(self.arena.params, self.arena.grad_views):
             p.grad = v
-        if self.collectives and self._capturing and ops.LANES is not None:
-            ops.LANES.cut(("call", self._finish_allreduce))     # lane capture: the waits sit between the last two graphs
+        if self.collectives and self._capturing and ops.STEP.lanes is not None:
+            ops.STEP.lanes.cut(("call", self._finish_allreduce))     # lane capture: the waits sit between the last two graphs
         self._finish_allreduce()
 
     def _issue_used_mask(self):
@@ -532,12 +523,7 @@ class DetectorTrainer:
             cost.backward()
             self.end_backward()
         finally:
-            ops.deactivate_prologues()
-            ops.GRAD_SLOTS = None
-            ops.GRAD_READY = None
-            ops.PENDING_SUMS = None
-            ops.SIDE_DEFER_JOIN = False
-            ops.defer_reduces(False)
+            ops.STEP.reset()
         self.step_count += 1
         self.optimizer_update()
         if stale:
@@ -555,23 +541,12 @@ class DetectorTrainer:
         except RuntimeError as err:
             import warnings
             dev = clips.device
-            ops.LANES = None
             self._capturing = False
             self._graph = None
             self._graph_key = None
             self._pending = None
             self._adam_left = None
-            ops.take_late_weights()
-            ops.deactivate_prologues()
-            ops.GRAD_SLOTS = ops.GRAD_READY = ops.PENDING_SUMS = None
-            ops.SIDE_DEFER_JOIN = False
-            try:
-                ops.defer_reduces(False)
-            except RuntimeError:
-                pass
-            for sd in ops._SIDES.values():          # launches the aborted capture recorded for the side lane: never issued
-                sd.pending.clear()
-                sd.keep.clear()
+            ops.STEP.reset(failed_capture=True)
             torch.cuda.synchronize(dev)
             self.launch = 'eager'
             self._eager_shapes = None
@@ -637,12 +612,7 @@ class DetectorTrainer:
             cost.backward()
             self.end_backward()
         finally:
-            ops.deactivate_prologues()
-            ops.GRAD_SLOTS = None
-            ops.GRAD_READY = None
-            ops.PENDING_SUMS = None
-            ops.SIDE_DEFER_JOIN = False
-            ops.defer_reduces(False)
+            ops.STEP.reset()
         keep = self._stash_skipped()
         span = getattr(self, "_adam_left", None) or (0, self.arena.numel)       # (what end_backward's early launches left)
         self._adam_captured(span[0], span[1])
@@ -742,7 +712,7 @@ class DetectorTrainer:
         plan = ops.LanePlan(ops.side_wgrads(dev).side)
         self._set_bias(self.step_count + 1)
         self._capturing = True
-        ops.LANES = plan
+        ops.STEP.lanes = plan
         from ..common import anet_dataset as _ad
         _ad.CAPTURE_IN_PROGRESS[0] = True           # background video readers must not call hipHostMalloc meanwhile
         try:
@@ -755,7 +725,7 @@ class DetectorTrainer:
                 finally:
                     plan.end_main()
         finally:
-            ops.LANES = None
+            ops.STEP.lanes = None
             self._capturing = False
             self._pending = None
             _ad.CAPTURE_IN_PROGRESS[0] = False
@@ -836,12 +806,7 @@ class DetectorTrainer:
             self._capturing = False
             model.detach_cut = False
             model.cut_leaf = None
-            ops.deactivate_prologues()
-            ops.GRAD_SLOTS = None
-            ops.GRAD_READY = None
-            ops.PENDING_SUMS = None
-            ops.SIDE_DEFER_JOIN = False
-            ops.defer_reduces(False)
+            ops.STEP.reset()
             self._pending = None
         if self._skipped:
             raise RuntimeError("capture_step(split=True): a parameter received no gradient; use eager launches")

@@ -33,7 +33,7 @@ def test_repeated_forward_backward_is_bit_identical(batch, iters, prec):
                 cost.backward()
                 tr.end_backward()
             finally:
-                ops.deactivate_prologues(); ops.GRAD_SLOTS = None; ops.GRAD_READY = None
+                ops.STEP.reset()
             torch.cuda.synchronize()
             cur = (float(cost.detach()), tr.arena.grad.detach().clone())
             if first is None:
@@ -73,7 +73,7 @@ def test_weight_gradients_on_the_side_stream_change_nothing(batch, prec):
                 cost.backward()
                 tr.end_backward()
             finally:
-                ops.deactivate_prologues(); ops.GRAD_SLOTS = None; ops.GRAD_READY = None
+                ops.STEP.reset()
             torch.cuda.synchronize()
             runs.append((side, float(cost.detach()), tr.arena.grad.detach().clone()))
         for side, c, g in runs[1:]:

@@ -135,7 +135,7 @@ def _reference(steps=3, ssl_rank0_from=None, anet=False, label_ring=False):
                     cost.backward()
                     tr.end_backward()
                 finally:
-                    ops.deactivate_prologues()
+                    ops.STEP.reset()
                 total += tr.arena.grad
                 states.append(ibm.detach().clone())
             tr.arena.grad.copy_(total)

@@ -122,3 +122,21 @@ def test_one_element_parameters_as_one_view_and_their_slot_index():
     idx = torch.tensor([(s.data_ptr() - grad.data_ptr()) // 4 for s in slots])
     grad.index_copy_(0, idx, torch.arange(1., 7.))
     assert [float(s) for s in slots] == [1., 2., 3., 4., 5., 6.]
+
+
+def test_one_backward_session_per_process_and_one_idempotent_reset():
+    """ops.STEP: a second trainer backward cannot open while one runs; reset() closes it and may be called again."""
+    import pytest
+    slots = ops.GradSlots(torch.zeros(10), torch.zeros(10), [0], [10])
+    ops.STEP.begin_backward(slots, None, early=True)
+    try:
+        assert ops.STEP.slots is slots and ops.STEP.pending_sums == [] and ops.STEP.defer_join
+        with pytest.raises(RuntimeError, match="already running"):
+            ops.STEP.begin_backward(slots, None, early=False)
+    finally:
+        ops.STEP.reset()
+    ops.STEP.reset()
+    assert ops.STEP.slots is None and ops.STEP.pending_sums is None and not ops.STEP.defer_join and not ops.STEP.defer
+    ops.STEP.begin_backward(slots, None, early=False)     # open again after the reset
+    ops.STEP.end_backward()
+    assert ops.STEP.slots is None

@@ -389,7 +389,7 @@ def test_weight_gradients_written_into_the_arena_match_the_copied_ones(ssl, monk
         tr.step(clips, targets, scores, *extra)
         grads.append(tr.arena.grad.clone())
         copied.append(n[0])
-        assert ops.GRAD_SLOTS is None
+        assert ops.STEP.slots is None
     assert torch.equal(grads[0], grads[1])
     assert float(grads[0].abs().max()) > 0
     assert copied[1] > 0.9 * grads[0].numel()

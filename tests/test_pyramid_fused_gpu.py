@@ -67,6 +67,8 @@ def test_fused_pyramid_nodes_equal_the_module_by_module_path(golden_dir, prec):
     fx = np.load(os.path.join(golden_dir, "thumos_b2.npz"))
     cost_a, out_a, g_a = _run(fx, False, prec)
     cost_b, out_b, g_b = _run(fx, True, prec)
+    from opental_amd.common import ops
+    assert not ops.STEP.pending_joins       # leaf inputs: no gradient was handed over on the early lane, no join left behind
     assert abs(cost_a - cost_b) <= 1e-6 * abs(cost_a), (cost_a, cost_b)
     for k in out_a:
         assert torch.equal(out_a[k], out_b[k]), k          # same kernels, same operands: forward values do not move

@@ -268,7 +268,7 @@ def test_trainer_arena_gradients_equal_plain_autograd(prec):
                 cost.backward()
                 tr.end_backward()
             finally:
-                ops.deactivate_prologues()
+                ops.STEP.reset()
             got = a.grad.detach().clone()
         assert bool(torch.isfinite(got).all()), int((~torch.isfinite(got)).sum())
         for p in a.params:

@@ -31,7 +31,7 @@ def main():
             cost.backward()
             tr.end_backward()
         finally:
-            ops.deactivate_prologues(); ops.GRAD_SLOTS = None; ops.GRAD_READY = None
+            ops.STEP.reset()
         torch.cuda.synchronize()
         g = a.grad.detach().clone()
         c = float(cost.detach())
