@@ -8,9 +8,15 @@
 A step = forward (I3D + temporal pyramid + heads) + MultiSegmentLoss (EDL/IBM + actionness + tIoU
 quality + boundary BCE) + backward + bucketed gradient all-reduce (RCCL, overlapped) + Adam, on a
 batch of synthetic 256x3x96x96 clips already resident in HBM.  `value` = world_size * batch /
-max-over-ranks step time.  Rank 0 prints ONE JSON line with `roofline` (the implicit-GEMM
-convolution, the kernel that dominates the step) and `cpu_baseline` (the CPU oracle timed on the
-host cores of this box on a bounded sample).
+max-over-ranks step time.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, picks the launch mode (--graph), warms up, times the steps, writes --dump-outputs
+and prints the line.  Everything else the benchmark measures runs only with --full, after the timed
+steps: `roofline` (the implicit-GEMM convolution, the kernel that dominates the step), `hbm_kernels`,
+`other_configs` (the other BASELINE configs), `cpu_baseline` (the CPU oracle timed on the host cores
+on a bounded sample) and, at N > 1, `config.allreduce_timeline`; those fields are null otherwise.
+
+    python bench.py --full
 """
 import argparse
 import json
@@ -504,18 +510,25 @@ def main():
     ap.add_argument("--ssl", action="store_true",
                     help="also run the self-supervised triplet branch every step (train.py:237-242 runs it when flags[0]): a second "
                          "backbone pass on the spliced clip + 3 BoundaryMaxPooling calls + triplet losses; eager launches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything besides the headline: roofline, HBM-bound kernel "
+                         "classes, the other BASELINE configs, CPU baselines and (N > 1) the all-reduce timeline; the --no-* "
+                         "options below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the short legs for the other BASELINE configs (fp32 parity path, ssl on, ActivityNet, inference, input pipeline)")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="with --full: skip the short legs for the other BASELINE configs (fp32 parity path, ssl on, ActivityNet, "
+                         "inference, input pipeline)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the two instrumented roofline steps")
     ap.add_argument("--no-hbm-kernels", action="store_true",
-                    help="skip the achieved-GB/s table of the HBM-bound kernel classes (tools/bench_hbm_kernels.py)")
+                    help="with --full: skip the achieved-GB/s table of the HBM-bound kernel classes (tools/bench_hbm_kernels.py)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32): cost, loss "
                          "terms, a fixed sample of the updated parameters and of the gradients (rank 0)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:       # a plain run: the headline alone, nothing after the timed steps but --dump-outputs
+        args.no_cpu_baseline = args.no_extras = args.no_roofline = args.no_hbm_kernels = True
     anet = args.recipe == "anet"
     if args.batch is None:
         args.batch = 2 if anet else 8
@@ -764,7 +777,7 @@ def main():
     # (HIP event on the issuing lane, ms after the step's first launch) and where the step waits for them -- the first N > 1
     # hardware run is then diagnosable from this line alone (which bucket is late, which lane issued it, how long the wait is)
     allreduce_timeline = None
-    if multi:
+    if multi and args.full:
         try:
             trainer.bucket_trace = []
             step()

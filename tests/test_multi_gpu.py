@@ -8,7 +8,7 @@ nn.DataParallel(net, device_ids=[0]) (AFSD/thumos14/train.py:316); SURVEY 8e.
 
 On a one-GPU box the same control flow can be exercised by hand with both ranks on cuda:0 and gloo collectives:
     OTAL_ONE_GPU=1 OTAL_DIST_BACKEND=gloo python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 \\
-        bench.py --gpus 2 --steps 4 --warmup 2 --no-extras --no-cpu-baseline
+        bench.py --gpus 2 --steps 4 --warmup 2 --full --no-extras --no-cpu-baseline
 (`test_two_rank_control_flow_on_one_gpu_with_gloo` below does exactly that; its throughput means nothing)."""
 import json
 import os
@@ -48,12 +48,13 @@ def test_two_rccl_ranks_stay_bit_identical_and_report_the_exposed_allreduce():
 
 def test_two_rank_control_flow_on_one_gpu_with_gloo():
     """Both ranks on cuda:0, gloo collectives on the device tensors: bench.py's N = 2 path end to end (rank agreement on the
-    launch mode, checksums, gathered timings) where only one GPU exists.  rccl_ranks is 0 here by construction."""
+    launch mode, checksums, gathered timings, the --full run's all-reduce timeline) where only one GPU exists.  rccl_ranks is
+    0 here by construction."""
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, OTAL_ONE_GPU="1", OTAL_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--batch", "2"] + ARGS
+           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--batch", "2", "--full"] + ARGS
     proc = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=1500)
     d = _line(proc)
     cfg = d["config"]
