@@ -341,12 +341,27 @@ int otal_decode_clips(const float* loc, const float* prop_loc, const float* prio
                       const float* offsets, const float* fps, float* seg, float* score, float* unct,
                       float* actn, unsigned char* flag, int nclips, int A, int K, float clip_length,
                       float conf_thresh, void* stream);
+/* otal_decode_clips_ex: otal_decode_clips for every THUMOS14 head, including the closed-set Softmax and EDL baselines
+ * (os_head false; test.py:79-162 with use_edl F / T).  Arguments as otal_decode_clips, plus:
+ *   score_fn    0 = Dirichlet mean with exp evidence (logits clamped to +-10), 1 = softmax exp(z - max) / sum (fp32);
+ *               other values: OTAL_E_UNSUPPORTED;
+ *   first_class 0 or 1; 1 drops class 0 (the background logit): score / flag are (nclips, K-1, A), while the softmax /
+ *               Dirichlet normalisation and the uncertainty K / S still run over all K logits.
+ * act / prop_act are nullable (together): without them no actionness factor is applied and flag = score > conf_thresh.
+ * unct / actn are nullable; when given, unct is 0 with score_fn 1 and actn is 0 without act.
+ * otal_decode_clips(...) == otal_decode_clips_ex(..., score_fn 0, first_class 0) bit for bit (it needs all four maps). */
+int otal_decode_clips_ex(const float* loc, const float* prop_loc, const float* priors, const float* conf,
+                         const float* prop_conf, const float* center, const float* act, const float* prop_act,
+                         const float* offsets, const float* fps, float* seg, float* score, float* unct,
+                         float* actn, unsigned char* flag, int nclips, int A, int K, float clip_length,
+                         float conf_thresh, int score_fn, int first_class, void* stream);
 /* otal_softnms_classes: for every (video, class) gather the flagged candidates of the video's clips
  * [clip_start[v], clip_start[v+1]) in clip-major / anchor-minor order and run softnms_v2
  * (AFSD/common/segment_utils.py:128-162; get_video_detections, test.py:165-200).
  * out: (nvideos*K, top_k, out_cols) rows [start,end,decayed score,unct,actionness] in original index
  * order; counts: (nvideos*K); out_index (nullable): (nvideos*K, top_k) source row = clip*A + anchor,
- * relative to the video's first clip.  max_clips bounds the clips of one video. */
+ * relative to the video's first clip.  max_clips bounds the clips of one video.  out_cols 3..5: unct may be NULL when
+ * out_cols == 3 and actn when out_cols <= 4 (the closed-set rows [start,end,score(,unct)]). */
 int otal_softnms_classes(const float* seg, const float* score, const float* unct, const float* actn,
                          const unsigned char* flag, const int* clip_start, int nvideos, int max_clips,
                          int A, int K, float sigma, int top_k, float score_threshold, float* out,
@@ -423,7 +438,15 @@ int otal_adam_flat_dev(float* p, const float* g, float* m, float* v, int64_t n, 
  * dconf, dprop_conf ((B,K,C)), dcenter, dact, dprop_act ((B,K)).  scratch: otal_detection_loss_scratch_floats.
  * cls_mode 1 = the as-shipped THUMOS14 dispatch (AFSD/thumos14/train.py:27-31 overwrites cls_loss_type 'edl' with
  * 'focal'): the two classification terms are FocalLoss_Ori(balance_index 0, alpha = focal_alpha, gamma 2,
- * size_average False) on the softmax scores of the positive rows (cls_loss.py:6-78); no IBM, no IoU calibration. */
+ * size_average False) on the softmax scores of the positive rows (cls_loss.py:6-78); no IBM, no IoU calibration.
+ * Closed-set baselines (os_head false, C = classes + 1 with class 0 = background; multisegment_loss.py:196-231 without
+ * os_head): EVERY anchor is classified against its matched label (0 where unmatched), normalised by N / PN as above.
+ *   cls_mode 2 = EvidenceLoss 'log' with exp evidence (thumos14_open_edl.yaml); ibm_active must be 0
+ *                (OTAL_E_UNSUPPORTED otherwise); iou_aware applies as in mode 0;
+ *   cls_mode 3 = FocalLoss_Ori(balance_index 0, alpha = focal_alpha, gamma 2) on the softmax scores (thumos14_softmax.yaml);
+ *                alpha[0] = focal_alpha belongs to the background.
+ * In modes 2 and 3 act / prop_act may be NULL: losses 5 and 6 and the dact / dprop_act gradient slots are written as 0.
+ * Any other cls_mode: OTAL_E_UNSUPPORTED. */
 size_t otal_detection_loss_scratch_floats(int B, int K);
 size_t otal_detection_loss_grad_floats(int B, int K, int C);
 int otal_detection_loss(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,

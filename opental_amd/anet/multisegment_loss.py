@@ -40,7 +40,8 @@ class MultiSegmentLoss(nn.Module):
         self.iou_aware = cls_loss_type == 'edl' and self.cls_loss.iou_aware
         self.os_head = os_head
         if not os_head:
-            raise NotImplementedError("closed-set (background-class) variant; OpenTAL uses os_head")
+            raise NotImplementedError("closed-set (background-class) variant: the ActivityNet Softmax / EDL baselines "
+                                      "are not supported; OpenTAL uses os_head")
         self.act_loss = ActionnessLoss(size_average=False, weight=0.1)
         self.size_average = size_average
         self.register_buffer('level_bounds', torch.tensor(bounds, dtype=torch.float32), persistent=False)

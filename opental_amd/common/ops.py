@@ -1434,15 +1434,17 @@ def adam_flat_dev(p, g, m, v, bias_corr, lr, beta1=0.9, beta2=0.999, eps=1e-8, w
 # ----------------------------------------------------------------------------- fused detection loss
 class DetectionLossFunction(torch.autograd.Function):
     """The seven loss terms of MultiSegmentLoss (EDL recipe) from ONE launch that also produces every gradient
-    (csrc/loss.hip); backward only scales the stored gradients by the incoming scalars."""
+    (csrc/loss.hip); backward only scales the stored gradients by the incoming scalars.  act / prop_act may be None
+    (closed-set cls_mode 2 / 3): the kernel gets NULL, and their gradients are None."""
 
     @staticmethod
     def forward(ctx, loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt, gvalid, weight_accum,
                 clip_length, overlap, ibm_active, num_bins, momentum, iou_aware, cls_mode=0, focal_alpha=0.25):
         B, K, C = conf.shape
         G = gt.shape[1]
-        tens = [t.contiguous().float() for t in (loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt)]
-        L.require_device(*tens)
+        tens = [None if t is None else t.contiguous().float()
+                for t in (loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt)]
+        L.require_device(*[t for t in tens if t is not None])
         gv = gvalid.contiguous().to(torch.uint8)
         lib = L.lib()
         lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
@@ -1452,13 +1454,14 @@ class DetectionLossFunction(torch.autograd.Function):
         losses = torch.empty(7, dtype=torch.float32, device=loc.device)
         grads = torch.empty(ng, dtype=torch.float32, device=loc.device)
         scratch = torch.empty(ns, dtype=torch.float32, device=loc.device)
-        L.check(lib.otal_detection_loss(*[L.ptr(t) for t in tens], L.ptr(gv), L.ptr(weight_accum), B, K, C, G,
+        L.check(lib.otal_detection_loss(*[None if t is None else L.ptr(t) for t in tens], L.ptr(gv), L.ptr(weight_accum), B, K, C, G,
                                         ctypes.c_float(clip_length), ctypes.c_float(overlap), int(ibm_active),
                                         int(num_bins), ctypes.c_float(momentum), int(iou_aware), int(cls_mode),
                                         ctypes.c_float(focal_alpha), L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream()),
                 "otal_detection_loss")
         ctx.save_for_backward(grads)
         ctx.dims = (B, K, C)
+        ctx.has_act = act is not None
         return tuple(losses[i] for i in range(7))
 
     @staticmethod
@@ -1479,6 +1482,8 @@ class DetectionLossFunction(torch.autograd.Function):
         d_loc, d_pl = take(2 * A, (B, K, 2)), take(2 * A, (B, K, 2))
         d_conf, d_pconf = take(A * C, (B, K, C)), take(A * C, (B, K, C))
         d_cen, d_act, d_pact = take(A, (B, K)), take(A, (B, K)), take(A, (B, K))
+        if not getattr(ctx, 'has_act', True):        # (AnetDetectionLossFunction shares this backward)
+            d_act = d_pact = None
         return (d_loc, d_conf, d_pl, d_pconf, d_cen, d_act, d_pact) + (None,) * 12
 
 

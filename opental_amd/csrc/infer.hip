@@ -1,6 +1,9 @@
 // opental_amd/csrc/infer.hip -- inference post-processing of the OpenTAL detector on gfx950:
 //   otal_decode_clips   : parse_output + decode_predictions + the per-class threshold test of
-//                         `filtering` (AFSD/thumos14/test.py:79-162) for a batch of clips, one launch;
+//                         `filtering` (AFSD/thumos14/test.py:79-162) for a batch of clips, one launch -- the OpenTAL
+//                         head (Dirichlet scores x actionness);
+//   otal_decode_clips_ex: the same with the score function (Dirichlet / softmax), the background class and the
+//                         actionness heads chosen by the caller -- the closed-set Softmax and EDL baselines;
 //   otal_softnms_classes: per (video, class) gather of the surviving candidates in the reference's
 //                         order (clip-major, anchor-minor) followed by Gaussian Soft-NMS
 //                         (softnms_v2, AFSD/common/segment_utils.py:128-162) -- one workgroup per
@@ -22,16 +25,23 @@ constexpr int NMS_THREADS = 256;
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// one workgroup per clip; A anchors, K classes.  Outputs: seg (clip,A,2) seconds; score (clip,K,A);
-// unct (clip,A); actn (clip,A); flag (clip,K,A) uint8.
+// one workgroup per clip; A anchors, K logits per anchor.  Outputs: seg (clip,A,2) seconds; score (clip,K-first_class,A);
+// unct (clip,A); actn (clip,A); flag (clip,K-first_class,A) uint8.
+// SOFTMAX false: Dirichlet mean with exp evidence (BDNet.py DirichletLayer); true: softmax, exp(z - max) / sum (nn.Softmax).
+// first_class 1 drops class 0 (the closed-set background) from score / flag.  act / prop_act NULL (no actionness heads):
+// no actionness factor and flag = score > conf_thresh.  unct / actn NULL: not written; with SOFTMAX or without act the
+// absent quantity is written as 0.
+template <bool SOFTMAX>
 __global__ __launch_bounds__(128) void decode_clips_kernel(
         const float* __restrict__ loc, const float* __restrict__ prop_loc, const float* __restrict__ priors,
         const float* __restrict__ conf, const float* __restrict__ prop_conf, const float* __restrict__ center,
         const float* __restrict__ act, const float* __restrict__ prop_act, const float* __restrict__ offsets,
         const float* __restrict__ fps, float* __restrict__ seg, float* __restrict__ score, float* __restrict__ unct,
         float* __restrict__ actn, unsigned char* __restrict__ flag, int A, int K, float clip_length,
-        float conf_thresh) {
+        float conf_thresh, int first_class) {
     const int c = blockIdx.x;
+    const int KO = K - first_class;
+    const bool has_act = act != nullptr;
     for (int i = threadIdx.x; i < A; i += blockDim.x) {
         const size_t ai = (size_t)c * A + i;
         // decode_predictions (test.py:114-120)
@@ -44,26 +54,43 @@ __global__ __launch_bounds__(128) void decode_clips_kernel(
         float s1 = fminf(fmaxf(pc + r1, 0.f), clip_length);
         seg[ai * 2] = (s0 + offsets[c]) / fps[c];
         seg[ai * 2 + 1] = (s1 + offsets[c]) / fps[c];
-        // Dirichlet mean + uncertainty (BDNet.py:538-561), evidence = exp(clamp(logit, +-10))
         const float* cf = conf + ai * K;
         const float* pf = prop_conf + ai * K;
-        float S = 0.f, PS = 0.f;
-        for (int k = 0; k < K; ++k) {
-            S += expf(fminf(fmaxf(cf[k], -10.f), 10.f)) + 1.0f;
-            PS += expf(fminf(fmaxf(pf[k], -10.f), 10.f)) + 1.0f;
+        float S = 0.f, PS = 0.f, M = 0.f, PM = 0.f;
+        if constexpr (SOFTMAX) {
+            M = cf[0]; PM = pf[0];
+            for (int k = 1; k < K; ++k) { M = fmaxf(M, cf[k]); PM = fmaxf(PM, pf[k]); }
+            for (int k = 0; k < K; ++k) { S += expf(cf[k] - M); PS += expf(pf[k] - PM); }
+        } else {
+            // Dirichlet mean + uncertainty (BDNet.py:538-561), evidence = exp(clamp(logit, +-10))
+            for (int k = 0; k < K; ++k) {
+                S += expf(fminf(fmaxf(cf[k], -10.f), 10.f)) + 1.0f;
+                PS += expf(fminf(fmaxf(pf[k], -10.f), 10.f)) + 1.0f;
+            }
         }
-        const float u = ((float)K / S + (float)K / PS) / 2.0f;
-        const float an = (sigmoidf_(act[ai]) + sigmoidf_(prop_act[ai])) / 2.0f;
+        const float an = has_act ? (sigmoidf_(act[ai]) + sigmoidf_(prop_act[ai])) / 2.0f : 0.f;
         const float ct = sigmoidf_(center[ai]);
-        unct[ai] = u;
-        actn[ai] = an;
-        for (int k = 0; k < K; ++k) {
-            const float a0 = (expf(fminf(fmaxf(cf[k], -10.f), 10.f)) + 1.0f) / S;
-            const float a1 = (expf(fminf(fmaxf(pf[k], -10.f), 10.f)) + 1.0f) / PS;
-            const float sc = (a0 + a1) / 2.0f * ct * an;
-            const size_t o = ((size_t)c * K + k) * A + i;
-            score[o] = sc;
-            flag[o] = (sc > conf_thresh) && (an > 0.5f);       // filtering (test.py:143-147)
+        if (unct) unct[ai] = SOFTMAX ? 0.f : ((float)K / S + (float)K / PS) / 2.0f;
+        if (actn) actn[ai] = an;
+        for (int k = first_class; k < K; ++k) {
+            float a0, a1;
+            if constexpr (SOFTMAX) {
+                a0 = expf(cf[k] - M) / S;
+                a1 = expf(pf[k] - PM) / PS;
+            } else {
+                a0 = (expf(fminf(fmaxf(cf[k], -10.f), 10.f)) + 1.0f) / S;
+                a1 = (expf(fminf(fmaxf(pf[k], -10.f), 10.f)) + 1.0f) / PS;
+            }
+            const size_t o = ((size_t)c * KO + (k - first_class)) * A + i;
+            if (has_act) {
+                const float sc = (a0 + a1) / 2.0f * ct * an;
+                score[o] = sc;
+                flag[o] = (sc > conf_thresh) && (an > 0.5f);       // filtering (test.py:143-147)
+            } else {
+                const float sc = (a0 + a1) / 2.0f * ct;
+                score[o] = sc;
+                flag[o] = sc > conf_thresh;
+            }
         }
     }
 }
@@ -225,18 +252,36 @@ __global__ __launch_bounds__(NMS_THREADS) void softnms_classes_kernel(
 
 }  // namespace
 
+extern "C" int otal_decode_clips_ex(const float* loc, const float* prop_loc, const float* priors, const float* conf,
+                                    const float* prop_conf, const float* center, const float* act,
+                                    const float* prop_act, const float* offsets, const float* fps, float* seg,
+                                    float* score, float* unct, float* actn, unsigned char* flag, int nclips, int A,
+                                    int K, float clip_length, float conf_thresh, int score_fn, int first_class,
+                                    void* stream) {
+    if (!loc || !prop_loc || !priors || !conf || !prop_conf || !center || (!act) != (!prop_act) || !offsets || !fps ||
+        !seg || !score || !flag) return OTAL_E_NULL;
+    if (nclips <= 0 || A <= 0 || K <= 0) return OTAL_E_SHAPE;
+    if (score_fn < 0 || score_fn > 1 || first_class < 0 || first_class > 1) return OTAL_E_UNSUPPORTED;
+    if (K - first_class <= 0) return OTAL_E_SHAPE;
+    if (score_fn == 1)
+        hipLaunchKernelGGL(decode_clips_kernel<true>, dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc, priors,
+                           conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
+                           clip_length, conf_thresh, first_class);
+    else
+        hipLaunchKernelGGL(decode_clips_kernel<false>, dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc, priors,
+                           conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
+                           clip_length, conf_thresh, first_class);
+    return otal_launch_status();
+}
+
 extern "C" int otal_decode_clips(const float* loc, const float* prop_loc, const float* priors, const float* conf,
                                  const float* prop_conf, const float* center, const float* act,
                                  const float* prop_act, const float* offsets, const float* fps, float* seg,
                                  float* score, float* unct, float* actn, unsigned char* flag, int nclips, int A,
                                  int K, float clip_length, float conf_thresh, void* stream) {
-    if (!loc || !prop_loc || !priors || !conf || !prop_conf || !center || !act || !prop_act || !offsets || !fps ||
-        !seg || !score || !unct || !actn || !flag) return OTAL_E_NULL;
-    if (nclips <= 0 || A <= 0 || K <= 0) return OTAL_E_SHAPE;
-    hipLaunchKernelGGL(decode_clips_kernel, dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc, priors,
-                       conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
-                       clip_length, conf_thresh);
-    return otal_launch_status();
+    if (!act || !prop_act || !unct || !actn) return OTAL_E_NULL;       // the OpenTAL head: every map present
+    return otal_decode_clips_ex(loc, prop_loc, priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score,
+                                unct, actn, flag, nclips, A, K, clip_length, conf_thresh, 0, 0, stream);
 }
 
 constexpr size_t NMS_LDS_LIMIT = 150 * 1024;      // working set of ~7600 candidates; beyond that the scratch path runs
@@ -252,9 +297,11 @@ extern "C" int otal_softnms_classes_ws(const float* seg, const float* score, con
                                        int A, int K, float sigma, int top_k, float score_threshold, float* out,
                                        int* counts, int* out_index, int out_cols, void* scratch, size_t scratch_bytes,
                                        int total_clips, void* stream) {
-    if (!seg || !score || !unct || !actn || !flag || !clip_start || !out || !counts) return OTAL_E_NULL;
     if (nvideos <= 0 || max_clips <= 0 || A <= 0 || K <= 0 || top_k <= 0 || out_cols < 3 || out_cols > 5)
         return OTAL_E_SHAPE;
+    // unct is read only for out_cols > 3, actn only for out_cols > 4 (closed-set rows: 3 or 4 columns)
+    if (!seg || !score || (out_cols > 3 && !unct) || (out_cols > 4 && !actn) || !flag || !clip_start || !out || !counts)
+        return OTAL_E_NULL;
     const size_t need = otal_softnms_scratch_bytes(total_clips, max_clips, A, K);
     const bool big = need != 0;
     if (big && (!scratch || scratch_bytes < need)) return OTAL_E_UNSUPPORTED;   // longest video exceeds LDS: scratch required

@@ -1,5 +1,6 @@
-// opental_amd/csrc/loss.hip -- MultiSegmentLoss + EvidenceLoss + ActionnessLoss of the OpenTAL final recipe,
-// forward AND backward, as ONE single-workgroup launch.
+// opental_amd/csrc/loss.hip -- MultiSegmentLoss + EvidenceLoss + ActionnessLoss of the OpenTAL final recipe (and the
+// FocalLoss_Ori / EvidenceLoss terms of the closed-set Softmax and EDL baselines), forward AND backward, as ONE
+// single-workgroup launch.
 //
 // Replaces (reference AFSD/thumos14): multisegment_loss.py:92-259 (anchor<->GT matching, GIoU / L1 / quality-BCE
 // terms, normalisers), cls_loss.py:132-168,212-278 (EvidenceLoss 'log' with exp evidence and the influence-balanced
@@ -16,7 +17,11 @@
 // Supported configurations: the final recipe -- evidence 'exp', loss_type 'log', os_head, size_average False, actionness
 // rank-term weight 0 -- and, with cls_mode = 1, the as-shipped THUMOS14 dispatch (train.py:27-31 overwrites 'edl' with
 // 'focal'): FocalLoss_Ori(balance_index 0, alpha 0.25, gamma 2) on softmax scores (cls_loss.py:6-78) instead
-// of the evidential terms (no IBM, no IoU calibration).  Everything else stays on the torch formulation.
+// of the evidential terms (no IBM, no IoU calibration).  Two closed-set baselines (os_head false: C = K + 1 logits, class 0
+// = background, EVERY anchor is classified against its matched label, multisegment_loss.py:196-231 without os_head):
+// cls_mode 2 = EvidenceLoss 'log' / exp (no IBM; IoU calibration as in mode 0), cls_mode 3 = FocalLoss_Ori on softmax scores.
+// Modes 2 and 3 have no actionness heads: act / prop_act may be NULL, losses 5 and 6 and their gradient slots are 0.
+// Everything else stays on the torch formulation.
 #include "common.h"
 
 namespace {
@@ -39,7 +44,8 @@ struct LossArgs {
     float clip, overlap;
     int ibm_active, num_bins, iou_aware;
     float momentum;
-    int cls_mode;                   // 0: EvidenceLoss (the OpenTAL recipe); 1: FocalLoss_Ori on softmax scores (as-shipped THUMOS14 dispatch)
+    int cls_mode;                   // 0: EvidenceLoss (the OpenTAL recipe); 1: FocalLoss_Ori on softmax scores (as-shipped THUMOS14 dispatch);
+                                    // 2 / 3: closed-set EvidenceLoss / FocalLoss_Ori over every anchor, target = matched label (0 = background)
     float focal_alpha;              // FocalLoss_Ori(balance_index=0, alpha): alpha for class 0, 1 - alpha for the others
 };
 constexpr int SCR = 12;             // loc_t0, loc_t1, conf_t, prop_conf_t, iou, prop_loc_t0, prop_loc_t1, ghat, slot, binpos, per, used
@@ -181,11 +187,12 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
 
     // ---- phases 2-4 (conf) and 5-7 (prop_conf): EvidenceLoss with IBM re-weighting (cls_loss.py:132-168)
     float loss_cls[2];
+    const bool closed = a.cls_mode >= 2;        // every anchor counts, y = the matched label itself
     for (int pass = 0; pass < 2; ++pass) {
         const float* logits = pass == 0 ? a.conf : a.prop_conf;
         float* gout = pass == 0 ? g_conf : g_pconf;
         const float norm = pass == 0 ? Nf : PNf;
-        if (a.cls_mode == 1) {
+        if (a.cls_mode == 1 || a.cls_mode == 3) {
             // FocalLoss_Ori(gamma 2, size_average False) on F.softmax(logits) of the positive rows (cls_loss.py:6-78,
             // multisegment_loss.py:196-216): loss = -alpha_y (1 - pt)^2 log(pt), pt = p_y + 1e-6
             float part = 0.f;
@@ -194,8 +201,8 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
                 const int tgt = (int)s[2 + pass];
                 const float* z = logits + (size_t)i * C;
                 float* gz = gout + (size_t)i * C;
-                if (tgt > 0) {
-                    const int y = tgt - 1;
+                if (tgt > 0 || closed) {
+                    const int y = closed ? min(tgt, C - 1) : tgt - 1;
                     float mx = z[0];
                     for (int k = 1; k < C; ++k) mx = fmaxf(mx, z[k]);
                     float S = 0.f;
@@ -230,7 +237,7 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
         for (int i = t; i < A; i += LT) {
             float* s = a.scratch + (size_t)i * SCR;
             const int tgt = (int)s[2 + pass];
-            const int y = max(tgt - 1, 0);
+            const int y = closed ? tgt : max(tgt - 1, 0);
             const Edl e = edl_row(staged ? zl + (size_t)i * C : logits + (size_t)i * C, C, y, a.num_bins);
             s[7] = e.ghat; s[8] = (float)e.slot; s[9] = (float)e.binpos; s[10] = e.per;
             s_val[i] = e.ghat; s_slot[i] = (unsigned char)e.slot; s_flag[i] = (tgt > 0 && e.binpos) ? 1 : 0;
@@ -259,13 +266,14 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
         for (int i = t; i < A; i += LT) {
             const float* s = a.scratch + (size_t)i * SCR;
             const int tgt = (int)s[2 + pass];
+            const bool cnt = tgt > 0 || closed;                 // the row is classified
             if constexpr (ST) {
                 float* z = zl + (size_t)i * C;                  // logits in, gradient row out (in place: element k is read before it is written)
                 const float wgt = (tgt > 0 && a.ibm_active) ? wacc[(int)s[8]] : 1.f;
-                if (tgt > 0) part += wgt * s[10];
-                const int y = tgt - 1;
+                if (cnt) part += wgt * s[10];
+                const int y = closed ? tgt : tgt - 1;
                 float S = 0.f, ay = 1.f;
-                if (tgt > 0 || cal) {
+                if (cnt || cal) {
                     for (int k = 0; k < C; ++k) {
                         const float al = expf(fminf(fmaxf(z[k], -10.f), 10.f)) + 1.f;
                         S += al;
@@ -285,17 +293,17 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
                 for (int k = 0; k < C; ++k) {
                     const float zk = z[k];
                     const float da = (zk >= -10.f && zk <= 10.f) ? expf(zk) : 0.f;      // clamp backward is inclusive
-                    float gk = tgt > 0 ? wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) * da / norm : 0.f;
+                    float gk = cnt ? wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) * da / norm : 0.f;
                     if (cal) gk += cg * da / (float)A;
                     z[k] = gk;
                 }
             } else {
             const float* z = logits + (size_t)i * C;
             float* gz = gout + (size_t)i * C;
-            if (tgt > 0) {
+            if (cnt) {
                 const float wgt = a.ibm_active ? wacc[(int)s[8]] : 1.f;
                 part += wgt * s[10];
-                const int y = tgt - 1;
+                const int y = closed ? tgt : tgt - 1;
                 float S = 0.f, ay = 1.f;
                 for (int k = 0; k < C; ++k) {
                     const float al = expf(fminf(fmaxf(z[k], -10.f), 10.f)) + 1.f;
@@ -395,8 +403,10 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
     const float loss_ct = block_sum(pct, red) / Nf;
 
     // ---- positive-unlabelled actionness BCE (cls_loss.py:288-339), rank term off (weight 0 in the final recipe)
-    float loss_a[2];
-    for (int pass = 0; pass < 2; ++pass) {
+    float loss_a[2] = {0.f, 0.f};
+    if (closed)                                 // no actionness heads: zero terms, zero gradient slots
+        for (int i = t; i < A; i += LT) { g_act[i] = 0.f; g_pact[i] = 0.f; }
+    for (int pass = 0; pass < (closed ? 0 : 2); ++pass) {
         const float* pred = pass == 0 ? a.act : a.prop_act;
         float* gout = pass == 0 ? g_act : g_pact;
         const int np = icnt[pass], nn = A - np;
@@ -814,22 +824,26 @@ extern "C" int otal_detection_loss(const float* loc, const float* conf, const fl
                                    int C, int G, float clip_length, float overlap_thresh, int ibm_active, int num_bins,
                                    float momentum, int iou_aware, int cls_mode, float focal_alpha, float* losses,
                                    float* grads, float* scratch, void* stream) {
-    if (!loc || !conf || !prop_loc || !prop_conf || !center || !act || !prop_act || !priors || !gt || !gvalid ||
+    const bool closed = cls_mode == 2 || cls_mode == 3;        // closed-set modes: no actionness heads
+    if (!loc || !conf || !prop_loc || !prop_conf || !center || (!closed && (!act || !prop_act)) || !priors || !gt || !gvalid ||
         !weight_accum || !losses || !grads || !scratch) return OTAL_E_NULL;
     if (B <= 0 || K <= 0 || C <= 0 || G <= 0) return OTAL_E_SHAPE;
-    if (num_bins <= 0 || num_bins > MAX_BINS || (long)B * K > MAX_A || cls_mode < 0 || cls_mode > 1) return OTAL_E_UNSUPPORTED;
+    if (num_bins <= 0 || num_bins > MAX_BINS || (long)B * K > MAX_A || cls_mode < 0 || cls_mode > 3) return OTAL_E_UNSUPPORTED;
+    if (cls_mode == 2 && ibm_active) return OTAL_E_UNSUPPORTED;    // closed-set EDL: no influence-balanced re-weighting
     LossArgs a;
     a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
     a.prop_act = prop_act; a.priors = priors; a.gt = gt; a.gvalid = gvalid; a.weight_accum = weight_accum;
     a.losses = losses; a.grads = grads; a.scratch = scratch;
     a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
-    a.ibm_active = cls_mode == 0 ? ibm_active : 0; a.num_bins = num_bins; a.iou_aware = cls_mode == 0 ? iou_aware : 0;
+    a.ibm_active = cls_mode == 0 ? ibm_active : 0; a.num_bins = num_bins;
+    a.iou_aware = (cls_mode == 0 || cls_mode == 2) ? iou_aware : 0;
     a.momentum = momentum; a.cls_mode = cls_mode; a.focal_alpha = focal_alpha;
-    // staged logits: EvidenceLoss mode and A * C floats within the dynamic LDS this kernel may add to its ~40 KB of static arrays
+    // staged logits: EvidenceLoss modes (0, 2) and A * C floats within the dynamic LDS this kernel may add to its ~40 KB of static
+    // arrays (C = 16: up to 1536 anchors, B * 126 anchors for B <= 12)
     const size_t stage = (size_t)B * K * C * sizeof(float);
     constexpr size_t STAGE_MAX = 96 * 1024;
     static int staged_ok = -1;          // -1: not asked yet; the attribute is set once per process
-    if (cls_mode == 0 && stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE")) {
+    if ((cls_mode == 0 || cls_mode == 2) && stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE")) {
         if (staged_ok < 0)
             staged_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(detection_loss_kernel<true>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAGE_MAX) == hipSuccess ? 1 : 0;

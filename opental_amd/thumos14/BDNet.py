@@ -40,9 +40,10 @@ def model_cfg_from(config=None):
     cfg = dict(DEFAULT_MODEL_CFG)
     if config is not None:
         cfg['num_classes'] = config['dataset']['num_classes']
-        for k in ('freeze_bn', 'freeze_bn_affine', 'evidence', 'dropout', 'os_head'):
+        for k in ('freeze_bn', 'freeze_bn_affine', 'evidence', 'dropout'):
             if k in config['model']:
                 cfg[k] = config['model'][k]
+        cfg['os_head'] = config['model'].get('os_head', False)     # BDNet.py:17: a config without the key is closed-set
         if config['model'].get('transformer', False) or config['model'].get('use_rpl', False):
             raise NotImplementedError("TransformerHead / RPLHead baselines are outside the OpenTAL hot path")
     return cfg

@@ -3,6 +3,10 @@ same constructor and the same 7-tuple result, vectorised over the batch and free
 synchronisation: anchor<->GT matching runs for all clips at once on padded targets, and every
 "select the positives, then reduce" of the reference is a masked reduction over all anchors.
 
+os_head=False is the closed-set variant of the Softmax and EDL baselines (configs thumos14_softmax.yaml,
+thumos14_open_edl.yaml): C = classes + 1 logits with class 0 = background, EVERY anchor is classified against its matched
+label, and there are no actionness terms (loss_act, loss_prop_act are None, multisegment_loss.py:196-231, :250-255).
+
 Reference quirks kept on purpose (documented in DESIGN.md):
   * the IoU-calibration term pairs iou_pred (stored prior-major, (126,B)) with logits flattened
     batch-major (multisegment_loss.py:116,:234-236) -- identical for batch 1, the yaml's batch size;
@@ -17,7 +21,7 @@ from ..common.input_pipeline import PaddedTargets
 from .cls_loss import ActionnessLoss, EvidenceLoss, FocalLoss_Ori
 
 _EPS = torch.finfo(torch.float32).eps
-FUSED = True      # single-launch HIP loss for the final recipe (set False to force the torch formulation)
+FUSED = True      # single-launch HIP loss for the final recipe and the closed-set baselines (set False to force the torch formulation)
 
 
 def _tiou(pred, target):
@@ -108,12 +112,11 @@ class MultiSegmentLoss(nn.Module):
         elif cls_loss_type == 'edl':
             self.cls_loss = EvidenceLoss(num_classes, edl_config, size_average=size_average)
         else:
-            raise NotImplementedError("rpl: baseline outside the OpenTAL hot path")
+            raise NotImplementedError(f"cls_loss_type {cls_loss_type!r}: the RPL / GCPL baselines are not supported")
         self.iou_aware = cls_loss_type == 'edl' and self.cls_loss.iou_aware
         self.os_head = os_head
-        if not os_head:
-            raise NotImplementedError("closed-set (background-class) variant; OpenTAL uses os_head")
-        self.act_loss = ActionnessLoss(size_average=size_average, cfg=act_config)
+        # the closed-set variant has no actionness heads (multisegment_loss.py:87-88)
+        self.act_loss = ActionnessLoss(size_average=size_average, cfg=act_config) if os_head else None
         self.size_average = size_average
 
     @torch.no_grad()
@@ -142,23 +145,52 @@ class MultiSegmentLoss(nn.Module):
         return loc_t, conf_t, prop_loc_t, prop_conf_t, iou
 
     def _fused_ok(self, loc):
-        """The single-launch HIP loss (csrc/loss.hip) covers the final recipe; other settings use the torch formulation."""
+        """The single-launch HIP loss (csrc/loss.hip) covers the final recipe and the closed-set baselines; other settings
+        use the torch formulation."""
+        return self._cls_mode(loc) is not None
+
+    def _cls_mode(self, loc):
+        """cls_mode of otal_detection_loss for this criterion, or None when the kernel does not cover it:
+        0 = EDL with actionness (OpenTAL), 1 = focal with actionness (as-shipped dispatch), 2 = closed-set EDL ('log', exp,
+        no IBM), 3 = closed-set focal."""
         cl = self.cls_loss
         common = (FUSED and loc.is_cuda and loc.dtype == torch.float32 and loc.shape[0] * loc.shape[1] <= 2048
-                  and self.os_head and not self.size_average and self.act_loss.weight == 0
-                  and not self.act_loss.size_average and not cl.size_average)
-        if self.cls_loss_type == 'focal':       # the as-shipped THUMOS14 dispatch (train.py:27-31, SURVEY H2)
-            return common and self._focal_alpha0 is not None
-        return (common and self.cls_loss_type == 'edl' and cl.loss_type == 'log' and cl.evidence == 'exp' and cl.num_bins <= 64)
+                  and not self.size_average and not cl.size_average)
+        if self.os_head:
+            common = common and self.act_loss.weight == 0 and not self.act_loss.size_average
+        if not common:
+            return None
+        if self.cls_loss_type == 'focal':       # the as-shipped THUMOS14 dispatch (train.py:27-31, SURVEY H2) / thumos14_softmax.yaml
+            return (1 if self.os_head else 3) if self._focal_alpha0 is not None else None
+        if self.cls_loss_type != 'edl' or cl.loss_type != 'log' or cl.evidence != 'exp' or cl.num_bins > 64:
+            return None
+        if self.os_head:
+            return 0
+        return None if cl.with_ibm else 2
 
     def forward(self, output_dict, targets, pre_locs=None):
         loc, conf = output_dict['loc'], output_dict['conf']
         prop_loc, prop_conf = output_dict['prop_loc'], output_dict['prop_conf']
         center, priors = output_dict['center'], output_dict['priors']
-        act, prop_act = output_dict['act'], output_dict['prop_act']
+        act, prop_act = output_dict.get('act'), output_dict.get('prop_act')
         B, K = loc.shape[0], priors.shape[0]
         C = self.num_classes
-        if self._fused_ok(loc):
+        mode = self._cls_mode(loc)
+        if mode is not None and not self.os_head:
+            from ..common.ops import DetectionLossFunction
+            gt, valid = as_padded(targets, loc.device)
+            cl = self.cls_loss
+            if mode == 3:
+                if getattr(self, '_no_ibm', None) is None or self._no_ibm.device != loc.device:
+                    self._no_ibm = torch.ones(1, dtype=torch.float32, device=loc.device)    # unused EMA slot of the ABI
+                wacc, nb, fa = self._no_ibm, 1, self._focal_alpha0
+            else:
+                wacc, nb, fa = cl.weight_accum, cl.num_bins, 0.25
+            out = DetectionLossFunction.apply(
+                loc, conf, prop_loc, prop_conf, center.reshape(B, K), None, None, priors[:, 0], gt, valid, wacc,
+                float(self.clip_length), float(self.overlap_thresh), False, nb, 0.0, bool(self.iou_aware), mode, fa)
+            return out[:5] + (None, None)
+        if mode is not None:
             from ..common.ops import DetectionLossFunction
             gt, valid = as_padded(targets, loc.device)
             cl = self.cls_loss
@@ -192,21 +224,28 @@ class MultiSegmentLoss(nn.Module):
             lg = logits.reshape(-1, C)
             t = tgt.reshape(-1)
             keep = t > 0
+            if not self.os_head:                # closed set: every anchor, its matched label (0 = background)
+                if self.cls_loss_type == 'focal':
+                    return self.cls_loss(F.softmax(lg, dim=1), t), keep
+                return self.cls_loss(lg, t), keep
             cls_id = (t - 1).clamp(min=0)
             if self.cls_loss_type == 'focal':
                 return self.cls_loss(F.softmax(lg, dim=1), cls_id, keep), keep
             return self.cls_loss(lg, cls_id, keep), keep
 
         loss_c, keep = classify(conf, conf_t)
-        loss_act, AN = self.act_loss(act.reshape(-1, 1), keep.to(act.dtype))
         loss_prop_c, pkeep = classify(prop_conf, prop_conf_t)
-        loss_prop_act, PAN = self.act_loss(prop_act.reshape(-1, 1), pkeep.to(act.dtype))
+        loss_act = loss_prop_act = None
+        if self.os_head:
+            loss_act, AN = self.act_loss(act.reshape(-1, 1), keep.to(act.dtype))
+            loss_prop_act, PAN = self.act_loss(prop_act.reshape(-1, 1), pkeep.to(act.dtype))
         N = pos.sum().clamp(min=1)
         PN = prop_pos.sum().clamp(min=1)
         if not self.size_average:
             loss_l, loss_c, loss_ct = loss_l / N, loss_c / N, loss_ct / N
             loss_prop_l, loss_prop_c = loss_prop_l / PN, loss_prop_c / PN
-            loss_act, loss_prop_act = loss_act / AN, loss_prop_act / PAN
+            if self.os_head:
+                loss_act, loss_prop_act = loss_act / AN, loss_prop_act / PAN
         if self.iou_aware:
             # reference pairing: iou_pred is (K,B) flattened prior-major against batch-major logits
             ious = iou_pred.transpose(0, 1).reshape(-1)

@@ -6,6 +6,9 @@ decode_predictions (:112-140), filtering (:143-162), get_video_detections (:165-
 the network in large batches (the reference runs b=1, test.py:227-235), then TWO launches do the
 rest -- otal_decode_clips (decode + per-class threshold for every clip) and otal_softnms_classes
 (gather + Soft-NMS for every (video, class)) -- with no host synchronisation until the final copy.
+The head decides the decode (test.py:79-162): the OpenTAL head (os_head + use_edl: Dirichlet scores x actionness) and the
+closed-set Softmax / EDL baselines (os_head false: softmax or Dirichlet scores over C = classes + 1 logits, the background
+class dropped, no actionness; otal_decode_clips_ex).
 Multi-GPU: shard the video list across ranks (as the reference's unused AFSD/anet/test.py:248-273
 sketches); there is no collective on this path.
 """
@@ -63,12 +66,26 @@ def prepare_windows(videos, windows, clip_length):
     return out
 
 
-def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01):
+def head_mode(net):
+    """(os_head, use_edl, evidence) of a THUMOS14 BDNet: which decode its outputs need.  A network that does not say is
+    taken for the OpenTAL head (os_head, use_edl, exp evidence)."""
+    return bool(getattr(net, 'os_head', True)), bool(getattr(net, 'use_edl', True)), getattr(net, 'evidence', 'exp')
+
+
+def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01, os_head=True, use_edl=True, evidence='exp'):
     """Batched parse_output + decode_predictions + threshold masks.  output_dict: model outputs for
-    `n` clips; offsets/fps: per-clip tensors or lists.  Returns dict(seg, score, unct, actn, flag)."""
+    `n` clips; offsets/fps: per-clip tensors or lists.  Returns dict(seg, score, unct, actn, flag).
+    os_head / use_edl / evidence: the network's head (head_mode).  The closed-set head (os_head False) has a background
+    logit, which score / flag leave out (K - 1 classes); unct is None without use_edl, actn None without os_head."""
+    if use_edl and evidence != 'exp':
+        raise NotImplementedError(f"evidence {evidence!r}: the decode kernel computes exp evidence only")
+    if os_head and not use_edl:
+        raise NotImplementedError("an actionness head with softmax scores is not a THUMOS14 configuration")
     loc = output_dict['loc'].contiguous()
     n, A, _ = loc.shape
     K = output_dict['conf'].shape[-1]
+    if not os_head:
+        return _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, use_edl)
     dev = loc.device
     offs = torch.as_tensor(offsets, dtype=torch.float32, device=dev).contiguous()
     fpst = torch.as_tensor(fps, dtype=torch.float32, device=dev).contiguous()
@@ -88,25 +105,63 @@ def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01):
     return dict(seg=seg, score=score, unct=unct, actn=actn, flag=flag)
 
 
-def decode_predictions(output_dict, idx, offset, sample_fps, clip_length=256):
+def _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, use_edl):
+    """The closed-set head: otal_decode_clips_ex with softmax (score_fn 1) or Dirichlet (0) scores, class 0 dropped and
+    no actionness (test.py:112-162 with os_head False)."""
+    n, A, _ = loc.shape
+    K = output_dict['conf'].shape[-1]
+    dev = loc.device
+    offs = torch.as_tensor(offsets, dtype=torch.float32, device=dev).contiguous()
+    fpst = torch.as_tensor(fps, dtype=torch.float32, device=dev).contiguous()
+    if fpst.numel() == 1:
+        fpst = fpst.expand(n).contiguous()
+    seg = torch.empty((n, A, 2), device=dev)
+    score = torch.empty((n, K - 1, A), device=dev)
+    unct = torch.empty((n, A), device=dev) if use_edl else None
+    flag = torch.empty((n, K - 1, A), dtype=torch.uint8, device=dev)
+    t = lambda k: output_dict[k].contiguous()
+    L.check(L.lib().otal_decode_clips_ex(L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(output_dict['priors'].contiguous()),
+                                         L.ptr(t('conf')), L.ptr(t('prop_conf')), L.ptr(t('center')), None, None,
+                                         L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score),
+                                         None if unct is None else L.ptr(unct), None, L.ptr(flag), n, A, K,
+                                         ctypes.c_float(clip_length), ctypes.c_float(conf_thresh), 0 if use_edl else 1, 1,
+                                         L.stream()), "otal_decode_clips_ex")
+    return dict(seg=seg, score=score, unct=unct, actn=None, flag=flag)
+
+
+def decode_predictions(output_dict, idx, offset, sample_fps, clip_length=256, os_head=True, use_edl=True, evidence='exp'):
     """Single-clip view with the reference's return values (test.py:112-140):
-    decoded_segments (A,2), conf_scores (K,A), uncertainty (A,), actionness (A,)."""
+    decoded_segments (A,2), conf_scores (K,A), uncertainty (A,) or None, actionness (A,) or None.
+    Closed-set heads: conf_scores holds the K - 1 non-background classes (row c = reference row c + 1)."""
     one = {k: (v[idx:idx + 1] if (v is not None and k != 'priors') else v) for k, v in output_dict.items()}
-    d = decode_clips(one, [float(offset)], [float(sample_fps)], clip_length)
-    return d['seg'][0], d['score'][0], d['unct'][0], d['actn'][0]
+    d = decode_clips(one, [float(offset)], [float(sample_fps)], clip_length, os_head=os_head, use_edl=use_edl,
+                     evidence=evidence)
+    first = lambda v: None if v is None else v[0]
+    return d['seg'][0], d['score'][0], first(d['unct']), first(d['actn'])
 
 
 def filtering(decoded_segments, conf_score_cls, uncertainty, actionness, conf_thresh, use_edl=True, os_head=True):
-    """test.py:143-162 for one class: (n,5) rows [start,end,score,unct,act] or None."""
-    m = (conf_score_cls > conf_thresh) & (actionness > 0.5)
+    """test.py:143-162 for one class: (n, 3 + use_edl + os_head) rows [start,end,score(,unct)(,act)] or None."""
+    m = conf_score_cls > conf_thresh
+    if os_head:
+        m = m & (actionness > 0.5)
     if int(m.sum()) == 0:
         return None
-    return torch.cat([decoded_segments[m], conf_score_cls[m, None], uncertainty[m, None], actionness[m, None]], -1)
+    cols = [decoded_segments[m], conf_score_cls[m, None]]
+    if use_edl:
+        cols.append(uncertainty[m, None])
+    if os_head:
+        cols.append(actionness[m, None])
+    return torch.cat(cols, -1)
 
 
 def softnms_classes(dec, clip_start, top_k=5000, sigma=0.5, score_threshold=0.001):
     """All (video, class) Soft-NMS problems in one launch.  clip_start: per-video clip ranges (V+1).
-    Returns rows (V,K,top_k,5), counts (V,K), index (V,K,top_k)."""
+    Returns rows (V,K,top_k,cols), counts (V,K), index (V,K,top_k); cols = 3 + use_edl + os_head, i.e. 5 for the OpenTAL
+    head ([start,end,score,unct,act]), 4 for the closed-set EDL and 3 for the Softmax baseline."""
+    cols = 3 + (dec.get('unct') is not None) + (dec.get('actn') is not None)
+    if dec.get('actn') is not None and dec.get('unct') is None:
+        raise NotImplementedError("actionness rows without uncertainty")
     n, K, A = dec['score'].shape
     dev = dec['score'].device
     cs = torch.as_tensor(clip_start, dtype=torch.int32, device=dev).contiguous()
@@ -114,23 +169,25 @@ def softnms_classes(dec, clip_start, top_k=5000, sigma=0.5, score_threshold=0.00
     starts = [int(v) for v in clip_start]
     max_clips = max(b - a for a, b in zip(starts[:-1], starts[1:]))
     tk = min(int(top_k), max_clips * A)
-    out = torch.zeros((V, K, tk, 5), device=dev)
+    out = torch.zeros((V, K, tk, cols), device=dev)
     counts = torch.zeros((V, K), dtype=torch.int32, device=dev)
     index = torch.zeros((V, K, tk), dtype=torch.int32, device=dev)
     lib = L.lib()
     lib.otal_softnms_scratch_bytes.restype = ctypes.c_size_t
     nbytes = int(lib.otal_softnms_scratch_bytes(int(n), int(max_clips), int(A), int(K)))   # > 0: a video exceeds the LDS working set
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    L.check(lib.otal_softnms_classes_ws(L.ptr(dec['seg']), L.ptr(dec['score']), L.ptr(dec['unct']),
-                                        L.ptr(dec['actn']), L.ptr(dec['flag']), L.ptr(cs), V, max_clips, A, K,
+    opt = lambda v: None if v is None else L.ptr(v)
+    L.check(lib.otal_softnms_classes_ws(L.ptr(dec['seg']), L.ptr(dec['score']), opt(dec.get('unct')),
+                                        opt(dec.get('actn')), L.ptr(dec['flag']), L.ptr(cs), V, max_clips, A, K,
                                         ctypes.c_float(sigma), tk, ctypes.c_float(score_threshold), L.ptr(out),
-                                        L.ptr(counts), L.ptr(index), 5, L.ptr(scratch), ctypes.c_size_t(nbytes), int(n),
+                                        L.ptr(counts), L.ptr(index), cols, L.ptr(scratch), ctypes.c_size_t(nbytes), int(n),
                                         L.stream()), "otal_softnms_classes_ws")
     return out, counts, index
 
 
 def get_video_detections(rows, counts, idx_to_class=None, top_k=5000, duration=None, drop_empty=False):
-    """test.py:165-200: per-video proposal list from the suppressed rows of one video (K,top_k,5).
+    """test.py:165-200: per-video proposal list from the suppressed rows of one video (K,top_k,cols).  Rows of 3 or 4
+    columns (closed-set heads) give 'uncertainty' / 'actionness' 0.0 where the column is absent (test.py:197-198).
     With `duration` (seconds) the cross-dataset variant, test_cross_data.py:178-215: segments are clipped to
     [0, duration] and the ones left empty are dropped (`drop_empty` alone: that script's THUMOS14 leg, which passes
     no duration but still drops empty segments)."""
@@ -147,7 +204,8 @@ def get_video_detections(rows, counts, idx_to_class=None, top_k=5000, duration=N
                     if end <= start:
                         continue
                 proposal_list.append({'label': name, 'score': float(r[2]), 'segment': [start, end],
-                                      'uncertainty': float(r[3]), 'actionness': float(r[4])})
+                                      'uncertainty': float(r[3]) if len(r) > 3 else 0.0,
+                                      'actionness': float(r[4]) if len(r) > 4 else 0.0})
     return proposal_list
 
 
@@ -160,6 +218,10 @@ def detect_batch(net, videos, sample_fps, clip_length=256, stride=128, conf_thre
     `flow_videos` (2-channel optical flow) and the two networks' RAW outputs are averaged before decoding."""
     if (flow_net is None) != (flow_videos is None):
         raise RuntimeError("detect_batch: flow_net and flow_videos go together")
+    os_head, use_edl, evidence = head_mode(net)
+    if flow_net is not None and head_mode(flow_net) != (os_head, use_edl, evidence):
+        raise RuntimeError(f"detect_batch: the rgb and flow networks have different heads "
+                           f"({(os_head, use_edl, evidence)} vs {head_mode(flow_net)})")
     clips, offsets, fps, clip_start = [], [], [], [0]
     for v, data in enumerate(videos):
         offs = get_offsets(data.shape[1], clip_length, stride)
@@ -177,15 +239,11 @@ def detect_batch(net, videos, sample_fps, clip_length=256, stride=128, conf_thre
         if flow_net is not None:
             out = fuse_outputs(out, flow_net(prepare_windows(flow_videos, clips[i:i + batch_clips], clip_length)))
         outs.append(out)
-    if flow_net is not None and 'unct' not in outs[0]:
-        # fuse_outputs only carries the uncertainty maps when BOTH networks produced them (use_edl + os_head); the reference's
-        # two-stream fusion of a closed-set model (thumos14.yaml) decodes softmax scores, which this decode kernel does not
-        raise NotImplementedError("two-stream fusion needs evidential (use_edl, os_head) networks on both streams")
-    keys = ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'act', 'prop_act', 'priors') + \
-        (('unct', 'prop_unct') if flow_net is not None else ())
+    keys = ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'priors') + (('act', 'prop_act') if os_head else ()) + \
+        (('unct', 'prop_unct') if flow_net is not None and use_edl else ())
     merged = {k: (torch.cat([o[k] for o in outs], 0) if k != 'priors' else outs[0][k]) for k in keys}
-    dec = decode_clips(merged, offsets, fps, clip_length, conf_thresh)
-    if flow_net is not None:
+    dec = decode_clips(merged, offsets, fps, clip_length, conf_thresh, os_head=os_head, use_edl=use_edl, evidence=evidence)
+    if flow_net is not None and use_edl:
         # the decode kernel derives the uncertainty from the (fused) logits; the reference averages the two networks'
         # OWN uncertainties instead (parse_output :105-108, decode_predictions :122) -- not the same number
         dec['unct'] = ((merged['unct'] + merged['prop_unct']) / 2.0).contiguous()
