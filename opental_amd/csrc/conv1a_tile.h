@@ -18,8 +18,7 @@ struct Conv1aTileArgs {
     int flags;                  // unused: kept so that the kernel argument offsets (and the kernel code) stay as they are
 };
 
-// 1 when the geometry is the tiled kernel's (To % 4 == 0, Ho % 4 == 0; everything else is checked by the caller)
-__attribute__((visibility("hidden"))) int conv1a_tile_eligible(int To, int Ho);
+// (which geometries it serves: conv_select.h, conv1a_tile_eligible)
 __attribute__((visibility("hidden"))) int launch_conv1a_tile(const Conv1aTileArgs& a, void* ws, size_t ws_bytes, hipStream_t st);
 
 }  // namespace otal_conv

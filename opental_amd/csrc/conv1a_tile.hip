@@ -24,6 +24,7 @@
 // so the two kernels agree bit for bit.  Measured (b = 8): 0.64 -> 0.41 ms per op, matrix pipe 33 -> 58 % busy.
 #include "common.h"
 #include "conv1a_tile.h"
+#include "conv_select.h"
 #include <type_traits>
 
 namespace {
@@ -51,7 +52,7 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-constexpr int TT = 4, TR = 4, WO = 48;                      // output tile: planes x rows x columns
+constexpr int TT = C1T_TT, TR = C1T_TR, WO = 48;            // output tile: planes x rows x columns (conv_select.h)
 constexpr int NPL = 2 * TT + 5, NR = 2 * TR + 5;            // input planes / rows under it
 constexpr int NC = 102, PITCH = NC * 8, PLANE = NR * PITCH; // pixels per patch row (w = -2 .. 99), bytes
 constexpr int NT = 512, NWAVE = NT / 64, WPOS = TT * TR * WO / NWAVE;      // 96 positions per wave
@@ -329,10 +330,6 @@ __global__ __launch_bounds__(256) void pack_conv1a_operand_order_kernel(unsigned
 }
 
 }  // namespace
-
-int otal_conv::conv1a_tile_eligible(int To, int Ho) {
-    return To % TT == 0 && Ho % TR == 0 && !OTAL_OPT("OTAL_CONV_1A_NOTILE");
-}
 
 int otal_conv::launch_conv1a_tile(const Conv1aTileArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     if ((2 * a.x_cs + (int64_t)a.Ti * a.Hi * 96) * 4 >= (1LL << 31)) return OTAL_E_UNSUPPORTED;

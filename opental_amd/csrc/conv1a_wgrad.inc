@@ -220,16 +220,6 @@ __global__ __launch_bounds__(256, 2) void conv1a_wgrad_direct_kernel(const W1aAr
     }
 }
 
-static inline bool conv1a_wgrad_eligible(const ConvGeom& g, int prec, const void* x, const void* dy) {
-    if (!prec || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NO1AW")) return false;
-    if (g.Cin != 3 || g.Cout > 64 || g.kt != 7 || g.kh != 7 || g.kw != 7 || g.st != 2 || g.sh != 2 || g.sw != 2) return false;
-    if (g.pt != 2 || g.ph != 2 || g.pw != 2 || g.Wi != 96 || g.Wo != C1_WO || g.Hi != 2 * g.Ho || g.Ti != 2 * g.To) return false;
-    if (g.To % 2 || g.Ho % 2 || g.x_bs % 4 || g.x_cs % 4 || g.y_bs % 4 || g.y_cs % 4) return false;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(dy) & 15)) return false;
-    const int64_t ex = gather_extent_bytes(g, MODE_FWD), ey = gather_extent_bytes(g, MODE_DGRAD);
-    return ex > 0 && ey > 0 && ex < (1LL << 31) && ey < (1LL << 31);
-}
-
 int launch_conv1a_wgrad(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     const ConvGeom& g = a.g;
     W1aArgs d;

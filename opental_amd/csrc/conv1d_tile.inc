@@ -211,20 +211,6 @@ __global__ __launch_bounds__(256) void conv1d_tile_kernel(const ConvArgs a) {
     for (int r = 0; r < 16; ++r) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), ro, vo[r], 0, 0);
 }
 
-static inline bool conv1d_tile_eligible(const ConvGeom& g, int mode, int prec, const void* src, const ConvArgs& a) {
-    if (!prec || mode == MODE_WGRAD || OTAL_OPT("OTAL_CONV_NO1DTILE")) return false;
-    if (g.Hi != 1 || g.Wi != 1 || g.Ho != 1 || g.Wo != 1 || g.kh != 1 || g.kw != 1 || g.st != 1 || g.To != g.Ti) return false;
-    if (!((g.kt == 1 && g.pt == 0) || (g.kt == 3 && g.pt == 1))) return false;
-    if (g.Ti > 4096) return false;
-    if ((mode == MODE_FWD ? g.Cout : g.Cin) > 2048) return false;    // (the collapsed projection's 29952-row GEMM is not a temporal layer)
-    const int C = mode == MODE_FWD ? g.Cin : g.Cout;
-    if (C % 128) return false;                              // whole K chunks (128 channels; 64 on the 256-position maps)
-    if (mode == MODE_DGRAD && a.emask) return false;       // the 1-D layers carry no fused ReLU / BN mask
-    if (((uintptr_t)src & 3)) return false;
-    const int64_t ext = gather_extent_bytes(g, mode);
-    return ext > 0 && ext < (1LL << 31);
-}
-
 template <int KT, int MODE>
 static int launch_c1t(const ConvArgs& a, dim3 grid, hipStream_t st) {
     constexpr int lds = 2 * ((64 + 8) * (128 * 2 + 16) + 32 * (KT * 128 * 2 + 16));

@@ -308,16 +308,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const S1Args a) 
     }
 }
 
-// the launch: eligibility, tile shape, grid
-static inline bool conv1x1_stream_eligible(const ConvGeom& g, int mode) {
-    if (OTAL_OPT("OTAL_CONV_NO1X1STREAM")) return false;
-    if (g.kt != 1 || g.kh != 1 || g.kw != 1 || g.st != 1 || g.sh != 1 || g.sw != 1 || g.nlev > 1) return false;
-    const int64_t P = conv_out_positions(g);
-    if (P != conv_in_positions(g) || P % 128) return false;
-    const int C = mode == MODE_FWD ? g.Cin : g.Cout;
-    return C % 8 == 0;
-}
-
+// the launch: tile shape, grid (eligibility: conv_select.h)
 template <int MODE>
 static int launch_conv1x1_stream(const ConvArgs& a, const unsigned short* wp, size_t wp_bytes, int Mpad, hipStream_t st) {
     const ConvGeom& g = a.g;

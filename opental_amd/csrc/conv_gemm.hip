@@ -21,6 +21,7 @@
 // Split-K writes fp32 slabs that a second kernel reduces in a fixed order (deterministic).
 #include "common.h"
 #include "conv_index.h"
+#include "conv_select.h"
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -37,14 +38,13 @@
 #include "conv1a_tile.h"
 namespace otal_conv {
 struct ConvArgs;
-// part 1's dispatcher: the launch for bf16-stored tensors (a.half / a.xhalf set), or OTAL_E_UNSUPPORTED
-__attribute__((visibility("hidden"))) int launch_half(int mode, ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st);
+// part 1: one step (conv_select.h: ConvKernel, vector width cw) of a plan for bf16-stored tensors on both sides of the layer
+__attribute__((visibility("hidden"))) int launch_half(int mode, int kernel, int cw, ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st);
 }  // namespace otal_conv
 
 namespace {
 
 constexpr int NT = 256;
-enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_WGRAD = 2 };
 // (NO_STORE / NO_BARRIER: never set.  conv_gemm_kernel still tests them: without the two run-time branches the compiler
 //  lays its loop out differently -- more SGPRs in some instantiations, a 20-byte private segment in two)
 enum { EPI_RELU = 1, EPI_ACCUM = 2, NO_STORE = 8, NO_BARRIER = 16, EPI_NPAD8 = 32 };
@@ -1796,8 +1796,6 @@ __global__ __launch_bounds__(256) void build_tap_table_kernel(int2* __restrict__
     tab[k] = e;
 }
 
-constexpr size_t TAB_PAD = 64;      // entries readable past K (a K step may run up to BK-1 rows over)
-static inline size_t tab_bytes(int K) { return (((size_t)K + TAB_PAD) * sizeof(int2) + 255) & ~(size_t)255; }
 
 // fixed-order reduction of the split-K slabs + the same epilogue.  V consecutive elements per thread (float4 when the
 // slab size allows); the loads of 8 splits are issued together and THEN added in split order -- the sum order (and so the
@@ -2109,42 +2107,6 @@ int fill_geom(ConvGeom& g, const int* d) {
     if ((int64_t)g.B * g.To * g.Ho * g.Wo >= (1LL << 31) || (int64_t)g.B * g.Ti * g.Hi * g.Wi >= (1LL << 31) ||
         (int64_t)g.Cin * g.kt * g.kh * g.kw >= (1LL << 31) || (int64_t)g.Cout * g.kt * g.kh * g.kw >= (1LL << 31)) return OTAL_E_SHAPE;
     return 0;
-}
-
-// tile height: least padded M, with a small penalty for the lower arithmetic intensity of short tiles
-// (192-row tiles for the chunked forward / data gradient: 2c forward +16 %; the weight gradient's measured -9 %)
-int choose_bm(int M, bool tall = false) {
-    if (tall && M % 192 == 0) return 192;                  // one 192-row tile re-fetches the gathered operand half as often
-    const int cand[4] = {128, 96, 64, 32};
-    const double pen[4] = {1.00, 1.03, 1.10, 1.30};
-    int best = 128;
-    double bc = 1e30;
-    for (int i = 0; i < 4; ++i) {
-        const double c = (double)((M + cand[i] - 1) / cand[i] * cand[i]) * pen[i];
-        if (c < bc) { bc = c; best = cand[i]; }
-    }
-    return best;
-}
-
-// choose split-K so that the grid fills the chip (256 CUs) without shredding K
-int choose_splits(int tiles, int K, int prec = 1, bool wgrad = false) {
-    // bf16: >= 8 K steps of 32 per split (fewer, larger slabs: measured +4 % step throughput over 4);
-    // fp32 parity path: 128 k per split as in the version the gradient-parity fixtures were validated with
-    // The vector weight-gradient kernel keeps 4 workgroups per CU resident and its K is huge (all positions): it wants two
-    // full waves of workgroups (2048; 512 left it at 2 waves per SIMD, 61 % of wave time parked).  Splits of >= 16 K steps:
-    // a K step is latency-bound (~1 us) when few workgroups are resident, so the small 1x1 / 1-D layers (18 k or 1 k
-    // positions, a handful of tiles) finish sooner as many short splits than as a few long ones (measured per step:
-    // 48 steps 407.6 clips/s, 24: 419.0, 12: 420.1, 6: 416.2).  Forward / data gradient keep the 512-workgroup target.
-    const bool wv = wgrad && prec;
-    const int target = wv ? 2048 : 512;
-    const int minsteps = wv ? 16 : (prec ? 8 : 4);
-    const int cap = wv ? 1024 : 384;
-    if (tiles >= target * 3 / 4) return 1;
-    int want = (target + tiles - 1) / tiles;
-    int maxs = K / (minsteps * 32);
-    if (maxs < 1) maxs = 1;
-    int s = want < maxs ? want : maxs;
-    return s < 1 ? 1 : (s > cap ? cap : s);
 }
 
 static const float* zero_word_address() {
@@ -2533,7 +2495,7 @@ __global__ __launch_bounds__(256) void pack_direct_kernel(unsigned* __restrict__
 // add up instead of overlapping.  Round 4: geometries with To % 4 == 0 and Ho % 4 == 0 (the training shapes) run on
 // conv1a_tile_fwd_kernel (conv1a_tile.hip: 4 x 4 x 48 tiles, persistent workgroups, weights in registers); this kernel
 // serves the rest and is the bit-exact reference of that one (tests/test_ops_gpu.py).
-constexpr int C1_TT = 2, C1_TR = 2, C1_WO = 48, C1_NPL = 9, C1_NR = 9, C1_NC = 104, C1_PITCH = C1_NC * 8;   // bytes per patch row
+constexpr int C1_NPL = 9, C1_NR = 9, C1_NC = 104, C1_PITCH = C1_NC * 8;   // bytes per patch row
 constexpr int C1_BNP = C1_TT * C1_TR * C1_WO, C1_NT = C1_BNP * 2, C1_PA = 80, C1_STEPS = 49;
 
 struct Conv1aArgs {
@@ -2708,20 +2670,10 @@ __global__ __launch_bounds__(C1_NT) void conv1a_direct_fwd_kernel(const Conv1aAr
     store_acc<MODE_FWD, WM, 1, BM>(a, acc, m0, n_wave, 0, 0, lane, 0, reinterpret_cast<float*>(smA[0]));
 }
 
-static inline bool conv1a_half_out_ok(const ConvGeom& g, const void* y) {
-    return g.y_bs % 8 == 0 && g.y_cs % 8 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-}
-static inline bool conv1a_direct_eligible(const ConvGeom& g, int mode, int prec, const void* x) {
-    if (!prec || mode != MODE_FWD || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NO1A")) return false;
-    if (g.Cin != 3 || g.kt != 7 || g.kh != 7 || g.kw != 7 || g.st != 2 || g.sh != 2 || g.sw != 2) return false;
-    if (g.pt != 2 || g.ph != 2 || g.pw != 2 || g.Wi != 96 || g.Wo != C1_WO || g.Hi != 2 * g.Ho || g.Ti != 2 * g.To) return false;
-    if (g.To % C1_TT || g.Ho % C1_TR || g.x_bs % 4 || g.x_cs % 4 || (reinterpret_cast<uintptr_t>(x) & 15)) return false;
-    return (int64_t)g.B * g.To * g.Ho * g.Wo < (1LL << 31);
-}
 static inline size_t conv1a_wp_bytes(int M) { return (((size_t)((M + 63) / 64 * 64) * C1_STEPS * 64) + 255) & ~(size_t)255; }
 
 int launch_conv1a_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (otal_conv::conv1a_tile_eligible(a.g.To, a.g.Ho) && !(a.flags & EPI_ACCUM)) {      // 4 x 4 x 48 tiles (conv1a_tile.hip)
+    if (conv1a_tile_eligible(a.g.To, a.g.Ho) && !(a.flags & EPI_ACCUM)) {      // 4 x 4 x 48 tiles (conv1a_tile.hip)
         otal_conv::Conv1aTileArgs t;
         t.x = a.x; t.w = a.w; t.wp = nullptr; t.out = a.out; t.scale = a.scale; t.shift = a.shift;
         t.x_bs = a.g.x_bs; t.x_cs = a.g.x_cs; t.y_bs = a.g.y_bs; t.y_cs = a.g.y_cs;
@@ -2755,7 +2707,7 @@ int launch_conv1a_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st)
 // operand is an aligned 16-byte LDS read, and the two shifted taps are the aligned neighbours funnel-shifted by one
 // element, with the taps that would cross a level boundary masked per position.  Partial sums go to split-K slabs
 // (split = sample x chunk), reduced in order by splitk_reduce_kernel.
-constexpr int W1_TC = 128, W1_PITCH = 304;      // positions per chunk; LDS row pitch in bytes (152 bf16: 2-way conflicts at most)
+constexpr int W1_PITCH = 304;      // LDS row pitch in bytes (152 bf16: 2-way conflicts at most); W1_TC positions per chunk
 
 template <int KT>
 __global__ __launch_bounds__(256) void conv_wgrad1d_kernel(const ConvArgs a, int nchunks, int units, int upw) {
@@ -2885,16 +2837,6 @@ __global__ __launch_bounds__(256) void conv_wgrad1d_kernel(const ConvArgs a, int
     }
 }
 
-static inline int wgrad1d_chunks(const ConvGeom& g) { return (g.Ti + W1_TC - 1) / W1_TC; }
-static inline bool wgrad1d_eligible(const ConvGeom& g, int prec, const void* x, const void* dy) {
-    if (!prec || OTAL_OPT("OTAL_CONV_NOW1D")) return false;
-    if (g.Hi != 1 || g.Wi != 1 || g.Ho != 1 || g.Wo != 1 || g.kh != 1 || g.kw != 1 || g.st != 1 || g.To != g.Ti) return false;
-    if (!((g.kt == 1 && g.pt == 0) || (g.kt == 3 && g.pt == 1))) return false;
-    if (g.Cin % 64 || (g.x_bs | g.x_cs | g.y_bs | g.y_cs) & 1) return false;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 7) return false;
-    return (int64_t)g.B * wgrad1d_chunks(g) <= 1024;
-}
-
 int launch_wgrad1d(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     const int nchunks = wgrad1d_chunks(a.g), units = a.g.B * nchunks;
     // units per workgroup = (sample, chunk) units folded into one split-K slab.  Round 2 (every reduction its own launch behind
@@ -2920,32 +2862,7 @@ int launch_wgrad1d(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     return 0;
 }
 
-// ---- chunked bf16 path: eligibility, workspace layout [chunk table][packed bf16 weights][split-K slabs]
-constexpr int CHUNK_PAD = 16;       // table entries readable past Kp/8 (two K steps of prefetch)
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-static inline int chunk_kp(int K) { return (K + 31) / 32 * 32; }
-static inline size_t chunk_tab_bytes(int K) { return align256(((size_t)chunk_kp(K) / 8 + CHUNK_PAD) * sizeof(int2)); }
-static inline size_t chunk_wp_bytes(int M, int BM, int K) {      // + one K step so the prefetch past Kp stays inside
-    return align256(((size_t)((M + BM - 1) / BM * BM) * chunk_kp(K) + 64) * sizeof(unsigned short));
-}
-// extent in bytes of the tensor the gather reads (channel-sliced views: strides come from the caller)
-static inline int64_t gather_extent_bytes(const ConvGeom& g, int mode, int esz = 4) {
-    if (mode == MODE_FWD) return esz * ((int64_t)(g.B - 1) * g.x_bs + (int64_t)(g.Cin - 1) * g.x_cs + conv_in_positions(g));
-    return esz * ((int64_t)(g.B - 1) * g.y_bs + (int64_t)(g.Cout - 1) * g.y_cs + conv_out_positions(g));
-}
-// bf16-stored tensors around a layer (H kernels): 16-byte runs of eight positions must stay inside a sample and be aligned
-static inline bool half_layout_ok(const ConvGeom& g, const void* x, const void* y) {
-    return conv_out_positions(g) % 8 == 0 && conv_in_positions(g) % 8 == 0 && g.x_bs % 8 == 0 && g.x_cs % 8 == 0 &&
-           g.y_bs % 8 == 0 && g.y_cs % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
-}
-static inline bool chunk_eligible(const ConvGeom& g, int mode, int prec) {
-    if (!prec || mode == MODE_WGRAD) return false;
-    const int C = mode == MODE_FWD ? g.Cin : g.Cout;
-    if (C % 8 && !(mode == MODE_FWD && g.kw >= 3)) return false;    // forward has the kw-vector mode
-    const int64_t ext = gather_extent_bytes(g, mode);
-    return ext > 0 && ext < (int64_t)0xfffffff0u;       // 32-bit buffer offsets
-}
-
+// ---- chunked bf16 path: workspace layout [chunk table][packed bf16 weights][split-K slabs] (eligibility: conv_select.h)
 // positions one thread may fetch with a single vector load (see conv_gemm_bf16c_kernel)
 static inline int chunk_vector_width(const ConvGeom& g) {
     if (g.st != 1 || g.sh != 1 || g.sw != 1 || g.nlev > 1) return 1;
@@ -3088,38 +3005,7 @@ int launch_chunked(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     return 0;
 }
 
-// ---- vector WGRAD: eligibility, workspace layout [position table][split-K slabs]
-constexpr int PTAB_PAD = 64;        // entries readable past the last group (two K steps of prefetch at CW = 2 -> 32)
-// stride-2 pair mode of the vector WGRAD (Conv3d_1a): window ends must stay within 4 elements of the row
-static inline bool wgrad_pair_mode(const ConvGeom& g, int prec) {
-    if (!prec || g.nlev > 1) return false;
-    if (g.sw != 2 || g.st > 2 || g.sh > 2 || g.kw > 7 || g.pw > 3 || g.Wo % 8 || conv_out_positions(g) % 32) return false;
-    if (g.Wi - (2 * (g.Wo - 8) - g.pw + 6) < 12) return false;      // last window: elements 0..11 inside the row
-    const int64_t ex = 4 * ((int64_t)(g.B - 1) * g.x_bs + (int64_t)(g.Cin - 1) * g.x_cs + conv_in_positions(g));
-    const int64_t ey = 4 * ((int64_t)(g.B - 1) * g.y_bs + (int64_t)(g.Cout - 1) * g.y_cs + conv_out_positions(g));
-    return ex > 0 && ey > 0 && ex < (int64_t)0xffffff00u && ey < (int64_t)0xfffffff0u;
-}
-static inline int wgrad_vector_width(const ConvGeom& g, int prec) {
-    if (!prec) return 0;
-    if (g.st != 1 || g.sh != 1 || g.sw != 1 || g.nlev > 1) return 0;
-    if (g.To != g.Ti || g.Ho != g.Hi || g.Wo != g.Wi) return 0;
-    if ((g.kw != 1 && g.kw != 3) || g.pw != (g.kw - 1) / 2) return 0;
-    if (conv_out_positions(g) % 32) return 0;
-    const int64_t ex = 4 * ((int64_t)(g.B - 1) * g.x_bs + (int64_t)(g.Cin - 1) * g.x_cs + conv_in_positions(g));
-    const int64_t ey = 4 * ((int64_t)(g.B - 1) * g.y_bs + (int64_t)(g.Cout - 1) * g.y_cs + conv_out_positions(g));
-    if (ex <= 0 || ey <= 0 || ex >= (int64_t)0xfffffff0u || ey >= (int64_t)0xfffffff0u) return 0;
-    // a 1x1x1 kernel has no shifted tap: any 8 consecutive positions of a sample are one contiguous vector, whatever the row
-    // length (6x6 planes were on 2-element vectors, 3x3 planes on the generic kernel)
-    if (g.kt == 1 && g.kh == 1 && g.kw == 1) return 8;
-    if (g.Wi % 8 == 0) return 8;
-    if (g.Wi % 4 == 0) return 4;
-    if (g.Wi % 2 == 0) return 2;
-    return 0;
-}
-static inline size_t ptab_bytes(const ConvGeom& g, int cw) {
-    return align256(((size_t)g.B * conv_out_positions(g) / cw + PTAB_PAD) * sizeof(int2));
-}
-
+// ---- vector WGRAD: workspace layout [position table][split-K slabs] (eligibility: conv_select.h)
 template <bool H = false>
 int launch_wgrad_vector(ConvArgs& a, int cw, void* ws, size_t ws_bytes, hipStream_t st) {
     const bool pair = a.g.sw == 2;
@@ -3191,57 +3077,7 @@ int launch_wgrad_vector(ConvArgs& a, int cw, void* ws, size_t ws_bytes, hipStrea
     return 0;
 }
 
-// ---- direct 3x3x3 path: eligibility and launch
-static inline int direct_bm(const ConvGeom& g, int M) {
-    if (M % 96 == 0) return 96;
-    // one workgroup per CU and launch round: where 64-row tiles of 256 positions need a second, nearly empty round (the 6x6
-    // planes of Mixed_4b..4d b1b forward: 4 x 72 = 288 workgroups) and 96-row tiles do not (3 x 72 = 216), the padded rows
-    // are cheaper than the round -- forward 43 / 68 / 76 us on 64-row tiles against 56 us for Mixed_4e's 216 tiles of 96
-    if (M > 96) {
-        const int64_t nt = (int64_t)g.B * conv_out_positions(g) / 256;
-        const int64_t w64 = (M + 63) / 64 * nt, w96 = (M + 95) / 96 * nt;
-        if (w64 <= 512 && (w96 + 255) / 256 * 96 < (w64 + 255) / 256 * 64) return 96;
-    }
-    if (M % 64 == 0) return 64;
-    // 16 .. 32 rows (data gradient of the Inception b2b layers: M = Cin = 16 / 24 / 32; forward of Mixed_3b.b2b): one 32-row
-    // MFMA tile per wave.  LDS-read-bound (9 weight + 9 position fragments per 9 MFMAs), but these layers are tiny and ran
-    // on the gather kernel at 25 .. 90 us for 0.1 .. 1 GFLOP of work per sample
-    if (M <= 32) return 32;
-    const int pad64 = (M + 63) / 64 * 64;
-    return (pad64 - M) * 100 <= M * 34 ? 64 : 0;     // accept <= 34 % padded rows (Mixed_4e: 144 -> 192)
-}
-// positions per workgroup: 256 (8 waves), or 128 (4 waves) when 256 would leave the chip half empty (the 6x6 planes of
-// Mixed_4x: 72 position tiles); 0 = too few tiles either way (no split-K on this path)
-static inline int direct_bnp(const ConvGeom& g, int M) {
-    const int BM = direct_bm(g, M);
-    if (!BM) return 0;
-    const int64_t tm = (M + BM - 1) / BM, NP = (int64_t)g.B * conv_out_positions(g);
-    // (140: the 144 tiles of a one-M-tile layer on the 6x6 planes still take the 128-position form -- Mixed_4b / 4e b2b forward
-    //  17.5 -> 10.1 us, 27.6 -> 12.9 us, Mixed_4b b1b data gradient 71 -> 54 us against the gather kernel; tools/micro_planes6.py)
-    const int min_tiles = OTAL_OPT("OTAL_CONV_DIRECT_MINTILES");
-    // 512 positions (two tiles per wave: the weight fragments are shared, the kernel turns MFMA-bound) when that still gives
-    // every CU two rounds of workgroups and the tile stays inside one sample
-    // (96-row tiles only: a 64-row tile of 256 positions fits TWICE per CU -- 16 waves -- and measured faster than one 512 tile)
-    if (BM == 96 && conv_out_positions(g) % 512 == 0 && tm * (NP / 512) >= OTAL_OPT("OTAL_CONV_DIRECT_MINTILES512")) return 512;
-    if (tm * (NP / 256) >= min_tiles) return 256;
-    if (tm * (NP / 128) >= min_tiles) return 128;
-    return 0;
-}
-static inline bool direct_eligible(const ConvGeom& g, int mode, int prec, int M) {
-    if (OTAL_OPT("OTAL_CONV_NODIRECT") || !prec || mode == MODE_WGRAD || g.nlev > 1) return false;
-    if (g.kt != 3 || g.kh != 3 || g.kw != 3 || g.st != 1 || g.sh != 1 || g.sw != 1 || g.pt != 1 || g.ph != 1 || g.pw != 1) return false;
-    if (g.To != g.Ti || g.Ho != g.Hi || g.Wo != g.Wi || g.Wi > 24) return false;
-    const int P = conv_out_positions(g);
-    const int C = mode == MODE_FWD ? g.Cin : g.Cout;
-    if (P % 256 || C % 16 || !direct_bnp(g, M)) return false;
-    const int64_t ext = gather_extent_bytes(g, mode);
-    return ext > 0 && ext < (1LL << 31);
-}
-static inline size_t direct_wp_bytes(const ConvGeom& g, int M, int C) {
-    const int BM = direct_bm(g, M);
-    return align256((size_t)((M + BM - 1) / BM * BM) * C * 27 * 2 + 1024);
-}
-
+// ---- direct 3x3x3 path: launch (eligibility, tile height and weight pack size: conv_select.h)
 template <int BM, int BNP, int PX = 48, bool H = false>
 constexpr int direct_lds_bytes() { return 2 * BM * 304 + 2 * (BNP + (H ? 56 : 52)) * PX + 16; }
 template <int BM, int MODE, bool XPF2 = false, bool H = false>
@@ -3320,118 +3156,34 @@ int launch_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
 #include "proj_gemm.inc"
 #include "wgrad1x1.inc"
 
-// Which H kernel serves a launch with bf16-stored tensors on both sides (0: none).  fwd / dgrad: 1 direct 3x3x3, 2 chunked;
-// wgrad: 3 direct, 4 wide 1x1, 5 vector (the number is the vector width + 16).  Shared by part 1's dispatcher and part 0's
-// otal_conv_half_storage() query; x / dy may be null (the query has no tensors: alignment is then the caller's contract).
-static inline int half_kernel_kind(const ConvGeom& g, int mode, const void* x, const void* dy) {
-    if (g.nlev > 1) return 0;
-    if (conv_out_positions(g) % 8 || conv_in_positions(g) % 8 || g.x_bs % 8 || g.x_cs % 8 || g.y_bs % 8 || g.y_cs % 8) return 0;
-    if (mode == MODE_FWD || mode == MODE_DGRAD) {
-        const int M = mode == MODE_FWD ? g.Cout : g.Cin, C = mode == MODE_FWD ? g.Cin : g.Cout;
-        if (direct_eligible(g, mode, 1, M) && !(g.Wi & 1)) return 1;
-        if (chunk_eligible(g, mode, 1) && C % 8 == 0 && conv_in_positions(g) == conv_out_positions(g)) return 2;
-        return 0;
-    }
-    if (wgrad_direct_eligible(g, 1, x, dy)) return 3;
-    if (wgrad1x1_wide_eligible(g, 1, x, dy)) return 4;
-    if (const int cw = wgrad_vector_width(g, 1)) return 16 + cw;
-    return 0;
-}
-
+// ---- one launch: the kernels of its plan (conv_select.h), first to last.  A kernel's result is final unless its step says
+// that OTAL_E_UNSUPPORTED moves on to the next one.  The caller's prologue region reaches a launcher only when it holds that
+// launcher's layout.
 #if OTAL_CONV_PART == 1
 // bf16-stored tensors on BOTH sides of a backbone layer (fwd: x and y; dgrad: dy, dx and the ReLU mask; wgrad: x and dy): the H
-// instantiations of the direct 3x3x3, chunked, direct / wide / vector weight-gradient kernels.  Anything else: unsupported.
+// instantiations of the direct 3x3x3, chunked, direct / wide / vector weight-gradient kernels.
 }  // namespace
-int otal_conv::launch_half(int mode, ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
-    const ConvGeom& g = a.g;
-    if (!a.prec || !a.xhalf || !a.half || (a.flags & EPI_ACCUM)) return OTAL_E_UNSUPPORTED;
-    const void* px = mode == MODE_DGRAD ? (const void*)a.out : (const void*)a.x;
-    const void* py = mode == MODE_FWD ? (const void*)a.out : (const void*)a.dy;
-    if ((reinterpret_cast<uintptr_t>(px) | reinterpret_cast<uintptr_t>(py)) & 15) return OTAL_E_UNSUPPORTED;
-    if (mode == MODE_DGRAD && a.emask && (!a.mhalf || (reinterpret_cast<uintptr_t>(a.emask) & 15))) return OTAL_E_UNSUPPORTED;
-    const int kind = half_kernel_kind(g, mode, px, py);
-    // a persistent prologue region holds what the fp32-tensor launch of this geometry would use (prologue_kind): the direct
-    // kernel's weight pack wherever that kernel is eligible -- not what the chunked kernel reads
-    if (kind == 2 && direct_eligible(g, mode, 1, mode == MODE_FWD ? g.Cout : g.Cin)) a.pre = nullptr;
-    if (mode == MODE_FWD) {
-        if (kind == 1) return launch_direct<MODE_FWD, true>(a, ws, ws_bytes, st);
-        if (kind == 2) return launch_chunked<MODE_FWD, true>(a, ws, ws_bytes, st);
-        return OTAL_E_UNSUPPORTED;
+int otal_conv::launch_half(int mode, int kernel, int cw, ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+    switch (kernel) {
+        case CK_DIRECT:
+            if (mode == MODE_FWD) return launch_direct<MODE_FWD, true>(a, ws, ws_bytes, st);
+            return launch_direct<MODE_DGRAD, true>(a, ws, ws_bytes, st);
+        case CK_CHUNKED:
+            if (mode == MODE_FWD) return launch_chunked<MODE_FWD, true>(a, ws, ws_bytes, st);
+            return launch_chunked<MODE_DGRAD, true>(a, ws, ws_bytes, st);
+        case CK_WGRAD_DIRECT: return launch_wgrad_direct<true>(a, ws, ws_bytes, st);
+        case CK_WGRAD1X1: return launch_wgrad1x1_wide<true>(a, ws, ws_bytes, st);
+        case CK_WGRAD_VECTOR: return launch_wgrad_vector<true>(a, cw, ws, ws_bytes, st);
+        default: return OTAL_E_UNSUPPORTED;
     }
-    if (mode == MODE_DGRAD) {
-        if (kind == 1) return launch_direct<MODE_DGRAD, true>(a, ws, ws_bytes, st);
-        if (kind == 2) return launch_chunked<MODE_DGRAD, true>(a, ws, ws_bytes, st);
-        return OTAL_E_UNSUPPORTED;
-    }
-    if (kind == 3) {
-        const int e = launch_wgrad_direct<true>(a, ws, ws_bytes, st);
-        if (e != OTAL_E_UNSUPPORTED) return e;              // slabs do not fit: the vector kernel
-        if (const int cw = wgrad_vector_width(g, 1)) return launch_wgrad_vector<true>(a, cw, ws, ws_bytes, st);
-        return e;
-    }
-    if (kind == 4) {
-        const int e = launch_wgrad1x1_wide<true>(a, ws, ws_bytes, st);
-        if (e != OTAL_E_UNSUPPORTED) return e;
-        if (const int cw = wgrad_vector_width(g, 1)) return launch_wgrad_vector<true>(a, cw, ws, ws_bytes, st);
-        return e;
-    }
-    if (kind > 16) return launch_wgrad_vector<true>(a, kind - 16, ws, ws_bytes, st);
-    return OTAL_E_UNSUPPORTED;
 }
 namespace {
 #endif
 
 #if OTAL_CONV_PART == 0
+// the generic tap-table kernel: any geometry (the data gradient packs W^T first when it is given the natural layout)
 template <int MODE>
-int launch_mode(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (a.xhalf) return otal_conv::launch_half(MODE, a, ws, ws_bytes, st);      // bf16-stored tensors on both sides: part 1
-    if constexpr (MODE == MODE_WGRAD) {
-        if (conv1a_wgrad_eligible(a.g, a.prec, a.x, a.dy) && (!a.half || a.g.y_bs % 8 + a.g.y_cs % 8 == 0)) {
-            const int e = launch_conv1a_wgrad(a, ws, ws_bytes, st);
-            if (e != OTAL_E_UNSUPPORTED || a.half) return e;
-        }
-        if (a.half) return OTAL_E_UNSUPPORTED;              // bf16-stored dy: the kernels above only
-        if (proj_wgrad_eligible(a.g, a.prec, a.x, a.dy)) {  // the pyramid projections: short K, no split (proj_gemm.inc)
-            const int e = launch_proj_wgrad(a, st);
-            if (e != OTAL_E_UNSUPPORTED) return e;
-        }
-        if (wgrad_direct_eligible(a.g, a.prec, a.x, a.dy)) {
-            const int e = launch_wgrad_direct(a, ws, ws_bytes, st);
-            if (e != OTAL_E_UNSUPPORTED) return e;          // slabs do not fit: the vector kernel below
-        }
-        if (wgrad1x1_wide_eligible(a.g, a.prec, a.x, a.dy)) {
-            const int e = launch_wgrad1x1_wide(a, ws, ws_bytes, st);
-            if (e != OTAL_E_UNSUPPORTED) return e;
-        }
-        if (wgrad_pair_mode(a.g, a.prec)) return launch_wgrad_vector(a, 8, ws, ws_bytes, st);
-        if (const int cw = wgrad_vector_width(a.g, a.prec)) return launch_wgrad_vector(a, cw, ws, ws_bytes, st);
-        if (wgrad1d_eligible(a.g, a.prec, a.x, a.dy)) {
-            const int e = launch_wgrad1d(a, ws, ws_bytes, st);
-            if (e != OTAL_E_UNSUPPORTED) return e;          // workspace too small for the slabs: the generic kernel below
-        }
-    }
-    if constexpr (MODE == MODE_FWD) {
-        if (proj_fwd_eligible(a.g, MODE, a.prec, a.x, a.w)) {
-            const int e = launch_proj_fwd(a, ws, ws_bytes, st);
-            if (e != OTAL_E_UNSUPPORTED) return e;
-        }
-        if (a.half) {       // bf16-stored y: Conv3d_1a's direct kernel and the direct 3x3x3 kernel
-            if (!OTAL_OPT("OTAL_CONV_NO1A") && conv1a_direct_eligible(a.g, MODE, a.prec, a.x) && conv1a_half_out_ok(a.g, a.out))
-                return launch_conv1a_direct(a, ws, ws_bytes, st);
-            if (direct_eligible(a.g, MODE, a.prec, a.M) && conv1a_half_out_ok(a.g, a.out)) return launch_direct<MODE>(a, ws, ws_bytes, st);
-            return OTAL_E_UNSUPPORTED;
-        }
-        if (conv1a_direct_eligible(a.g, MODE, a.prec, a.x)) return launch_conv1a_direct(a, ws, ws_bytes, st);
-    }
-    if (a.half) return OTAL_E_UNSUPPORTED;
-    if constexpr (MODE != MODE_WGRAD) {
-        if (conv1d_tile_eligible(a.g, MODE, a.prec, MODE == MODE_FWD ? (const void*)a.x : (const void*)a.dy, a)) {
-            const int e = launch_conv1d_tile<MODE>(a, ws, ws_bytes, st);
-            if (e != OTAL_E_UNSUPPORTED) return e;
-        }
-        if (direct_eligible(a.g, MODE, a.prec, a.M)) return launch_direct<MODE>(a, ws, ws_bytes, st);
-        if (chunk_eligible(a.g, MODE, a.prec)) return launch_chunked<MODE>(a, ws, ws_bytes, st);
-    }
+int launch_generic(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     if constexpr (MODE == MODE_DGRAD) {
         if (a.w_natural) {          // the generic kernel wants W^T packed (Cin, Cout, kvol): build it at the front of the workspace
             const int kvol = conv_kvol(a.g);
@@ -3502,19 +3254,62 @@ int launch_mode(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
         else hipLaunchKernelGGL((conv_gemm_kernel<BM_, 128, WM_, WN_, MODE, AV_, 0>), grid, dim3(NT), 0, st, a);        \
     } while (0)
     const bool av = a.a_vec4 != 0;
-    if (false) {
-    } else {
-        if (BMsel == 128) { if (av) OTAL_LAUNCH(128, 2, 2, true); else OTAL_LAUNCH(128, 2, 2, false); }
-        else if (BMsel == 96) { if (av) OTAL_LAUNCH(96, 3, 1, true); else OTAL_LAUNCH(96, 3, 1, false); }
-        else if (BMsel == 64) { if (av) OTAL_LAUNCH(64, 2, 1, true); else OTAL_LAUNCH(64, 2, 1, false); }
-        else OTAL_LAUNCH(32, 1, 1, false);
-    }
+    if (BMsel == 128) { if (av) OTAL_LAUNCH(128, 2, 2, true); else OTAL_LAUNCH(128, 2, 2, false); }
+    else if (BMsel == 96) { if (av) OTAL_LAUNCH(96, 3, 1, true); else OTAL_LAUNCH(96, 3, 1, false); }
+    else if (BMsel == 64) { if (av) OTAL_LAUNCH(64, 2, 1, true); else OTAL_LAUNCH(64, 2, 1, false); }
+    else OTAL_LAUNCH(32, 1, 1, false);
 #undef OTAL_LAUNCH
     if (int e = otal_launch_status()) return e;
     if (splits > 1) {
         return launch_splitk_reduce<MODE>(a, st);
     }
     return 0;
+}
+
+// one step of a plan on fp32-stored tensors (or a bf16-stored output-side tensor: Conv3d_1a's kernels, the direct kernel)
+template <int MODE>
+int launch_kernel(const ConvStep& s, ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+    if constexpr (MODE == MODE_WGRAD) {
+        switch (s.kernel) {
+            case CK_CONV1A_WGRAD: return launch_conv1a_wgrad(a, ws, ws_bytes, st);
+            case CK_PROJ_WGRAD: return launch_proj_wgrad(a, st);
+            case CK_WGRAD_DIRECT: return launch_wgrad_direct(a, ws, ws_bytes, st);
+            case CK_WGRAD1X1: return launch_wgrad1x1_wide(a, ws, ws_bytes, st);
+            case CK_WGRAD_VECTOR: return launch_wgrad_vector(a, s.cw, ws, ws_bytes, st);
+            case CK_WGRAD1D: return launch_wgrad1d(a, ws, ws_bytes, st);
+        }
+    } else {
+        switch (s.kernel) {
+            case CK_PROJ: if constexpr (MODE == MODE_FWD) return launch_proj_fwd(a, ws, ws_bytes, st); break;
+            case CK_CONV1A: if constexpr (MODE == MODE_FWD) return launch_conv1a_direct(a, ws, ws_bytes, st); break;
+            case CK_CONV1D_TILE: return launch_conv1d_tile<MODE>(a, ws, ws_bytes, st);
+            case CK_DIRECT: return launch_direct<MODE>(a, ws, ws_bytes, st);
+            case CK_CHUNKED: return launch_chunked<MODE>(a, ws, ws_bytes, st);
+        }
+    }
+    if (s.kernel == CK_GENERIC) return launch_generic<MODE>(a, ws, ws_bytes, st);
+    return OTAL_E_UNSUPPORTED;
+}
+
+template <int MODE>
+int launch_mode(ConvArgs& a, int precision, void* ws, size_t ws_bytes, hipStream_t st) {
+    ConvQuery q = {};
+    q.g = a.g;
+    q.mode = MODE;
+    q.precision = precision;
+    q.accumulate = (a.flags & EPI_ACCUM) ? 1 : 0;
+    q.has_mask = a.emask ? 1 : 0;
+    q.x = (uintptr_t)a.x; q.w = (uintptr_t)a.w; q.dy = (uintptr_t)a.dy; q.out = (uintptr_t)a.out; q.mask = (uintptr_t)a.emask;
+    const ConvPlan p = conv_plan(q);
+    const void* pre = a.pre;
+    int e = OTAL_E_UNSUPPORTED;
+    for (int i = 0; i < p.n; ++i) {
+        const ConvStep& s = p.step[i];
+        a.pre = conv_step_prologue(s.kernel) == p.prologue ? pre : nullptr;
+        e = a.xhalf ? otal_conv::launch_half(MODE, s.kernel, s.cw, a, ws, ws_bytes, st) : launch_kernel<MODE>(s, a, ws, ws_bytes, st);
+        if (e != OTAL_E_UNSUPPORTED || !s.next) return e;
+    }
+    return e;
 }
 #endif      // OTAL_CONV_PART == 0
 
@@ -3566,7 +3361,7 @@ extern "C" int otal_conv_fwd(const int* geom, const int64_t* strides, const floa
     if ((a.half || a.xhalf) && !a.prec) return OTAL_E_UNSUPPORTED;
     if (a.xhalf && !a.half) return OTAL_E_UNSUPPORTED;      // a bf16 x is only served together with a bf16 y
     a.pre = prologue;
-    return launch_mode<MODE_FWD>(a, ws, ws_bytes, (hipStream_t)stream);
+    return launch_mode<MODE_FWD>(a, precision, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int otal_conv_dgrad(const int* geom, const int64_t* strides, const float* dy, const float* wt_packed,
@@ -3590,7 +3385,7 @@ extern "C" int otal_conv_dgrad(const int* geom, const int64_t* strides, const fl
     if ((a.half || a.xhalf || a.mhalf) && !a.prec) return OTAL_E_UNSUPPORTED;
     if (a.half != a.xhalf || (a.mhalf && !a.xhalf) || (out_mask && a.xhalf && !a.mhalf)) return OTAL_E_UNSUPPORTED;   // all three bf16, or none
     a.pre = prologue;
-    return launch_mode<MODE_DGRAD>(a, ws, ws_bytes, (hipStream_t)stream);
+    return launch_mode<MODE_DGRAD>(a, precision, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int otal_conv_wgrad(const int* geom, const int64_t* strides, const float* x, const float* dy,
@@ -3609,7 +3404,7 @@ extern "C" int otal_conv_wgrad(const int* geom, const int64_t* strides, const fl
     if ((a.half || a.xhalf) && !a.prec) return OTAL_E_UNSUPPORTED;
     if (a.xhalf && !a.half) return OTAL_E_UNSUPPORTED;      // a bf16 x is only served together with a bf16 dy
     a.pre = prologue;
-    return launch_mode<MODE_WGRAD>(a, ws, ws_bytes, (hipStream_t)stream);
+    return launch_mode<MODE_WGRAD>(a, precision, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ---- pair launches: two problems of one geometry in one grid (the 1-D temporal layers only: anything else is
@@ -3637,7 +3432,7 @@ extern "C" int otal_conv_fwd_pair(const int* geom, const int64_t* strides, const
     a.flags = relu ? EPI_RELU : 0;
     a.prec = (precision & 1) ? 1 : 0;
     a.pre = prologue ? prologue[0] : nullptr; a.pre2 = prologue ? prologue[1] : nullptr;
-    if (!conv1d_tile_eligible(a.g, MODE_FWD, a.prec, a.x, a) || ((uintptr_t)a.x2 & 3)) return OTAL_E_UNSUPPORTED;
+    if (!conv1d_tile_eligible(a.g, MODE_FWD, a.prec, a.x, false) || ((uintptr_t)a.x2 & 3)) return OTAL_E_UNSUPPORTED;
     return launch_conv1d_tile<MODE_FWD>(a, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -3653,7 +3448,7 @@ extern "C" int otal_conv_dgrad_pair(const int* geom, const int64_t* strides, con
     a.w_natural = (precision & 2) ? 1 : 0;
     a.pre = prologue ? prologue[0] : nullptr; a.pre2 = prologue ? prologue[1] : nullptr;
     if (!a.w_natural) return OTAL_E_UNSUPPORTED;            // forward-layout weights only (the prologue re-orders them)
-    if (!conv1d_tile_eligible(a.g, MODE_DGRAD, a.prec, a.dy, a) || ((uintptr_t)a.dy2 & 3)) return OTAL_E_UNSUPPORTED;
+    if (!conv1d_tile_eligible(a.g, MODE_DGRAD, a.prec, a.dy, false) || ((uintptr_t)a.dy2 & 3)) return OTAL_E_UNSUPPORTED;
     return launch_conv1d_tile<MODE_DGRAD>(a, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -3672,17 +3467,10 @@ extern "C" int otal_conv_wgrad_pair(const int* geom, const int64_t* strides, con
 // 1 when this geometry has a kernel for the bf16-STORED large operand (precision bit 2): fwd -> y, wgrad / dgrad -> dy.
 // Pointer alignment (16 bytes) and strides that are multiples of 8 elements are the caller's side of the contract.
 extern "C" int otal_conv_half_storage(const int* geom, const int64_t* strides, int mode, int precision) {
-    ConvArgs a = {};
-    if (!geom || !strides || fill_geom(a.g, geom) || !(precision & 1)) return 0;
-    a.g.x_bs = strides[0]; a.g.x_cs = strides[1]; a.g.y_bs = strides[2]; a.g.y_cs = strides[3];
-    if (a.g.y_bs % 8 || a.g.y_cs % 8) return 0;
-    if (precision & 8) return half_kernel_kind(a.g, mode, nullptr, nullptr) ? 1 : 0;      // bf16 on both sides of the layer
-    if (mode == MODE_FWD) {
-        if (conv1a_direct_eligible(a.g, MODE_FWD, 1, nullptr) && !OTAL_OPT("OTAL_CONV_NO1A")) return 1;
-        return direct_eligible(a.g, MODE_FWD, 1, a.g.Cout) ? 1 : 0;
-    }
-    if (mode == MODE_WGRAD) return conv1a_wgrad_eligible(a.g, 1, nullptr, nullptr) ? 1 : 0;
-    return 0;
+    ConvGeom g;
+    if (!geom || !strides || fill_geom(g, geom)) return 0;
+    g.x_bs = strides[0]; g.x_cs = strides[1]; g.y_bs = strides[2]; g.y_cs = strides[3];
+    return conv_half_storage(g, mode, precision);
 }
 
 extern "C" int otal_conv_pack_wt(const float* w, float* wt, int Cout, int Cin, int kvol, void* stream) {
@@ -3696,20 +3484,6 @@ extern "C" int otal_conv_pack_wt(const float* w, float* wt, int Cout, int Cin, i
 
 // ---- persistent prologues (tables + packed bf16 weights in a caller-owned region) ------------------------------------
 namespace {
-// which prologue a launch with this geometry would run: 0 none (generic kernel), 1 chunk path (fwd / dgrad), 2 position table
-int prologue_kind(const ConvGeom& g, int mode, int precision) {
-    const int prec = precision & 1;
-    if (mode == MODE_WGRAD) {
-        if (wgrad_pair_mode(g, prec)) return 2;
-        return wgrad_vector_width(g, prec) ? 2 : 0;
-    }
-    const int M = mode == MODE_FWD ? g.Cout : g.Cin;
-    if (mode == MODE_FWD && g.kt == 1 && g.kh == g.Hi && g.kw == g.Wi && g.Hi * g.Wi == 36 && g.Ho == 1 && g.Wo == 1 &&
-        g.Cin % 4 == 0 && !OTAL_OPT("OTAL_CONV_NOPROJ")) return 0;       // the projection GEMM reads the fp32 weights in place
-    if (conv1a_direct_eligible(g, mode, prec, nullptr)) return 0;
-    if (direct_eligible(g, mode, prec, M)) return 3;      // the direct kernel's weight pack
-    return chunk_eligible(g, mode, prec) ? 1 : 0;
-}
 int fill_args_for_prologue(ConvArgs& a, const int* geom, const int64_t* strides, int mode, const float* w, int precision) {
     if (int e = fill_geom(a.g, geom)) return e;
     a.g.x_bs = strides[0]; a.g.x_cs = strides[1]; a.g.y_bs = strides[2]; a.g.y_cs = strides[3];
@@ -3725,16 +3499,10 @@ int fill_args_for_prologue(ConvArgs& a, const int* geom, const int64_t* strides,
 }  // namespace
 
 extern "C" size_t otal_conv_prologue_bytes(const int* geom, const int64_t* strides, int mode, int precision) {
-    ConvArgs a = {};
-    if (!geom || !strides || fill_args_for_prologue(a, geom, strides, mode, nullptr, precision)) return 0;
-    const int kind = prologue_kind(a.g, mode, precision);
-    if (kind == 1) {
-        const bool kwv = mode == MODE_FWD && (a.g.Cin % 8) != 0;
-        return chunk_tab_bytes(a.K) + chunk_wp_bytes(a.M, choose_bm(a.M, !kwv), a.K);
-    }
-    if (kind == 2) return ptab_bytes(a.g, a.g.sw == 2 ? 8 : wgrad_vector_width(a.g, a.prec));
-    if (kind == 3) return direct_wp_bytes(a.g, a.M, mode == MODE_FWD ? a.g.Cin : a.g.Cout);
-    return 0;
+    ConvGeom g;
+    if (!geom || !strides || fill_geom(g, geom)) return 0;
+    g.x_bs = strides[0]; g.x_cs = strides[1]; g.y_bs = strides[2]; g.y_cs = strides[3];
+    return conv_prologue_bytes(g, mode, precision & 1);
 }
 
 extern "C" size_t otal_conv_prologue_desc_bytes(void) { return sizeof(PrepDesc); }
@@ -3746,10 +3514,10 @@ extern "C" int otal_conv_prologue(const int* geom, const int64_t* strides, int m
     if (!geom || !strides || !region) return OTAL_E_NULL;
     ConvArgs a = {};
     if (int e = fill_args_for_prologue(a, geom, strides, mode, w, precision)) return e;
-    const int kind = prologue_kind(a.g, mode, precision);
-    if (kind == 0 || region_bytes < otal_conv_prologue_bytes(geom, strides, mode, precision)) return OTAL_E_UNSUPPORTED;
+    const int layout = conv_prologue_layout(a.g, mode, a.prec);
+    if (layout == PRO_NONE || region_bytes < otal_conv_prologue_bytes(geom, strides, mode, precision)) return OTAL_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    if (kind == 2) {
+    if (layout == PRO_PTAB) {
         const int cw = a.g.sw == 2 ? 8 : wgrad_vector_width(a.g, a.prec);
         a.fd = make_conv_fastdiv(a.g);
         const int ngroups = a.K / cw, npad = ngroups + PTAB_PAD;
@@ -3760,7 +3528,7 @@ extern "C" int otal_conv_prologue(const int* geom, const int64_t* strides, int m
     }
     if (!w) return OTAL_E_NULL;
     PrepDesc d;
-    if (kind == 3) {
+    if (layout == PRO_DIRECT) {
         d = PrepDesc{};
         const int BM = direct_bm(a.g, a.M);
         d.wp = reinterpret_cast<unsigned*>(region); d.wsrc = w; d.g = a.g; d.M = a.M; d.Mpad = (a.M + BM - 1) / BM * BM;

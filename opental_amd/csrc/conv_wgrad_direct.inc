@@ -695,19 +695,6 @@ __global__ __launch_bounds__(512) void conv3_wgrad_planes3_kernel(const WD3Args 
     wd3_epilogue<MT, 16>(a, acc, ci0, m0, split, wave, lane, smem);
 }
 
-static inline bool wgrad_direct_eligible(const ConvGeom& g, int prec, const void* x, const void* dy) {
-    if (!prec || OTAL_OPT("OTAL_CONV_NOWDIRECT") || g.nlev > 1) return false;
-    if (g.kt != 3 || g.kh != 3 || g.kw != 3 || g.st != 1 || g.sh != 1 || g.sw != 1 || g.pt != 1 || g.ph != 1 || g.pw != 1) return false;
-    if (g.To != g.Ti || g.Ho != g.Hi || g.Wo != g.Wi) return false;
-    const bool planes6 = g.Wi == 6 && g.Hi == 6 && g.Ti % 4 == 0;
-    const bool planes3 = g.Wi == 3 && g.Hi == 3 && g.Ti % 16 == 0;
-    if (!((g.Wi == 24 && g.Hi % 4 == 0) || (g.Wi == 12 && g.Hi == 12) || planes6 || planes3) || g.Cin % 2) return false;
-    if (g.Cin < (planes3 ? 32 : 64) || g.Cout < 64) return false;
-    if (((uintptr_t)x & 15) || ((uintptr_t)dy & 15) || g.x_cs % 4 || g.x_bs % 4 || g.y_cs % 4 || g.y_bs % 4) return false;
-    const int64_t ex = gather_extent_bytes(g, MODE_FWD), ey = gather_extent_bytes(g, MODE_DGRAD);
-    return ex > 0 && ey > 0 && ex < (1LL << 31) && ey < (1LL << 31);
-}
-
 template <int BM, int PW, int PR, bool H>
 static int launch_wd3(const WD3Args& d, dim3 grid, hipStream_t st) {
     constexpr int XB = 4 * (PR + 2) * (PW + 2) * 64, AB = BM * (PR * PW * 2 + 16);

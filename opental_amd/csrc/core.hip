@@ -19,7 +19,7 @@ extern "C" const char* otal_error_string(int code) {
     return "unknown error";
 }
 
-// ---- run-time switches (common.h: OTAL_OPTIONS) ---------------------------------------------------------------------
+// ---- run-time switches (options.h: OTAL_OPTIONS) --------------------------------------------------------------------
 // A switch takes its initial value from the environment variable of the same name, read ONCE at its first lookup: the
 // launch path never calls getenv (it used to, ~10 times per convolution launch).  otal_set_option changes a switch at run
 // time; a name that is not in the table is refused.

@@ -8,7 +8,7 @@
 // this 61 MB-weight layer.  Here both tiles are staged with 16-byte loads along K -- fp32 weights straight from the
 // parameter arena (no packed copy, no prologue), converted to bf16 on the way into LDS -- in K steps of four input
 // channels (144 k); split-K over channel ranges, slabs reduced (+ bias) in order by splitk_reduce_kernel.
-constexpr int PJ_HW = 36, PJ_KS = 4 * PJ_HW, PJ_PITCH = PJ_KS * 2 + 16;
+constexpr int PJ_KS = 4 * PJ_HW, PJ_PITCH = PJ_KS * 2 + 16;     // (PJ_HW, the 36 positions of a plane: conv_select.h)
 
 __global__ __launch_bounds__(256) void proj_fwd_kernel(const ConvArgs a, int ci_per_split) {
     constexpr int Q = PJ_KS / 4;                            // 16-byte quads per row and K step
@@ -109,17 +109,6 @@ __global__ __launch_bounds__(256) void proj_fwd_kernel(const ConvArgs a, int ci_
     }
 }
 
-static inline bool proj_fwd_eligible(const ConvGeom& g, int mode, int prec, const void* x, const void* w) {
-    if (!prec || mode != MODE_FWD || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NOPROJ")) return false;
-    if (g.kt != 1 || g.st != 1 || g.kh != g.Hi || g.kw != g.Wi || g.Ho != 1 || g.Wo != 1 || g.To != g.Ti) return false;
-    if (g.Hi * g.Wi != PJ_HW || g.ph != 0 || g.pw != 0 || g.pt != 0 || g.Cin % 4) return false;
-    // (16-byte loads at 4-byte aligned addresses are legal on gfx950 -- tools/ubench/alignprobe.hip; a weight inside the
-    //  flat parameter arena is only 4-byte aligned)
-    if (((uintptr_t)x & 3) || ((uintptr_t)w & 3)) return false;
-    const int64_t ex = gather_extent_bytes(g, MODE_FWD), ew = 4 * (int64_t)g.Cout * g.Cin * PJ_HW;
-    return ex > 0 && ex < (1LL << 31) && ew < (1LL << 31);
-}
-
 int launch_proj_fwd(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     const ConvGeom& g = a.g;
     const int tm = (a.M + 63) / 64, nb = g.B * ((g.To + 63) / 64);
@@ -159,7 +148,7 @@ int launch_proj_fwd(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
 //     the MFMA fragments read as 16-byte pieces.  The 3 x 3 projection (HW = 9: quads straddle channels) loads per element;
 //   * the four row tiles of one column tile are dealt to ONE XCD (workgroups go to the XCDs round-robin): the x tile is
 //     fetched into that L2 once.
-constexpr int PW_KS = 32, PW_PITCH = PW_KS * 2 + 16;        // frames per K step; LDS row pitch (bytes) of both tiles
+constexpr int PW_PITCH = PW_KS * 2 + 16;        // LDS row pitch (bytes) of both tiles (PW_KS frames per K step)
 
 template <bool QUAD>
 __global__ __launch_bounds__(256) void proj_wgrad_kernel(const ConvArgs a, int HW, int tilesM, int tilesN) {
@@ -303,17 +292,6 @@ __global__ __launch_bounds__(256) void proj_wgrad_kernel(const ConvArgs a, int H
 #pragma unroll
             for (int r = 0; r < 16; ++r) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), ro, vo[r], 0, 0);
         }
-}
-
-static inline bool proj_wgrad_eligible(const ConvGeom& g, int prec, const void* x, const void* dy) {
-    if (!prec || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NOPROJW")) return false;
-    if (g.kt != 1 || g.st != 1 || g.kh != g.Hi || g.kw != g.Wi || g.Ho != 1 || g.Wo != 1 || g.To != g.Ti) return false;
-    if (g.ph != 0 || g.pw != 0 || g.pt != 0 || g.Hi * g.Wi < 2) return false;          // (a 1 x 1 plane is a 1 x 1 x 1 layer: other kernels)
-    if (g.To % PW_KS || g.y_cs < g.To || (g.y_cs & 3) || (g.y_bs & 3)) return false;    // whole K steps; 16-byte dc loads
-    if (((uintptr_t)x & 15) || ((uintptr_t)dy & 15) || (g.x_bs & 3) || (g.x_cs & 3)) return false;
-    const int64_t ex = gather_extent_bytes(g, MODE_FWD), ey = gather_extent_bytes(g, MODE_DGRAD);
-    const int64_t eo = 4 * (int64_t)g.Cout * g.Cin * g.Hi * g.Wi;
-    return ex > 0 && ey > 0 && ex < (1LL << 31) && ey < (1LL << 31) && eo < (1LL << 31);
 }
 
 int launch_proj_wgrad(ConvArgs& a, hipStream_t st) {

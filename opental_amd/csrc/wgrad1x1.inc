@@ -109,17 +109,6 @@ __global__ __launch_bounds__(512) void wgrad1x1_wide_kernel(const ConvArgs a) {
     }
 }
 
-static inline bool wgrad1x1_wide_eligible(const ConvGeom& g, int prec, const void* x, const void* dy) {
-    if (!prec || g.nlev > 1 || OTAL_OPT("OTAL_CONV_NOW1X1")) return false;
-    if (g.kt != 1 || g.kh != 1 || g.kw != 1 || g.st != 1 || g.sh != 1 || g.sw != 1) return false;
-    if (g.To != g.Ti || g.Ho != g.Hi || g.Wo != g.Wi) return false;
-    if (g.Hi == 1 && g.Wi == 1) return false;               // the 1-D layers have their own weight-gradient kernel
-    if (conv_out_positions(g) % 32 || (int64_t)g.Cout * g.Cin > (1 << 20)) return false;
-    if (((uintptr_t)x & 3) || ((uintptr_t)dy & 3)) return false;
-    const int64_t ex = gather_extent_bytes(g, MODE_FWD), ey = gather_extent_bytes(g, MODE_DGRAD);
-    return ex > 0 && ey > 0 && ex < (1LL << 31) && ey < (1LL << 31);
-}
-
 template <int MT, bool H>
 static int launch_w1x1(const ConvArgs& a, dim3 grid, hipStream_t st) {
     constexpr int lds = 2 * (MT * 32 + 256) * 80;
