@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define OTAL_ABI_VERSION 24
+#define OTAL_ABI_VERSION 25
 
 /* argument errors */
 #define OTAL_E_NULL      (-1)  /* null pointer */
@@ -202,6 +202,12 @@ int otal_conv_defer_reduces(int on);
 size_t otal_conv_deferred_end(void);
 int otal_conv_deferred_count(void);
 int otal_conv_flush_reduces(void* stream);
+
+/* Which kernel served the calling thread's most recent otal_conv_fwd / _dgrad / _wgrad (ABI 25): "generic", "proj", "conv1a",
+ * "conv1d_tile", "direct", "chunked", "conv1a_wgrad", "proj_wgrad", "wgrad_direct", "wgrad1x1_wide", "vector" or "wgrad1d";
+ * "" after a call that failed.  A static string, valid for the life of the process; for tests that must know whether a
+ * kernel ran or refused and passed the launch on. */
+const char* otal_conv_last_kernel(void);
 
 /* (Cout,Cin,kvol) -> (Cin,Cout,kvol): the A operand of the data-gradient GEMM. */
 int otal_conv_pack_wt(const float* w, float* wt, int Cout, int Cin, int kvol, void* stream);

@@ -3291,6 +3291,9 @@ int launch_kernel(const ConvStep& s, ConvArgs& a, void* ws, size_t ws_bytes, hip
     return OTAL_E_UNSUPPORTED;
 }
 
+// the kernel that served this thread's most recent otal_conv_fwd / _dgrad / _wgrad ("" after a failure): otal_conv_last_kernel()
+thread_local const char* g_last_kernel = "";
+
 template <int MODE>
 int launch_mode(ConvArgs& a, int precision, void* ws, size_t ws_bytes, hipStream_t st) {
     ConvQuery q = {};
@@ -3307,6 +3310,7 @@ int launch_mode(ConvArgs& a, int precision, void* ws, size_t ws_bytes, hipStream
         const ConvStep& s = p.step[i];
         a.pre = conv_step_prologue(s.kernel) == p.prologue ? pre : nullptr;
         e = a.xhalf ? otal_conv::launch_half(MODE, s.kernel, s.cw, a, ws, ws_bytes, st) : launch_kernel<MODE>(s, a, ws, ws_bytes, st);
+        if (e == 0) g_last_kernel = conv_kernel_name(s.kernel);
         if (e != OTAL_E_UNSUPPORTED || !s.next) return e;
     }
     return e;
@@ -3348,6 +3352,7 @@ extern "C" size_t otal_conv_workspace_bytes(const int* geom, int mode) {
 extern "C" int otal_conv_fwd(const int* geom, const int64_t* strides, const float* x, const float* w,
                              const float* scale, const float* shift, float* y, int relu, int precision,
                              const void* prologue, void* ws, size_t ws_bytes, void* stream) {
+    g_last_kernel = "";
     if (!geom || !strides || !x || !w || !y) return OTAL_E_NULL;
     ConvArgs a = {};
     if (int e = fill_geom(a.g, geom)) return e;
@@ -3367,6 +3372,7 @@ extern "C" int otal_conv_fwd(const int* geom, const int64_t* strides, const floa
 extern "C" int otal_conv_dgrad(const int* geom, const int64_t* strides, const float* dy, const float* wt_packed,
                                float* dx, int accumulate, const float* out_mask, const float* out_scale,
                                int precision, const void* prologue, void* ws, size_t ws_bytes, void* stream) {
+    g_last_kernel = "";
     if (!geom || !strides || !dy || !wt_packed || !dx) return OTAL_E_NULL;
     if ((out_mask == nullptr) != (out_scale == nullptr)) return OTAL_E_NULL;
     ConvArgs a = {};
@@ -3391,6 +3397,7 @@ extern "C" int otal_conv_dgrad(const int* geom, const int64_t* strides, const fl
 extern "C" int otal_conv_wgrad(const int* geom, const int64_t* strides, const float* x, const float* dy,
                                float* dw, int accumulate, int precision,
                                const void* prologue, void* ws, size_t ws_bytes, void* stream) {
+    g_last_kernel = "";
     if (!geom || !strides || !x || !dy || !dw) return OTAL_E_NULL;
     ConvArgs a = {};
     if (int e = fill_geom(a.g, geom)) return e;
@@ -3560,6 +3567,8 @@ extern "C" int otal_conv_prologue_batch(int n, const void* device_descs, const i
     return otal_launch_status();
 }
 
+
+extern "C" const char* otal_conv_last_kernel(void) { return g_last_kernel; }
 
 extern "C" int otal_conv_defer_reduces(int on) {
     std::lock_guard<std::recursive_mutex> lock(g_defer.mu);

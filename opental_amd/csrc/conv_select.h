@@ -272,6 +272,24 @@ enum ConvKernel {
     CK_PROJ, CK_CONV1A, CK_CONV1D_TILE, CK_DIRECT, CK_CHUNKED,                  // forward / data gradient
     CK_CONV1A_WGRAD, CK_PROJ_WGRAD, CK_WGRAD_DIRECT, CK_WGRAD1X1, CK_WGRAD_VECTOR, CK_WGRAD1D,   // weight gradient
 };
+// the kernel's name as the plans, the CPU harness and otal_conv_last_kernel() spell it
+static inline const char* conv_kernel_name(int kernel) {
+    switch (kernel) {
+        case CK_GENERIC: return "generic";
+        case CK_PROJ: return "proj";
+        case CK_CONV1A: return "conv1a";
+        case CK_CONV1D_TILE: return "conv1d_tile";
+        case CK_DIRECT: return "direct";
+        case CK_CHUNKED: return "chunked";
+        case CK_CONV1A_WGRAD: return "conv1a_wgrad";
+        case CK_PROJ_WGRAD: return "proj_wgrad";
+        case CK_WGRAD_DIRECT: return "wgrad_direct";
+        case CK_WGRAD1X1: return "wgrad1x1_wide";
+        case CK_WGRAD_VECTOR: return "vector";
+        case CK_WGRAD1D: return "wgrad1d";
+    }
+    return "?";
+}
 // what a persistent prologue region holds (otal_conv_prologue): nothing, the chunk table + packed weights (chunked and
 // 1-D tile kernels), the position table (vector weight gradient), the direct kernel's weight pack
 enum ConvPrologue { PRO_NONE = 0, PRO_CHUNK = 1, PRO_PTAB = 2, PRO_DIRECT = 3 };

@@ -30,23 +30,7 @@ extern "C" int cpu_set_option(const char* name, int value) {
     return -1;
 }
 
-extern "C" const char* cpu_kernel_name(int kernel) {
-    switch (kernel) {
-        case CK_GENERIC: return "generic";
-        case CK_PROJ: return "proj";
-        case CK_CONV1A: return "conv1a";
-        case CK_CONV1D_TILE: return "conv1d_tile";
-        case CK_DIRECT: return "direct";
-        case CK_CHUNKED: return "chunked";
-        case CK_CONV1A_WGRAD: return "conv1a_wgrad";
-        case CK_PROJ_WGRAD: return "proj_wgrad";
-        case CK_WGRAD_DIRECT: return "wgrad_direct";
-        case CK_WGRAD1X1: return "wgrad1x1_wide";
-        case CK_WGRAD_VECTOR: return "vector";
-        case CK_WGRAD1D: return "wgrad1d";
-    }
-    return "?";
-}
+extern "C" const char* cpu_kernel_name(int kernel) { return conv_kernel_name(kernel); }
 
 // addr: the addresses (or their residues mod 16) of x, w, dy, out, mask.  out[0] = steps, out[1] = prologue layout, then per
 // step {kernel, vector width, 1 when OTAL_E_UNSUPPORTED moves on}.

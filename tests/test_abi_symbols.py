@@ -35,8 +35,9 @@ def test_every_declared_symbol_is_exported(lib):
     assert not missing, missing
 
 
-def test_abi_version_and_error_strings(lib):
-    assert lib.otal_abi_version() == 24
+def test_abi_version_25_and_error_strings(lib):
+    """ABI 25 added otal_conv_last_kernel (include/opental_hip.h)."""
+    assert lib.otal_abi_version() == 25
     lib.otal_error_string.restype = ctypes.c_char_p
     assert b"batch" in lib.otal_error_string(-4)
     assert lib.otal_error_string(0) == b"success"
