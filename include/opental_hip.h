@@ -476,6 +476,24 @@ int otal_detection_loss_anet(const float* loc, const float* conf, const float* p
                              float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
                              int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
                              float* losses, float* grads, float* scratch, void* stream);
+/* otal_detection_loss_anet_ex: otal_detection_loss_anet for the ActivityNet1.3 closed-set Softmax and EDL baselines as well
+ * (os_head false: anet_softmax.yaml, anet_edl.yaml; multisegment_loss.py:226-257 without os_head).  Arguments as
+ * otal_detection_loss_anet, plus cls_mode and focal_alpha, numbered as otal_detection_loss's:
+ *   cls_mode 0 = the OpenTAL recipe above: otal_detection_loss_anet(...) == otal_detection_loss_anet_ex(..., 0, any, ...)
+ *                bit for bit;
+ *   cls_mode 2 = EvidenceLoss 'log' with exp evidence over all C logits (class 0 = background), EVERY anchor against its
+ *                matched label (0 where unmatched); ibm_active must be 0 (OTAL_E_UNSUPPORTED otherwise); iou_aware as in
+ *                mode 0, with u = C / S;
+ *   cls_mode 3 = FocalLoss_Ori(balance_index 0, alpha = focal_alpha, gamma 2) on the softmax scores of every anchor;
+ *                alpha[0] = focal_alpha belongs to the background; ibm_active and iou_aware are ignored.
+ * In modes 2 and 3 act / prop_act may be NULL and act_weight / act_margin are ignored: losses 5 and 6 and the dact /
+ * dprop_act gradient slots are written as 0.  Any other cls_mode: OTAL_E_UNSUPPORTED. */
+int otal_detection_loss_anet_ex(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                                const float* center, const float* act, const float* prop_act, const float* priors2,
+                                const float* gt, const unsigned char* gvalid, int B, int K, int C, int G,
+                                float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
+                                int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
+                                int cls_mode, float focal_alpha, float* losses, float* grads, float* scratch, void* stream);
 
 /* Backward of otal_detection_loss in one launch: the gradients w.r.t. the seven head outputs from the stored per-loss
  * gradients (`grads` as written by otal_detection_loss) and the incoming gradients of the seven losses g7[i] (device

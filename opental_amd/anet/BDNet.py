@@ -30,9 +30,10 @@ def model_cfg_from(config=None):
     cfg = dict(DEFAULT_MODEL_CFG)
     if config is not None:
         cfg['num_classes'] = config['dataset']['num_classes']
-        for k in ('freeze_bn', 'freeze_bn_affine', 'evidence', 'os_head', 'backbone_model'):
+        for k in ('freeze_bn', 'freeze_bn_affine', 'evidence', 'backbone_model'):
             if k in config['model']:
                 cfg[k] = config['model'][k]
+        cfg['os_head'] = config['model'].get('os_head', False)     # BDNet.py:16: a config without the key is closed-set
     return cfg
 
 

@@ -16,6 +16,8 @@ import torch.nn.functional as F
 
 from ..thumos14.cls_loss import FocalLoss_Ori as _FocalLoss, _evidence
 
+THUMOS14_ONLY_KEYS = ('soft_label', 'with_focal', 'alpha', 'gamma', 'with_ibloss', 'ib_start')
+
 
 class FocalLoss_Ori(_FocalLoss):
     """Per-sample sums: prob (B,K,C), target (B,K), mask (B,K) -> (B,)."""
@@ -39,6 +41,14 @@ class EvidenceLoss(nn.Module):
         self.evidence = cfg['evidence']
         if cfg.get('with_ghm', False):
             raise NotImplementedError("with_ghm: ablation variant outside the opental recipe")
+        # Options of the THUMOS14 EvidenceLoss (thumos14/cls_loss.py:82-117) that this one (anet/cls_loss.py:79-101) does not
+        # have.  The THUMOS14 yamls name them even when they are off, so a config that carries them was written for the
+        # other recipe; the reference would drop them silently (`with_focal: true` or `soft_label: 0.1` would then train
+        # another loss than the config says).
+        other = sorted(k for k in THUMOS14_ONLY_KEYS if k in cfg)
+        if other:
+            raise NotImplementedError(f"edl_config keys of the THUMOS14 EvidenceLoss, which the ActivityNet1.3 recipe does "
+                                      f"not have: {other}")
         if self.loss_type not in ('log', 'digamma'):
             raise NotImplementedError(self.loss_type)
         self.iou_aware = cfg.get('iou_aware', False)

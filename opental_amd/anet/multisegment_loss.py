@@ -6,6 +6,10 @@ targets with masked per-sample reductions -- no host synchronisation.
 What differs from the THUMOS14 loss and is reproduced: per-level regression bounds on max(left, right) (:69-84,
 :156-166); refined-stage positives use min(overlap_thresh, best IoU among the sample's positives) (:178-184);
 smooth-L1 for the refinement (:206); IoU calibration pairs each sample's logits with its own IoUs (:259-261).
+
+os_head=False is the closed-set variant of the Softmax and EDL baselines (configs anet_softmax.yaml, anet_edl.yaml):
+C = 151 logits with class 0 = background, EVERY anchor is classified against its matched label (0 where unmatched), and
+there are no actionness terms (loss_act, loss_prop_act are None, :226-257, :282-286).
 """
 import torch
 import torch.nn as nn
@@ -31,18 +35,21 @@ class MultiSegmentLoss(nn.Module):
         if size_average:
             raise NotImplementedError("size_average: the reference's `x /= N if not size_average else x` divides a "
                                       "loss by itself in that mode; the recipe never sets it")
+        self._focal_alpha0 = None
         if cls_loss_type == 'focal':
             self.cls_loss = FocalLoss_Ori(num_classes, balance_index=0, size_average=False, alpha=0.25)
+            al = self.cls_loss.alpha            # still on the host here: decide once whether the HIP kernel's form applies
+            if (self.cls_loss.gamma == 2 and al.numel() >= 2 and bool((al[1:] == al[1]).all())
+                    and abs(float(al[0]) + float(al[1]) - 1.0) < 1e-6):
+                self._focal_alpha0 = float(al[0])
         elif cls_loss_type == 'edl':
             self.cls_loss = EvidenceLoss(num_classes, edl_config, size_average=False)
         else:
             raise NotImplementedError(cls_loss_type)
         self.iou_aware = cls_loss_type == 'edl' and self.cls_loss.iou_aware
         self.os_head = os_head
-        if not os_head:
-            raise NotImplementedError("closed-set (background-class) variant: the ActivityNet Softmax / EDL baselines "
-                                      "are not supported; OpenTAL uses os_head")
-        self.act_loss = ActionnessLoss(size_average=False, weight=0.1)
+        # the closed-set variant has no actionness heads (:101-102)
+        self.act_loss = ActionnessLoss(size_average=False, weight=0.1) if os_head else None
         self.size_average = size_average
         self.register_buffer('level_bounds', torch.tensor(bounds, dtype=torch.float32), persistent=False)
 
@@ -89,26 +96,52 @@ class MultiSegmentLoss(nn.Module):
         return self._bounds_host
 
     def _fused_ok(self, loc, conf, priors):
-        """The HIP loss of this recipe (csrc/loss.hip, otal_detection_loss_anet) covers what configs/anet_opental.yaml trains
-        with; other settings stay on the torch formulation below."""
+        return self._cls_mode(loc, conf, priors) is not None
+
+    def _cls_mode(self, loc, conf, priors):
+        """cls_mode of the HIP loss of this recipe (csrc/loss.hip, otal_detection_loss_anet_ex) for this criterion, or None
+        where the torch formulation below runs: 0 = what configs/anet_opental.yaml trains with (EDL with actionness),
+        2 = closed-set EDL ('log', exp, no IBM; anet_edl.yaml), 3 = closed-set focal (anet_softmax.yaml)."""
         cl = self.cls_loss
         if not (FUSED and loc.is_cuda and loc.dtype == torch.float32 and priors.shape[0] <= 1024 and priors.shape[1] == 2
-                and self.cls_loss_type == 'edl' and cl.loss_type == 'log' and cl.evidence == 'exp' and not cl.size_average
-                and cl.num_cls == conf.shape[-1] and cl.num_cls < 32768 and not self.act_loss.size_average
+                and conf.shape[-1] == self.num_classes and self.num_classes < 32768 and not cl.size_average
                 and self.level_bounds.shape[0] <= 8):        # (the kernel keeps labels in 16 bits and <= MAX_LEVELS_A = 8 levels)
-            return False
+            return None
+        if self.os_head:
+            if not (self.cls_loss_type == 'edl' and cl.loss_type == 'log' and cl.evidence == 'exp'
+                    and not self.act_loss.size_average):
+                return None
+            mode = 0
+        elif self.cls_loss_type == 'focal':
+            if self._focal_alpha0 is None:
+                return None
+            mode = 3
+        elif cl.loss_type == 'log' and cl.evidence == 'exp' and not cl.with_ibm:
+            mode = 2
+        else:
+            return None
         # the kernel clamps a prior's level id into the table; the torch path would raise on an out-of-range one: keep the
         # torch path's behaviour for such priors (checked once per priors tensor -- one host read, not one per step)
         key = (priors.data_ptr(), priors._version, tuple(priors.shape))
         if getattr(self, '_lvl_checked', None) != key:
             self._lvl_ok = bool(0 <= int(priors[:, 1].min()) and int(priors[:, 1].max()) < self.level_bounds.shape[0])
             self._lvl_checked = key
-        return self._lvl_ok
+        return mode if self._lvl_ok else None
 
     def forward(self, predictions, targets, pre_locs=None):
         loc, conf, prop_loc, prop_conf, center, priors, act, prop_act = predictions
         B, K = loc.shape[0], priors.shape[0]
-        if self._fused_ok(loc, conf, priors):
+        mode = self._cls_mode(loc, conf, priors)
+        if mode is not None and not self.os_head:
+            from ..common.ops import AnetDetectionLossFunction
+            gt, valid = as_padded(targets, loc.device)
+            iou_aware = mode == 2 and self.iou_aware
+            out = AnetDetectionLossFunction.apply(
+                loc, conf, prop_loc, prop_conf, center.reshape(B, K), None, None, priors, gt, valid, self._bounds_list(),
+                float(self.clip_length), float(self.overlap_thresh), False, 0.0, bool(iou_aware), 0.0, 0.0, mode,
+                0.25 if mode == 2 else self._focal_alpha0)
+            return out[:5] + (None, None)
+        if mode is not None:
             from ..common.ops import AnetDetectionLossFunction
             gt, valid = as_padded(targets, loc.device)
             cl = self.cls_loss
@@ -133,20 +166,25 @@ class MultiSegmentLoss(nn.Module):
 
         def classify(logits, tgt):
             keep = tgt > 0
-            cls_id = (tgt - 1).clamp(min=0)
+            if self.os_head:
+                cls_id, mask = (tgt - 1).clamp(min=0), keep
+            else:                               # closed set: every anchor, its matched label (0 = background)
+                cls_id, mask = tgt, torch.ones_like(keep)
             if self.cls_loss_type == 'focal':
-                return self.cls_loss(F.softmax(logits, dim=-1), cls_id, keep), keep
-            return self.cls_loss(logits, cls_id, keep), keep
+                return self.cls_loss(F.softmax(logits, dim=-1), cls_id, mask), keep
+            return self.cls_loss(logits, cls_id, mask), keep
 
         loss_c, keep = classify(conf, conf_t)
-        loss_act, AN = self.act_loss(act.view(B, K), keep.to(act.dtype))
         loss_prop_c, pkeep = classify(prop_conf, prop_conf_t)
-        loss_prop_act, PAN = self.act_loss(prop_act.view(B, K), pkeep.to(act.dtype))
         N = pos.sum(-1).clamp(min=1)
         PN = prop_pos.sum(-1).clamp(min=1)
         loss_l, loss_c, loss_ct = loss_l / N, loss_c / N, loss_ct / N
         loss_prop_l, loss_prop_c = loss_prop_l / PN, loss_prop_c / PN
-        loss_act, loss_prop_act = loss_act / AN, loss_prop_act / PAN
         if self.iou_aware:
             loss_prop_c = loss_prop_c + self.cls_loss.iou_calib(prop_conf, iou_pred, mean=True)
+        if not self.os_head:
+            return tuple(v.sum() / B for v in (loss_l, loss_c, loss_prop_l, loss_prop_c, loss_ct)) + (None, None)
+        loss_act, AN = self.act_loss(act.view(B, K), keep.to(act.dtype))
+        loss_prop_act, PAN = self.act_loss(prop_act.view(B, K), pkeep.to(act.dtype))
+        loss_act, loss_prop_act = loss_act / AN, loss_prop_act / PAN
         return tuple(v.sum() / B for v in (loss_l, loss_c, loss_prop_l, loss_prop_c, loss_ct, loss_act, loss_prop_act))

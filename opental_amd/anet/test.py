@@ -3,9 +3,10 @@ prepare_clip (:83-92), decode_prediction (:95-132), filtering (:135-156), get_vi
 
 A video is ONE 768-frame clip here (the data is resampled to the clip length, anet/test.py:71-80), so a batch of videos
 is a batch of clips: the network runs on them together and the same two launches as THUMOS14 finish the job --
-otal_decode_clips (refine + decode + Dirichlet scores + thresholds, for every clip) and otal_softnms_classes (one
-workgroup per (video, class)).  Differences from the THUMOS14 file that are kept: short videos are padded with 127.5
-(mid-grey), the confidence threshold is 0.001, proposals are clipped to [0, duration] and empty ones dropped.
+otal_decode_clips (refine + decode + Dirichlet scores + thresholds, for every clip; otal_decode_clips_ex for the closed-set
+Softmax and EDL heads) and otal_softnms_classes (one workgroup per (video, class)).  Differences from the THUMOS14 file
+that are kept: short videos are padded with 127.5 (mid-grey), the confidence threshold is 0.001, proposals are clipped to
+[0, duration] and empty ones dropped.
 """
 import torch
 
@@ -31,25 +32,32 @@ def _heads(output_dict):
     return d
 
 
-def decode_clips(output_dict, fps, clip_length=CLIP_LENGTH, conf_thresh=0.001):
-    """Batched decode_prediction + the threshold masks of filtering for n videos (offset 0)."""
+def decode_clips(output_dict, fps, clip_length=CLIP_LENGTH, conf_thresh=0.001, os_head=True, use_edl=True, evidence='exp'):
+    """Batched decode_prediction + the threshold masks of filtering for n videos (offset 0).  os_head / use_edl / evidence:
+    the network's head (thumos14.test.head_mode).  The closed-set heads (os_head False: anet_softmax.yaml with softmax
+    scores, anet_edl.yaml with Dirichlet scores) leave the background logit out of score / flag, so row c is the
+    reference's class c + 1, and apply no actionness factor or mask (anet/test.py:95-156 with os_head False)."""
     n = output_dict['loc'].shape[0]
-    return _t.decode_clips(_heads(output_dict), [0.0] * n, fps, clip_length, conf_thresh)
+    return _t.decode_clips(_heads(output_dict), [0.0] * n, fps, clip_length, conf_thresh, os_head=os_head,
+                           use_edl=use_edl, evidence=evidence)
 
 
-def decode_prediction(output_dict, idx=0, sample_fps=1.0, clip_length=CLIP_LENGTH):
+def decode_prediction(output_dict, idx=0, sample_fps=1.0, clip_length=CLIP_LENGTH, os_head=True, use_edl=True, evidence='exp'):
     """Single-clip view: decoded_segments (A,2) in SECONDS (the reference divides by fps in filtering), conf_scores
-    (K,A), uncertainty (A,), actionness (A,)."""
-    return _t.decode_predictions(_heads(output_dict), idx, 0.0, sample_fps, clip_length)
+    (K,A), uncertainty (A,) or None without use_edl, actionness (A,) or None without os_head."""
+    return _t.decode_predictions(_heads(output_dict), idx, 0.0, sample_fps, clip_length, os_head=os_head, use_edl=use_edl,
+                                 evidence=evidence)
 
 
-def filtering(decoded_segments, conf_score_cls, uncertainty, actionness, conf_thresh=0.001):
-    return _t.filtering(decoded_segments, conf_score_cls, uncertainty, actionness, conf_thresh)
+def filtering(decoded_segments, conf_score_cls, uncertainty, actionness, conf_thresh=0.001, use_edl=True, os_head=True):
+    return _t.filtering(decoded_segments, conf_score_cls, uncertainty, actionness, conf_thresh, use_edl=use_edl,
+                        os_head=os_head)
 
 
 def get_video_prediction(rows, counts, duration, idx_to_class=None):
-    """anet/test.py:159-200: the proposal list of one video from its suppressed rows (K,top_k,5), clipped to
-    [0, duration]; proposals that end before they start are dropped."""
+    """anet/test.py:159-200: the proposal list of one video from its suppressed rows (K,top_k,cols), clipped to
+    [0, duration]; proposals that end before they start are dropped.  cols is 5 for the OpenTAL head, 4 for the closed-set
+    EDL head and 3 for the Softmax head: 'uncertainty' / 'actionness' are 0.0 where the column is absent (:197-198)."""
     rows, counts = rows.cpu().numpy(), counts.cpu().numpy()
     proposal_list = []
     for cl in range(rows.shape[0]):
@@ -62,23 +70,26 @@ def get_video_prediction(rows, counts, duration, idx_to_class=None):
             if end <= start:
                 continue
             proposal_list.append({'label': name, 'score': float(r[2]), 'segment': [start, end],
-                                  'uncertainty': float(r[3]), 'actionness': float(r[4])})
+                                  'uncertainty': float(r[3]) if len(r) > 3 else 0.0,
+                                  'actionness': float(r[4]) if len(r) > 4 else 0.0})
     return proposal_list
 
 
 @torch.no_grad()
 def detect_batch(net, videos, sample_fps, durations, idx_to_class=None, clip_length=CLIP_LENGTH, conf_thresh=0.001,
                  top_k=5000, nms_sigma=0.85, batch_clips=4):
-    """videos: list of uint8 (C,T,96,96) device tensors (centre-cropped).  Returns {index: proposal list}."""
+    """videos: list of uint8 (C,T,96,96) device tensors (centre-cropped).  Returns {index: proposal list}.  The network's
+    head (os_head, use_edl, evidence) picks the decode."""
+    os_head, use_edl, evidence = _t.head_mode(net)
     outs = []
     for i in range(0, len(videos), batch_clips):
         # one launch per forward pass; same values as prepare_clip per video (127.5 padded before the normalisation IS 0.0)
         batch = _t.prepare_windows(videos, [(j, 0) for j in range(i, min(i + batch_clips, len(videos)))], clip_length)
         outs.append(net(batch))
-    merged = {k: (torch.cat([o[k] for o in outs], 0) if k != 'priors' else outs[0][k])
-              for k in ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'act', 'prop_act', 'priors')}
+    keys = ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'priors') + (('act', 'prop_act') if os_head else ())
+    merged = {k: (torch.cat([o[k] for o in outs], 0) if k != 'priors' else outs[0][k]) for k in keys}
     fps = [float(f) for f in sample_fps]
-    dec = decode_clips(merged, fps, clip_length, conf_thresh)
+    dec = decode_clips(merged, fps, clip_length, conf_thresh, os_head=os_head, use_edl=use_edl, evidence=evidence)
     rows, counts, _ = _t.softnms_classes(dec, list(range(len(videos) + 1)), top_k, nms_sigma)
     return {v: get_video_prediction(rows[v], counts[v], durations[v], idx_to_class) for v in range(len(videos))}
 

@@ -21,6 +21,8 @@
 // = background, EVERY anchor is classified against its matched label, multisegment_loss.py:196-231 without os_head):
 // cls_mode 2 = EvidenceLoss 'log' / exp (no IBM; IoU calibration as in mode 0), cls_mode 3 = FocalLoss_Ori on softmax scores.
 // Modes 2 and 3 have no actionness heads: act / prop_act may be NULL, losses 5 and 6 and their gradient slots are 0.
+// The ActivityNet1.3 form (detection_loss_anet_kernel, below) takes the same cls_mode numbers for its OpenTAL recipe (0)
+// and its two closed-set baselines (2, 3) through otal_detection_loss_anet_ex.
 // Everything else stays on the torch formulation.
 #include "common.h"
 
@@ -497,7 +499,13 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
 // with |z|_1 NOT detached (cls_loss.py:137, :225-232; no EMA state); the actionness loss keeps its rank hinge (weight 0.1);
 // the IoU calibration is each sample's own mean.  Gradients use the layout of otal_detection_loss, already divided by B.
 // It replaced ~250 ATen launches of this package's own torch formulation of that file (2.4 ms of kernel time per step).
-constexpr int LA = 1024;            // threads per sample: FOUR lanes per anchor -- the class loops (150 classes, five passes
+// The closed-set Softmax and EDL baselines (anet_softmax.yaml, anet_edl.yaml: os_head false, C = 151 logits with class 0 =
+// background, EVERY anchor classified against its matched label, multisegment_loss.py:226-257 without os_head) are the
+// template's other two instances, numbered as otal_detection_loss's cls_mode: 2 = EvidenceLoss 'log' / exp (no IBM; IoU
+// calibration as in mode 0, u = C / S over all C logits), 3 = FocalLoss_Ori(balance_index 0, alpha = focal_alpha, gamma 2)
+// on the softmax scores.  They have no actionness heads: that phase is skipped, losses 5 / 6 and their gradient slots are 0.
+// Mode 0 is the OpenTAL form above, instantiated from the same source as before the closed-set modes were added.
+constexpr int LA = 1024;           // threads per sample: FOUR lanes per anchor -- the class loops (150 classes, five passes
 constexpr int LQ = LA / 4;          // with an exp each) are split over them and finished with two shuffles; 256 anchors per sweep
 constexpr int MAX_KA = 1024;        // anchors per sample
 constexpr int MAX_LEVELS_A = 8;
@@ -513,11 +521,17 @@ struct AnetLossArgs {
     float coeff, act_weight, act_margin;
     float lb[MAX_LEVELS_A], rb[MAX_LEVELS_A];
     int nlev;
+    float focal_alpha;              // mode 3: FocalLoss_Ori alpha of class 0; 1 - focal_alpha for the others
 };
 
 __device__ __forceinline__ float quad_sum(float v) {        // sum over the four lanes of an anchor (same wave)
     v += __shfl_xor(v, 1);
     v += __shfl_xor(v, 2);
+    return v;
+}
+__device__ __forceinline__ float quad_max(float v) {        // maximum over the four lanes of an anchor (same wave)
+    v = fmaxf(v, __shfl_xor(v, 1));
+    v = fmaxf(v, __shfl_xor(v, 2));
     return v;
 }
 __device__ float bsumA(float v, float* red) {
@@ -553,7 +567,9 @@ __device__ float bmaxA(float v, int idx, float* red, int* redi, int* arg) {
     return r;
 }
 
+template <int MODE>         // cls_mode: 0 (OpenTAL), 2 (closed-set EDL), 3 (closed-set focal)
 __global__ __launch_bounds__(LA) void detection_loss_anet_kernel(const AnetLossArgs a) {
+    static_assert(MODE == 0 || MODE == 2 || MODE == 3, "cls_mode 0, 2 or 3");
     __shared__ float red[LA];
     __shared__ int redi[LA];
     __shared__ float s_lt0[MAX_KA], s_lt1[MAX_KA], s_iou[MAX_KA], s_pl0[MAX_KA], s_pl1[MAX_KA], s_pred[MAX_KA];
@@ -615,7 +631,68 @@ __global__ __launch_bounds__(LA) void detection_loss_anet_kernel(const AnetLossA
 
     // ---- classification: EvidenceLoss 'log' with exp evidence (anet/cls_loss.py:120-141), per sample
     float loss_cls[2];
-    for (int pass = 0; pass < 2; ++pass) {
+    // closed set (modes 2, 3): every anchor against its matched label y (0 = background), normalised by N / PN
+    for (int pass = 0; pass < (MODE == 0 ? 0 : 2); ++pass) {
+        const float* logits = pass == 0 ? a.conf : a.prop_conf;
+        float* gout = pass == 0 ? g_conf : g_pconf;
+        const float norm = (pass == 0 ? Nf : PNf) * (float)a.B;
+        float part = 0.f;
+        for (int k0 = 0; k0 < K; k0 += LQ) {            // (uniform trip count: the shuffles below need all four lanes)
+            const int k = k0 + q4;
+            const bool live = k < K;
+            const int i = b * K + (live ? k : 0);
+            const int y = !live ? 0 : (pass == 0 ? (int)s_ct[k] : (int)s_pct[k]);
+            const float* z = logits + (size_t)i * C;
+            float* gz = gout + (size_t)i * C;
+            if constexpr (MODE == 2) {
+                // EvidenceLoss 'log', exp evidence, no IBM (cls_loss.py:120-141, :212-236): per = log S - log alpha_y
+                float S = 0.f, ay = 0.f;
+                if (live)
+                    for (int c = sub; c < C; c += 4) {
+                        const float al = expf(fminf(fmaxf(z[c], -10.f), 10.f)) + 1.f;
+                        S += al;
+                        if (c == y) ay = al;
+                    }
+                S = quad_sum(S); ay = quad_sum(ay);
+                if (live) {
+                    if (lead) part += logf(S) - logf(ay);
+                    for (int c = sub; c < C; c += 4) {
+                        const float zc = z[c];
+                        const float da = (zc >= -10.f && zc <= 10.f) ? expf(zc) : 0.f;     // clamp backward is inclusive
+                        gz[c] = (1.f / S - (c == y ? 1.f / ay : 0.f)) * da / norm;
+                    }
+                }
+            } else {
+                // FocalLoss_Ori(gamma 2) on F.softmax(logits) (cls_loss.py:6-75): -alpha_y (1 - pt)^2 log(pt), pt = p_y + 1e-6
+                float mx = -INFINITY;
+                if (live)
+                    for (int c = sub; c < C; c += 4) mx = fmaxf(mx, z[c]);
+                mx = quad_max(mx);
+                float S = 0.f, ey = 0.f;
+                if (live)
+                    for (int c = sub; c < C; c += 4) {
+                        const float e = expf(z[c] - mx);
+                        S += e;
+                        if (c == y) ey = e;
+                    }
+                S = quad_sum(S); ey = quad_sum(ey);
+                if (live) {
+                    const float py = ey / S, pt = py + 1e-6f;
+                    const float al = y == 0 ? a.focal_alpha : 1.f - a.focal_alpha;
+                    const float om = 1.f - pt, lg = logf(pt);
+                    if (lead) part += -(om * om) * (al * lg);
+                    const float dpt = -al * (-2.f * om * lg + om * om / pt);       // d loss / d pt
+                    for (int c = sub; c < C; c += 4) {
+                        const float pc = expf(z[c] - mx) / S;
+                        gz[c] = dpt * py * ((c == y ? 1.f : 0.f) - pc) / norm;
+                    }
+                }
+            }
+        }
+        loss_cls[pass] = bsumA(part, red) / (pass == 0 ? Nf : PNf);
+    }
+    // OpenTAL (mode 0): the positives only, y = label - 1
+    for (int pass = 0; pass < (MODE == 0 ? 2 : 0); ++pass) {
         const float* logits = pass == 0 ? a.conf : a.prop_conf;
         float* gout = pass == 0 ? g_conf : g_pconf;
         const float norm = (pass == 0 ? Nf : PNf) * (float)a.B;
@@ -741,7 +818,11 @@ __global__ __launch_bounds__(LA) void detection_loss_anet_kernel(const AnetLossA
 
     // ---- positive-unlabelled actionness BCE with the rank hinge (anet/cls_loss.py:249-296), per sample
     float loss_a[2];
-    for (int pass = 0; pass < 2; ++pass) {
+    if constexpr (MODE != 0) {                      // closed set: no actionness heads, zero terms and gradient slots
+        loss_a[0] = loss_a[1] = 0.f;
+        for (int k = t; k < K; k += LA) { g_act[(size_t)b * K + k] = 0.f; g_pact[(size_t)b * K + k] = 0.f; }
+    }
+    for (int pass = 0; pass < (MODE == 0 ? 2 : 0); ++pass) {
         const float* pred = (pass == 0 ? a.act : a.prop_act) + (size_t)b * K;
         float* gout = (pass == 0 ? g_act : g_pact) + (size_t)b * K;
         const short* tg = pass == 0 ? s_ct : s_pct;
@@ -858,27 +939,47 @@ extern "C" int otal_detection_loss(const float* loc, const float* conf, const fl
 }
 
 
+extern "C" int otal_detection_loss_anet_ex(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                                           const float* center, const float* act, const float* prop_act, const float* priors2,
+                                           const float* gt, const unsigned char* gvalid, int B, int K, int C, int G,
+                                           float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
+                                           int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
+                                           int cls_mode, float focal_alpha, float* losses, float* grads, float* scratch,
+                                           void* stream) {
+    const bool closed = cls_mode == 2 || cls_mode == 3;        // closed-set modes: no actionness heads
+    if (!loc || !conf || !prop_loc || !prop_conf || !center || (!closed && (!act || !prop_act)) || !priors2 || !gt ||
+        !gvalid || !level_bounds || !losses || !grads || !scratch) return OTAL_E_NULL;
+    if (B <= 0 || K <= 0 || C <= 0 || G <= 0 || nlev <= 0) return OTAL_E_SHAPE;
+    if (K > MAX_KA || nlev > MAX_LEVELS_A || !(cls_mode == 0 || closed)) return OTAL_E_UNSUPPORTED;
+    if (cls_mode == 2 && ibm_active) return OTAL_E_UNSUPPORTED;    // closed-set EDL: no influence-balanced re-weighting
+    AnetLossArgs a;
+    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
+    a.prop_act = prop_act; a.priors = priors2; a.gt = gt; a.gvalid = gvalid; a.terms = scratch; a.grads = grads;
+    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
+    a.ibm_active = cls_mode == 0 ? ibm_active : 0; a.iou_aware = cls_mode == 3 ? 0 : iou_aware;
+    a.coeff = ibm_coeff; a.act_weight = act_weight; a.act_margin = act_margin;
+    a.nlev = nlev; a.focal_alpha = focal_alpha;
+    for (int l = 0; l < MAX_LEVELS_A; ++l) { a.lb[l] = l < nlev ? level_bounds[2 * l] : 0.f; a.rb[l] = l < nlev ? level_bounds[2 * l + 1] : 0.f; }
+    if (cls_mode == 0)
+        hipLaunchKernelGGL(detection_loss_anet_kernel<0>, dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
+    else if (cls_mode == 2)
+        hipLaunchKernelGGL(detection_loss_anet_kernel<2>, dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(detection_loss_anet_kernel<3>, dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
+    if (int e = otal_launch_status()) return e;
+    hipLaunchKernelGGL(detection_loss_anet_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scratch, losses, B);
+    return otal_launch_status();
+}
+
 extern "C" int otal_detection_loss_anet(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
                                         const float* center, const float* act, const float* prop_act, const float* priors2,
                                         const float* gt, const unsigned char* gvalid, int B, int K, int C, int G,
                                         float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
                                         int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
                                         float* losses, float* grads, float* scratch, void* stream) {
-    if (!loc || !conf || !prop_loc || !prop_conf || !center || !act || !prop_act || !priors2 || !gt || !gvalid ||
-        !level_bounds || !losses || !grads || !scratch) return OTAL_E_NULL;
-    if (B <= 0 || K <= 0 || C <= 0 || G <= 0 || nlev <= 0) return OTAL_E_SHAPE;
-    if (K > MAX_KA || nlev > MAX_LEVELS_A) return OTAL_E_UNSUPPORTED;
-    AnetLossArgs a;
-    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
-    a.prop_act = prop_act; a.priors = priors2; a.gt = gt; a.gvalid = gvalid; a.terms = scratch; a.grads = grads;
-    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
-    a.ibm_active = ibm_active; a.iou_aware = iou_aware; a.coeff = ibm_coeff; a.act_weight = act_weight; a.act_margin = act_margin;
-    a.nlev = nlev;
-    for (int l = 0; l < MAX_LEVELS_A; ++l) { a.lb[l] = l < nlev ? level_bounds[2 * l] : 0.f; a.rb[l] = l < nlev ? level_bounds[2 * l + 1] : 0.f; }
-    hipLaunchKernelGGL(detection_loss_anet_kernel, dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
-    if (int e = otal_launch_status()) return e;
-    hipLaunchKernelGGL(detection_loss_anet_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scratch, losses, B);
-    return otal_launch_status();
+    return otal_detection_loss_anet_ex(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors2, gt, gvalid, B, K, C, G,
+                                       clip_length, overlap_thresh, level_bounds, nlev, ibm_active, ibm_coeff, iou_aware,
+                                       act_weight, act_margin, 0, 0.25f, losses, grads, scratch, stream);
 }
 
 // ---- backward of the fused detection loss: the seven head gradients from the stored per-loss gradients and the incoming
