@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define OTAL_ABI_VERSION 25
+#define OTAL_ABI_VERSION 26
 
 /* argument errors */
 #define OTAL_E_NULL      (-1)  /* null pointer */
@@ -238,6 +238,16 @@ int otal_gn_relu_bwd_pair(const float* const* dy, const int64_t* dy_batch_stride
  * every GroupNorm backward (21 per step); the destinations may be slices of a flat gradient arena. */
 int otal_sum_partials(int n_items, const float* const* partial, float* const* dst0, float* const* dst1,
                       float* const* dst2, const int* channels, const int* batches, void* stream);
+
+/* Which kernel served the calling thread's most recent max-pool, GroupNorm or glue call (ABI 26): otal_maxpool3d_* -> the
+ * instantiation ("maxpool133_s2_w8_nn_fwd", "maxpoolk33_s2_bwd<3,bf16,bf16>" = <kt, x or dx storage, y or dy storage>,
+ * "maxpool333_rows_fwd<12,f32>", "maxpool333_sep_bwd<6,v4>", "maxpool3d_fwd_lds<333/111>", "maxpool3d_bwd<generic>", ...);
+ * otal_gn_relu_* -> the host-side path ("gn_relu_fwd<single>" / "<pair>", "gn_relu_bwd<pair,keep_dx,terms=0>",
+ * "gn_relu_bwd<single,no_keep_dx,terms=3>"); otal_sum_partials -> "sum_partials"; otal_convert_storage ->
+ * "convert_storage<to_bf16>" / "<to_f32>"; otal_masked_scale_copy -> "masked_scale_copy<4>" / "<1>" (vector width);
+ * otal_pyramid_merge_fwd / _bwd -> "pyramid_merge_fwd" / "_bwd".  "" after a call that launched nothing.  A static string,
+ * valid for the life of the process; for tests that must know which of a call's kernels ran. */
+const char* otal_layer_last_kernel(void);
 
 /* ------------------------------------------------------------------ MaxPool3dSamePadding ----
  * geom: 17 ints B,C, Ti,Hi,Wi, To,Ho,Wo, kt,kh,kw, st,sh,sw, pt,ph,pw (front pads; ZERO padding);

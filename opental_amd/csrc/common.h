@@ -34,3 +34,12 @@ static inline int otal_launch_status() {
     return e == hipSuccess ? 0 : (int)e;
 }
 static inline int ilog2_ceil(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+
+// the kernel (or host-side path) that served this thread's most recent max-pool / GroupNorm / glue call, "" after a call that
+// launched nothing: otal_layer_last_kernel().  Entry points clear it first and name what they launched through this helper.
+extern thread_local const char* g_layer_kernel;
+static inline int otal_layer_launched(const char* name) {
+    const int e = otal_launch_status();
+    g_layer_kernel = e == 0 ? name : "";
+    return e;
+}

@@ -307,6 +307,7 @@ int fill_levels(GnLevels& L, int T, int nlev, const int* lev) {
 extern "C" int otal_gn_relu_fwd(const float* x, const float* gamma, const float* beta, float* y, float* stats,
                                 int B, int C, int T, int G, float eps, int relu, int nlev, const int* lev,
                                 void* stream) {
+    g_layer_kernel = "";
     if (!x || !gamma || !beta || !y || !stats) return OTAL_E_NULL;
     if (B <= 0 || C <= 0 || T <= 0 || G <= 0 || C % G) return OTAL_E_SHAPE;
     GnLevels L;
@@ -317,12 +318,13 @@ extern "C" int otal_gn_relu_fwd(const float* x, const float* gamma, const float*
     if (int e = allow_large_lds(gn_relu_fwd_kernel, lds, large_ok)) return e;
     hipLaunchKernelGGL(gn_relu_fwd_kernel, dim3(B * G), dim3(256), lds, (hipStream_t)stream,
                        x, gamma, beta, y, stats, C, T, G, eps, relu, L, GnFwdAlt{}, (int64_t)C * T, (int64_t)T);
-    return otal_launch_status();
+    return otal_layer_launched("gn_relu_fwd<single>");
 }
 
 extern "C" int otal_gn_relu_fwd_to(const float* x, const float* gamma, const float* beta, float* y, int64_t y_bs, int64_t y_cs,
                                    float* stats, int B, int C, int T, int G, float eps, int relu, int nlev, const int* lev,
                                    void* stream) {
+    g_layer_kernel = "";
     if (!x || !gamma || !beta || !y || !stats) return OTAL_E_NULL;
     if (B <= 0 || C <= 0 || T <= 0 || G <= 0 || C % G || y_cs < T || y_bs < 0) return OTAL_E_SHAPE;
     GnLevels L;
@@ -333,12 +335,13 @@ extern "C" int otal_gn_relu_fwd_to(const float* x, const float* gamma, const flo
     if (int e = allow_large_lds(gn_relu_fwd_kernel, lds, large_ok)) return e;
     hipLaunchKernelGGL(gn_relu_fwd_kernel, dim3(B * G), dim3(256), lds, (hipStream_t)stream,
                        x, gamma, beta, y, stats, C, T, G, eps, relu, L, GnFwdAlt{}, y_bs, y_cs);
-    return otal_launch_status();
+    return otal_layer_launched("gn_relu_fwd<single>");
 }
 
 extern "C" int otal_gn_relu_fwd_pair(const float* const* x, const float* const* gamma, const float* const* beta, float* const* y,
                                      float* const* stats, int B, int C, int T, int G, float eps, int relu, int nlev,
                                      const int* lev, void* stream) {
+    g_layer_kernel = "";
     if (!x || !gamma || !beta || !y || !stats) return OTAL_E_NULL;
     for (int i = 0; i < 2; ++i) if (!x[i] || !gamma[i] || !beta[i] || !y[i] || !stats[i]) return OTAL_E_NULL;
     if (B <= 0 || C <= 0 || T <= 0 || G <= 0 || C % G) return OTAL_E_SHAPE;
@@ -349,12 +352,13 @@ extern "C" int otal_gn_relu_fwd_pair(const float* const* x, const float* const* 
     const GnFwdAlt alt = {x[1], gamma[1], beta[1], y[1], stats[1]};
     hipLaunchKernelGGL(gn_relu_fwd_kernel, dim3(B * G, 2), dim3(256), lds, (hipStream_t)stream,
                        x[0], gamma[0], beta[0], y[0], stats[0], C, T, G, eps, relu, L, alt, (int64_t)C * T, (int64_t)T);
-    return otal_launch_status();
+    return otal_layer_launched("gn_relu_fwd<pair>");
 }
 
 extern "C" int otal_gn_relu_fwd_pair_to(const float* const* x, const float* const* gamma, const float* const* beta,
                                         float* const* y, int64_t y_bs, int64_t y_cs, float* const* stats, int B, int C, int T,
                                         int G, float eps, int relu, int nlev, const int* lev, void* stream) {
+    g_layer_kernel = "";
     if (!x || !gamma || !beta || !y || !stats) return OTAL_E_NULL;
     for (int i = 0; i < 2; ++i) if (!x[i] || !gamma[i] || !beta[i] || !y[i] || !stats[i]) return OTAL_E_NULL;
     if (B <= 0 || C <= 0 || T <= 0 || G <= 0 || C % G || y_cs < T || y_bs < 0) return OTAL_E_SHAPE;
@@ -365,12 +369,13 @@ extern "C" int otal_gn_relu_fwd_pair_to(const float* const* x, const float* cons
     const GnFwdAlt alt = {x[1], gamma[1], beta[1], y[1], stats[1]};
     hipLaunchKernelGGL(gn_relu_fwd_kernel, dim3(B * G, 2), dim3(256), lds, (hipStream_t)stream,
                        x[0], gamma[0], beta[0], y[0], stats[0], C, T, G, eps, relu, L, alt, y_bs, y_cs);
-    return otal_launch_status();
+    return otal_layer_launched("gn_relu_fwd<pair>");
 }
 
 extern "C" int otal_gn_relu_bwd(const float* dy, int64_t dy_batch_stride, const float* x, const float* gamma, const float* beta,
                                 const float* stats, float* dx, float* partial, int B, int C, int T, int G,
                                 int relu, int nlev, const int* lev, void* stream) {
+    g_layer_kernel = "";
     if (!dy || !x || !gamma || !beta || !stats || !dx || !partial) return OTAL_E_NULL;
     if (B <= 0 || C <= 0 || T <= 0 || G <= 0 || C % G) return OTAL_E_SHAPE;
     if (dy_batch_stride == 0) dy_batch_stride = (int64_t)C * T;
@@ -385,12 +390,13 @@ extern "C" int otal_gn_relu_bwd(const float* dy, int64_t dy_batch_stride, const 
     if (int e = allow_large_lds(gn_relu_bwd_kernel, lds, large_ok)) return e;
     hipLaunchKernelGGL(gn_relu_bwd_kernel, dim3(B * G), dim3(256), lds, (hipStream_t)stream,
                        dy, x, gamma, beta, stats, dx, partial, C, T, G, relu, L, dy_batch_stride, keep_dx, GnBwdAlt{}, GnTerms{});
-    return otal_launch_status();
+    return otal_layer_launched(keep_dx ? "gn_relu_bwd<single,keep_dx,terms=0>" : "gn_relu_bwd<single,no_keep_dx,terms=0>");
 }
 
 extern "C" int otal_gn_relu_bwd_sum(int n_terms, const float* const* dy, const int64_t* dy_bs, const int64_t* dy_cs, const int* dy_T,
                                     const float* x, const float* gamma, const float* beta, const float* stats, float* dx,
                                     float* partial, int B, int C, int T, int G, int relu, int nlev, const int* lev, void* stream) {
+    g_layer_kernel = "";
     if (!dy || !dy_bs || !dy_cs || !dy_T || !x || !gamma || !beta || !stats || !dx || !partial) return OTAL_E_NULL;
     if (B <= 0 || C <= 0 || T <= 0 || G <= 0 || C % G || n_terms < 1 || n_terms > 3) return OTAL_E_SHAPE;
     GnTerms tm = {};
@@ -410,13 +416,17 @@ extern "C" int otal_gn_relu_bwd_sum(int n_terms, const float* const* dy, const i
     if (int e = allow_large_lds(gn_relu_bwd_kernel, lds, large_ok)) return e;
     hipLaunchKernelGGL(gn_relu_bwd_kernel, dim3(B * G), dim3(256), lds, (hipStream_t)stream,
                        dy[0], x, gamma, beta, stats, dx, partial, C, T, G, relu, L, (int64_t)C * T, keep_dx, GnBwdAlt{}, tm);
-    return otal_launch_status();
+    static const char* const names[2][3] = {
+        {"gn_relu_bwd<single,no_keep_dx,terms=1>", "gn_relu_bwd<single,no_keep_dx,terms=2>", "gn_relu_bwd<single,no_keep_dx,terms=3>"},
+        {"gn_relu_bwd<single,keep_dx,terms=1>", "gn_relu_bwd<single,keep_dx,terms=2>", "gn_relu_bwd<single,keep_dx,terms=3>"}};
+    return otal_layer_launched(names[keep_dx][n_terms - 1]);
 }
 
 extern "C" int otal_gn_relu_bwd_pair(const float* const* dy, const int64_t* dy_batch_stride, const float* const* x,
                                      const float* const* gamma, const float* const* beta, const float* const* stats,
                                      float* const* dx, float* const* partial, int B, int C, int T, int G, int relu, int nlev,
                                      const int* lev, void* stream) {
+    g_layer_kernel = "";
     if (!dy || !dy_batch_stride || !x || !gamma || !beta || !stats || !dx || !partial) return OTAL_E_NULL;
     int64_t bs[2];
     for (int i = 0; i < 2; ++i) {
@@ -434,7 +444,7 @@ extern "C" int otal_gn_relu_bwd_pair(const float* const* dy, const int64_t* dy_b
     const GnBwdAlt alt = {dy[1], x[1], gamma[1], beta[1], stats[1], dx[1], partial[1], bs[1]};
     hipLaunchKernelGGL(gn_relu_bwd_kernel, dim3(B * G, 2), dim3(256), lds, (hipStream_t)stream,
                        dy[0], x[0], gamma[0], beta[0], stats[0], dx[0], partial[0], C, T, G, relu, L, bs[0], keep_dx, alt, GnTerms{});
-    return otal_launch_status();
+    return otal_layer_launched(keep_dx ? "gn_relu_bwd<pair,keep_dx,terms=0>" : "gn_relu_bwd<pair,no_keep_dx,terms=0>");
 }
 
 // ---- batch sums of the backward's partials, MANY layers per launch.  Item i: dst{0,1,2}[i][c] = sum_b partial[i][(b*3 + r)*C + c]
@@ -462,6 +472,7 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const SumItems it) {
 
 extern "C" int otal_sum_partials(int n_items, const float* const* partial, float* const* dst0, float* const* dst1,
                                  float* const* dst2, const int* channels, const int* batches, void* stream) {
+    g_layer_kernel = "";
     if (!partial || !dst0 || !dst1 || !dst2 || !channels || !batches) return OTAL_E_NULL;
     if (n_items < 0) return OTAL_E_SHAPE;
     for (int i0 = 0; i0 < n_items; i0 += SP_MAX) {
@@ -476,7 +487,7 @@ extern "C" int otal_sum_partials(int n_items, const float* const* partial, float
             cmax = channels[i0 + i] > cmax ? channels[i0 + i] : cmax;
         }
         hipLaunchKernelGGL(sum_partials_kernel, dim3((cmax + 255) / 256, n, 3), dim3(256), 0, (hipStream_t)stream, it);
-        if (int e = otal_launch_status()) return e;
+        if (int e = otal_layer_launched("sum_partials")) return e;
     }
     return 0;
 }

@@ -176,6 +176,7 @@ __global__ __launch_bounds__(256) void convert_storage_kernel(const void* __rest
 
 extern "C" int otal_convert_storage(const void* src, int64_t src_bs, int64_t src_cs, void* dst, int64_t dst_bs, int64_t dst_cs,
                                     int to_bf16, int B, int C, int P, void* stream) {
+    g_layer_kernel = "";
     if (!src || !dst) return OTAL_E_NULL;
     if (B <= 0 || C <= 0 || P <= 0) return OTAL_E_SHAPE;
     if (P % 8 || src_bs % 8 || src_cs % 8 || dst_bs % 8 || dst_cs % 8 ||
@@ -184,7 +185,7 @@ extern "C" int otal_convert_storage(const void* src, int64_t src_bs, int64_t src
     const dim3 grid((unsigned)((total + 255) / 256));
     if (to_bf16) hipLaunchKernelGGL(convert_storage_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, src_bs, src_cs, dst, dst_bs, dst_cs, C, P / 8, total);
     else hipLaunchKernelGGL(convert_storage_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, src_bs, src_cs, dst, dst_bs, dst_cs, C, P / 8, total);
-    return otal_launch_status();
+    return otal_layer_launched(to_bf16 ? "convert_storage<to_bf16>" : "convert_storage<to_f32>");
 }
 
 extern "C" int otal_proposal_windows(const float* loc, float* seg, float* frame_seg, int B, int nlev,
@@ -230,6 +231,7 @@ extern "C" int otal_adam_flat_dev(float* p, const float* g, float* m, float* v, 
 extern "C" int otal_masked_scale_copy(const float* src, const int64_t* src_strides, const float* z, const int64_t* z_strides,
                                       const float* scale, float* dst, const int64_t* dst_strides, int accumulate, int B, int C,
                                       int T, int S, void* stream) {
+    g_layer_kernel = "";
     if (!src || !z || !dst || !src_strides || !z_strides || !dst_strides) return OTAL_E_NULL;
     if (B <= 0 || C <= 0 || T <= 0 || S <= 0) return OTAL_E_SHAPE;
     const Strides3 ss{src_strides[0], src_strides[1], src_strides[2]}, zs{z_strides[0], z_strides[1], z_strides[2]},
@@ -242,7 +244,7 @@ extern "C" int otal_masked_scale_copy(const float* src, const int64_t* src_strid
     const dim3 grid((unsigned)((total + 255) / 256));
     if (v4) hipLaunchKernelGGL(masked_scale_copy_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, src, ss, z, zs, scale, dst, ds, C, T, S, total, accumulate);
     else hipLaunchKernelGGL(masked_scale_copy_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, ss, z, zs, scale, dst, ds, C, T, S, total, accumulate);
-    return otal_launch_status();
+    return otal_layer_launched(v4 ? "masked_scale_copy<4>" : "masked_scale_copy<1>");
 }
 
 // ---- pyramid merge (AFSD/thumos14/BDNet.py:310-326): the two projected maps p0 (B,C,t0) and p1 (B,C,t0/2) -> the first two
@@ -296,16 +298,18 @@ __global__ __launch_bounds__(256) void pyramid_merge_bwd_kernel(const float* __r
 
 extern "C" int otal_pyramid_merge_fwd(const float* p0, const float* p1, float* packed, float* frame, int B, int C, int t0,
                                       int T, int up, void* stream) {
+    g_layer_kernel = "";
     if (!p0 || !p1 || !packed || !frame) return OTAL_E_NULL;
     if (B <= 0 || C <= 0 || t0 <= 0 || (t0 & 1) || up <= 0 || T < t0 + t0 / 2) return OTAL_E_SHAPE;
     hipLaunchKernelGGL(pyramid_merge_fwd_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)stream, p0, p1, packed, frame, B * C, t0, T, up);
-    return otal_launch_status();
+    return otal_layer_launched("pyramid_merge_fwd");
 }
 extern "C" int otal_pyramid_merge_bwd(const float* da, const float* db, const float* dframe, const float* dnext, float* dp0,
                                       float* dp1, int B, int C, int t0, int T, int up, void* stream) {
+    g_layer_kernel = "";
     if (!da || !dframe || !dp0 || !dp1) return OTAL_E_NULL;
     if (B <= 0 || C <= 0 || t0 <= 0 || (t0 & 1) || t0 > 1024 || up <= 0 || T < t0 + t0 / 2) return OTAL_E_SHAPE;
     hipLaunchKernelGGL(pyramid_merge_bwd_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)stream, da, db, dframe, dnext, dp0, dp1,
                        B * C, t0, T, up);
-    return otal_launch_status();
+    return otal_layer_launched("pyramid_merge_bwd");
 }

@@ -1389,6 +1389,20 @@ int bwd_planes(const PoolGeom& g, int& tlo_max, size_t& lds) {
     return 0;
 }
 
+// the instantiation OTAL_POOL_DISPATCH picks, as otal_layer_last_kernel() spells it (kind: 0 fwd, 1 fwd_lds, 2 bwd, 3 bwd_lds)
+static const char* pool_inst_name(const PoolGeom& g, int kind) {
+    static const char* const names[4][5] = {
+        {"maxpool3d_fwd<133/122>", "maxpool3d_fwd<333/111>", "maxpool3d_fwd<333/222>", "maxpool3d_fwd<222/222>", "maxpool3d_fwd<generic>"},
+        {"maxpool3d_fwd_lds<133/122>", "maxpool3d_fwd_lds<333/111>", "maxpool3d_fwd_lds<333/222>", "maxpool3d_fwd_lds<222/222>",
+         "maxpool3d_fwd_lds<generic>"},
+        {"maxpool3d_bwd<133/122>", "maxpool3d_bwd<333/111>", "maxpool3d_bwd<333/222>", "maxpool3d_bwd<222/222>", "maxpool3d_bwd<generic>"},
+        {"maxpool3d_bwd_lds<133/122>", "maxpool3d_bwd_lds<333/111>", "maxpool3d_bwd_lds<333/222>", "maxpool3d_bwd_lds<222/222>",
+         "maxpool3d_bwd_lds<generic>"}};
+    const int kk = g.kt * 100 + g.kh * 10 + g.kw, ss = g.st * 100 + g.sh * 10 + g.sw;
+    const int i = kk == 133 && ss == 122 ? 0 : kk == 333 && ss == 111 ? 1 : kk == 333 && ss == 222 ? 2 : kk == 222 && ss == 222 ? 3 : 4;
+    return names[kind][i];
+}
+
 #define OTAL_POOL_DISPATCH(KERNEL, GRID, LDS, ...)                                                              \
     do {                                                                                                         \
         const int kk = g.kt * 100 + g.kh * 10 + g.kw, ss = g.st * 100 + g.sh * 10 + g.sw;                        \
@@ -1404,6 +1418,7 @@ int bwd_planes(const PoolGeom& g, int& tlo_max, size_t& lds) {
 // io (forward): bit 0 -- x is stored as bf16, bit 1 -- y is stored as bf16 (only together with bit 0)
 static int pool_fwd(const int* geom, const int64_t* strides, const float* x, float* y, unsigned char* argtap,
                     unsigned char* signbits, void* stream, int io = 0) {
+    g_layer_kernel = "";
     if (!geom || !strides || !x || !y || !argtap) return OTAL_E_NULL;
     const bool nonneg = (io & 4) != 0;      // the caller guarantees x >= +0 (a conv + ReLU output): ordered-key kernels
     io &= 3;
@@ -1416,9 +1431,11 @@ static int pool_fwd(const int* geom, const int64_t* strides, const float* x, flo
         const int n2 = g.To * g.Ho * (g.Wo / 2);
         const dim3 grid((n2 + 255) / 256, g.B * g.C);
         const FastDiv fW2 = make_fastdiv((uint32_t)(g.Wo / 2));
+        const char* name;
         if (io == 3 && kind == 1 && g.Wi % 8 == 0 && g.x_bs % 8 == 0 && g.x_cs % 8 == 0 && g.y_bs % 4 == 0 && g.y_cs % 4 == 0 &&
             (reinterpret_cast<uintptr_t>(argtap) & 3) == 0 && (!signbits || (reinterpret_cast<uintptr_t>(signbits) & 1) == 0)) {           // eight input columns per thread
             const int n4 = g.To * g.Ho * (g.Wo / 4);
+            name = nonneg ? "maxpool133_s2_w8_nn_fwd" : "maxpool133_s2_w8_fwd";
             if (nonneg)
                 hipLaunchKernelGGL(maxpool133_s2_w8_nn_fwd_kernel, dim3((n4 + 255) / 256, g.B * g.C), dim3(256), 0, st_, x, y, argtap, g,
                                    make_fastdiv((uint32_t)(g.Wo / 4)), signbits);
@@ -1426,14 +1443,21 @@ static int pool_fwd(const int* geom, const int64_t* strides, const float* x, flo
                 hipLaunchKernelGGL(maxpool133_s2_w8_fwd_kernel, dim3((n4 + 255) / 256, g.B * g.C), dim3(256), 0, st_, x, y, argtap, g,
                                    make_fastdiv((uint32_t)(g.Wo / 4)), signbits);
         } else if (io == 3) {   // bf16 in, bf16 out
+            name = kind == 1 ? "maxpoolk33_s2_fwd<1,bf16,bf16>" : "maxpoolk33_s2_fwd<3,bf16,bf16>";
             if (kind == 1) hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<1, true, true>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
             else hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<3, true, true>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
         } else if (io == 1) {   // bf16-stored input (8-byte rows), fp32 output: the (1,3,3)/(1,2,2) pools
             if (kind != 1) return OTAL_E_UNSUPPORTED;
+            name = "maxpoolk33_s2_fwd<1,bf16,f32>";
             hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<1, true>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
-        } else if (kind == 1) hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<1, false>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
-        else hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<3, false>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
-        return otal_launch_status();
+        } else if (kind == 1) {
+            name = "maxpoolk33_s2_fwd<1,f32,f32>";
+            hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<1, false>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
+        } else {
+            name = "maxpoolk33_s2_fwd<3,f32,f32>";
+            hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<3, false>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
+        }
+        return otal_layer_launched(name);
     }
     if (is_333_s1(g)) {
         const int P = g.Hi, Q = P + 2;
@@ -1455,7 +1479,7 @@ static int pool_fwd(const int* geom, const int64_t* strides, const float* x, flo
             const size_t lds = (size_t)2 * (TT + 2) * P * P * sizeof(float);
             if (P == 12) hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<12, true>), rgrid, dim3(256), lds, st_, x, y, argtap, g, TT);
             else hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<6, true>), rgrid, dim3(256), lds, st_, x, y, argtap, g, TT);
-            return otal_launch_status();
+            return otal_layer_launched(P == 12 ? "maxpool333_rows_fwd<12,bf16>" : "maxpool333_rows_fwd<6,bf16>");
         }
         if (vec && vy && (P == 12 || P == 6) && !OTAL_OPT("OTAL_POOL_NOROWS")) {     // one row per thread
             const int TT = 256 / P - 2;
@@ -1463,12 +1487,12 @@ static int pool_fwd(const int* geom, const int64_t* strides, const float* x, flo
             const size_t lds = (size_t)2 * (TT + 2) * P * P * sizeof(float);
             if (P == 12) hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<12>), rgrid, dim3(256), lds, st_, x, y, argtap, g, TT);
             else hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<6>), rgrid, dim3(256), lds, st_, x, y, argtap, g, TT);
-            return otal_launch_status();
+            return otal_layer_launched(P == 12 ? "maxpool333_rows_fwd<12,f32>" : "maxpool333_rows_fwd<6,f32>");
         }
         if (P == 12) hipLaunchKernelGGL(maxpool333_sep_fwd_kernel<12>, grid, dim3(256), need(tt), st_, x, y, argtap, g, tt, vec);
         else if (P == 6) hipLaunchKernelGGL(maxpool333_sep_fwd_kernel<6>, grid, dim3(256), need(tt), st_, x, y, argtap, g, tt, vec);
         else hipLaunchKernelGGL(maxpool333_sep_fwd_kernel<3>, grid, dim3(256), need(tt), st_, x, y, argtap, g, tt, vec);
-        return otal_launch_status();
+        return otal_layer_launched(P == 12 ? "maxpool333_sep_fwd<12>" : P == 6 ? "maxpool333_sep_fwd<6>" : "maxpool333_sep_fwd<3>");
     }
     if (io) return OTAL_E_UNSUPPORTED;      // bf16 tensors: the strided 3x3 pools and the 12 x 12 / 6 x 6 branch pools only
     size_t lds = 0;
@@ -1483,13 +1507,14 @@ static int pool_fwd(const int* geom, const int64_t* strides, const float* x, flo
         const dim3 grid((g.To * g.Ho * g.Wo + 255) / 256, g.B * g.C);
         OTAL_POOL_DISPATCH(maxpool3d_fwd_kernel, grid, 0, x, y, argtap, g);
     }
-    return otal_launch_status();
+    return otal_layer_launched(pool_inst_name(g, tt > 0 ? 1 : 0));
 }
 
 // io (backward): bit 0 -- dx is stored as bf16, bit 1 -- dy is stored as bf16, bit 2 -- out_mask is a bf16 tensor
 static int pool_bwd(const int* geom, const int64_t* strides, const float* dy, const unsigned char* argtap, float* dx,
                     int accumulate, const float* out_mask, const float* out_scale, const unsigned char* signbits, void* stream,
                     int io = 0) {
+    g_layer_kernel = "";
     if (!geom || !strides || !dy || !dx || !argtap) return OTAL_E_NULL;
     if (((out_mask == nullptr) && (signbits == nullptr)) != (out_scale == nullptr)) return OTAL_E_NULL;
     if (out_mask && signbits) return OTAL_E_NULL;
@@ -1506,19 +1531,33 @@ static int pool_bwd(const int* geom, const int64_t* strides, const float* dy, co
         const int n4 = g.Ti * (g.Hi / 2) * (g.Wi / 4);
         const dim3 grid((n4 + 255) / 256, g.B * g.C);
         const FastDiv fW4 = make_fastdiv((uint32_t)(g.Wi / 4)), fH2 = make_fastdiv((uint32_t)(g.Hi / 2));
+        const char* name;
         if (all_half && kind == 1 && g.Wi % 8 == 0 && g.x_bs % 8 == 0 && g.x_cs % 8 == 0 && g.y_bs % 4 == 0 && g.y_cs % 4 == 0 &&
             (reinterpret_cast<uintptr_t>(argtap) & 3) == 0 && (!signbits || (reinterpret_cast<uintptr_t>(signbits) & 1) == 0)) {
             const int n8 = g.Ti * (g.Hi / 2) * (g.Wi / 8);
+            name = "maxpool133_s2_w8_bwd";
             hipLaunchKernelGGL(maxpool133_s2_w8_bwd_kernel, dim3((n8 + 255) / 256, g.B * g.C), dim3(256), 0, st_, dy, argtap, dx, g, out_scale,
                                make_fastdiv((uint32_t)(g.Wi / 8)), fH2, signbits);
-        } else if (all_half && kind == 1) hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, true, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        else if (all_half && g.Wi == 12 && g.x_bs % 4 == 0 && g.x_cs % 4 == 0 && g.y_bs % 2 == 0 && g.y_cs % 2 == 0)
+        } else if (all_half && kind == 1) {
+            name = "maxpoolk33_s2_bwd<1,bf16,bf16>";
+            hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, true, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
+        } else if (all_half && g.Wi == 12 && g.x_bs % 4 == 0 && g.x_cs % 4 == 0 && g.y_bs % 2 == 0 && g.y_cs % 2 == 0) {
+            name = "maxpool333_s2_w12_bwd";
             hipLaunchKernelGGL(maxpool333_s2_w12_bwd_kernel, dim3((g.To * (g.Hi / 2) + 255) / 256, g.B * g.C), dim3(256), 0, st_, dy, argtap, dx, g, out_scale, signbits);
-        else if (all_half) hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<3, true, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        else if (io == 1) hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        else if (kind == 1) hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, false>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        else hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<3, false>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        return otal_launch_status();
+        } else if (all_half) {
+            name = "maxpoolk33_s2_bwd<3,bf16,bf16>";
+            hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<3, true, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
+        } else if (io == 1) {
+            name = "maxpoolk33_s2_bwd<1,bf16,f32>";
+            hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
+        } else if (kind == 1) {
+            name = "maxpoolk33_s2_bwd<1,f32,f32>";
+            hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, false>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
+        } else {
+            name = "maxpoolk33_s2_bwd<3,f32,f32>";
+            hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<3, false>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
+        }
+        return otal_layer_launched(name);
     }
     if (is_333_s1(g)) {
         const int PP = g.Hi * g.Wi, ti = POOL_SEP_ELEMS / PP;
@@ -1540,7 +1579,7 @@ static int pool_bwd(const int* geom, const int64_t* strides, const float* dy, co
             const size_t lds = (size_t)2 * (TIr + 2) * P * P * sizeof(float) + (size_t)(TIr + 2) * P * TB;
             if (P == 12) hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<12, true>), rgrid, dim3(256), lds, st_, dy, argtap, dx, g, TIr, accumulate, out_mask, out_scale);
             else hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<6, true>), rgrid, dim3(256), lds, st_, dy, argtap, dx, g, TIr, accumulate, out_mask, out_scale);
-            return otal_launch_status();
+            return otal_layer_launched(P == 12 ? "maxpool333_rows_bwd<12,bf16>" : "maxpool333_rows_bwd<6,bf16>");
         }
         if (v2 && (g.Hi == 12 || g.Hi == 6) && !OTAL_OPT("OTAL_POOL_NOROWS")) {      // one input row per thread
             const int P = g.Hi, TIr = 256 / P - 2, TB = P == 12 ? 12 : 8;
@@ -1548,14 +1587,15 @@ static int pool_bwd(const int* geom, const int64_t* strides, const float* dy, co
             const size_t lds = (size_t)2 * (TIr + 2) * P * P * sizeof(float) + (size_t)(TIr + 2) * P * TB;
             if (P == 12) hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<12>), rgrid, dim3(256), lds, st_, dy, argtap, dx, g, TIr, accumulate, out_mask, out_scale);
             else hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<6>), rgrid, dim3(256), lds, st_, dy, argtap, dx, g, TIr, accumulate, out_mask, out_scale);
-            return otal_launch_status();
+            return otal_layer_launched(P == 12 ? "maxpool333_rows_bwd<12,f32>" : "maxpool333_rows_bwd<6,f32>");
         }
         if (g.Hi == 12 && v4) hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<12, true>), grid, dim3(256), l3, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale);
         else if (g.Hi == 6 && v4) hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<6, true>), grid, dim3(256), l3, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale);
         else if (g.Hi == 12) hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<12, false>), grid, dim3(256), l3, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale);
         else if (g.Hi == 6) hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<6, false>), grid, dim3(256), l3, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale);
         else hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<3, false>), grid, dim3(256), l3, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale);
-        return otal_launch_status();
+        return otal_layer_launched(g.Hi == 12 ? (v4 ? "maxpool333_sep_bwd<12,v4>" : "maxpool333_sep_bwd<12>")
+                                   : g.Hi == 6 ? (v4 ? "maxpool333_sep_bwd<6,v4>" : "maxpool333_sep_bwd<6>") : "maxpool333_sep_bwd<3>");
     }
     if (io) return OTAL_E_UNSUPPORTED;
     size_t lds = 0;
@@ -1568,8 +1608,11 @@ static int pool_bwd(const int* geom, const int64_t* strides, const float* dy, co
         const dim3 grid((g.Ti * g.Hi * g.Wi + 255) / 256, g.B * g.C);
         OTAL_POOL_DISPATCH(maxpool3d_bwd_kernel, grid, 0, dy, argtap, dx, g, accumulate, out_mask, out_scale);
     }
-    return otal_launch_status();
+    return otal_layer_launched(pool_inst_name(g, ti > 0 ? 3 : 2));
 }
+
+thread_local const char* g_layer_kernel = "";
+extern "C" const char* otal_layer_last_kernel(void) { return g_layer_kernel; }
 
 extern "C" int otal_maxpool3d_fwd(const int* geom, const int64_t* strides, const float* x, float* y,
                                   unsigned char* argtap, void* stream) {
@@ -1590,12 +1633,14 @@ extern "C" size_t otal_maxpool3d_signbits_bytes(const int* geom, const int64_t* 
 }
 extern "C" int otal_maxpool3d_fwd_signbits(const int* geom, const int64_t* strides, const float* x, float* y,
                                            unsigned char* argtap, unsigned char* signbits, void* stream) {
+    g_layer_kernel = "";
     if (!signbits) return OTAL_E_NULL;
     return pool_fwd(geom, strides, x, y, argtap, signbits, stream);
 }
 extern "C" int otal_maxpool3d_bwd_signbits(const int* geom, const int64_t* strides, const float* dy, const unsigned char* argtap,
                                            float* dx, int accumulate, const unsigned char* signbits, const float* out_scale,
                                            void* stream) {
+    g_layer_kernel = "";
     if (!signbits || !out_scale) return OTAL_E_NULL;
     return pool_bwd(geom, strides, dy, argtap, dx, accumulate, nullptr, out_scale, signbits, stream);
 }
@@ -1603,11 +1648,13 @@ extern "C" int otal_maxpool3d_bwd_signbits(const int* geom, const int64_t* strid
 // convolution that writes bf16 (otal_conv_fwd precision bit 2): MaxPool3d_2a reads 302 MB instead of 604 MB.
 extern "C" int otal_maxpool3d_fwd_signbits_h(const int* geom, const int64_t* strides, const void* x_bf16, float* y,
                                              unsigned char* argtap, unsigned char* signbits, void* stream) {
+    g_layer_kernel = "";
     if (!signbits) return OTAL_E_NULL;
     return pool_fwd(geom, strides, static_cast<const float*>(x_bf16), y, argtap, signbits, stream, 1);
 }
 extern "C" int otal_maxpool3d_bwd_signbits_h(const int* geom, const int64_t* strides, const float* dy, const unsigned char* argtap,
                                              void* dx_bf16, const unsigned char* signbits, const float* out_scale, void* stream) {
+    g_layer_kernel = "";
     if (!signbits || !out_scale) return OTAL_E_NULL;
     return pool_bwd(geom, strides, dy, argtap, static_cast<float*>(dx_bf16), 0, nullptr, out_scale, signbits, stream, 1);
 }

@@ -35,9 +35,9 @@ def test_every_declared_symbol_is_exported(lib):
     assert not missing, missing
 
 
-def test_abi_version_25_and_error_strings(lib):
-    """ABI 25 added otal_conv_last_kernel (include/opental_hip.h)."""
-    assert lib.otal_abi_version() == 25
+def test_abi_version_26_and_error_strings(lib):
+    """ABI 26 added otal_layer_last_kernel (include/opental_hip.h)."""
+    assert lib.otal_abi_version() == 26
     lib.otal_error_string.restype = ctypes.c_char_p
     assert b"batch" in lib.otal_error_string(-4)
     assert lib.otal_error_string(0) == b"success"
