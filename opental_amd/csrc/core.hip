@@ -67,6 +67,10 @@ extern "C" int otal_get_option(const char* name, int dflt) {
     return i < 0 ? dflt : *otal_option_slot(i);
 }
 
+// ---- the kernel that served this thread's most recent max-pool / GroupNorm / glue call (common.h: otal_layer_launched)
+thread_local const char* g_layer_kernel = "";
+extern "C" const char* otal_layer_last_kernel(void) { return g_layer_kernel; }
+
 // ---- stream fork / join ---------------------------------------------------------------------------------------------
 // A ring of events: hipStreamWaitEvent takes the event's state at the time of the call, so an event may be recorded again
 // once its wait has been issued.

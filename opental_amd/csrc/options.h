@@ -1,5 +1,6 @@
 // opental_amd/csrc/options.h -- the library's named run-time switches.  No HIP types in here: common.h includes it for the
-// kernels' translation units, conv_select.h for the kernel choice, and tests/cpu_conv_select.cpp serves the defaults on the CPU.
+// kernels' translation units, conv_select.h and pool_select.h for the kernel choice, and tests/cpu_options.h serves the defaults
+// to their CPU harnesses.
 #pragma once
 
 // Named run-time switches: the kernel-selection references the tests flip (otal_set_option).  The table is the only place

@@ -17,20 +17,9 @@
 #include "common.h"
 #include <cstdlib>
 
-#include "conv_index.h"
+#include "pool_select.h"
 
 namespace {
-
-struct PoolGeom {
-    int B, C, Ti, Hi, Wi, To, Ho, Wo;
-    int kt, kh, kw, st, sh, sw, pt, ph, pw;
-    int64_t x_bs, x_cs, y_bs, y_cs;
-    FastDiv fWo, fHo, fWi, fHi;
-    // LDS-staged kernels
-    int HL, WL;            // forward: staged input plane incl. halo  ((Ho-1)*sh + kh, (Wo-1)*sw + kw)
-    int HLo, WLo, ho_min, wo_min;   // backward: staged dy/arg plane incl. halo, first staged ho / wo (<= 0)
-    FastDiv fPo, fPi, fPL, fWL, fPLo, fWLo;   // Ho*Wo, Hi*Wi, HL*WL, WL, HLo*WLo, WLo
-};
 
 // KT..SW > 0: compile-time kernel / stride (the four pools of I3D); 0: read them from the geometry.
 template <int KT, int KH, int KW, int ST, int SH, int SW>
@@ -390,27 +379,6 @@ __global__ __launch_bounds__(256) void maxpool3d_bwd_lds_kernel(const float* __r
     }
 }
 
-int fill(PoolGeom& g, const int* d, const int64_t* s) {
-    // d: B,C, Ti,Hi,Wi, To,Ho,Wo, kt,kh,kw, st,sh,sw, pt,ph,pw
-    g.B = d[0]; g.C = d[1]; g.Ti = d[2]; g.Hi = d[3]; g.Wi = d[4]; g.To = d[5]; g.Ho = d[6]; g.Wo = d[7];
-    g.kt = d[8]; g.kh = d[9]; g.kw = d[10]; g.st = d[11]; g.sh = d[12]; g.sw = d[13];
-    g.pt = d[14]; g.ph = d[15]; g.pw = d[16];
-    for (int i = 0; i < 14; ++i) if (d[i] <= 0) return OTAL_E_SHAPE;
-    if (g.kt * g.kh * g.kw > 254) return OTAL_E_UNSUPPORTED;
-    if ((int64_t)g.B * g.C > 65535) return OTAL_E_UNSUPPORTED;
-    if ((int64_t)g.Ti * g.Hi * g.Wi >= (1LL << 31)) return OTAL_E_SHAPE;
-    g.x_bs = s[0]; g.x_cs = s[1]; g.y_bs = s[2]; g.y_cs = s[3];
-    g.fWo = make_fastdiv(g.Wo); g.fHo = make_fastdiv(g.Ho); g.fWi = make_fastdiv(g.Wi); g.fHi = make_fastdiv(g.Hi);
-    g.HL = (g.Ho - 1) * g.sh + g.kh; g.WL = (g.Wo - 1) * g.sw + g.kw;
-    const int ch = (g.kh + g.sh - 1) / g.sh, cw = (g.kw + g.sw - 1) / g.sw;
-    g.ho_min = -(ch - 1); g.wo_min = -(cw - 1);
-    g.HLo = (g.Hi - 1 + g.ph) / g.sh - g.ho_min + 1; g.WLo = (g.Wi - 1 + g.pw) / g.sw - g.wo_min + 1;
-    g.fPo = make_fastdiv((uint32_t)(g.Ho * g.Wo)); g.fPi = make_fastdiv((uint32_t)(g.Hi * g.Wi));
-    g.fPL = make_fastdiv((uint32_t)(g.HL * g.WL)); g.fWL = make_fastdiv((uint32_t)g.WL);
-    g.fPLo = make_fastdiv((uint32_t)(g.HLo * g.WLo)); g.fWLo = make_fastdiv((uint32_t)g.WLo);
-    return 0;
-}
-
 // ---- 3x3x3 / stride 1 / pad 1 on P x P planes (the nine Inception branch pools: P = 12, 6, 3), SEPARABLE.  max over the 3x3x3 window = max_dt PM[t+dt-1][h][w], PM[t'][h][w] = max_dh
 // RM[t'][h+dh-1][w], RM[t'][h''][w] = max_dw x[t'][h''][w+dw-1] (zero halo everywhere): three 1-D maxima of three values
 // instead of 27 compare/select pairs per output (the flat kernels are VALU-bound: 156 us for the 254 MB of Mixed_3b's
@@ -612,7 +580,6 @@ __global__ __launch_bounds__(256) void maxpool333_rows_fwd_kernel(const float* _
     }
 }
 
-constexpr int POOL_SEP_ELEMS = 1152;     // input elements per backward workgroup (8 planes of 12x12, 32 of 6x6, 128 of 3x3)
 // V4: every tensor is 16-byte aligned and the plane size a multiple of 4 -> float4 / uchar4 global accesses (the scalar
 // version issued 27 memory instructions per thread and tile: texture-addresser-bound at 2.5 TB/s)
 template <int P, bool V4>
@@ -1345,274 +1312,95 @@ __global__ __launch_bounds__(256) void maxpool133_s2_w8_bwd_kernel(const float* 
                                                                       f2h_pair_rne(s[i][4], s[i][5]), f2h_pair_rne(s[i][6], s[i][7]));
 }
 
-// 1: the (1,3,3)/(1,2,2) pools, 3: the (3,3,3)/(2,2,2) pool, 0: not one of them (or misaligned operands)
-static inline int strided_k33_kind(const PoolGeom& g, const void* x, const void* y) {
-    if (!(g.kh == 3 && g.kw == 3 && g.sh == 2 && g.sw == 2 && g.pt == 0 && g.ph == 0 && g.pw == 0 && g.Hi % 2 == 0 &&
-          g.Wi % 4 == 0 && g.Ho == g.Hi / 2 && g.Wo == g.Wi / 2 && g.x_bs % 4 == 0 && g.x_cs % 4 == 0 && g.y_bs % 2 == 0 &&
-          g.y_cs % 2 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0) ||
-        OTAL_OPT("OTAL_POOL_NO133"))
-        return 0;
-    if (g.kt == 1 && g.st == 1 && g.To == g.Ti) return 1;
-    if (g.kt == 3 && g.st == 2 && g.Ti % 2 == 0 && g.To == g.Ti / 2) return 3;
-    return 0;
-}
-
-constexpr size_t POOL_LDS_BUDGET = 48 * 1024;
-// the Inception branch pools: 3x3x3, stride 1, pad 1, square planes of side 12 / 6 / 3 with T unchanged
-static inline bool is_333_s1(const PoolGeom& g) {
-    return g.kt == 3 && g.kh == 3 && g.kw == 3 && g.st == 1 && g.sh == 1 && g.sw == 1 && g.pt == 1 && g.ph == 1 && g.pw == 1 &&
-           g.Hi == g.Wi && (g.Hi == 12 || g.Hi == 6 || g.Hi == 3) && g.To == g.Ti && g.Ho == g.Hi && g.Wo == g.Wi &&
-           (int64_t)g.Ti * g.Hi * g.Wi < (1LL << 30);
-}
-// output planes per block (forward): ~4096 outputs, staged input planes within the LDS budget; 0 = does not fit
-int fwd_planes(const PoolGeom& g, size_t& lds) {
-    int tt = 4096 / (g.Ho * g.Wo);
-    if (tt < 1) tt = 1;
-    if (tt > g.To) tt = g.To;
-    for (; tt >= 1; --tt) {
-        lds = (size_t)((tt - 1) * g.st + g.kt) * g.HL * g.WL * sizeof(float);
-        if (lds <= POOL_LDS_BUDGET) return tt;
-    }
-    return 0;
-}
-// input planes per block (backward) + the largest number of output planes a block stages
-int bwd_planes(const PoolGeom& g, int& tlo_max, size_t& lds) {
-    int ti = 4096 / (g.Hi * g.Wi);
-    if (ti < 1) ti = 1;
-    if (ti > g.Ti) ti = g.Ti;
-    const int ct = (g.kt + g.st - 1) / g.st;
-    for (; ti >= 1; --ti) {
-        tlo_max = (ti - 1 + g.st - 1) / g.st + ct + 1;      // >= toB - toA + 1 for every tile origin
-        lds = (size_t)tlo_max * g.HLo * g.WLo * (sizeof(float) + 1) + 16;
-        if (lds <= POOL_LDS_BUDGET) return ti;
-    }
-    return 0;
-}
-
-// the instantiation OTAL_POOL_DISPATCH picks, as otal_layer_last_kernel() spells it (kind: 0 fwd, 1 fwd_lds, 2 bwd, 3 bwd_lds)
-static const char* pool_inst_name(const PoolGeom& g, int kind) {
-    static const char* const names[4][5] = {
-        {"maxpool3d_fwd<133/122>", "maxpool3d_fwd<333/111>", "maxpool3d_fwd<333/222>", "maxpool3d_fwd<222/222>", "maxpool3d_fwd<generic>"},
-        {"maxpool3d_fwd_lds<133/122>", "maxpool3d_fwd_lds<333/111>", "maxpool3d_fwd_lds<333/222>", "maxpool3d_fwd_lds<222/222>",
-         "maxpool3d_fwd_lds<generic>"},
-        {"maxpool3d_bwd<133/122>", "maxpool3d_bwd<333/111>", "maxpool3d_bwd<333/222>", "maxpool3d_bwd<222/222>", "maxpool3d_bwd<generic>"},
-        {"maxpool3d_bwd_lds<133/122>", "maxpool3d_bwd_lds<333/111>", "maxpool3d_bwd_lds<333/222>", "maxpool3d_bwd_lds<222/222>",
-         "maxpool3d_bwd_lds<generic>"}};
-    const int kk = g.kt * 100 + g.kh * 10 + g.kw, ss = g.st * 100 + g.sh * 10 + g.sw;
-    const int i = kk == 133 && ss == 122 ? 0 : kk == 333 && ss == 111 ? 1 : kk == 333 && ss == 222 ? 2 : kk == 222 && ss == 222 ? 3 : 4;
-    return names[kind][i];
-}
-
-#define OTAL_POOL_DISPATCH(KERNEL, GRID, LDS, ...)                                                              \
-    do {                                                                                                         \
-        const int kk = g.kt * 100 + g.kh * 10 + g.kw, ss = g.st * 100 + g.sh * 10 + g.sw;                        \
-        if (kk == 133 && ss == 122) hipLaunchKernelGGL((KERNEL<1, 3, 3, 1, 2, 2>), GRID, dim3(256), LDS, st_, __VA_ARGS__); \
-        else if (kk == 333 && ss == 111) hipLaunchKernelGGL((KERNEL<3, 3, 3, 1, 1, 1>), GRID, dim3(256), LDS, st_, __VA_ARGS__); \
-        else if (kk == 333 && ss == 222) hipLaunchKernelGGL((KERNEL<3, 3, 3, 2, 2, 2>), GRID, dim3(256), LDS, st_, __VA_ARGS__); \
-        else if (kk == 222 && ss == 222) hipLaunchKernelGGL((KERNEL<2, 2, 2, 2, 2, 2>), GRID, dim3(256), LDS, st_, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<0, 0, 0, 0, 0, 0>), GRID, dim3(256), LDS, st_, __VA_ARGS__);            \
-    } while (0)
-
 }  // namespace
-
-// io (forward): bit 0 -- x is stored as bf16, bit 1 -- y is stored as bf16 (only together with bit 0)
+// The launches: pool_choose() (pool_select.h) names the kernel, its grid and LDS size; a case only passes the arguments.  io
+// (forward): bit 0 -- x is stored as bf16, bit 1 -- y is stored as bf16 (only together with bit 0), bit 2 -- x >= +0 (nonneg)
 static int pool_fwd(const int* geom, const int64_t* strides, const float* x, float* y, unsigned char* argtap,
                     unsigned char* signbits, void* stream, int io = 0) {
     g_layer_kernel = "";
     if (!geom || !strides || !x || !y || !argtap) return OTAL_E_NULL;
-    const bool nonneg = (io & 4) != 0;      // the caller guarantees x >= +0 (a conv + ReLU output): ordered-key kernels
-    io &= 3;
-    if (io != 0 && io != 1 && io != 3) return OTAL_E_UNSUPPORTED;
-    PoolGeom g;
-    if (int e = fill(g, geom, strides)) return e;
+    PoolQuery q = {};
+    q.dir = POOL_FWD; q.io = io; q.nonneg = (io & 4) != 0; q.has_signbits = signbits != nullptr; q.geom_rc = fill(q.g, geom, strides);
+    q.x = (uintptr_t)x; q.y = (uintptr_t)y; q.argtap = (uintptr_t)argtap; q.signbits = (uintptr_t)signbits;
+    const PoolChoice c = pool_choose(q);
+    if (c.rc) return c.rc;
+    const PoolGeom& g = q.g;
+    const dim3 grid(c.gx, c.gy), block(256);
     hipStream_t st_ = (hipStream_t)stream;
-    if ((signbits || io == 1) && !strided_k33_kind(g, x, y)) return OTAL_E_UNSUPPORTED;
-    if (const int kind = strided_k33_kind(g, x, y)) {
-        const int n2 = g.To * g.Ho * (g.Wo / 2);
-        const dim3 grid((n2 + 255) / 256, g.B * g.C);
-        const FastDiv fW2 = make_fastdiv((uint32_t)(g.Wo / 2));
-        const char* name;
-        if (io == 3 && kind == 1 && g.Wi % 8 == 0 && g.x_bs % 8 == 0 && g.x_cs % 8 == 0 && g.y_bs % 4 == 0 && g.y_cs % 4 == 0 &&
-            (reinterpret_cast<uintptr_t>(argtap) & 3) == 0 && (!signbits || (reinterpret_cast<uintptr_t>(signbits) & 1) == 0)) {           // eight input columns per thread
-            const int n4 = g.To * g.Ho * (g.Wo / 4);
-            name = nonneg ? "maxpool133_s2_w8_nn_fwd" : "maxpool133_s2_w8_fwd";
-            if (nonneg)
-                hipLaunchKernelGGL(maxpool133_s2_w8_nn_fwd_kernel, dim3((n4 + 255) / 256, g.B * g.C), dim3(256), 0, st_, x, y, argtap, g,
-                                   make_fastdiv((uint32_t)(g.Wo / 4)), signbits);
-            else
-                hipLaunchKernelGGL(maxpool133_s2_w8_fwd_kernel, dim3((n4 + 255) / 256, g.B * g.C), dim3(256), 0, st_, x, y, argtap, g,
-                                   make_fastdiv((uint32_t)(g.Wo / 4)), signbits);
-        } else if (io == 3) {   // bf16 in, bf16 out
-            name = kind == 1 ? "maxpoolk33_s2_fwd<1,bf16,bf16>" : "maxpoolk33_s2_fwd<3,bf16,bf16>";
-            if (kind == 1) hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<1, true, true>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
-            else hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<3, true, true>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
-        } else if (io == 1) {   // bf16-stored input (8-byte rows), fp32 output: the (1,3,3)/(1,2,2) pools
-            if (kind != 1) return OTAL_E_UNSUPPORTED;
-            name = "maxpoolk33_s2_fwd<1,bf16,f32>";
-            hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<1, true>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
-        } else if (kind == 1) {
-            name = "maxpoolk33_s2_fwd<1,f32,f32>";
-            hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<1, false>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
-        } else {
-            name = "maxpoolk33_s2_fwd<3,f32,f32>";
-            hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<3, false>), grid, dim3(256), 0, st_, x, y, argtap, g, fW2, signbits);
-        }
-        return otal_layer_launched(name);
+    const FastDiv fW2 = make_fastdiv((uint32_t)(g.Wo / 2)), fW4 = make_fastdiv((uint32_t)(g.Wo / 4));
+    switch (c.kernel) {
+        case PK_W8_NN_FWD: hipLaunchKernelGGL(maxpool133_s2_w8_nn_fwd_kernel, grid, block, c.lds, st_, x, y, argtap, g, fW4, signbits); break;
+        case PK_W8_FWD: hipLaunchKernelGGL(maxpool133_s2_w8_fwd_kernel, grid, block, c.lds, st_, x, y, argtap, g, fW4, signbits); break;
+        case PK_K33_FWD_1HH: hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<1, true, true>), grid, block, c.lds, st_, x, y, argtap, g, fW2, signbits); break;
+        case PK_K33_FWD_3HH: hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<3, true, true>), grid, block, c.lds, st_, x, y, argtap, g, fW2, signbits); break;
+        case PK_K33_FWD_1HF: hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<1, true>), grid, block, c.lds, st_, x, y, argtap, g, fW2, signbits); break;
+        case PK_K33_FWD_1FF: hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<1, false>), grid, block, c.lds, st_, x, y, argtap, g, fW2, signbits); break;
+        case PK_K33_FWD_3FF: hipLaunchKernelGGL((maxpoolk33_s2_fwd_kernel<3, false>), grid, block, c.lds, st_, x, y, argtap, g, fW2, signbits); break;
+        case PK_ROWS_FWD_12H: hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<12, true>), grid, block, c.lds, st_, x, y, argtap, g, c.planes); break;
+        case PK_ROWS_FWD_6H: hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<6, true>), grid, block, c.lds, st_, x, y, argtap, g, c.planes); break;
+        case PK_ROWS_FWD_12: hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<12>), grid, block, c.lds, st_, x, y, argtap, g, c.planes); break;
+        case PK_ROWS_FWD_6: hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<6>), grid, block, c.lds, st_, x, y, argtap, g, c.planes); break;
+        case PK_SEP_FWD_12: hipLaunchKernelGGL(maxpool333_sep_fwd_kernel<12>, grid, block, c.lds, st_, x, y, argtap, g, c.planes, c.vec); break;
+        case PK_SEP_FWD_6: hipLaunchKernelGGL(maxpool333_sep_fwd_kernel<6>, grid, block, c.lds, st_, x, y, argtap, g, c.planes, c.vec); break;
+        case PK_SEP_FWD_3: hipLaunchKernelGGL(maxpool333_sep_fwd_kernel<3>, grid, block, c.lds, st_, x, y, argtap, g, c.planes, c.vec); break;
+        case PK_FWD_133: hipLaunchKernelGGL((maxpool3d_fwd_kernel<1, 3, 3, 1, 2, 2>), grid, block, c.lds, st_, x, y, argtap, g); break;
+        case PK_FWD_333S1: hipLaunchKernelGGL((maxpool3d_fwd_kernel<3, 3, 3, 1, 1, 1>), grid, block, c.lds, st_, x, y, argtap, g); break;
+        case PK_FWD_333S2: hipLaunchKernelGGL((maxpool3d_fwd_kernel<3, 3, 3, 2, 2, 2>), grid, block, c.lds, st_, x, y, argtap, g); break;
+        case PK_FWD_222: hipLaunchKernelGGL((maxpool3d_fwd_kernel<2, 2, 2, 2, 2, 2>), grid, block, c.lds, st_, x, y, argtap, g); break;
+        case PK_FWD_ANY: hipLaunchKernelGGL((maxpool3d_fwd_kernel<0, 0, 0, 0, 0, 0>), grid, block, c.lds, st_, x, y, argtap, g); break;
+        case PK_FWD_LDS_333S1: hipLaunchKernelGGL((maxpool3d_fwd_lds_kernel<3, 3, 3, 1, 1, 1>), grid, block, c.lds, st_, x, y, argtap, g, c.planes); break;
+        case PK_FWD_LDS_ANY: hipLaunchKernelGGL((maxpool3d_fwd_lds_kernel<0, 0, 0, 0, 0, 0>), grid, block, c.lds, st_, x, y, argtap, g, c.planes); break;
+        default: return OTAL_E_UNSUPPORTED;
     }
-    if (is_333_s1(g)) {
-        const int P = g.Hi, Q = P + 2;
-        int tt = 1152 / (P * P);
-        tt = tt < 1 ? 1 : (tt > g.To ? g.To : tt);
-        auto need = [&](int t) { return (size_t)(t + 2) * (Q * Q + Q * P) * sizeof(float) + (size_t)(t + 2) * (Q * P + P * P); };
-        while (tt > 1 && need(tt) > POOL_LDS_BUDGET) --tt;
-        const dim3 grid((g.To + tt - 1) / tt, g.B * g.C);
-        const int vec = (g.x_bs % 4 == 0 && g.x_cs % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) ? 1 : 0;
-        const bool vy = g.y_bs % 4 == 0 && g.y_cs % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-                        (reinterpret_cast<uintptr_t>(argtap) & 3) == 0;
-        if (io == 3) {          // bf16 in / out: the row-per-thread kernels (12 x 12, 6 x 6 planes; 16-byte aligned channel planes)
-            const bool ok = (P == 12 || P == 6) && g.x_bs % 8 == 0 && g.x_cs % 8 == 0 && g.y_bs % 8 == 0 && g.y_cs % 8 == 0 &&
-                            ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 &&
-                            (reinterpret_cast<uintptr_t>(argtap) & 3) == 0;
-            if (!ok) return OTAL_E_UNSUPPORTED;
-            const int TT = 256 / P - 2;
-            const dim3 rgrid((g.To + TT - 1) / TT, g.B * g.C);
-            const size_t lds = (size_t)2 * (TT + 2) * P * P * sizeof(float);
-            if (P == 12) hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<12, true>), rgrid, dim3(256), lds, st_, x, y, argtap, g, TT);
-            else hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<6, true>), rgrid, dim3(256), lds, st_, x, y, argtap, g, TT);
-            return otal_layer_launched(P == 12 ? "maxpool333_rows_fwd<12,bf16>" : "maxpool333_rows_fwd<6,bf16>");
-        }
-        if (vec && vy && (P == 12 || P == 6) && !OTAL_OPT("OTAL_POOL_NOROWS")) {     // one row per thread
-            const int TT = 256 / P - 2;
-            const dim3 rgrid((g.To + TT - 1) / TT, g.B * g.C);
-            const size_t lds = (size_t)2 * (TT + 2) * P * P * sizeof(float);
-            if (P == 12) hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<12>), rgrid, dim3(256), lds, st_, x, y, argtap, g, TT);
-            else hipLaunchKernelGGL((maxpool333_rows_fwd_kernel<6>), rgrid, dim3(256), lds, st_, x, y, argtap, g, TT);
-            return otal_layer_launched(P == 12 ? "maxpool333_rows_fwd<12,f32>" : "maxpool333_rows_fwd<6,f32>");
-        }
-        if (P == 12) hipLaunchKernelGGL(maxpool333_sep_fwd_kernel<12>, grid, dim3(256), need(tt), st_, x, y, argtap, g, tt, vec);
-        else if (P == 6) hipLaunchKernelGGL(maxpool333_sep_fwd_kernel<6>, grid, dim3(256), need(tt), st_, x, y, argtap, g, tt, vec);
-        else hipLaunchKernelGGL(maxpool333_sep_fwd_kernel<3>, grid, dim3(256), need(tt), st_, x, y, argtap, g, tt, vec);
-        return otal_layer_launched(P == 12 ? "maxpool333_sep_fwd<12>" : P == 6 ? "maxpool333_sep_fwd<6>" : "maxpool333_sep_fwd<3>");
-    }
-    if (io) return OTAL_E_UNSUPPORTED;      // bf16 tensors: the strided 3x3 pools and the 12 x 12 / 6 x 6 branch pools only
-    size_t lds = 0;
-    // staging pays when the taps overlap (stride 1: every input is read kvol times); the strided pools read each input
-    // ~2 times and were measured faster with direct loads (r01: 230 vs 514 us for the 1x3x3 / (1,2,2) pool)
-    const bool overlap = g.st == 1 && g.sh == 1 && g.sw == 1;
-    const int tt = overlap ? fwd_planes(g, lds) : 0;
-    if (tt > 0) {
-        const dim3 grid((g.To + tt - 1) / tt, g.B * g.C);
-        OTAL_POOL_DISPATCH(maxpool3d_fwd_lds_kernel, grid, lds, x, y, argtap, g, tt);
-    } else {
-        const dim3 grid((g.To * g.Ho * g.Wo + 255) / 256, g.B * g.C);
-        OTAL_POOL_DISPATCH(maxpool3d_fwd_kernel, grid, 0, x, y, argtap, g);
-    }
-    return otal_layer_launched(pool_inst_name(g, tt > 0 ? 1 : 0));
+    return otal_layer_launched(pool_kernel_name(c.kernel));
 }
 
 // io (backward): bit 0 -- dx is stored as bf16, bit 1 -- dy is stored as bf16, bit 2 -- out_mask is a bf16 tensor
 static int pool_bwd(const int* geom, const int64_t* strides, const float* dy, const unsigned char* argtap, float* dx,
-                    int accumulate, const float* out_mask, const float* out_scale, const unsigned char* signbits, void* stream,
-                    int io = 0) {
+                    int acc, const float* mask, const float* scale, const unsigned char* signbits, void* stream, int io = 0) {
     g_layer_kernel = "";
     if (!geom || !strides || !dy || !dx || !argtap) return OTAL_E_NULL;
-    if (((out_mask == nullptr) && (signbits == nullptr)) != (out_scale == nullptr)) return OTAL_E_NULL;
-    if (out_mask && signbits) return OTAL_E_NULL;
-    const bool all_half = (io & 3) == 3 && (!out_mask || (io & 4));
-    if (io != 0 && io != 1 && !all_half) return OTAL_E_UNSUPPORTED;
-    PoolGeom g;
-    if (int e = fill(g, geom, strides)) return e;
+    PoolQuery q = {};
+    q.dir = POOL_BWD; q.io = io; q.accumulate = acc; q.has_mask = mask != nullptr; q.has_scale = scale != nullptr; q.has_signbits = signbits != nullptr;
+    q.x = (uintptr_t)dx; q.y = (uintptr_t)dy; q.argtap = (uintptr_t)argtap; q.signbits = (uintptr_t)signbits; q.mask = (uintptr_t)mask;
+    q.geom_rc = fill(q.g, geom, strides);
+    const PoolChoice c = pool_choose(q);
+    if (c.rc) return c.rc;
+    const PoolGeom& g = q.g;
+    const dim3 grid(c.gx, c.gy), block(256);
     hipStream_t st_ = (hipStream_t)stream;
-    const int kind = (!out_mask || (reinterpret_cast<uintptr_t>(out_mask) & 15) == 0) ? strided_k33_kind(g, dx, dy) : 0;
-    if ((signbits || io == 1) && !kind) return OTAL_E_UNSUPPORTED;
-    if (io == 1 && kind != 1) return OTAL_E_UNSUPPORTED;
-    if (io && kind && (accumulate || out_mask)) return OTAL_E_UNSUPPORTED;      // bf16-stored dx of a strided pool: plain store, sign-bit mask
-    if (kind) {
-        const int n4 = g.Ti * (g.Hi / 2) * (g.Wi / 4);
-        const dim3 grid((n4 + 255) / 256, g.B * g.C);
-        const FastDiv fW4 = make_fastdiv((uint32_t)(g.Wi / 4)), fH2 = make_fastdiv((uint32_t)(g.Hi / 2));
-        const char* name;
-        if (all_half && kind == 1 && g.Wi % 8 == 0 && g.x_bs % 8 == 0 && g.x_cs % 8 == 0 && g.y_bs % 4 == 0 && g.y_cs % 4 == 0 &&
-            (reinterpret_cast<uintptr_t>(argtap) & 3) == 0 && (!signbits || (reinterpret_cast<uintptr_t>(signbits) & 1) == 0)) {
-            const int n8 = g.Ti * (g.Hi / 2) * (g.Wi / 8);
-            name = "maxpool133_s2_w8_bwd";
-            hipLaunchKernelGGL(maxpool133_s2_w8_bwd_kernel, dim3((n8 + 255) / 256, g.B * g.C), dim3(256), 0, st_, dy, argtap, dx, g, out_scale,
-                               make_fastdiv((uint32_t)(g.Wi / 8)), fH2, signbits);
-        } else if (all_half && kind == 1) {
-            name = "maxpoolk33_s2_bwd<1,bf16,bf16>";
-            hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, true, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        } else if (all_half && g.Wi == 12 && g.x_bs % 4 == 0 && g.x_cs % 4 == 0 && g.y_bs % 2 == 0 && g.y_cs % 2 == 0) {
-            name = "maxpool333_s2_w12_bwd";
-            hipLaunchKernelGGL(maxpool333_s2_w12_bwd_kernel, dim3((g.To * (g.Hi / 2) + 255) / 256, g.B * g.C), dim3(256), 0, st_, dy, argtap, dx, g, out_scale, signbits);
-        } else if (all_half) {
-            name = "maxpoolk33_s2_bwd<3,bf16,bf16>";
-            hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<3, true, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        } else if (io == 1) {
-            name = "maxpoolk33_s2_bwd<1,bf16,f32>";
-            hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, true>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        } else if (kind == 1) {
-            name = "maxpoolk33_s2_bwd<1,f32,f32>";
-            hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, false>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        } else {
-            name = "maxpoolk33_s2_bwd<3,f32,f32>";
-            hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<3, false>), grid, dim3(256), 0, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale, fW4, fH2, signbits);
-        }
-        return otal_layer_launched(name);
+    const FastDiv fW4 = make_fastdiv((uint32_t)(g.Wi / 4)), fW8 = make_fastdiv((uint32_t)(g.Wi / 8)), fH2 = make_fastdiv((uint32_t)(g.Hi / 2));
+    switch (c.kernel) {
+        case PK_W8_BWD: hipLaunchKernelGGL(maxpool133_s2_w8_bwd_kernel, grid, block, c.lds, st_, dy, argtap, dx, g, scale, fW8, fH2, signbits); break;
+        case PK_W12_BWD: hipLaunchKernelGGL(maxpool333_s2_w12_bwd_kernel, grid, block, c.lds, st_, dy, argtap, dx, g, scale, signbits); break;
+        case PK_K33_BWD_1HH: hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, true, true>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale, fW4, fH2, signbits); break;
+        case PK_K33_BWD_3HH: hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<3, true, true>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale, fW4, fH2, signbits); break;
+        case PK_K33_BWD_1HF: hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, true>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale, fW4, fH2, signbits); break;
+        case PK_K33_BWD_1FF: hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<1, false>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale, fW4, fH2, signbits); break;
+        case PK_K33_BWD_3FF: hipLaunchKernelGGL((maxpoolk33_s2_bwd_kernel<3, false>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale, fW4, fH2, signbits); break;
+        case PK_ROWS_BWD_12H: hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<12, true>), grid, block, c.lds, st_, dy, argtap, dx, g, c.planes, acc, mask, scale); break;
+        case PK_ROWS_BWD_6H: hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<6, true>), grid, block, c.lds, st_, dy, argtap, dx, g, c.planes, acc, mask, scale); break;
+        case PK_ROWS_BWD_12: hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<12>), grid, block, c.lds, st_, dy, argtap, dx, g, c.planes, acc, mask, scale); break;
+        case PK_ROWS_BWD_6: hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<6>), grid, block, c.lds, st_, dy, argtap, dx, g, c.planes, acc, mask, scale); break;
+        case PK_SEP_BWD_12V4: hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<12, true>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale); break;
+        case PK_SEP_BWD_6V4: hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<6, true>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale); break;
+        case PK_SEP_BWD_12: hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<12, false>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale); break;
+        case PK_SEP_BWD_6: hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<6, false>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale); break;
+        case PK_SEP_BWD_3: hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<3, false>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale); break;
+        case PK_BWD_133: hipLaunchKernelGGL((maxpool3d_bwd_kernel<1, 3, 3, 1, 2, 2>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale); break;
+        case PK_BWD_333S1: hipLaunchKernelGGL((maxpool3d_bwd_kernel<3, 3, 3, 1, 1, 1>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale); break;
+        case PK_BWD_333S2: hipLaunchKernelGGL((maxpool3d_bwd_kernel<3, 3, 3, 2, 2, 2>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale); break;
+        case PK_BWD_222: hipLaunchKernelGGL((maxpool3d_bwd_kernel<2, 2, 2, 2, 2, 2>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale); break;
+        case PK_BWD_ANY: hipLaunchKernelGGL((maxpool3d_bwd_kernel<0, 0, 0, 0, 0, 0>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale); break;
+        case PK_BWD_LDS_133: hipLaunchKernelGGL((maxpool3d_bwd_lds_kernel<1, 3, 3, 1, 2, 2>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale, c.planes, c.tlo_max); break;
+        case PK_BWD_LDS_333S1: hipLaunchKernelGGL((maxpool3d_bwd_lds_kernel<3, 3, 3, 1, 1, 1>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale, c.planes, c.tlo_max); break;
+        case PK_BWD_LDS_333S2: hipLaunchKernelGGL((maxpool3d_bwd_lds_kernel<3, 3, 3, 2, 2, 2>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale, c.planes, c.tlo_max); break;
+        case PK_BWD_LDS_222: hipLaunchKernelGGL((maxpool3d_bwd_lds_kernel<2, 2, 2, 2, 2, 2>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale, c.planes, c.tlo_max); break;
+        case PK_BWD_LDS_ANY: hipLaunchKernelGGL((maxpool3d_bwd_lds_kernel<0, 0, 0, 0, 0, 0>), grid, block, c.lds, st_, dy, argtap, dx, g, acc, mask, scale, c.planes, c.tlo_max); break;
+        default: return OTAL_E_UNSUPPORTED;
     }
-    if (is_333_s1(g)) {
-        const int PP = g.Hi * g.Wi, ti = POOL_SEP_ELEMS / PP;
-        const size_t l3 = (size_t)((ti + 2) * PP + 2 * ti * PP) * sizeof(float) + (size_t)(ti + 2) * PP;
-        const dim3 grid((g.Ti + ti - 1) / ti, g.B * g.C);
-        const bool v4 = g.Hi != 3 && g.x_bs % 4 == 0 && g.x_cs % 4 == 0 && g.y_bs % 4 == 0 && g.y_cs % 4 == 0 &&
-                        ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(out_mask) |
-                          reinterpret_cast<uintptr_t>(argtap)) & 15) == 0 && ((int64_t)g.To * PP) % 4 == 0;
-        const bool v2 = g.x_bs % 4 == 0 && g.x_cs % 4 == 0 && g.y_bs % 4 == 0 && g.y_cs % 4 == 0 &&
-                        ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(out_mask) |
-                          reinterpret_cast<uintptr_t>(argtap)) & 15) == 0;
-        if (io) {               // bf16 dy / dx / mask: the row-per-thread kernels (12 x 12, 6 x 6 planes; 16-byte aligned channel planes)
-            const bool ok = all_half && (g.Hi == 12 || g.Hi == 6) && g.x_bs % 8 == 0 && g.x_cs % 8 == 0 && g.y_bs % 8 == 0 && g.y_cs % 8 == 0 &&
-                            ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(out_mask) |
-                              reinterpret_cast<uintptr_t>(argtap)) & 15) == 0;
-            if (!ok) return OTAL_E_UNSUPPORTED;
-            const int P = g.Hi, TIr = 256 / P - 2, TB = P == 12 ? 12 : 8;
-            const dim3 rgrid((g.Ti + TIr - 1) / TIr, g.B * g.C);
-            const size_t lds = (size_t)2 * (TIr + 2) * P * P * sizeof(float) + (size_t)(TIr + 2) * P * TB;
-            if (P == 12) hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<12, true>), rgrid, dim3(256), lds, st_, dy, argtap, dx, g, TIr, accumulate, out_mask, out_scale);
-            else hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<6, true>), rgrid, dim3(256), lds, st_, dy, argtap, dx, g, TIr, accumulate, out_mask, out_scale);
-            return otal_layer_launched(P == 12 ? "maxpool333_rows_bwd<12,bf16>" : "maxpool333_rows_bwd<6,bf16>");
-        }
-        if (v2 && (g.Hi == 12 || g.Hi == 6) && !OTAL_OPT("OTAL_POOL_NOROWS")) {      // one input row per thread
-            const int P = g.Hi, TIr = 256 / P - 2, TB = P == 12 ? 12 : 8;
-            const dim3 rgrid((g.Ti + TIr - 1) / TIr, g.B * g.C);
-            const size_t lds = (size_t)2 * (TIr + 2) * P * P * sizeof(float) + (size_t)(TIr + 2) * P * TB;
-            if (P == 12) hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<12>), rgrid, dim3(256), lds, st_, dy, argtap, dx, g, TIr, accumulate, out_mask, out_scale);
-            else hipLaunchKernelGGL((maxpool333_rows_bwd_kernel<6>), rgrid, dim3(256), lds, st_, dy, argtap, dx, g, TIr, accumulate, out_mask, out_scale);
-            return otal_layer_launched(P == 12 ? "maxpool333_rows_bwd<12,f32>" : "maxpool333_rows_bwd<6,f32>");
-        }
-        if (g.Hi == 12 && v4) hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<12, true>), grid, dim3(256), l3, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale);
-        else if (g.Hi == 6 && v4) hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<6, true>), grid, dim3(256), l3, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale);
-        else if (g.Hi == 12) hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<12, false>), grid, dim3(256), l3, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale);
-        else if (g.Hi == 6) hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<6, false>), grid, dim3(256), l3, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale);
-        else hipLaunchKernelGGL((maxpool333_sep_bwd_kernel<3, false>), grid, dim3(256), l3, st_, dy, argtap, dx, g, accumulate, out_mask, out_scale);
-        return otal_layer_launched(g.Hi == 12 ? (v4 ? "maxpool333_sep_bwd<12,v4>" : "maxpool333_sep_bwd<12>")
-                                   : g.Hi == 6 ? (v4 ? "maxpool333_sep_bwd<6,v4>" : "maxpool333_sep_bwd<6>") : "maxpool333_sep_bwd<3>");
-    }
-    if (io) return OTAL_E_UNSUPPORTED;
-    size_t lds = 0;
-    int tlo_max = 0;
-    const int ti = bwd_planes(g, tlo_max, lds);
-    if (ti > 0) {
-        const dim3 grid((g.Ti + ti - 1) / ti, g.B * g.C);
-        OTAL_POOL_DISPATCH(maxpool3d_bwd_lds_kernel, grid, lds, dy, argtap, dx, g, accumulate, out_mask, out_scale, ti, tlo_max);
-    } else {
-        const dim3 grid((g.Ti * g.Hi * g.Wi + 255) / 256, g.B * g.C);
-        OTAL_POOL_DISPATCH(maxpool3d_bwd_kernel, grid, 0, dy, argtap, dx, g, accumulate, out_mask, out_scale);
-    }
-    return otal_layer_launched(pool_inst_name(g, ti > 0 ? 3 : 2));
+    return otal_layer_launched(pool_kernel_name(c.kernel));
 }
-
-thread_local const char* g_layer_kernel = "";
-extern "C" const char* otal_layer_last_kernel(void) { return g_layer_kernel; }
 
 extern "C" int otal_maxpool3d_fwd(const int* geom, const int64_t* strides, const float* x, float* y,
                                   unsigned char* argtap, void* stream) {
@@ -1628,7 +1416,7 @@ extern "C" size_t otal_maxpool3d_signbits_bytes(const int* geom, const int64_t* 
     if (!geom || !strides) return 0;
     PoolGeom g;
     if (fill(g, geom, strides)) return 0;
-    if (!strided_k33_kind(g, nullptr, nullptr)) return 0;
+    if (!strided_k33_kind(g)) return 0;
     return (size_t)g.B * g.C * g.Ti * (g.Hi / 2) * (g.Wi / 4);
 }
 extern "C" int otal_maxpool3d_fwd_signbits(const int* geom, const int64_t* strides, const float* x, float* y,

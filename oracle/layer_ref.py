@@ -12,7 +12,7 @@ Every summing result comes with an element-wise error scale e and a term count K
     |got - ref| <= C * 2^-24 * f(K) * e + r * |ref|
 with one constant C per family (f and C: tests/test_layer_calls_gpu.py), r the storage rounding of the output (bf16 or fp32).
 
-Winner bytes.  Two encodings, chosen by the geometry alone (pool3d.hip is_333_s1):
+Winner bytes.  Two encodings, chosen by the geometry alone (pool_select.h is_333_s1):
   * LINEAR -- every pool except the one below: the byte holds the winner's tap (dt * kh + dh) * kw + dw, 255 when a padded
     zero won;
   * STAGED -- 3x3x3, stride 1, pad 1, To == Ti, square planes of side 12, 6 or 3 (the Inception branch pools): the maximum is
@@ -76,7 +76,7 @@ def levels(T, nlev, lev):
 
 # ------------------------------------------------------------------------------------------------ max-pool
 def staged(d):
-    """True where the kernels write STAGED winner bytes (pool3d.hip is_333_s1): the 3x3x3 / stride 1 / pad 1 pools on square
+    """True where the kernels write STAGED winner bytes (csrc/pool_select.h is_333_s1): the 3x3x3 / stride 1 / pad 1 pools on square
     planes of side 12, 6 or 3 with T unchanged.  Every other geometry: LINEAR bytes."""
     return (tuple(d[k] for k in ("kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw")) == (3, 3, 3, 1, 1, 1, 1, 1, 1)
             and d["Hi"] == d["Wi"] and d["Hi"] in (12, 6, 3) and d["To"] == d["Ti"] and d["Ho"] == d["Hi"] and d["Wo"] == d["Wi"])

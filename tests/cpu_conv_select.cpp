@@ -1,19 +1,7 @@
 // tests/cpu_conv_select.cpp -- CPU harness: the kernel choice of the convolution library (opental_amd/csrc/conv_select.h),
-// compiled with g++ by tests/test_conv_select_cpu.py.  The run-time switches answer with their table defaults (options.h),
-// whatever the environment says, unless cpu_set_option() changes one.
-#include <cstring>
+// compiled with g++ by tests/test_conv_select_cpu.py.  The run-time switches: tests/cpu_options.h.
 #include "conv_select.h"
-
-static int g_options[OTAL_NUM_OPTIONS];
-static bool g_options_set = false;
-
-int* otal_option_slot(int index) {
-    if (!g_options_set) {
-        for (int i = 0; i < OTAL_NUM_OPTIONS; ++i) g_options[i] = OTAL_OPTIONS[i].dflt;
-        g_options_set = true;
-    }
-    return &g_options[index];
-}
+#include "cpu_options.h"
 
 static void fill(ConvGeom& g, const int* d, const int64_t* s) {
     g.B = d[0]; g.Cin = d[1]; g.Cout = d[2]; g.Ti = d[3]; g.Hi = d[4]; g.Wi = d[5];
@@ -22,12 +10,6 @@ static void fill(ConvGeom& g, const int* d, const int64_t* s) {
     g.nlev = d[18];
     for (int i = 0; i <= OTAL_CONV_MAX_LEVELS; ++i) g.lev[i] = d[19 + i];
     g.x_bs = s[0]; g.x_cs = s[1]; g.y_bs = s[2]; g.y_cs = s[3];
-}
-
-extern "C" int cpu_set_option(const char* name, int value) {
-    for (int i = 0; i < OTAL_NUM_OPTIONS; ++i)
-        if (!strcmp(OTAL_OPTIONS[i].name, name)) { *otal_option_slot(i) = value; return 0; }
-    return -1;
 }
 
 extern "C" const char* cpu_kernel_name(int kernel) { return conv_kernel_name(kernel); }

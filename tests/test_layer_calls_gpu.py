@@ -16,8 +16,10 @@ written, everything else in the buffers (other channels, slack, a guard tail) ke
 winner bytes, sign bits and conversions match exactly; every summed result meets
     |got - ref| <= C * 2^-24 * f(K) * e + r * |ref|
 with ONE constant C per family (C_POOL, C_GN, C_GLUE) and r the output's storage rounding; otal_layer_last_kernel() names
-the kernel.  A GroupNorm backward's ReLU mask is the LIBRARY forward's y > 0, so a forward / backward disagreement is a
+the kernel, and for a pool it is the kernel (or the refusal) pool_choose() answers for the same call on the CPU
+(opental_amd/csrc/pool_select.h through tests/cpu_pool_select.cpp).  A GroupNorm backward's ReLU mask is the LIBRARY forward's y > 0, so a forward / backward disagreement is a
 full-size error.  The last item checks that every kernel name in POOL_KERNELS / GN_PATHS was reached."""
+import contextlib
 import ctypes
 import os
 import re
@@ -26,6 +28,7 @@ import numpy as np
 import pytest
 import torch
 
+import pool_select_harness as PS
 from oracle import layer_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -57,7 +60,6 @@ POOL_KERNELS = (
     "maxpool333_sep_bwd<12,v4>", "maxpool333_sep_bwd<6,v4>", "maxpool333_sep_bwd<12>", "maxpool333_sep_bwd<6>",
     "maxpool333_sep_bwd<3>") + tuple(f"maxpool3d_bwd{s}<{k}>" for s in ("", "_lds")
                                      for k in ("133/122", "333/111", "333/222", "222/222", "generic"))
-# (maxpool3d_fwd_lds<133/122>, <333/222> and <222/222> are compiled but unreachable: only stride-1 pools stage their input)
 GN_PATHS = ("gn_relu_fwd<single>", "gn_relu_fwd<pair>", "gn_relu_bwd<single,keep_dx,terms=0>",
             "gn_relu_bwd<single,no_keep_dx,terms=0>", "gn_relu_bwd<pair,keep_dx,terms=0>", "gn_relu_bwd<single,keep_dx,terms=1>",
             "gn_relu_bwd<single,keep_dx,terms=2>", "gn_relu_bwd<single,keep_dx,terms=3>", "gn_relu_bwd<single,no_keep_dx,terms=3>")
@@ -174,17 +176,32 @@ ITEMS = items()
 
 
 # ------------------------------------------------------------------------------------------------ library state
-@pytest.fixture(scope="module")
-def lib():
+@contextlib.contextmanager
+def default_library():
+    """The loaded library with every option at its table default (restored afterwards)."""
     from opental_amd import _lib as L
     lib = L.lib()
     lib.otal_layer_last_kernel.restype = ctypes.c_char_p
     saved = [(n, lib.otal_get_option(n.encode(), d)) for n, d in OPTIONS]
     for n, d in OPTIONS:
         L.set_option(n, d)
-    yield lib
-    for n, v in saved:
-        L.set_option(n, v)
+    try:
+        yield lib
+    finally:
+        for n, v in saved:
+            L.set_option(n, v)
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    """pool_choose() on the CPU (tests/cpu_pool_select.cpp): the kernel each pool launch must report."""
+    return PS.build(tmp_path_factory.mktemp("cpupoolselect"))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    with default_library() as lib:
+        yield lib
     if WORST:
         print("\nlargest err / bound per kernel:")
         for k in sorted(WORST):
@@ -294,7 +311,7 @@ def pool_launch(lib, entry, ga, sa, x, y, arg, bits, io):
     return lib.otal_maxpool3d_fwd_io(ga, sa, x.ptr(), y.ptr(), arg.ptr(), bp, io, st)
 
 
-def run_pool_fwd(lib, label, d, strides, addr, entry, io, nonneg, has_bits, switches, gen):
+def run_pool_fwd(lib, label, d, strides, addr, entry, io, nonneg, has_bits, switches, gen, expect):
     B, C = d["B"], d["C"]
     xs, ys = [B, C, d["Ti"], d["Hi"], d["Wi"]], [B, C, d["To"], d["Ho"], d["Wo"]]
     x_st = [strides[0], strides[1]] + dense(xs[2:])
@@ -316,6 +333,7 @@ def run_pool_fwd(lib, label, d, strides, addr, entry, io, nonneg, has_bits, swit
     finally:
         set_switches(switches, False)
     torch.cuda.synchronize()
+    assert (rc, name) == expect, f"{label}: the library answered {(rc, name)}, pool_choose() {expect}"
     for b_ in (y, arg) + ((bits,) if bits is not None else ()):
         b_.outside_intact(label)
     if rc == E_UNSUPPORTED:
@@ -338,7 +356,7 @@ def run_pool_fwd(lib, label, d, strides, addr, entry, io, nonneg, has_bits, swit
     return rc, name
 
 
-def run_pool_bwd(lib, label, d, strides, addr, entry, io, acc, has_mask, has_scale, has_bits, switches, gen):
+def run_pool_bwd(lib, label, d, strides, addr, entry, io, acc, has_mask, has_scale, has_bits, switches, gen, expect):
     from opental_amd import _lib as L
     B, C = d["B"], d["C"]
     xs, ys = [B, C, d["Ti"], d["Hi"], d["Wi"]], [B, C, d["To"], d["Ho"], d["Wo"]]
@@ -397,6 +415,7 @@ def run_pool_bwd(lib, label, d, strides, addr, entry, io, acc, has_mask, has_sca
     finally:
         set_switches(switches, False)
     torch.cuda.synchronize()
+    assert (rc, name) == expect, f"{label}: the library answered {(rc, name)}, pool_choose() {expect}"
     dx.outside_intact(label)
     if rc == E_UNSUPPORTED:
         assert name == "", name
@@ -737,35 +756,57 @@ def pool_call(f, d, variant):
     return entry, io, acc, mask, scale, bits
 
 
-@pytest.mark.parametrize("item", ITEMS, ids=[it[0] for it in ITEMS])
-def test_layer_call(lib, item):
-    label, i, f, variant, switches = item
+def pool_item(item):
+    """(d, strides, addr, call) of a pool item as it is launched: B clipped to two samples (samples beyond the second change
+    nothing but the grid's height), the variant applied; call = pool_call()'s tuple."""
+    _, i, f, variant, _ = item
     if isinstance(i, tuple):
-        d, addr, eps = R.unpack(f, i[1]), list(i[2]), 1e-5
-        seed = sum(i[1]) % 100003
+        d, addr = R.unpack(f, i[1]), list(i[2])
     else:
-        (d, addr), eps = row(i), float(Z["eps"][i])
-        seed = 1000 + i
-        if f.startswith("pool"):
-            d["B"] = min(d["B"], 2)         # samples beyond the second change nothing but the grid's height
-    gen = torch.Generator(device=DEV).manual_seed(seed + len(label))
+        d, addr = row(i)
+        d["B"] = min(d["B"], 2)
     if variant == "unaligned":
         addr = [4] * 5
+    if variant == "argodd":
+        addr = addr[:2] + [1] + addr[3:]
+    return d, [d["x_bs"], d["x_cs"], d["y_bs"], d["y_cs"]], addr, pool_call(f, d, variant)
+
+
+def pool_ints(d, strides, call):
+    """The integer columns of a pool call in the layout of oracle.layer_ref.FIELDS, as passed (call[0] is the entry point)."""
+    return [d[k] for k in R.GEOM] + list(strides) + [int(v) for v in call[1:]]
+
+
+def run_pool(lib, H, label, f, d, strides, addr, call, switches, gen):
+    """Launches the call and checks it; the return code and the kernel must be those pool_choose() answers on the CPU."""
+    c = PS.choose(H, f, pool_ints(d, strides, call), addr, switches)
+    expect = (c["rc"], c["kernel"])
     if f == "pool_fwd":
-        entry, io, nonneg, bits = pool_call(f, d, variant)
-        if variant == "argodd":
-            addr = addr[:2] + [1] + addr[3:]
-        strides = [d["x_bs"], d["x_cs"], d["y_bs"], d["y_cs"]]
-        rc, name = run_pool_fwd(lib, label, d, strides, addr, entry, io, nonneg, bits, switches, gen)
+        entry, io, nonneg, bits = call
+        return run_pool_fwd(lib, label, d, strides, addr, entry, io, nonneg, bits, switches, gen, expect)
+    entry, io, acc, mask, scale, bits = call
+    return run_pool_bwd(lib, label, d, strides, addr, entry, io, acc, mask, scale, bits, switches, gen, expect)
+
+
+def item_seed(item):
+    label, i = item[0], item[1]
+    return (sum(i[1]) % 100003 if isinstance(i, tuple) else 1000 + i) + len(label)
+
+
+@pytest.mark.parametrize("item", ITEMS, ids=[it[0] for it in ITEMS])
+def test_layer_call(lib, harness, item):
+    label, i, f, variant, switches = item
+    gen = torch.Generator(device=DEV).manual_seed(item_seed(item))
+    if f.startswith("pool"):
+        d, strides, addr, call = pool_item(item)
+        rc, name = run_pool(lib, harness, label, f, d, strides, addr, call, switches, gen)
         assert rc == 0 or variant is not None or switches, f"{label}: the recorded call was refused ({rc})"
-    elif f == "pool_bwd":
-        entry, io, acc, mask, scale, bits = pool_call(f, d, variant)
-        if variant == "argodd":
-            addr = addr[:2] + [1] + addr[3:]
-        strides = [d["x_bs"], d["x_cs"], d["y_bs"], d["y_cs"]]
-        rc, name = run_pool_bwd(lib, label, d, strides, addr, entry, io, acc, mask, scale, bits, switches, gen)
-        assert rc == 0 or variant is not None or switches, f"{label}: the recorded call was refused ({rc})"
-    elif f == "gn_fwd":
+        return
+    if isinstance(i, tuple):
+        d, addr, eps = R.unpack(f, i[1]), list(i[2]), 1e-5
+    else:
+        (d, addr), eps = row(i), float(Z["eps"][i])
+    if f == "gn_fwd":
         entry = str(Z["entry"][i]) if not isinstance(i, tuple) else ("otal_gn_relu_fwd_pair" if d["pair"] else "otal_gn_relu_fwd")
         run_gn_fwd(lib, label, d, eps, entry, gen)
     elif f == "gn_bwd":
@@ -783,22 +824,27 @@ def test_layer_call(lib, item):
 
 
 # ------------------------------------------------------------------------------------------------ refusals
-def test_documented_refusals_write_nothing(lib):
+def pool_refusals():
+    """(label, family, d, strides, addr, call): the documented pool refusals."""
+    out = []
+    # io = 1 (bf16 x, fp32 y) on a pool that is not a strided 3x3 pool
+    d = dict(zip(R.GEOM, pool_geom((4, 6, 6), (3, 3, 3), (1, 1, 1))))
+    P, Po = 4 * 36, 4 * 36
+    out.append(("refuse-io1", "pool_fwd", d, [2 * P, P, 2 * Po, Po], [0] * 5, ("otal_maxpool3d_fwd_io", 1, 0, 0)))
+    # accumulate into a bf16 dx of a strided pool
+    d = dict(zip(R.GEOM, pool_geom((2, 8, 16), (1, 3, 3), (1, 2, 2))))
+    P, Po = 2 * 8 * 16, 2 * 4 * 8
+    out.append(("refuse-acc-bf16", "pool_bwd", d, [2 * P, P, 2 * Po, Po], [0] * 5, ("otal_maxpool3d_bwd_io", 3, 1, 0, 1, 1)))
+    return out
+
+
+def test_documented_refusals_write_nothing(lib, harness):
     from opental_amd import _lib as L
     gen = torch.Generator(device=DEV).manual_seed(5)
     st = L.stream()
-    # io = 1 (bf16 x, fp32 y) on a pool that is not a strided 3x3 pool
-    g = pool_geom((4, 6, 6), (3, 3, 3), (1, 1, 1))
-    d = dict(zip(R.GEOM, g))
-    P, Po = 4 * 36, 4 * 36
-    rc, name = run_pool_fwd(lib, "refuse-io1", d, [2 * P, P, 2 * Po, Po], [0] * 5, "otal_maxpool3d_fwd_io", 1, 0, 0, (), gen)
-    assert rc == E_UNSUPPORTED and name == ""
-    # accumulate into a bf16 dx of a strided pool
-    g = pool_geom((2, 8, 16), (1, 3, 3), (1, 2, 2))
-    d = dict(zip(R.GEOM, g))
-    P, Po = 2 * 8 * 16, 2 * 4 * 8
-    rc, name = run_pool_bwd(lib, "refuse-acc-bf16", d, [2 * P, P, 2 * Po, Po], [0] * 5, "otal_maxpool3d_bwd_io", 3, 1, 0, 1, 1, (), gen)
-    assert rc == E_UNSUPPORTED and name == ""
+    for label, f, d, strides, addr, call in pool_refusals():
+        rc, name = run_pool(lib, harness, label, f, d, strides, addr, call, (), gen)
+        assert rc == E_UNSUPPORTED and name == ""
     # pyramid merge: odd t0 (both directions), t0 > 1024 (backward: its level-0 row lives in LDS)
     B, C = 1, 2
     for t0, fwd in ((7, True), (7, False), (1026, False)):

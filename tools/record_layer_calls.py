@@ -1,6 +1,7 @@
 """Records every max-pool, GroupNorm and glue call of the model's workloads, for tests/test_layer_calls_gpu.py.
 
     python tools/record_layer_calls.py record OUT.npz     # on the GPU: every call -> OUT.npz, distinct ones -> the golden file
+    python tools/record_layer_calls.py pool_choice OUT.npz   # on the GPU: the kernel every pool item of the test gets
 
 `record` runs what tools/record_conv_calls.py runs -- one eager THUMOS14 training step at b = 8 and at b = 1, one ActivityNet
 step at b = 2 and one inference batch (bench.py's models, synthetic clips, bf16 operands) -- and a second THUMOS14 step at b = 8
@@ -9,6 +10,13 @@ keeps the entry point, the integer arguments in the layout of oracle.layer_ref.F
 accumulate, which nullable operands were given, summed terms, level table), GroupNorm's eps, and each pointer's address
 mod 16 in the order of oracle.layer_ref.ADDRS.  tests/golden/layer_calls.npz keeps one row per distinct call, from the first
 workload that made it.
+
+`pool_choice` is the fixture of tests/test_pool_select_cpu.py (tests/golden/pool_choice.npz): it makes every pool item of
+tests/test_layer_calls_gpu.py -- the recorded rows, their variants, pool_extra() and the documented refusals -- exactly as
+the test makes it (the test's own functions, value checks included) and keeps per item the label, the family, the integer
+columns of FIELDS as passed after the variant, the five address residues, the switches set, the return code and
+otal_layer_last_kernel().  Record it with the library whose choice is to be pinned, BEFORE a change to the selection (the
+test's functions also hold every answer against the CPU harness of the working tree, so the two must agree at that point).
 """
 import ctypes
 import os
@@ -226,5 +234,34 @@ def record(out):
     print(f"{len(c)} calls, {len(keep)} distinct -> {GOLDEN}; distinct rows per workload: {per}")
 
 
+def pool_choice(out):
+    import torch
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import tempfile
+    import test_layer_calls_gpu as T
+    rows = []
+    with T.default_library() as lib, tempfile.TemporaryDirectory() as tmp:
+        H = T.PS.build(tmp)
+        for item in T.ITEMS:
+            label, i, f, _, switches = item
+            if not f.startswith("pool"):
+                continue
+            d, strides, addr, call = T.pool_item(item)
+            gen = torch.Generator(device=T.DEV).manual_seed(T.item_seed(item))
+            rc, name = T.run_pool(lib, H, label, f, d, strides, addr, call, switches, gen)
+            rows.append((label, f, T.pool_ints(d, strides, call), addr, switches, rc, name, -1 if isinstance(i, tuple) else i))
+        gen = torch.Generator(device=T.DEV).manual_seed(5)
+        for label, f, d, strides, addr, call in T.pool_refusals():
+            rc, name = T.run_pool(lib, H, label, f, d, strides, addr, call, (), gen)
+            rows.append((label, f, T.pool_ints(d, strides, call), addr, (), rc, name, -1))
+    width = len(FIELDS["pool_bwd"])
+    np.savez_compressed(out, label=np.array([r[0] for r in rows]), family=np.array([r[1] for r in rows]),
+                        ints=np.array([r[2] + [0] * (width - len(r[2])) for r in rows], np.int64),
+                        addr16=np.array([r[3] for r in rows], np.int64), switches=np.array([",".join(r[4]) for r in rows]),
+                        rc=np.array([r[5] for r in rows], np.int64), kernel=np.array([r[6] for r in rows]),
+                        row=np.array([r[7] for r in rows], np.int64))     # row: the item's row of layer_calls.npz, -1 = none
+    print(f"{len(rows)} pool items, {len(set(r[6] for r in rows) - {''})} kernels, {sum(r[5] != 0 for r in rows)} refusals -> {out}")
+
+
 if __name__ == "__main__":
-    {"record": record}[sys.argv[1]](sys.argv[2])
+    {"record": record, "pool_choice": pool_choice}[sys.argv[1]](sys.argv[2])
