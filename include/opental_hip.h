@@ -394,6 +394,50 @@ int otal_softnms_classes_ws(const float* seg, const float* score, const float* u
                             int* counts, int* out_index, int out_cols, void* scratch, size_t scratch_bytes,
                             int total_clips, void* stream);
 
+/* ------------------------------------------------------------------ OpenMax baseline (csrc/openmax.hip) ----
+ * Added under ABI 26 (new symbols only).  Feature rows are addressed by ELEMENT strides: row n (0 <= n < N), channel d at
+ *     feat + (n / rows_per_batch) * sb + (n % rows_per_batch) * sr + d * sc,
+ * so a contiguous (B, A, D) tensor (rows_per_batch A, sb A*D, sr D, sc 1) and a permuted view of a channel-major (B, D, A)
+ * map (sb D*A, sr 1, sc A) are both read in place, each element once; both give the same bits.  MAVs are contiguous
+ * (K, D) float, 16-byte aligned.  Limits: K <= 16, D <= 512, D % 16 == 0 (what one workgroup stages in LDS); beyond them
+ * OTAL_E_UNSUPPORTED.  All sums over D run in fp32 in one fixed order (16 partial sums, channel d in partial d % 16, then a tree).
+ *
+ * otal_openmax_dist: compute_eucos_dist (AFSD/thumos14/openmax.py:7-9; the loops of test_openmax.py:319,324 and
+ * openmax.py:56-62): dist = ||mav - f||_2 / 200 + (1 - cos(mav, f)).  labels NULL: dist is (N, K), every row against every
+ * MAV.  labels (N) int32: dist is (N), row n against MAV labels[n]; a label outside [0, K) gives -1. */
+int otal_openmax_dist(const float* feat, int N, int rows_per_batch, int64_t sb, int64_t sr, int64_t sc, const float* mav,
+                      int K, int D, const int* labels, float* dist, void* stream);
+/* otal_openmax_class_means: the per-class np.mean of test_openmax.py:317-318,322-323.  means (K, D) = mean of the rows with
+ * labels[n] == k (0 for a class without rows), counts (K) int32; labels outside [0, K) are ignored.  Fixed summation order,
+ * no floating-point atomics: two runs give the same bits.  Any K and D. */
+int otal_openmax_class_means(const float* feat, int N, int rows_per_batch, int64_t sb, int64_t sr, int64_t sc,
+                             const int* labels, int K, int D, float* means, int* counts, void* stream);
+/* otal_openmax_probs: OpenMax.forward (openmax.py:42-86) for N rows in one launch.  logits: row n, class j at
+ * logits[n * ldl + j] (ldl >= K; a `conf[:, 1:]` view has ldl = K + 1).  wb (K, 3) float = per class, prepared in float64
+ * from the libMR fit (MetaRecognition.cpp:141-152,:211-216): off = small_score + (scale - translate), 1 / scale, shape;
+ * w_score(d) = -expm1(-exp(shape * log1p((d - off) / scale))), 0 where the translated argument is <= 0.  R: the alpha rank,
+ * 1 <= R <= K (else OTAL_E_UNSUPPORTED); the i-th largest logit gets alpha (R + 1 - i) / R, equal logits rank the higher
+ * index first (numpy `argsort()[::-1]`).  probs (N, K + 1): column 0 is P(unknown).  The softmax subtracts the maximum
+ * exponent (same value as the reference, no overflow). */
+int otal_openmax_probs(const float* logits, int64_t ldl, const float* feat, int N, int rows_per_batch, int64_t sb, int64_t sr,
+                       int64_t sc, const float* mav, const float* wb, int K, int D, int R, float* probs, void* stream);
+/* otal_decode_clips_openmax: decode_output + the threshold test of `filtering` (test_openmax.py:141-189) for nclips clips in
+ * one launch, next to otal_decode_clips_ex and with its output layout: seg (nclips, A, 2) seconds, score (nclips, K, A),
+ * flag (nclips, K, A) uint8 = score > conf_thresh, K = C - first_class (conf / prop_conf are (nclips, A, C); the first
+ * `first_class` logits -- the background -- are dropped, test_openmax.py:158-159), plus unknown (nclips, A) =
+ * (P0 + P0_prop) / 2 * sigmoid(center), the reference's score row 0.  score = (P + P_prop) / 2 * sigmoid(center) with
+ * P = OpenMax(mav, wb)(conf[:, first_class:], feat) and P_prop = OpenMax(mav_prop, wb_prop)(prop_conf[:, first_class:], F),
+ * F = feat when refined_feature == 0 -- the reference as shipped feeds the COARSE feature to the refined stage
+ * (test_openmax.py:159) -- and prop_feat when refined_feature == 1 (prop_feat / prop_feat_strides may be NULL otherwise).
+ * feat_strides / prop_feat_strides: HOST arrays {sb, sr, sc} of (nclips, A, D) views.  No (N, K + 1) intermediate is written. */
+int otal_decode_clips_openmax(const float* loc, const float* prop_loc, const float* priors, const float* conf,
+                              const float* prop_conf, const float* center, const float* offsets, const float* fps,
+                              const float* feat, const float* prop_feat, const int64_t* feat_strides,
+                              const int64_t* prop_feat_strides, const float* mav, const float* mav_prop, const float* wb,
+                              const float* wb_prop, float* seg, float* score, float* unknown, unsigned char* flag,
+                              int nclips, int A, int C, int first_class, int D, int R, int refined_feature,
+                              float clip_length, float conf_thresh, void* stream);
+
 /* ------------------------------------------------------------------ detection-head convolutions ----
  * The skinny Unit1D heads of one CoarsePyramid stage (AFSD/thumos14/BDNet.py:205-272, :337-353, :399-412;
  * AFSD/common/layers.py:178-214: SAME pad + nn.Conv1d(512, cout, k) + bias, cout = 1 / 2 / num_classes, k = 1 / 3) as
