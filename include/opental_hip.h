@@ -462,6 +462,21 @@ int otal_head_convs_bwd_parts(int n_heads, int n_inputs, const int* in_idx, cons
                         const float* const* x, const float* const* w, const float* const* dy, float* const* dx,
                         float* const* dw, float* const* db, int B, int C, int N, int nlev, const int* lev, int parts, void* stream);
 
+/* ------------------------------------------------------------------ distance head (RPL / GCPL baselines) ----
+ * RPLHead with one centre per class and the 'l2' metric (AFSD/common/layers.py:314-351; the conf_head / prop_conf_head of
+ * AFSD/thumos14/BDNet.py:218-219,:248-249 under use_rpl), on the channel-major map where it lies:
+ *   x (B, D, N), centers (C, D) -> dist (B, C, N),  dist[b][c][n] = 1/D sum_d (x[b][d][n] - centers[c][d])^2
+ * as the direct sum of squared differences in fp32 (the reference expands |f|^2 - 2 f.c + |c|^2 around a matmul, between
+ * two permuted copies).  ONE launch.  Backward, g (B, C, N):
+ *   dx[b][d][n]    = 2/D sum_c g[b][c][n] (x[b][d][n] - centers[c][d])          parts bit 0 (dx NULL: not needed)
+ *   dcenters[c][d] = 2/D sum_{b,n} g[b][c][n] (centers[c][d] - x[b][d][n])      parts bit 1
+ * one launch each, independent (a caller may put them on different streams, as with otal_head_convs_bwd_parts).
+ * Every sum runs in a fixed order with plain stores: no floating-point atomics, two runs give the same bits.
+ * Limits: C <= 21, D <= 512, D % 16 == 0 (OTAL_E_UNSUPPORTED beyond). */
+int otal_rpl_head_fwd(const float* x, const float* centers, float* dist, int B, int C, int D, int N, void* stream);
+int otal_rpl_head_bwd(const float* x, const float* centers, const float* g, float* dx, float* dcenters, int B, int C, int D,
+                      int N, int parts, void* stream);
+
 /* ------------------------------------------------------------------ gradient hand-over to the backbone ----
  * dst[b][c][t][s] (+)= (z[b][c][t][s] > 0 ? scale[c] : 0) * src[b][c][t][s]   (scale NULL: 1; accumulate != 0: +=).
  * Every tensor has its own element strides {batch, channel, frame} and unit stride along s (the H*W plane), so src may be
@@ -548,6 +563,27 @@ int otal_detection_loss_anet_ex(const float* loc, const float* conf, const float
                                 float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
                                 int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
                                 int cls_mode, float focal_alpha, float* losses, float* grads, float* scratch, void* stream);
+
+/* otal_detection_loss_rpl: the closed-set form of otal_detection_loss for the RPL and GCPL baselines (thumos14_open_rpl.yaml,
+ * thumos14_open_gcpl.yaml; AFSD/thumos14/cls_loss.py:342-378 RPLoss, multisegment_loss.py:101-105,:201-204,:225-228).
+ * Arguments as otal_detection_loss without the IBM / EMA state and the actionness maps; conf / prop_conf (B,K,C) are the
+ * DISTANCES of otal_rpl_head_fwd.  Matching, the three localisation / quality terms, the layout of losses, grads and scratch
+ * and otal_detection_loss_bwd are shared with cls_mode 2 / 3; losses 5 and 6 and the dact / dprop_act slots are 0.
+ * The regulariser's (feats - centers[y]).pow(2).mean(1) equals d_i = dist[i][y_i], so the features are not an argument: their
+ * gradient and the centres' are d loss / d dist pushed through otal_rpl_head_bwd.  With A = B K, CE_i the softmax
+ * cross-entropy of row i against its matched label (0 = background), w = weight_pl:
+ *   gcpl 0 (RPL)   coarse   (sum_i CE_i(dist_i / T) + w sum_i (d_i - radius)^2) / N
+ *                  refined  ((1/A) sum_i CE_i(dist_i / T) + (w/A) sum_i (d_i - radius)^2) / PN
+ *   gcpl 1 (GCPL)  coarse   (sum_i CE_i(-dist_i / T) + w/(2A) sum_i d_i) / N
+ *                  refined  ((1/A) sum_i CE_i(-dist_i / T) + w/(2A) sum_i d_i) / PN
+ * (the refined stage's mean that is still divided by PN, and GCPL's always-mean regulariser, are the reference's).
+ * radius is the reference's never-trained one-element parameter (0).  gcpl other than 0 / 1, temperature <= 0 or
+ * B K > 2048: OTAL_E_UNSUPPORTED. */
+int otal_detection_loss_rpl(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                            const float* center, const float* priors, const float* gt, const unsigned char* gvalid,
+                            int B, int K, int C, int G, float clip_length, float overlap_thresh, int gcpl,
+                            float temperature, float weight_pl, float radius, float* losses, float* grads, float* scratch,
+                            void* stream);
 
 /* Backward of otal_detection_loss in one launch: the gradients w.r.t. the seven head outputs from the stored per-loss
  * gradients (`grads` as written by otal_detection_loss) and the incoming gradients of the seven losses g7[i] (device

@@ -1,6 +1,6 @@
 """Layer primitives of the detection path on MI355X, with the reference's constructor signatures
 and state-dict key names (AFSD/common/layers.py): Unit1D (:178-214), Unit3D (:106-175),
-MaxPool3dSamePadding (:9-35).  The arithmetic runs in libopental_hip.so (implicit-GEMM
+MaxPool3dSamePadding (:9-35), RPLHead (:314-351).  The arithmetic runs in libopental_hip.so (implicit-GEMM
 convolution on MFMA, fused GroupNorm+ReLU, virtual SAME padding); nn.Conv1d / nn.Conv3d /
 nn.GroupNorm objects are kept only as parameter containers so checkpoints stay interchangeable.
 
@@ -198,6 +198,39 @@ class ConvGNReLU(nn.Sequential):
             conv, k, s, sv = unit.conv3d, unit._kernel_shape, unit._stride, unit.padding == 'spatial_valid'
         return ConvGNReLUFunction.apply(x, conv.weight, conv.bias, gn.weight, gn.bias, k, s, sv, levels,
                                         gn.num_groups, gn.eps)
+
+
+class RPLHead(nn.Module):
+    """The distance head of the RPL / GCPL baselines (layers.py:314-351): one learnable centre per class,
+    dist[b, c, n] = mean_d (f[b, d, n] - centers[c, d])^2 for a channel-major map f (B, D, N) -> (B, C, N).
+    Device fp32 maps go through ops.RPLHeadFunction (the direct form, one launch); anything else through the reference's
+    expanded torch formulation |f|^2 - 2 f.c + |c|^2.  Several centres per class and the 'dot' metric are not supported."""
+
+    def __init__(self, in_channels, num_classes, num_centers=1, init='random'):
+        super(RPLHead, self).__init__()
+        if num_centers != 1:
+            raise NotImplementedError("RPLHead: one centre per class (the THUMOS14 configs' num_centers=1)")
+        self.feat_dim = in_channels
+        self.num_classes = num_classes
+        self.num_centers = num_centers
+        if init == 'random':
+            self.centers = nn.Parameter(0.1 * torch.randn(num_classes * num_centers, self.feat_dim))
+        else:
+            self.centers = nn.Parameter(torch.zeros(num_classes * num_centers, self.feat_dim))
+
+    def forward(self, raw_features, center=None, metric='l2'):
+        if metric != 'l2':
+            raise NotImplementedError(f"RPLHead metric {metric!r}: only 'l2'")
+        centers = self.centers if center is None else center
+        if raw_features.is_cuda and raw_features.dtype == torch.float32 and centers.dtype == torch.float32:
+            return ops.RPLHeadFunction.apply(raw_features, centers)
+        num_times = raw_features.size(-1)
+        features = raw_features.permute(0, 2, 1).contiguous().view(-1, self.feat_dim)       # (B N, D)
+        f_2 = torch.sum(torch.pow(features, 2), dim=1, keepdim=True)
+        c_2 = torch.sum(torch.pow(centers, 2), dim=1, keepdim=True)
+        dist = f_2 - 2 * torch.matmul(features, torch.transpose(centers, 1, 0)) + torch.transpose(c_2, 1, 0)
+        dist = dist / float(features.shape[1])
+        return dist.view(-1, num_times, self.num_classes).permute(0, 2, 1).contiguous()
 
 
 class MaxPool3dFunction(Function):

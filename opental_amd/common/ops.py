@@ -1526,6 +1526,40 @@ class AnetDetectionLossFunction(torch.autograd.Function):
         return DetectionLossFunction.backward(ctx, *gs)[:7] + (None,) * 13
 
 
+class RPLDetectionLossFunction(torch.autograd.Function):
+    """The five terms of the closed-set MultiSegmentLoss with the RPL / GCPL classification terms (cls_loss.RPLoss) and all
+    their gradients from one launch (csrc/loss.hip: otal_detection_loss_rpl); backward = the shared otal_detection_loss_bwd.
+    conf / prop_conf are the DISTANCE maps (B,K,C) of RPLHeadFunction: the regulariser needs only dist[i][y_i], so the
+    features and the centres get their whole gradient through d conf / d prop_conf."""
+
+    @staticmethod
+    def forward(ctx, loc, conf, prop_loc, prop_conf, center, priors, gt, gvalid, clip_length, overlap, gcpl, temperature,
+                weight_pl, radius):
+        B, K, C = conf.shape
+        G = gt.shape[1]
+        tens = [t.contiguous().float() for t in (loc, conf, prop_loc, prop_conf, center, priors, gt)]
+        L.require_device(*tens)
+        gv = gvalid.contiguous().to(torch.uint8)
+        lib = L.lib()
+        lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
+        lib.otal_detection_loss_scratch_floats.restype = ctypes.c_size_t
+        losses = torch.empty(7, dtype=torch.float32, device=loc.device)
+        grads = torch.empty(lib.otal_detection_loss_grad_floats(B, K, C), dtype=torch.float32, device=loc.device)
+        scratch = torch.empty(lib.otal_detection_loss_scratch_floats(B, K), dtype=torch.float32, device=loc.device)
+        L.check(lib.otal_detection_loss_rpl(*[L.ptr(t) for t in tens], L.ptr(gv), B, K, C, G, ctypes.c_float(clip_length),
+                                            ctypes.c_float(overlap), int(bool(gcpl)), ctypes.c_float(temperature),
+                                            ctypes.c_float(weight_pl), ctypes.c_float(radius), L.ptr(losses), L.ptr(grads),
+                                            L.ptr(scratch), L.stream()), "otal_detection_loss_rpl")
+        ctx.save_for_backward(grads)
+        ctx.dims = (B, K, C)
+        ctx.has_act = False
+        return tuple(losses[i] for i in range(5))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        return DetectionLossFunction.backward(ctx, *gs, None, None)[:5] + (None,) * 9
+
+
 # ----------------------------------------------------------------------------- head output tails
 _SLOT_INDEX = {}        # arena offsets of a group of one-element gradient slots, as a device index tensor
 
@@ -1704,6 +1738,53 @@ class HeadConvsFunction(torch.autograd.Function):
             L.check(L.lib().otal_head_convs_bwd(*meta, VP(xs), VP(ws), VP(dys), VP(dxs), VP(dws), VP(dbs), B, C, N, nlev, lev, L.stream()),
                     "otal_head_convs_bwd")
         return (None, None, None) + tuple(dxs) + tuple(dws) + tuple(dbs)
+
+
+class RPLHeadFunction(torch.autograd.Function):
+    """RPLHead's distance map (AFSD/common/layers.py:327-351, one centre per class, 'l2'): x (B,D,N), centers (C,D) ->
+    dist (B,C,N) = mean_d (x - centers)^2, one launch forward (csrc/rplhead.hip); backward one launch for dx and one for
+    dcenters, the latter on the weight-gradient lane into the centres' arena slot when the trainer runs one."""
+
+    @staticmethod
+    def forward(ctx, x, centers):
+        x, centers = x.contiguous(), centers.contiguous()
+        L.require_device(x, centers)
+        if x.dtype != torch.float32 or centers.dtype != torch.float32 or x.dim() != 3 or centers.dim() != 2 \
+                or centers.shape[1] != x.shape[1]:
+            raise RuntimeError("rpl_head: x (B,D,N) and centers (C,D) in fp32")
+        B, D, N = x.shape
+        C = centers.shape[0]
+        dist = torch.empty((B, C, N), dtype=torch.float32, device=x.device)
+        L.check(L.lib().otal_rpl_head_fwd(L.ptr(x), L.ptr(centers), L.ptr(dist), B, C, D, N, L.stream()), "otal_rpl_head_fwd")
+        ctx.dims = (B, C, D, N)
+        ctx.save_for_backward(x, centers)
+        return dist
+
+    @staticmethod
+    def backward(ctx, g):
+        x, centers = ctx.saved_tensors
+        B, C, D, N = ctx.dims
+        g = g.contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        slot = grad_slot(centers) if ctx.needs_input_grad[1] else None
+        dcen = slot if slot is not None else (torch.empty_like(centers) if ctx.needs_input_grad[1] else None)
+        run = lambda dxp, dcp, parts: L.check(L.lib().otal_rpl_head_bwd(
+            L.ptr(x), L.ptr(centers), L.ptr(g), dxp, dcp, B, C, D, N, parts, L.stream()), "otal_rpl_head_bwd")
+        opt = lambda t: None if t is None else L.ptr(t)
+        side = side_wgrads(x.device)
+        if dcen is None:
+            if dx is not None:
+                run(L.ptr(dx), None, 1)
+        elif side.on and slot is not None and STEP.defer_join:
+            if dx is not None:
+                run(L.ptr(dx), None, 1)
+            dst = dcen.detach()
+            side.pending.append(lambda: run(None, L.ptr(dst), 2))
+            side.keep.append((x, g, centers))
+            side.node_end(True)
+        else:
+            run(opt(dx), L.ptr(dcen), 3 if dx is not None else 2)
+        return dx, dcen
 
 
 def head_convs(levels, items):

@@ -49,6 +49,9 @@ struct LossArgs {
     int cls_mode;                   // 0: EvidenceLoss (the OpenTAL recipe); 1: FocalLoss_Ori on softmax scores (as-shipped THUMOS14 dispatch);
                                     // 2 / 3: closed-set EvidenceLoss / FocalLoss_Ori over every anchor, target = matched label (0 = background)
     float focal_alpha;              // FocalLoss_Ori(balance_index=0, alpha): alpha for class 0, 1 - alpha for the others
+    // the RPL / GCPL instance (otal_detection_loss_rpl): conf / prop_conf are distances to the class centres
+    int gcpl;                       // 0: RPL, cross-entropy on dist / T; 1: GCPL, on -dist / T
+    float temperature, weight_pl, radius;
 };
 constexpr int SCR = 12;             // loc_t0, loc_t1, conf_t, prop_conf_t, iou, prop_loc_t0, prop_loc_t1, ghat, slot, binpos, per, used
 
@@ -128,7 +131,11 @@ __device__ Edl edl_row(const float* z, int C, int y, int num_bins) {
 // prop_conf pass folded in: same operands, same order of additions as the separate loop below) and leave with coalesced
 // stores.  One anchor per thread reads its C = 21 logits at an 84-byte stride: every one of the ~230 load / store
 // instructions per wave touched 64 different cache lines -- on ONE compute unit that was ~80 of the kernel's 107 us.
-template <bool ST>
+// RPL (otal_detection_loss_rpl, the closed-set RPL / GCPL baselines; cls_loss.py:342-378, multisegment_loss.py:201-204,:225-228):
+// the two classification passes are a softmax cross-entropy on +-dist / T of EVERY anchor against its matched label plus a
+// regulariser on d_i = dist[i][y_i] -- (feats - centers[y]).pow(2).mean(1) IS d_i, so the 512-wide features are never read and
+// their gradient (and the centres') flows through d dist.  Everything else is the closed-set form of the kernel.
+template <bool ST, bool RPL = false>
 __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
     extern __shared__ __attribute__((aligned(16))) float zl[];       // ST: A * C floats (logits, then gradients, of the current pass)
     __shared__ float red[LT];
@@ -234,6 +241,45 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
             for (int q = t; q < n4; q += LT) reinterpret_cast<float4*>(zl)[q] = reinterpret_cast<const float4*>(logits)[q];
             for (int q = 4 * n4 + t; q < AC; q += LT) zl[q] = logits[q];
             __syncthreads();
+        }
+        if constexpr (RPL) {
+            // coarse:  (sum_i CE_i + reg) / N;  refined: ((1/A) sum_i CE_i + reg) / PN -- the reference asks for the mean there
+            // (reduction=True, multisegment_loss.py:228) and still divides by PN (:248).
+            // reg:  RPL  w sum_i (d_i - radius)^2, a mean over A in the refined stage (F.mse_loss with the pass's reduction);
+            //       GCPL w / (2 A) sum_i d_i in both stages (F.mse_loss(feats, centers[y]) / 2 is always a mean over A * D).
+            const float sgn = a.gcpl ? -1.f : 1.f;
+            const float ce_w = pass == 0 ? 1.f : 1.f / (float)A;
+            const float reg_w = a.gcpl ? a.weight_pl / (2.f * (float)A) : (pass == 0 ? a.weight_pl : a.weight_pl / (float)A);
+            float part_ce = 0.f, part_reg = 0.f;
+            for (int i = t; i < A; i += LT) {
+                const int y = min((int)a.scratch[(size_t)i * SCR + 2 + pass], C - 1);
+                const float* z = ST ? zl + (size_t)i * C : logits + (size_t)i * C;
+                float* gz = ST ? zl + (size_t)i * C : gout + (size_t)i * C;      // ST: in place, element k is read before it is written
+                float mx = sgn * z[0] / a.temperature;
+                for (int k = 1; k < C; ++k) mx = fmaxf(mx, sgn * z[k] / a.temperature);
+                float S = 0.f;
+                for (int k = 0; k < C; ++k) S += expf(sgn * z[k] / a.temperature - mx);
+                const float dy = z[y];
+                part_ce += logf(S) - (sgn * dy / a.temperature - mx);
+                float dreg;
+                if (a.gcpl) { part_reg += dy; dreg = reg_w; }
+                else { const float e = dy - a.radius; part_reg += e * e; dreg = reg_w * 2.f * e; }
+                for (int k = 0; k < C; ++k) {
+                    const float pk = expf(sgn * z[k] / a.temperature - mx) / S;
+                    float gk = ce_w * (sgn / a.temperature) * (pk - (k == y ? 1.f : 0.f));
+                    if (k == y) gk += dreg;
+                    gz[k] = gk / norm;
+                }
+            }
+            if constexpr (ST) {
+                __syncthreads();
+                const int n4 = (reinterpret_cast<uintptr_t>(gout) & 15) == 0 ? AC >> 2 : 0;
+                for (int q = t; q < n4; q += LT) reinterpret_cast<float4*>(gout)[q] = reinterpret_cast<const float4*>(zl)[q];
+                for (int q = 4 * n4 + t; q < AC; q += LT) gout[q] = zl[q];
+            }
+            const float ce = block_sum(part_ce, red), reg = block_sum(part_reg, red);
+            loss_cls[pass] = (ce_w * ce + reg_w * reg) / norm;
+            continue;
         }
         const bool cal = ST && pass == 1 && a.iou_aware;
         for (int i = t; i < A; i += LT) {
@@ -935,6 +981,42 @@ extern "C" int otal_detection_loss(const float* loc, const float* conf, const fl
         (void)hipGetLastError();
     }
     hipLaunchKernelGGL(detection_loss_kernel<false>, dim3(1), dim3(LT), 0, (hipStream_t)stream, a);
+    return otal_launch_status();
+}
+
+
+// The RPL / GCPL baselines (thumos14_open_rpl.yaml, thumos14_open_gcpl.yaml): the closed-set form of the kernel above with
+// the distance classification terms.  conf / prop_conf are the (B, K, C) distance maps of otal_rpl_head_fwd.
+extern "C" int otal_detection_loss_rpl(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                                       const float* center, const float* priors, const float* gt, const unsigned char* gvalid,
+                                       int B, int K, int C, int G, float clip_length, float overlap_thresh, int gcpl,
+                                       float temperature, float weight_pl, float radius, float* losses, float* grads,
+                                       float* scratch, void* stream) {
+    if (!loc || !conf || !prop_loc || !prop_conf || !center || !priors || !gt || !gvalid || !losses || !grads || !scratch)
+        return OTAL_E_NULL;
+    if (B <= 0 || K <= 0 || C <= 0 || G <= 0) return OTAL_E_SHAPE;
+    if ((long)B * K > MAX_A || (gcpl != 0 && gcpl != 1) || !(temperature > 0.f)) return OTAL_E_UNSUPPORTED;
+    LossArgs a{};
+    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center;
+    a.priors = priors; a.gt = gt; a.gvalid = gvalid; a.losses = losses; a.grads = grads; a.scratch = scratch;
+    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
+    a.cls_mode = 4 + gcpl;              // internal: a closed-set mode (>= 2) that is neither EDL nor focal
+    a.focal_alpha = 0.25f;
+    a.gcpl = gcpl; a.temperature = temperature; a.weight_pl = weight_pl; a.radius = radius;
+    const size_t stage = (size_t)B * K * C * sizeof(float);
+    constexpr size_t STAGE_MAX = 96 * 1024;
+    static int staged_ok = -1;          // -1: not asked yet; the attribute is set once per process
+    if (stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE")) {
+        if (staged_ok < 0)
+            staged_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(detection_loss_kernel<true, true>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAGE_MAX) == hipSuccess ? 1 : 0;
+        if (staged_ok == 1) {
+            hipLaunchKernelGGL((detection_loss_kernel<true, true>), dim3(1), dim3(LT), stage, (hipStream_t)stream, a);
+            return otal_launch_status();
+        }
+        (void)hipGetLastError();
+    }
+    hipLaunchKernelGGL((detection_loss_kernel<false, true>), dim3(1), dim3(LT), 0, (hipStream_t)stream, a);
     return otal_launch_status();
 }
 

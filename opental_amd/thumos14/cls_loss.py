@@ -1,6 +1,6 @@
 """Classification / actionness losses of OpenTAL with the reference's class names and constructor
 arguments (AFSD/thumos14/cls_loss.py: FocalLoss_Ori :6-78, EvidenceLoss :81-285, ActionnessLoss
-:288-339), re-expressed for the GPU: every function takes ALL anchors plus a boolean mask and
+:288-339, RPLoss :342-378), re-expressed for the GPU: every function takes ALL anchors plus a boolean mask and
 uses masked sums, scatter-adds and rank masks, so there is no boolean-mask gather, no `.item()`
 and no Python loop over bins -- i.e. no host synchronisation inside the training step
 (the reference syncs ~60 times per step in these losses).
@@ -156,3 +156,35 @@ class ActionnessLoss(nn.Module):
             rank_loss = torch.clamp(self.margin - neg_max + pos_max, min=0.0)
             loss = loss + self.weight * torch.where(top_m > 0, rank_loss, torch.zeros_like(rank_loss))
         return loss, count
+
+
+class RPLoss(nn.Module):
+    """The classification term of the RPL and GCPL baselines (cls_loss.py:342-378) on the distances of RPLHead:
+    softmax cross-entropy on dist / T (RPL: far from the reciprocal points) or -dist / T (GCPL: near the prototypes), plus
+    a regulariser on the distance to the label's own centre.  Written in terms of dist and d_i = dist[i, y_i]: the
+    reference's (feats - centers[labels]).pow(2).mean(1) IS d_i, so `feats` and `centers` are accepted for the reference's
+    signature and not read -- their gradient flows through dist.
+      RPL   CE + weight_pl * mse(d, radius), both with the call's reduction ('sum'; 'mean' with reduction=True)
+      GCPL  CE + weight_pl * mean(d) / 2 -- F.mse_loss(feats, centers[labels]) / 2 is a mean over A * D whatever the reduction
+    `radius` is a one-element parameter of the reference's criterion that no optimizer ever holds (train.py:321 passes
+    net.parameters() only): it stays 0, and is a plain attribute here."""
+
+    def __init__(self, num_classes, cfg, size_average=False):
+        super(RPLoss, self).__init__()
+        self.weight_pl = cfg['weight_pl'] if 'weight_pl' in cfg else 0.1
+        self.temp = cfg['temperature'] if 'temperature' in cfg else 1
+        self.gcpl = cfg['gcpl'] if 'gcpl' in cfg else False
+        self.radius = 0.0
+        self.size_average = size_average
+        self.num_cls = num_classes
+
+    def forward(self, dist, targets, feats=None, centers=None, reduction=False):
+        mean = self.size_average or reduction
+        labels = targets.view(-1)
+        d = dist.gather(1, labels.view(-1, 1)).squeeze(1)
+        if self.gcpl:
+            loss = F.cross_entropy(-dist / self.temp, labels, reduction='mean' if mean else 'sum')
+            return loss + self.weight_pl * (d.mean() / 2)
+        loss = F.cross_entropy(dist / self.temp, labels, reduction='mean' if mean else 'sum')
+        e = (d - self.radius) ** 2
+        return loss + self.weight_pl * (e.mean() if mean else e.sum())

@@ -6,19 +6,22 @@ synchronisation: anchor<->GT matching runs for all clips at once on padded targe
 os_head=False is the closed-set variant of the Softmax and EDL baselines (configs thumos14_softmax.yaml,
 thumos14_open_edl.yaml): C = classes + 1 logits with class 0 = background, EVERY anchor is classified against its matched
 label, and there are no actionness terms (loss_act, loss_prop_act are None, multisegment_loss.py:196-231, :250-255).
+cls_loss_type='rpl' (thumos14_open_rpl.yaml, thumos14_open_gcpl.yaml; closed-set only): conf / prop_conf are the distances of
+RPLHead and the two classification terms are cls_loss.RPLoss (multisegment_loss.py:201-204, :225-228).
 
 Reference quirks kept on purpose (documented in DESIGN.md):
   * the IoU-calibration term pairs iou_pred (stored prior-major, (126,B)) with logits flattened
     batch-major (multisegment_loss.py:116,:234-236) -- identical for batch 1, the yaml's batch size;
   * the tIoU target of the quality head carries gradient into loc / prop_loc (it is not detached,
-    multisegment_loss.py:176-187).
+    multisegment_loss.py:176-187);
+  * 'rpl': the refined stage asks RPLoss for the MEAN over the anchors (reduction=True, :228) and still divides by PN (:248).
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from ..common.input_pipeline import PaddedTargets
-from .cls_loss import ActionnessLoss, EvidenceLoss, FocalLoss_Ori
+from .cls_loss import ActionnessLoss, EvidenceLoss, FocalLoss_Ori, RPLoss
 
 _EPS = torch.finfo(torch.float32).eps
 FUSED = True      # single-launch HIP loss for the final recipe and the closed-set baselines (set False to force the torch formulation)
@@ -111,8 +114,14 @@ class MultiSegmentLoss(nn.Module):
                 self._focal_alpha0 = float(al[0])
         elif cls_loss_type == 'edl':
             self.cls_loss = EvidenceLoss(num_classes, edl_config, size_average=size_average)
+        elif cls_loss_type == 'rpl':
+            if rpl_config is None:
+                raise NotImplementedError("cls_loss_type 'rpl' needs the rpl_config of the RPL / GCPL yaml")
+            if os_head:
+                raise NotImplementedError("cls_loss_type 'rpl' with os_head: the distance head is closed-set only")
+            self.cls_loss = RPLoss(num_classes, rpl_config, size_average=size_average)
         else:
-            raise NotImplementedError(f"cls_loss_type {cls_loss_type!r}: the RPL / GCPL baselines are not supported")
+            raise NotImplementedError(f"cls_loss_type {cls_loss_type!r}")
         self.iou_aware = cls_loss_type == 'edl' and self.cls_loss.iou_aware
         self.os_head = os_head
         # the closed-set variant has no actionness heads (multisegment_loss.py:87-88)
@@ -152,7 +161,7 @@ class MultiSegmentLoss(nn.Module):
     def _cls_mode(self, loc):
         """cls_mode of otal_detection_loss for this criterion, or None when the kernel does not cover it:
         0 = EDL with actionness (OpenTAL), 1 = focal with actionness (as-shipped dispatch), 2 = closed-set EDL ('log', exp,
-        no IBM), 3 = closed-set focal."""
+        no IBM), 3 = closed-set focal.  'rpl' is an entry of its own (otal_detection_loss_rpl): 'rpl'."""
         cl = self.cls_loss
         common = (FUSED and loc.is_cuda and loc.dtype == torch.float32 and loc.shape[0] * loc.shape[1] <= 2048
                   and not self.size_average and not cl.size_average)
@@ -160,6 +169,8 @@ class MultiSegmentLoss(nn.Module):
             common = common and self.act_loss.weight == 0 and not self.act_loss.size_average
         if not common:
             return None
+        if self.cls_loss_type == 'rpl':
+            return 'rpl' if float(cl.temp) > 0 else None
         if self.cls_loss_type == 'focal':       # the as-shipped THUMOS14 dispatch (train.py:27-31) / thumos14_softmax.yaml
             return (1 if self.os_head else 3) if self._focal_alpha0 is not None else None
         if self.cls_loss_type != 'edl' or cl.loss_type != 'log' or cl.evidence != 'exp' or cl.num_bins > 64:
@@ -176,6 +187,14 @@ class MultiSegmentLoss(nn.Module):
         B, K = loc.shape[0], priors.shape[0]
         C = self.num_classes
         mode = self._cls_mode(loc)
+        if mode == 'rpl':
+            from ..common.ops import RPLDetectionLossFunction
+            gt, valid = as_padded(targets, loc.device)
+            cl = self.cls_loss
+            out = RPLDetectionLossFunction.apply(
+                loc, conf, prop_loc, prop_conf, center.reshape(B, K), priors[:, 0], gt, valid, float(self.clip_length),
+                float(self.overlap_thresh), bool(cl.gcpl), float(cl.temp), float(cl.weight_pl), float(cl.radius))
+            return out + (None, None)
         if mode is not None and not self.os_head:
             from ..common.ops import DetectionLossFunction
             gt, valid = as_padded(targets, loc.device)
@@ -220,11 +239,13 @@ class MultiSegmentLoss(nn.Module):
         bce = torch.clamp(x, min=0) - x * q + torch.log1p(torch.exp(-x.abs()))
         loss_ct = torch.where(pos, bce, zero).sum()
 
-        def classify(logits, tgt):
+        def classify(logits, tgt, refined=False):
             lg = logits.reshape(-1, C)
             t = tgt.reshape(-1)
             keep = t > 0
             if not self.os_head:                # closed set: every anchor, its matched label (0 = background)
+                if self.cls_loss_type == 'rpl':
+                    return self.cls_loss(lg, t, reduction=refined), keep
                 if self.cls_loss_type == 'focal':
                     return self.cls_loss(F.softmax(lg, dim=1), t), keep
                 return self.cls_loss(lg, t), keep
@@ -234,7 +255,7 @@ class MultiSegmentLoss(nn.Module):
             return self.cls_loss(lg, cls_id, keep), keep
 
         loss_c, keep = classify(conf, conf_t)
-        loss_prop_c, pkeep = classify(prop_conf, prop_conf_t)
+        loss_prop_c, pkeep = classify(prop_conf, prop_conf_t, refined=True)
         loss_act = loss_prop_act = None
         if self.os_head:
             loss_act, AN = self.act_loss(act.reshape(-1, 1), keep.to(act.dtype))

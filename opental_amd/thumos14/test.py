@@ -72,7 +72,28 @@ def head_mode(net):
     return bool(getattr(net, 'os_head', True)), bool(getattr(net, 'use_edl', True)), getattr(net, 'evidence', 'exp')
 
 
-def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01, os_head=True, use_edl=True, evidence='exp'):
+def rpl_flags(config):
+    """(use_rpl, use_gcpl) of a parsed config, as test.py:268-269 reads them: the distance head of the RPL / GCPL baselines
+    and whether its scores are the softmax of the NEGATED distances."""
+    use_rpl = bool(config['model'].get('use_rpl', False))
+    rc = config['training'].get('rpl_config') or {}
+    return use_rpl, bool(use_rpl and rc.get('gcpl', False))
+
+
+def rpl_logits(output_dict, use_gcpl=False):
+    """The classification maps the closed-set softmax decode reads for the distance head (parse_output, test.py:85-87): the
+    distances themselves for RPL, their negation for GCPL.  Host or device tensors.
+    Applied to the (fused) maps: both streams' maps are distances, so a two-stream GCPL run scores softmax(-(rgb + flow) / 2).
+    Reference hazard: its parse_output negates the rgb stream BEFORE the average and leaves the flow stream as it is
+    (test.py:85-87 then :96-99), i.e. softmax((flow - rgb) / 2) -- pinned in tests/golden/rpl.npz (dec_gcpl_fus1_*) and
+    reproduced in tests/test_rpl_gpu.py, not adopted.  Single-stream runs are unaffected."""
+    if not use_gcpl:
+        return output_dict
+    return dict(output_dict, conf=-output_dict['conf'], prop_conf=-output_dict['prop_conf'])
+
+
+def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01, os_head=True, use_edl=True, evidence='exp',
+                 use_gcpl=False):
     """Batched parse_output + decode_predictions + threshold masks.  output_dict: model outputs for
     `n` clips; offsets/fps: per-clip tensors or lists.  Returns dict(seg, score, unct, actn, flag).
     os_head / use_edl / evidence: the network's head (head_mode).  The closed-set head (os_head False) has a background
@@ -81,6 +102,9 @@ def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01, o
         raise NotImplementedError(f"evidence {evidence!r}: the decode kernel computes exp evidence only")
     if os_head and not use_edl:
         raise NotImplementedError("an actionness head with softmax scores is not a THUMOS14 configuration")
+    if use_gcpl and (os_head or use_edl):
+        raise NotImplementedError("use_gcpl belongs to the closed-set softmax decode of the distance head")
+    output_dict = rpl_logits(output_dict, use_gcpl)
     loc = output_dict['loc'].contiguous()
     n, A, _ = loc.shape
     K = output_dict['conf'].shape[-1]
@@ -129,13 +153,14 @@ def _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, u
     return dict(seg=seg, score=score, unct=unct, actn=None, flag=flag)
 
 
-def decode_predictions(output_dict, idx, offset, sample_fps, clip_length=256, os_head=True, use_edl=True, evidence='exp'):
+def decode_predictions(output_dict, idx, offset, sample_fps, clip_length=256, os_head=True, use_edl=True, evidence='exp',
+                       use_gcpl=False):
     """Single-clip view with the reference's return values (test.py:112-140):
     decoded_segments (A,2), conf_scores (K,A), uncertainty (A,) or None, actionness (A,) or None.
     Closed-set heads: conf_scores holds the K - 1 non-background classes (row c = reference row c + 1)."""
     one = {k: (v[idx:idx + 1] if (v is not None and k != 'priors') else v) for k, v in output_dict.items()}
     d = decode_clips(one, [float(offset)], [float(sample_fps)], clip_length, os_head=os_head, use_edl=use_edl,
-                     evidence=evidence)
+                     evidence=evidence, use_gcpl=use_gcpl)
     first = lambda v: None if v is None else v[0]
     return d['seg'][0], d['score'][0], first(d['unct']), first(d['actn'])
 
@@ -242,7 +267,8 @@ def detect_batch(net, videos, sample_fps, clip_length=256, stride=128, conf_thre
     keys = ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'priors') + (('act', 'prop_act') if os_head else ()) + \
         (('unct', 'prop_unct') if flow_net is not None and use_edl else ())
     merged = {k: (torch.cat([o[k] for o in outs], 0) if k != 'priors' else outs[0][k]) for k in keys}
-    dec = decode_clips(merged, offsets, fps, clip_length, conf_thresh, os_head=os_head, use_edl=use_edl, evidence=evidence)
+    dec = decode_clips(merged, offsets, fps, clip_length, conf_thresh, os_head=os_head, use_edl=use_edl, evidence=evidence,
+                       use_gcpl=bool(getattr(net, 'use_gcpl', False)))
     if flow_net is not None and use_edl:
         # the decode kernel derives the uncertainty from the (fused) logits; the reference averages the two networks'
         # OWN uncertainties instead (parse_output :105-108, decode_predictions :122) -- not the same number
@@ -378,9 +404,12 @@ def main(argv=None):
     torch.cuda.set_device(dev)
     ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
     flow_net, data_path, flow_path = None, ds['video_data_path'], None
+    use_rpl, use_gcpl = rpl_flags(config)
     if te.get('fusion', False):             # build_model(fusion=True), test.py:24-40: rgb + flow networks, their own checkpoints
-        net = BDNet(in_channels=3, training=False, use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
-        flow_net = BDNet(in_channels=2, training=False, use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
+        net = BDNet(in_channels=3, training=False, use_edl=md.get('use_edl', False), use_rpl=use_rpl,
+                    cfg=model_cfg_from(config))
+        flow_net = BDNet(in_channels=2, training=False, use_edl=md.get('use_edl', False), use_rpl=use_rpl,
+                    cfg=model_cfg_from(config))
         if not random_init:
             net.load_state_dict(torch.load(te.get('rgb_checkpoint_path', './models/thumos14/checkpoint-15.ckpt'), map_location='cpu'))
             flow_net.load_state_dict(torch.load(te.get('flow_checkpoint_path', './models/thumos14_flow/checkpoint-16.ckpt'), map_location='cpu'))
@@ -388,10 +417,12 @@ def main(argv=None):
         data_path = te.get('rgb_data_path', './datasets/thumos14/test_npy/')
         flow_path = te.get('flow_data_path', './datasets/thumos14/test_flow_npy/')
     else:
-        net = BDNet(in_channels=md['in_channels'], training=False, use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
+        net = BDNet(in_channels=md['in_channels'], training=False, use_edl=md.get('use_edl', False), use_rpl=use_rpl,
+                    cfg=model_cfg_from(config))
         if not random_init:
             net.load_state_dict(torch.load(te['checkpoint_path'], map_location='cpu'))
     net = net.to(dev).eval()
+    net.use_gcpl = use_gcpl                 # GCPL: scores are the softmax of the negated distances (detect_batch)
     video_infos = get_video_info(config['dataset']['testing']['video_info_path'])
     _, idx_to_class = get_class_index_map(config['dataset']['class_info_path'])
     results = test(net, video_infos, data_path, idx_to_class, ds['clip_length'], ds['clip_stride'], ds['crop_size'],

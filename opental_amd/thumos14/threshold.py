@@ -56,7 +56,10 @@ def main(argv=None):
     dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
     torch.cuda.set_device(dev)
     ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
-    net = BDNet(in_channels=md['in_channels'], training=False, use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
+    use_rpl, use_gcpl = T.rpl_flags(config)
+    net = BDNet(in_channels=md['in_channels'], training=False, use_edl=md.get('use_edl', False), use_rpl=use_rpl,
+                cfg=model_cfg_from(config))
+    net.use_gcpl = use_gcpl                 # GCPL: scores are the softmax of the negated distances
     if not random_init:
         net.load_state_dict(torch.load(te['checkpoint_path'], map_location='cpu'))
     net = net.to(dev).eval()

@@ -1034,10 +1034,10 @@ def loss_dispatch(config, as_shipped=False):
     """cls_loss_type of the run.  The reference derives it TWICE (train.py:27 then :31): 'edl' if edl_loss, and then
     overwrites it with 'rpl' if rpl_loss else 'focal' -- so its shipped THUMOS14 recipe trains FocalLoss_Ori (SURVEY
     H2).  Default here: what the config says (edl_loss -> 'edl', the OpenTAL method); `as_shipped=True` reproduces
-    the overwrite."""
+    the overwrite.  rpl_loss wins in both (the reference's line 31 agrees): the RPL / GCPL baselines."""
     tr = config['training']
     if tr.get('rpl_loss', False):
-        raise NotImplementedError("RPL baseline is outside the OpenTAL hot path")
+        return 'rpl'
     if as_shipped:
         return 'focal'
     return 'edl' if tr.get('edl_loss', False) else 'focal'
@@ -1057,7 +1057,8 @@ def build_training(config, device, as_shipped=False, random_init=False, dist_gro
     os_head = md.get('os_head', False)
     num_cls = config['dataset']['num_classes'] - 1 if os_head else config['dataset']['num_classes']
     crit = MultiSegmentLoss(num_cls, tr['piou'], 1.0, cls_loss_type=loss_dispatch(config, as_shipped),
-                            edl_config=tr.get('edl_config'), os_head=os_head, act_config=tr.get('act_config'),
+                            edl_config=tr.get('edl_config'), rpl_config=tr.get('rpl_config'), os_head=os_head,
+                            act_config=tr.get('act_config'),
                             clip_length=config['dataset']['training']['clip_length']).to(device)
     weights = dict(lw=tr['lw'], cw=tr['cw'], ctw=tr['ctw'], actw=tr.get('actw', 1.0), ssl=tr['ssl'])
     trainer = DetectorTrainer(net, crit, weights, lr=tr['learning_rate'], weight_decay=tr['weight_decay'],
