@@ -531,6 +531,29 @@ int otal_detection_loss(const float* loc, const float* conf, const float* prop_l
                         int iou_aware, int cls_mode, float focal_alpha, float* losses, float* grads, float* scratch,
                         void* stream);
 
+/* otal_detection_loss_ex: otal_detection_loss for the THUMOS14 loss ablations as well (configs/ablations/
+ * thumos14_opental_{focal,ghm,ib,noACT}.yaml; AFSD/thumos14/cls_loss.py:221-256).  Arguments as otal_detection_loss, plus
+ * `reweight`, the rule that weighs the EvidenceLoss rows that count (the positives in cls_mode 0, every anchor in cls_mode 2),
+ * and rw_gamma.  An additive entry: OTAL_ABI_VERSION is unchanged.
+ *   reweight 0 = otal_detection_loss(...) bit for bit, and cls_mode 2 accepts ibm_active as well: the IBM EMA over EVERY
+ *                anchor of a closed set (noACT: os_head false with with_ibm);
+ *   reweight 1 = focal-EDL: w = a_y (1 - max_k alpha_k / S)^rw_gamma with a_0 = focal_alpha, a_k = 1 - focal_alpha; the
+ *                weight is NOT detached, the gradient includes per * dw/dz through the first maximum;
+ *   reweight 2 = GHM: rows are binned by g = |1/alpha_y - C/S| into num_bins bins (edges i / num_bins, the last + 1e-6); bin
+ *                0 also counts the M (C - 1) zeros of the other columns of the M rows that count; a populated bin's weight is
+ *                1 / (its population, or with momentum > 0 its EMA weight_accum[i] = m * weight_accum[i] + (1 - m) * population)
+ *                divided by the number of populated bins.  weight_accum (num_bins) is that EMA, updated in place (conf first,
+ *                then prop_conf); momentum >= 0.  Counts are exact: the result does not depend on the order of the rows;
+ *   reweight 3 = influence-balanced loss: w = 1 / (g |z|_1), no epsilon.
+ * reweight 1..3 need cls_mode 0 or 2 and ibm_active 0; an epoch below the rule's start passes reweight 0 (the caller gates).
+ * Anything else: OTAL_E_UNSUPPORTED, before any read or launch. */
+int otal_detection_loss_ex(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                           const float* center, const float* act, const float* prop_act, const float* priors,
+                           const float* gt, const unsigned char* gvalid, float* weight_accum, int B, int K, int C, int G,
+                           float clip_length, float overlap_thresh, int ibm_active, int num_bins, float momentum,
+                           int iou_aware, int cls_mode, float focal_alpha, int reweight, float rw_gamma, float* losses,
+                           float* grads, float* scratch, void* stream);
+
 /* The same for the ActivityNet1.3 recipe (ABI 22): AFSD/anet/multisegment_loss.py:87-301 with anet/cls_loss.py:78-246
  * (EvidenceLoss 'log', exp evidence, the closed-form influence-balanced weight 1 / (|z|_1 exp(ibm_coeff g) + 1e-10) whose
  * |z|_1 carries gradient, IoU calibration as each sample's mean) and :249-296 (ActionnessLoss with its rank hinge:

@@ -1439,7 +1439,8 @@ class DetectionLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt, gvalid, weight_accum,
-                clip_length, overlap, ibm_active, num_bins, momentum, iou_aware, cls_mode=0, focal_alpha=0.25):
+                clip_length, overlap, ibm_active, num_bins, momentum, iou_aware, cls_mode=0, focal_alpha=0.25, reweight=0,
+                rw_gamma=0.0):
         B, K, C = conf.shape
         G = gt.shape[1]
         tens = [None if t is None else t.contiguous().float()
@@ -1454,11 +1455,15 @@ class DetectionLossFunction(torch.autograd.Function):
         losses = torch.empty(7, dtype=torch.float32, device=loc.device)
         grads = torch.empty(ng, dtype=torch.float32, device=loc.device)
         scratch = torch.empty(ns, dtype=torch.float32, device=loc.device)
-        L.check(lib.otal_detection_loss(*[None if t is None else L.ptr(t) for t in tens], L.ptr(gv), L.ptr(weight_accum), B, K, C, G,
-                                        ctypes.c_float(clip_length), ctypes.c_float(overlap), int(ibm_active),
-                                        int(num_bins), ctypes.c_float(momentum), int(iou_aware), int(cls_mode),
-                                        ctypes.c_float(focal_alpha), L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream()),
-                "otal_detection_loss")
+        head = [None if t is None else L.ptr(t) for t in tens] + [
+            L.ptr(gv), L.ptr(weight_accum), B, K, C, G, ctypes.c_float(clip_length), ctypes.c_float(overlap), int(ibm_active),
+            int(num_bins), ctypes.c_float(momentum), int(iou_aware), int(cls_mode), ctypes.c_float(focal_alpha)]
+        tail = [L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream()]
+        if int(reweight) != 0 or (int(cls_mode) == 2 and ibm_active):
+            # a re-weighting rule of the loss ablations, or IBM over a closed set (noACT): the extended entry
+            L.check(lib.otal_detection_loss_ex(*head, int(reweight), ctypes.c_float(rw_gamma), *tail), "otal_detection_loss_ex")
+        else:
+            L.check(lib.otal_detection_loss(*head, *tail), "otal_detection_loss")
         ctx.save_for_backward(grads)
         ctx.dims = (B, K, C)
         ctx.has_act = act is not None
@@ -1484,7 +1489,7 @@ class DetectionLossFunction(torch.autograd.Function):
         d_cen, d_act, d_pact = take(A, (B, K)), take(A, (B, K)), take(A, (B, K))
         if not getattr(ctx, 'has_act', True):        # (AnetDetectionLossFunction shares this backward)
             d_act = d_pact = None
-        return (d_loc, d_conf, d_pl, d_pconf, d_cen, d_act, d_pact) + (None,) * 12
+        return (d_loc, d_conf, d_pl, d_pconf, d_cen, d_act, d_pact) + (None,) * 14
 
 
 class AnetDetectionLossFunction(torch.autograd.Function):

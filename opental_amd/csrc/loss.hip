@@ -52,6 +52,7 @@ struct LossArgs {
     // the RPL / GCPL instance (otal_detection_loss_rpl): conf / prop_conf are distances to the class centres
     int gcpl;                       // 0: RPL, cross-entropy on dist / T; 1: GCPL, on -dist / T
     float temperature, weight_pl, radius;
+    float rw_gamma;                 // focal-EDL (RW 1): the exponent of (1 - max_k alpha_k / S)
 };
 constexpr int SCR = 12;             // loc_t0, loc_t1, conf_t, prop_conf_t, iou, prop_loc_t0, prop_loc_t1, ghat, slot, binpos, per, used
 
@@ -103,7 +104,7 @@ __device__ TIoU tiou_grad(float p0, float p1, float t0, float t1) {
 }
 
 // EvidenceLoss statistics of one anchor row (cls_loss.py:132-160): per = log S - log alpha_y, IBM slot
-struct Edl { float per, S, ay, ghat; int slot, binpos; };
+struct Edl { float per, S, ay, ghat, gnorm; int slot, binpos; };
 __device__ Edl edl_row(const float* z, int C, int y, int num_bins) {
     Edl e;
     float S = 0.f, l1 = 0.f, ay = 1.f;
@@ -117,7 +118,7 @@ __device__ Edl edl_row(const float* z, int C, int y, int num_bins) {
     e.per = logf(S) - logf(ay);
     const float u = (float)C / S;
     const float gnorm = fabsf(1.f / ay - u);
-    e.ghat = gnorm * l1;
+    e.ghat = gnorm * l1; e.gnorm = gnorm;
     const long bins = (long)ceilf(gnorm * (float)num_bins);
     e.binpos = bins > 0 ? 1 : 0;
     long sl = (bins - 1) % num_bins;
@@ -126,6 +127,25 @@ __device__ Edl edl_row(const float* z, int C, int y, int num_bins) {
     return e;
 }
 
+// GHM (cls_loss.py:99-104,:228-249): the bin of a gradient length, edges[b] <= g < edges[b + 1] with edges[b] = b / num_bins in
+// double rounded to float (the reference compares a float tensor with python floats) and 1e-6 added to the last one; -1: none
+__device__ int ghm_bin(float g, int num_bins) {
+    auto edge = [&](int b) { return (float)((double)b / (double)num_bins + (b == num_bins ? 1e-6 : 0.0)); };
+    int b = min(max((int)(g * (float)num_bins), 0), num_bins - 1);
+    if (g < edge(b)) --b;
+    else if (g >= edge(b + 1)) ++b;
+    return (b >= 0 && b < num_bins && g >= edge(b) && g < edge(b + 1)) ? b : -1;
+}
+
+// RW: the re-weighting rule of the EvidenceLoss rows (cls_loss.py:221-272), an instance each so that the final recipe's code
+// (RW 0) is the one it was before the loss ablations were added:
+//   0  none, or with ibm_active the influence-balanced EMA of the POSITIVE rows (the OpenTAL recipe)
+//   1  focal-EDL: w = alpha_y (1 - max_k alpha_k / S)^gamma, NOT detached -- the gradient carries per * dw/dz (the first maximum)
+//   2  GHM: w = 1 / (population of the row's gradient-length bin) / (number of populated bins); weight_accum holds the
+//      populations' EMA (momentum > 0).  Counts are whole numbers in float: exact, whatever the order
+//   3  influence-balanced loss, closed form: w = 1 / (g |z|_1), no epsilon
+//   4  the EMA of rule 0 over EVERY row of a closed set (thumos14_opental_noACT.yaml: os_head false with IBM)
+// Rules 1-3 apply to the rows that count: the positives (cls_mode 0) or every anchor (cls_mode 2).
 // ST (EvidenceLoss mode, A * C floats fit the dynamic LDS): the logits of a pass are copied to LDS with coalesced 16-byte loads,
 // every class loop reads them there, the gradient rows are written over them in place (with the IoU-calibration term of the
 // prop_conf pass folded in: same operands, same order of additions as the separate loop below) and leave with coalesced
@@ -135,7 +155,7 @@ __device__ Edl edl_row(const float* z, int C, int y, int num_bins) {
 // the two classification passes are a softmax cross-entropy on +-dist / T of EVERY anchor against its matched label plus a
 // regulariser on d_i = dist[i][y_i] -- (feats - centers[y]).pow(2).mean(1) IS d_i, so the 512-wide features are never read and
 // their gradient (and the centres') flows through d dist.  Everything else is the closed-set form of the kernel.
-template <bool ST, bool RPL = false>
+template <bool ST, bool RPL = false, int RW = 0>
 __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
     extern __shared__ __attribute__((aligned(16))) float zl[];       // ST: A * C floats (logits, then gradients, of the current pass)
     __shared__ float red[LT];
@@ -288,9 +308,47 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
             const int y = closed ? tgt : max(tgt - 1, 0);
             const Edl e = edl_row(staged ? zl + (size_t)i * C : logits + (size_t)i * C, C, y, a.num_bins);
             s[7] = e.ghat; s[8] = (float)e.slot; s[9] = (float)e.binpos; s[10] = e.per;
+            if constexpr (RW == 2) {
+                const int gb = ghm_bin(e.gnorm, a.num_bins);
+                s[8] = (float)gb;
+                s_slot[i] = (unsigned char)(gb < 0 ? 255 : gb); s_flag[i] = (tgt > 0 || closed) ? 1 : 0;
+            } else if constexpr (RW == 4) {
+                s_val[i] = e.ghat; s_slot[i] = (unsigned char)e.slot; s_flag[i] = e.binpos ? 1 : 0;
+            } else {
             s_val[i] = e.ghat; s_slot[i] = (unsigned char)e.slot; s_flag[i] = (tgt > 0 && e.binpos) ? 1 : 0;
+            }
         }
         __syncthreads();
+        if constexpr (RW == 2) {    // the histogram pass of the IBM rule below, counts only; then wave 0 = one lane per bin
+            const int bin = t % MAX_BINS, seg = t / MAX_BINS;
+            const int per_seg = (A + HSEG - 1) / HSEG;
+            float cnt = 0.f;
+            if (bin < a.num_bins) {
+                const int hi = min(A, (seg + 1) * per_seg);
+                for (int i = seg * per_seg; i < hi; ++i)
+                    if (s_flag[i] && s_slot[i] == bin) cnt += 1.f;
+            }
+            h_cnt[seg][bin] = cnt;
+            __syncthreads();
+            if (t < MAX_BINS) {
+                float cc = 0.f;
+                if (t < a.num_bins)
+                    for (int sg = 0; sg < HSEG; ++sg) cc += h_cnt[sg][t];
+                // the reference bins every element of |1 / alpha - u| * y: the zeros of the other C - 1 columns of the M rows
+                // that count fall into bin 0
+                if (t == 0) cc += (float)(closed ? A : icnt[pass]) * (float)(C - 1);
+                const bool valid = cc > 0.f;
+                const int nvalid = __popcll(__ballot(valid));
+                float w = 0.f;
+                if (valid) {
+                    if (a.momentum > 0.f) { wacc[t] = a.momentum * wacc[t] + (1.f - a.momentum) * cc; w = 1.f / wacc[t]; }
+                    else w = 1.f / cc;
+                    w = w / (float)nvalid;
+                }
+                h_tot[0][t] = w;            // the weight of a row in bin t
+            }
+            __syncthreads();
+        } else
         if (a.ibm_active) {     // the 50-bin EMA, deterministic: thread = (segment of anchors, bin) sums its segment in
                                 // index order, then one thread per bin adds the HSEG partials in segment order
             const int bin = t % MAX_BINS, seg = t / MAX_BINS;
@@ -317,15 +375,32 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
             const bool cnt = tgt > 0 || closed;                 // the row is classified
             if constexpr (ST) {
                 float* z = zl + (size_t)i * C;                  // logits in, gradient row out (in place: element k is read before it is written)
-                const float wgt = (tgt > 0 && a.ibm_active) ? wacc[(int)s[8]] : 1.f;
-                if (cnt) part += wgt * s[10];
+                float wgt;
+                if constexpr (RW == 0) wgt = (tgt > 0 && a.ibm_active) ? wacc[(int)s[8]] : 1.f;
+                else if constexpr (RW == 4) wgt = a.ibm_active ? wacc[(int)s[8]] : 1.f;
+                else if constexpr (RW == 2) wgt = (cnt && s[8] >= 0.f) ? h_tot[0][(int)s[8]] : 0.f;
+                else if constexpr (RW == 3) wgt = cnt ? 1.f / s[7] : 0.f;
+                else wgt = 0.f;
+                if (RW != 1 && cnt) part += wgt * s[10];
                 const int y = closed ? tgt : tgt - 1;
-                float S = 0.f, ay = 1.f;
+                float S = 0.f, ay = 1.f, amax = 0.f;
+                int kmax = 0;
                 if (cnt || cal) {
                     for (int k = 0; k < C; ++k) {
                         const float al = expf(fminf(fmaxf(z[k], -10.f), 10.f)) + 1.f;
                         S += al;
                         if (k == y) ay = al;
+                        if constexpr (RW == 1) { if (al > amax) { amax = al; kmax = k; } }
+                    }
+                }
+                float fp = 0.f, fq = 0.f;       // focal-EDL: p = max_k alpha_k / S and per * (dw / dp) / S
+                if constexpr (RW == 1) {
+                    if (cnt) {
+                        fp = amax / S;
+                        const float om = 1.f - fp, fal = y == 0 ? a.focal_alpha : 1.f - a.focal_alpha;
+                        wgt = fal * powf(om, a.rw_gamma);
+                        fq = s[10] * (-fal * a.rw_gamma * powf(om, a.rw_gamma - 1.f)) / S;
+                        part += wgt * s[10];
                     }
                 }
                 float cg = 0.f;                                 // IoU calibration (the separate loop of the unstaged form, see there)
@@ -341,7 +416,11 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
                 for (int k = 0; k < C; ++k) {
                     const float zk = z[k];
                     const float da = (zk >= -10.f && zk <= 10.f) ? expf(zk) : 0.f;      // clamp backward is inclusive
-                    float gk = cnt ? wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) * da / norm : 0.f;
+                    float gk;
+                    if constexpr (RW == 1)      // d alpha_kmax / S / d alpha_k = ((k == kmax) - p) / S
+                        gk = cnt ? (wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) + fq * ((k == kmax ? 1.f : 0.f) - fp)) * da / norm : 0.f;
+                    else
+                        gk = cnt ? wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) * da / norm : 0.f;
                     if (cal) gk += cg * da / (float)A;
                     z[k] = gk;
                 }
@@ -349,19 +428,36 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
             const float* z = logits + (size_t)i * C;
             float* gz = gout + (size_t)i * C;
             if (cnt) {
-                const float wgt = a.ibm_active ? wacc[(int)s[8]] : 1.f;
-                part += wgt * s[10];
+                float wgt;
+                if constexpr (RW == 0 || RW == 4) wgt = a.ibm_active ? wacc[(int)s[8]] : 1.f;
+                else if constexpr (RW == 2) wgt = s[8] >= 0.f ? h_tot[0][(int)s[8]] : 0.f;
+                else if constexpr (RW == 3) wgt = 1.f / s[7];
+                else wgt = 0.f;
+                if (RW != 1) part += wgt * s[10];
                 const int y = closed ? tgt : tgt - 1;
-                float S = 0.f, ay = 1.f;
+                float S = 0.f, ay = 1.f, amax = 0.f;
+                int kmax = 0;
                 for (int k = 0; k < C; ++k) {
                     const float al = expf(fminf(fmaxf(z[k], -10.f), 10.f)) + 1.f;
                     S += al;
                     if (k == y) ay = al;
+                    if constexpr (RW == 1) { if (al > amax) { amax = al; kmax = k; } }
+                }
+                float fp = 0.f, fq = 0.f;       // focal-EDL, as in the staged form
+                if constexpr (RW == 1) {
+                    fp = amax / S;
+                    const float om = 1.f - fp, fal = y == 0 ? a.focal_alpha : 1.f - a.focal_alpha;
+                    wgt = fal * powf(om, a.rw_gamma);
+                    fq = s[10] * (-fal * a.rw_gamma * powf(om, a.rw_gamma - 1.f)) / S;
+                    part += wgt * s[10];
                 }
                 for (int k = 0; k < C; ++k) {
                     const float zk = z[k];
                     const float da = (zk >= -10.f && zk <= 10.f) ? expf(zk) : 0.f;      // clamp backward is inclusive
-                    gz[k] = wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) * da / norm;
+                    if constexpr (RW == 1)
+                        gz[k] = (wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) + fq * ((k == kmax ? 1.f : 0.f) - fp)) * da / norm;
+                    else
+                        gz[k] = wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) * da / norm;
                 }
             } else {
                 for (int k = 0; k < C; ++k) gz[k] = 0.f;
@@ -945,43 +1041,85 @@ extern "C" size_t otal_detection_loss_grad_floats(int B, int K, int C) {
     return 4 * 2 * A + 2 * A * C + 3 * A;
 }
 
+namespace {
+// one launch of detection_loss_kernel<., false, RW>: the staged form when the pass's logits fit the dynamic LDS
+template <int RW>
+int launch_detection_loss(const LossArgs& a, bool edl, hipStream_t stream) {
+    // staged logits: EvidenceLoss modes (0, 2) and A * C floats within the dynamic LDS this kernel may add to its ~40 KB of static
+    // arrays (C = 16: up to 1536 anchors, B * 126 anchors for B <= 12); 40 + 96 KB stays inside the 160 KB of a gfx950 compute unit
+    const size_t stage = (size_t)a.B * a.K * a.C * sizeof(float);
+    constexpr size_t STAGE_MAX = 96 * 1024;
+    static int staged_ok = -1;          // -1: not asked yet; the attribute is set once per process (and per instance)
+    if (edl && stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE")) {
+        if (staged_ok < 0)
+            staged_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(detection_loss_kernel<true, false, RW>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAGE_MAX) == hipSuccess ? 1 : 0;
+        if (staged_ok == 1) {
+            hipLaunchKernelGGL((detection_loss_kernel<true, false, RW>), dim3(1), dim3(LT), stage, stream, a);
+            return otal_launch_status();
+        }
+        (void)hipGetLastError();
+    }
+    hipLaunchKernelGGL((detection_loss_kernel<false, false, RW>), dim3(1), dim3(LT), 0, stream, a);
+    return otal_launch_status();
+}
+
+// ex: otal_detection_loss_ex (the re-weighting rules of the loss ablations, and IBM over a closed set)
+int detection_loss_entry(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                         const float* center, const float* act, const float* prop_act, const float* priors,
+                         const float* gt, const unsigned char* gvalid, float* weight_accum, int B, int K,
+                         int C, int G, float clip_length, float overlap_thresh, int ibm_active, int num_bins,
+                         float momentum, int iou_aware, int cls_mode, float focal_alpha, int reweight, float rw_gamma,
+                         bool ex, float* losses, float* grads, float* scratch, void* stream) {
+    const bool closed = cls_mode == 2 || cls_mode == 3;        // closed-set modes: no actionness heads
+    if (!loc || !conf || !prop_loc || !prop_conf || !center || (!closed && (!act || !prop_act)) || !priors || !gt || !gvalid ||
+        !weight_accum || !losses || !grads || !scratch) return OTAL_E_NULL;
+    if (B <= 0 || K <= 0 || C <= 0 || G <= 0) return OTAL_E_SHAPE;
+    if (num_bins <= 0 || num_bins > MAX_BINS || (long)B * K > MAX_A || cls_mode < 0 || cls_mode > 3) return OTAL_E_UNSUPPORTED;
+    if (cls_mode == 2 && ibm_active && !ex) return OTAL_E_UNSUPPORTED;    // closed-set EDL with IBM: otal_detection_loss_ex only
+    if (reweight < 0 || reweight > 3) return OTAL_E_UNSUPPORTED;
+    if (reweight != 0 && ((cls_mode != 0 && cls_mode != 2) || ibm_active)) return OTAL_E_UNSUPPORTED;
+    if (reweight == 2 && !(momentum >= 0.f)) return OTAL_E_UNSUPPORTED;
+    LossArgs a{};
+    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
+    a.prop_act = prop_act; a.priors = priors; a.gt = gt; a.gvalid = gvalid; a.weight_accum = weight_accum;
+    a.losses = losses; a.grads = grads; a.scratch = scratch;
+    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
+    const bool closed_ibm = cls_mode == 2 && ibm_active;
+    a.ibm_active = (cls_mode == 0 || closed_ibm) ? ibm_active : 0; a.num_bins = num_bins;
+    a.iou_aware = (cls_mode == 0 || cls_mode == 2) ? iou_aware : 0;
+    a.momentum = momentum; a.cls_mode = cls_mode; a.focal_alpha = focal_alpha; a.rw_gamma = rw_gamma;
+    const bool edl = cls_mode == 0 || cls_mode == 2;
+    switch (closed_ibm ? 4 : reweight) {
+        case 1: return launch_detection_loss<1>(a, edl, (hipStream_t)stream);
+        case 2: return launch_detection_loss<2>(a, edl, (hipStream_t)stream);
+        case 3: return launch_detection_loss<3>(a, edl, (hipStream_t)stream);
+        case 4: return launch_detection_loss<4>(a, edl, (hipStream_t)stream);
+        default: return launch_detection_loss<0>(a, edl, (hipStream_t)stream);
+    }
+}
+}  // namespace
+
 extern "C" int otal_detection_loss(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
                                    const float* center, const float* act, const float* prop_act, const float* priors,
                                    const float* gt, const unsigned char* gvalid, float* weight_accum, int B, int K,
                                    int C, int G, float clip_length, float overlap_thresh, int ibm_active, int num_bins,
                                    float momentum, int iou_aware, int cls_mode, float focal_alpha, float* losses,
                                    float* grads, float* scratch, void* stream) {
-    const bool closed = cls_mode == 2 || cls_mode == 3;        // closed-set modes: no actionness heads
-    if (!loc || !conf || !prop_loc || !prop_conf || !center || (!closed && (!act || !prop_act)) || !priors || !gt || !gvalid ||
-        !weight_accum || !losses || !grads || !scratch) return OTAL_E_NULL;
-    if (B <= 0 || K <= 0 || C <= 0 || G <= 0) return OTAL_E_SHAPE;
-    if (num_bins <= 0 || num_bins > MAX_BINS || (long)B * K > MAX_A || cls_mode < 0 || cls_mode > 3) return OTAL_E_UNSUPPORTED;
-    if (cls_mode == 2 && ibm_active) return OTAL_E_UNSUPPORTED;    // closed-set EDL: no influence-balanced re-weighting
-    LossArgs a;
-    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
-    a.prop_act = prop_act; a.priors = priors; a.gt = gt; a.gvalid = gvalid; a.weight_accum = weight_accum;
-    a.losses = losses; a.grads = grads; a.scratch = scratch;
-    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
-    a.ibm_active = cls_mode == 0 ? ibm_active : 0; a.num_bins = num_bins;
-    a.iou_aware = (cls_mode == 0 || cls_mode == 2) ? iou_aware : 0;
-    a.momentum = momentum; a.cls_mode = cls_mode; a.focal_alpha = focal_alpha;
-    // staged logits: EvidenceLoss modes (0, 2) and A * C floats within the dynamic LDS this kernel may add to its ~40 KB of static
-    // arrays (C = 16: up to 1536 anchors, B * 126 anchors for B <= 12)
-    const size_t stage = (size_t)B * K * C * sizeof(float);
-    constexpr size_t STAGE_MAX = 96 * 1024;
-    static int staged_ok = -1;          // -1: not asked yet; the attribute is set once per process
-    if ((cls_mode == 0 || cls_mode == 2) && stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE")) {
-        if (staged_ok < 0)
-            staged_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(detection_loss_kernel<true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAGE_MAX) == hipSuccess ? 1 : 0;
-        if (staged_ok == 1) {
-            hipLaunchKernelGGL(detection_loss_kernel<true>, dim3(1), dim3(LT), stage, (hipStream_t)stream, a);
-            return otal_launch_status();
-        }
-        (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL(detection_loss_kernel<false>, dim3(1), dim3(LT), 0, (hipStream_t)stream, a);
-    return otal_launch_status();
+    return detection_loss_entry(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt, gvalid, weight_accum, B, K, C,
+                                G, clip_length, overlap_thresh, ibm_active, num_bins, momentum, iou_aware, cls_mode, focal_alpha,
+                                0, 0.f, false, losses, grads, scratch, stream);
+}
+
+extern "C" int otal_detection_loss_ex(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                                      const float* center, const float* act, const float* prop_act, const float* priors,
+                                      const float* gt, const unsigned char* gvalid, float* weight_accum, int B, int K,
+                                      int C, int G, float clip_length, float overlap_thresh, int ibm_active, int num_bins,
+                                      float momentum, int iou_aware, int cls_mode, float focal_alpha, int reweight,
+                                      float rw_gamma, float* losses, float* grads, float* scratch, void* stream) {
+    return detection_loss_entry(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt, gvalid, weight_accum, B, K, C,
+                                G, clip_length, overlap_thresh, ibm_active, num_bins, momentum, iou_aware, cls_mode, focal_alpha,
+                                reweight, rw_gamma, true, losses, grads, scratch, stream);
 }
 
 

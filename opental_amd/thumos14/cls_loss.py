@@ -50,31 +50,52 @@ class FocalLoss_Ori(nn.Module):
         return loss.mean() if self.size_average else loss.sum()
 
 
+REWEIGHT = {None: 0, 'ibm': 0, 'focal': 1, 'ghm': 2, 'ib': 3}     # `reweight` of otal_detection_loss_ex (IBM is its ibm_active)
+
+
 class EvidenceLoss(nn.Module):
     """EDL loss ('log' / 'digamma' / 'mse', evidence exp / relu / softplus) with influence-balanced (IBM) re-weighting from
-    a 50-bin EMA (cls_loss.py:186-285) and the IoU-calibration term (cls_loss.py:120-129).  The final recipe's
-    combination (exp / log / IBM) runs inside the single-launch HIP loss (csrc/loss.hip); the other kinds use this masked
-    torch formulation on the device."""
+    a 50-bin EMA (cls_loss.py:186-285) and the IoU-calibration term (cls_loss.py:120-129), and the three re-weightings of the
+    loss ablations for 'log' / 'digamma' (cls_loss.py:221-256): focal-EDL, GHM and the closed-form influence-balanced loss.
+    The exp / log combinations run inside the single-launch HIP loss (csrc/loss.hip); the other kinds use this masked torch
+    formulation on the device."""
 
     def __init__(self, num_cls, cfg, size_average=False):
         super(EvidenceLoss, self).__init__()
         self.num_cls = num_cls
         self.loss_type = cfg['loss_type']
         self.evidence = cfg['evidence']
-        for flag in ('with_focal', 'with_ghm', 'with_ibloss'):
-            if cfg.get(flag, False):
-                raise NotImplementedError(f"{flag}: ablation variant outside the opental_final recipe")
         if self.loss_type not in ('log', 'digamma', 'mse'):
             raise NotImplementedError(self.loss_type)
         if cfg.get('soft_label', 0.0):
             raise NotImplementedError("soft_label")
         self.iou_aware = cfg.get('iou_aware', False)
+        # the loss ablations (configs/ablations/thumos14_opental_{focal,ghm,ib}.yaml; cls_loss.py:94-108): one re-weighting
+        # rule applies per call, in the order of the reference's elif chain -- see reweight()
+        self.with_focal = cfg.get('with_focal', False)
+        self.with_ghm = cfg.get('with_ghm', False)
+        self.with_ibloss = cfg.get('with_ibloss', False)
         self.with_ibm = cfg.get('with_ibm', False)
         self.ibm_start = cfg.get('ibm_start', 0)
+        self.ghm_start = cfg.get('ghm_start', 0)
+        self.ib_start = cfg.get('ib_start', 10)
         self.num_bins = cfg.get('num_bins', 50)
         self.momentum = cfg.get('momentum', 0.99)
+        self.gamma = cfg['gamma'] if self.with_focal else 0.0
+        self.focal_alpha = cfg['alpha'] if self.with_focal else 0.25
+        if self.with_focal:
+            a = torch.ones(num_cls) * (1 - cfg['alpha'])
+            a[0] = cfg['alpha']         # class id 0: the background of a closed set, the FIRST ACTION under os_head (ids are label - 1)
+            self.register_buffer('alpha_class', a, persistent=False)
         # checkpointed here (the reference forgets to save it, SURVEY section 5)
         self.register_buffer('weight_accum', torch.ones(self.num_bins))
+        if self.with_ghm:
+            # the GHM bin populations (an EMA when momentum > 0), carried from call to call; a buffer of the ghm configs only,
+            # so every other criterion's state dict keeps its keys
+            self.register_buffer('acc_sum', torch.zeros(self.num_bins))
+            e = [float(x) / self.num_bins for x in range(self.num_bins + 1)]
+            e[-1] += 1e-6
+            self.register_buffer('edges', torch.tensor(e, dtype=torch.float32), persistent=False)
         self.epoch, self.total_epoch = 0, 25
         self.size_average = size_average
 
@@ -86,6 +107,26 @@ class EvidenceLoss(nn.Module):
         u = self.num_cls / (self.evidence_func(logits) + 1).sum(dim=-1)
         reg = -ious * torch.log(1 - u) - (1 - ious) * torch.log(u)
         return reg.mean() if mean else reg.sum()
+
+    def reweight(self):
+        """The re-weighting rule of this call, by the reference's elif chain (cls_loss.py:221-272): 'focal' (ungated), 'ghm'
+        (epoch >= ghm_start), 'ib' (epoch >= ib_start), 'ibm' (epoch >= ibm_start) or None.  The number otal_detection_loss_ex
+        takes is REWEIGHT[rule]."""
+        if self.with_focal:
+            return 'focal'
+        if self.with_ghm and self.epoch >= self.ghm_start:
+            return 'ghm'
+        if self.with_ibloss and self.epoch >= self.ib_start:
+            return 'ib'
+        if self.with_ibm and self.epoch >= self.ibm_start:
+            return 'ibm'
+        return None
+
+    def state(self):
+        """The tensor this criterion carries from step to step (None without one): the IBM EMA or the GHM bin populations."""
+        if self.with_ghm and not self.with_focal:
+            return self.acc_sum
+        return self.weight_accum if self.with_ibm else None
 
     def forward(self, logit, target, mask=None):
         """logit (N,K), target (N,) in [0,K) (any valid id where mask is False), mask (N,) bool."""
@@ -104,7 +145,36 @@ class EvidenceLoss(nn.Module):
         func = torch.log if self.loss_type == 'log' else torch.digamma
         a_y = alpha.gather(1, target.view(-1, 1))
         per = (func(S) - func(a_y)).view(-1)          # sum_k y_k (f(S) - f(alpha_k)) with one-hot y
-        if self.with_ibm and self.epoch >= self.ibm_start:
+        rule = self.reweight()
+        if rule == 'focal':
+            # alpha_y (1 - max_k alpha_k / S)^gamma, NOT detached (cls_loss.py:224-227): the weight carries gradient
+            score = (alpha / S).max(1)[0]
+            per = self.alpha_class[target] * torch.pow(1.0 - score, self.gamma) * per
+        elif rule == 'ghm':
+            with torch.no_grad():
+                g = torch.abs(1 / a_y.view(-1) - self.num_cls / S.view(-1))
+                m = mask.to(g.dtype)
+                inbin = ((g.unsqueeze(1) >= self.edges[:-1]) & (g.unsqueeze(1) < self.edges[1:])).to(g.dtype)    # (N, bins)
+                cnt = (inbin * m.unsqueeze(1)).sum(0)
+                # the reference bins every element of |1/alpha - u| * y: the zeros of the C - 1 other columns of each of the
+                # M counted rows fall into bin 0 (cls_loss.py:232-237)
+                cnt[0] += m.sum() * (self.num_cls - 1)
+                valid = cnt > 0
+                if self.momentum > 0:
+                    self.acc_sum.copy_(torch.where(valid, self.momentum * self.acc_sum + (1 - self.momentum) * cnt, self.acc_sum))
+                    pop = self.acc_sum
+                else:
+                    pop = cnt
+                wbin = torch.where(valid, 1.0 / pop.clamp(min=1e-30), torch.zeros_like(pop))
+                w = (inbin * wbin).sum(1) / valid.sum().clamp(min=1)
+            per = w * per
+        elif rule == 'ib':
+            with torch.no_grad():
+                g = torch.abs(1 / a_y.view(-1) - self.num_cls / S.view(-1))
+                w = 1 / (g * logit.abs().sum(1))                # no epsilon, as the reference (cls_loss.py:254)
+                w = torch.where(mask, w, torch.zeros_like(w))   # (a row that does not count must not send 0 * inf backwards)
+            per = w * per
+        elif rule == 'ibm':
             with torch.no_grad():
                 u = self.num_cls / S.view(-1)
                 gnorm = torch.abs(1 / a_y.view(-1) - u)

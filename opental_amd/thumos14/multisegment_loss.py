@@ -3,6 +3,10 @@ same constructor and the same 7-tuple result, vectorised over the batch and free
 synchronisation: anchor<->GT matching runs for all clips at once on padded targets, and every
 "select the positives, then reduce" of the reference is a masked reduction over all anchors.
 
+The loss ablations of the paper (configs/ablations/thumos14_opental_{focal,ghm,ib,hardmib,noMIB,noIoUC,noACT}.yaml) differ from
+the final recipe only in model.os_head and training.edl_config; all seven run through the single-launch loss (otal_detection_loss_ex
+for the focal / ghm / ib re-weightings and for noACT = closed-set EDL with IBM).
+
 os_head=False is the closed-set variant of the Softmax and EDL baselines (configs thumos14_softmax.yaml,
 thumos14_open_edl.yaml): C = classes + 1 logits with class 0 = background, EVERY anchor is classified against its matched
 label, and there are no actionness terms (loss_act, loss_prop_act are None, multisegment_loss.py:196-231, :250-255).
@@ -160,8 +164,9 @@ class MultiSegmentLoss(nn.Module):
 
     def _cls_mode(self, loc):
         """cls_mode of otal_detection_loss for this criterion, or None when the kernel does not cover it:
-        0 = EDL with actionness (OpenTAL), 1 = focal with actionness (as-shipped dispatch), 2 = closed-set EDL ('log', exp,
-        no IBM), 3 = closed-set focal.  'rpl' is an entry of its own (otal_detection_loss_rpl): 'rpl'."""
+        0 = EDL with actionness (OpenTAL), 1 = focal with actionness (as-shipped dispatch), 2 = closed-set EDL ('log', exp;
+        with IBM it is the noACT ablation), 3 = closed-set focal.  'rpl' is an entry of its own (otal_detection_loss_rpl): 'rpl'.
+        The loss ablations (with_focal / with_ghm / with_ibloss) are modes 0 and 2 with the `reweight` of _reweight()."""
         cl = self.cls_loss
         common = (FUSED and loc.is_cuda and loc.dtype == torch.float32 and loc.shape[0] * loc.shape[1] <= 2048
                   and not self.size_average and not cl.size_average)
@@ -175,9 +180,16 @@ class MultiSegmentLoss(nn.Module):
             return (1 if self.os_head else 3) if self._focal_alpha0 is not None else None
         if self.cls_loss_type != 'edl' or cl.loss_type != 'log' or cl.evidence != 'exp' or cl.num_bins > 64:
             return None
-        if self.os_head:
-            return 0
-        return None if cl.with_ibm else 2
+        return 0 if self.os_head else 2
+
+    def _reweight(self):
+        """(ibm_active, reweight, rw_gamma, focal_alpha, state) of otal_detection_loss_ex for this call: the rule EvidenceLoss.
+        reweight() picks at the current epoch, and the state tensor it reads and updates (the GHM populations or the IBM EMA)."""
+        from .cls_loss import REWEIGHT
+        cl = self.cls_loss
+        rule = cl.reweight()
+        state = cl.acc_sum if rule == 'ghm' else cl.weight_accum
+        return rule == 'ibm', REWEIGHT[rule], float(cl.gamma), float(cl.focal_alpha), state
 
     def forward(self, output_dict, targets, pre_locs=None):
         loc, conf = output_dict['loc'], output_dict['conf']
@@ -203,11 +215,13 @@ class MultiSegmentLoss(nn.Module):
                 if getattr(self, '_no_ibm', None) is None or self._no_ibm.device != loc.device:
                     self._no_ibm = torch.ones(1, dtype=torch.float32, device=loc.device)    # unused EMA slot of the ABI
                 wacc, nb, fa = self._no_ibm, 1, self._focal_alpha0
+                ibm, rw, gamma, mom = False, 0, 0.0, 0.0
             else:
-                wacc, nb, fa = cl.weight_accum, cl.num_bins, 0.25
+                ibm, rw, gamma, fa, wacc = self._reweight()
+                nb, mom = cl.num_bins, float(cl.momentum) if (ibm or rw) else 0.0
             out = DetectionLossFunction.apply(
                 loc, conf, prop_loc, prop_conf, center.reshape(B, K), None, None, priors[:, 0], gt, valid, wacc,
-                float(self.clip_length), float(self.overlap_thresh), False, nb, 0.0, bool(self.iou_aware), mode, fa)
+                float(self.clip_length), float(self.overlap_thresh), ibm, nb, mom, bool(self.iou_aware), mode, fa, rw, gamma)
             return out[:5] + (None, None)
         if mode is not None:
             from ..common.ops import DetectionLossFunction
@@ -220,10 +234,11 @@ class MultiSegmentLoss(nn.Module):
                     loc, conf, prop_loc, prop_conf, center.reshape(B, K), act.reshape(B, K), prop_act.reshape(B, K),
                     priors[:, 0], gt, valid, self._no_ibm, float(self.clip_length), float(self.overlap_thresh),
                     False, 1, 0.0, False, 1, self._focal_alpha0)
+            ibm, rw, gamma, fa, state = self._reweight()
             return DetectionLossFunction.apply(
                 loc, conf, prop_loc, prop_conf, center.reshape(B, K), act.reshape(B, K), prop_act.reshape(B, K),
-                priors[:, 0], gt, valid, cl.weight_accum, float(self.clip_length), float(self.overlap_thresh),
-                bool(cl.with_ibm and cl.epoch >= cl.ibm_start), cl.num_bins, float(cl.momentum), bool(self.iou_aware))
+                priors[:, 0], gt, valid, state, float(self.clip_length), float(self.overlap_thresh),
+                ibm, cl.num_bins, float(cl.momentum), bool(self.iou_aware), 0, fa, rw, gamma)
         loc_t, conf_t, prop_loc_t, prop_conf_t, iou_pred = self.match(loc.detach(), priors, targets)
         pos, prop_pos = conf_t > 0, prop_conf_t > 0
         zero = loc.new_zeros(())

@@ -13,8 +13,9 @@
   * nothing in the step synchronises with the host (the reference does ~20 .item()/.cpu() per
     step for logging): losses are returned as device tensors.
 
-Loss-state policy under data parallelism: EvidenceLoss.weight_accum (50 floats) is averaged
-across ranks after each step that updates it; the per-rank normalisers N / PN / AN stay
+Loss-state policy under data parallelism: the criterion's cross-step loss state -- EvidenceLoss.weight_accum
+(the IBM EMA, 50 floats) or, for the GHM ablation, EvidenceLoss.acc_sum (the bin populations' EMA, num_bins
+floats) -- is averaged across ranks after each step that updates it; the per-rank normalisers N / PN / AN stay
 per-rank, i.e. the optimised objective is the mean over ranks of per-rank losses.
 """
 import numpy as np
@@ -411,9 +412,15 @@ class DetectorTrainer:
         self._ibm_work = dist.all_reduce(self._ibm_state(), op=dist.ReduceOp.SUM, group=self.group, async_op=True)
 
     def _ibm_state(self):
-        if getattr(self.criterion, 'cls_loss_type', None) == 'edl' and getattr(self.criterion.cls_loss, 'with_ibm', False):
+        """The criterion's cross-step loss state (module docstring): the IBM EMA, the GHM populations, or None."""
+        cl = getattr(self.criterion, 'cls_loss', None)
+        if getattr(self.criterion, 'cls_loss_type', None) != 'edl':
+            return None
+        if hasattr(cl, 'state'):
+            return cl.state()
+        if getattr(cl, 'with_ibm', False):
             # (the ActivityNet EvidenceLoss uses the closed-form IBM weight: no cross-step state to average -> None)
-            return getattr(self.criterion.cls_loss, 'weight_accum', None)
+            return getattr(cl, 'weight_accum', None)
         return None
 
     def end_backward(self):
@@ -526,9 +533,15 @@ class DetectorTrainer:
             ops.STEP.reset()
         self.step_count += 1
         self.optimizer_update()
+        result = cost.detach(), _detached(losses)
         if stale:
+            # This step's autograd graph must be gone before the capture begins.  While `cost` lives, so do the parameters'
+            # AccumulateGrad nodes, which carry the stream they were created on (this eager step's); the captured forward
+            # would find them again, and the engine would hand their gradients over with an event from the capturing stream
+            # to that stream -- a fork into the capture that nothing joins, on which hipStreamEndCapture crashes.
+            del cost, losses
             self.capture_step(clips, targets, scores, warmup=0, split=was_split, lanes=was_lanes)
-        return cost.detach(), _detached(losses)
+        return result
 
     def _try_capture_lanes(self, clips, targets, scores):
         """The drivers' in-step capture.  A capture that cannot be had -- a parameter without a gradient (an unused head:
@@ -566,7 +579,9 @@ class DetectorTrainer:
         ibm = None
         if cl is not None and hasattr(cl, 'epoch'):
             ibm = (bool(getattr(cl, 'with_ibm', False)), int(cl.epoch) >= int(getattr(cl, 'ibm_start', 0)),
-                   float(getattr(cl, 'annealing_coef', 0.0)) if hasattr(cl, 'annealing_coef') else None)
+                   float(getattr(cl, 'annealing_coef', 0.0)) if hasattr(cl, 'annealing_coef') else None,
+                   # the re-weighting rule in force (focal / ghm / ib / ibm): crossing ghm_start or ib_start re-captures
+                   cl.reweight() if hasattr(cl, 'reweight') else None)
         return (float(self.lr), float(self._base_lr), tuple(float(g) for _, _, g in self._group_ranges), float(self.wd),
                 tuple(self.betas), float(self.eps), self.world, bool(self.collectives), ibm,
                 tuple(sorted((k, float(v)) for k, v in self.w.items())))
@@ -962,7 +977,7 @@ class DetectorTrainer:
 
     def save_model(self, epoch, checkpoint_path, train_state_path):
         """`save_model` of the reference (train.py:106-118): weights as checkpoint-{epoch}.ckpt (the same 446 keys),
-        optimizer + RNG states as checkpoint_{epoch}.ckpt, plus the '-latest' links.  Extra key 'weight_accum': the IBM
+        optimizer + RNG states as checkpoint_{epoch}.ckpt, plus the '-latest' links.  Extra keys 'weight_accum' / 'acc_sum': the IBM
         EMA state, which the reference forgets to checkpoint (it is a registered buffer here, so it is in the weights
         file as well when present)."""
         import os, random
@@ -975,9 +990,10 @@ class DetectorTrainer:
             states.append(torch.cuda.get_rng_state())
         state_file = os.path.join(train_state_path, 'checkpoint_{}.ckpt'.format(epoch))
         extra = {}
-        wa = getattr(getattr(self.criterion, 'cls_loss', None), 'weight_accum', None)
-        if wa is not None:
-            extra['weight_accum'] = wa.detach().clone()
+        for key in ('weight_accum', 'acc_sum'):         # the IBM EMA; the GHM populations (with_ghm criteria only)
+            wa = getattr(getattr(self.criterion, 'cls_loss', None), key, None)
+            if wa is not None:
+                extra[key] = wa.detach().clone()
         torch.save(dict({'optimizer': self.optimizer_state_dict(), 'state': states}, **extra), state_file)
         for src, dst in ((model_file, os.path.join(checkpoint_path, 'checkpoint-latest.ckpt')),
                          (state_file, os.path.join(train_state_path, 'checkpoint_latest.ckpt'))):
@@ -1004,8 +1020,9 @@ class DetectorTrainer:
             st = torch.load(os.path.join(train_state_path, 'checkpoint_{}.ckpt'.format(resume)), map_location='cpu',
                             weights_only=False)
             self.load_optimizer_state_dict(st['optimizer'])
-            if 'weight_accum' in st and hasattr(getattr(self.criterion, 'cls_loss', None), 'weight_accum'):
-                self.criterion.cls_loss.weight_accum.copy_(st['weight_accum'])
+            for key in ('weight_accum', 'acc_sum'):
+                if key in st and hasattr(getattr(self.criterion, 'cls_loss', None), key):
+                    getattr(self.criterion.cls_loss, key).copy_(st[key])
             if restore_rng:
                 states = st['state']
                 random.setstate(states[0]); np.random.set_state(states[1]); torch.set_rng_state(states[2])
