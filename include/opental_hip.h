@@ -675,6 +675,27 @@ int otal_bmp_fwd_levels_to(const float* in, const float* seg, float* out, int64_
 int otal_bmp_bwd_levels_from(const float* grad_out, int64_t pooled_bs, const float* in, const float* seg, float* grad_in, int B,
                              int C, int nlev, const int* t_start, const int* n_start, void* stream);
 
+/* ------------------------------------------------------------------ evaluation: greedy matching (csrc/eval.hip) ----
+ * The prediction -> ground-truth matching of AFSD/evaluation/eval_detection.py (compute_average_precision_detection
+ * :323-402, split_results_by_gt :405-456) for every group and tIoU threshold in ONE launch; the rule is stated in
+ * opental_amd/evaluation/match.py (match_reference).  pred_seg (N, 2) and gt_seg (M, 2) hold [start, end] in fp64, sorted by
+ * group; pred_start / gt_start are (ngroups + 1) non-decreasing offsets ending at N / M.  Predictions of a group are visited
+ * in row order, a ground truth is taken once per threshold, thresholds are independent problems.  out (nthr, N):
+ *   out[t][i] >= 0  the row of gt_seg that prediction i takes at thresholds[t]: among the untaken ground truths of its group
+ *                   with not (tIoU < thresholds[t]) the one with the largest tIoU, the lowest row among equal tIoU;
+ *   out[t][i] = -1  no such ground truth and some ground truth of the group has tIoU < thresholds[t], or the group has none;
+ *   out[t][i] = -2  every ground truth of the group clears thresholds[t] and all are taken.
+ * tIoU is fp64 in the operation order of utils_eval.segment_iou with an IEEE division, so every comparison equals numpy's.
+ * *nonfinite (one int, zeroed by the caller) counts what makes the result unusable: every (prediction, ground truth) pair
+ * with a non-finite tIoU (0 / 0 of two zero-length segments; treated as "not < threshold") and every group with
+ * predictions and more than OTAL_EVAL_MAX_GT ground truths (all its predictions are written as -1).  A caller that reads a
+ * non-zero counter discards `out`.  Pointers 16-byte aligned (segments) else OTAL_E_UNSUPPORTED; nthr > 32:
+ * OTAL_E_UNSUPPORTED; ngroups < 0 or nthr < 1: OTAL_E_SHAPE; ngroups == 0 launches nothing.  An additive entry:
+ * OTAL_ABI_VERSION is unchanged. */
+#define OTAL_EVAL_MAX_GT 1024
+int otal_eval_match(const double* pred_seg, const int* pred_start, const double* gt_seg, const int* gt_start,
+                    const double* thresholds, int ngroups, int nthr, int* out, int* nonfinite, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,9 @@ def lib():
         L.otal_error_string.argtypes = [ctypes.c_int]
         if L.otal_abi_version() != ABI_VERSION:
             raise RuntimeError("libopental_hip.so ABI version mismatch; rebuild")
+        # otal_eval_match (csrc/eval.hip): five device arrays, ngroups, nthr, out, the non-finite counter, the stream
+        L.otal_eval_match.restype = ctypes.c_int
+        L.otal_eval_match.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3
         _lib = L
     return _lib
 

@@ -1911,3 +1911,27 @@ class BoundaryLossesFunction(torch.autograd.Function):
                                             L.int_array([d.shape[2] for d in dxs]), B, _opt(gs[0]), _opt(gs[1]), L.stream()),
                 "otal_boundary_scale")
         return (None, None, None) + tuple(outs)
+
+
+def eval_match(pred_seg, pred_start, gt_seg, gt_start, thresholds):
+    """The greedy prediction -> ground-truth matching of the evaluation for every group and tIoU threshold in one launch
+    (otal_eval_match, csrc/eval.hip; the rule: evaluation/match.py).  pred_seg (N, 2) / gt_seg (M, 2) fp64 sorted by group,
+    pred_start / gt_start (ngroups + 1) int32 offsets ending at N / M, thresholds (nthr <= 32) fp64, all on the device.
+    -> (out (nthr, N) int32: the matched row of gt_seg, -1 or -2; nonfinite (1,) int32: non-zero = discard `out`)."""
+    L.require_device(pred_seg, pred_start, gt_seg, gt_start, thresholds)
+    if pred_seg.dtype != torch.float64 or gt_seg.dtype != torch.float64 or thresholds.dtype != torch.float64 \
+            or pred_start.dtype != torch.int32 or gt_start.dtype != torch.int32:
+        raise RuntimeError("eval_match: segments and thresholds in float64, offsets in int32")
+    if pred_seg.dim() != 2 or pred_seg.shape[1] != 2 or gt_seg.dim() != 2 or gt_seg.shape[1] != 2 \
+            or pred_start.dim() != 1 or pred_start.shape != gt_start.shape or pred_start.numel() < 1 or thresholds.dim() != 1:
+        raise RuntimeError("eval_match: pred_seg (N, 2), gt_seg (M, 2), pred_start / gt_start (ngroups + 1), thresholds (nthr,)")
+    N, ngroups, nthr = pred_seg.shape[0], pred_start.numel() - 1, thresholds.numel()
+    out = torch.empty((nthr, N), dtype=torch.int32, device=pred_seg.device)
+    nonfinite = torch.zeros(1, dtype=torch.int32, device=pred_seg.device)
+    if N == 0 or ngroups == 0:
+        return out, nonfinite
+    if gt_seg.shape[0] == 0:        # an empty tensor has no address to pass; the offsets say that no row of it is read
+        gt_seg = gt_seg.new_zeros((1, 2))
+    L.check(L.lib().otal_eval_match(L.ptr(pred_seg), L.ptr(pred_start), L.ptr(gt_seg), L.ptr(gt_start), L.ptr(thresholds),
+                                    ngroups, nthr, L.ptr(out), L.ptr(nonfinite), L.stream()), "otal_eval_match")
+    return out, nonfinite

@@ -6,6 +6,9 @@ Same class name, constructor arguments and `evaluate(type=...)` results as the r
 instead of pandas frames + joblib (the reference walks data frames row by row; here a prediction row is an index into
 parallel arrays).  Pinned against the imported reference by oracle/pin_evaluation.py -> tests/golden/eval_*.json.
 
+`device='cuda'` routes the two matching passes (pre_evaluate, evaluate('AP')) through the device kernel of match.py /
+csrc/eval.hip; None or 'cpu' is the numpy code below.  The metric arithmetic stays on the host in fp64 either way.
+
 Not restated: the Wilderness-Impact variant (`evaluate('WI')`) -- the reference's own drivers have it commented out
 (thumos14/eval_open.py:77-80) -- and the plotting helpers (save_curve_data).
 """
@@ -13,6 +16,7 @@ import json
 
 import numpy as np
 
+from . import match
 from .utils_eval import (average_precision_score, interpolated_prec_rec, open_set_detection_rate, roc_auc_score,
                          roc_curve, segment_iou)
 
@@ -25,7 +29,7 @@ class ANETdetection(object):
                  ground_truth_fields=GROUND_TRUTH_FIELDS, prediction_fields=PREDICTION_FIELDS,
                  tiou_thresholds=np.linspace(0.5, 0.95, 10), ood_threshold=None, ood_scoring='confidence',
                  subset=['validation'], openset=False, draw_auc=False, curve_data_path=None, verbose=False,
-                 check_status=False, dataset='thumos14'):
+                 check_status=False, dataset='thumos14', device=None):
         if not ground_truth_filename:
             raise IOError('Please input a valid ground truth file.')
         if not prediction_filename:
@@ -45,6 +49,10 @@ class ANETdetection(object):
         self.ap = None
         assert dataset in ['thumos14', 'anet', 'thumos_anet']
         self.dataset = dataset
+        if device not in (None, 'cpu', 'cuda'):
+            raise ValueError("device is None, 'cpu' or 'cuda', got %r" % (device,))
+        self.device = device or 'cpu'
+        self._plans = {}        # device path: the group-sorted arrays (and their uploads) of the split pass and the AP pass
         self.blocked_videos = list()
         self.activity_index = self.get_activity_index(cls_idx_detection)
         self.ground_truth, self.video_lst = self._import_ground_truth(ground_truth_filename)
@@ -109,13 +117,35 @@ class ANETdetection(object):
         rows = [(vid, r) for vid, dets in results.items() if vid in known_videos
                 for r in dets if r['label'] in self.activity_index]
         ood = np.array([ood_of(r) for _, r in rows], dtype=np.float64)
-        label = np.array([self.activity_index[r['label']] for _, r in rows], dtype=np.int64)
+        self._closed_label = np.array([self.activity_index[r['label']] for _, r in rows], dtype=np.int64)
+        label = self._closed_label.copy()
         if self.openset and self.ood_threshold is not None:
             label[ood < self.ood_threshold] = self.activity_index['__unknown__']
         seg = np.array([r['segment'][:2] for _, r in rows], dtype=np.float64).reshape(-1, 2)
         return {'video-id': np.array([vid for vid, _ in rows], dtype=object), 't-start': seg[:, 0].copy(),
                 't-end': seg[:, 1].copy(), 'label': label,
                 'score': np.array([r['score'] for _, r in rows], dtype=np.float64), 'ood_score': ood}
+
+    def set_ood_threshold(self, thr):
+        """Relabel the detections for another open-set threshold without re-reading the JSON: in the open-set protocol a
+        detection whose out-of-distribution score is below `thr` becomes '__unknown__'; None restores the labels of the file."""
+        self.ood_threshold = thr
+        label = self._closed_label.copy()
+        if self.openset and thr is not None:
+            label[self.prediction['ood_score'] < thr] = self.activity_index['__unknown__']
+        self.prediction['label'] = label
+        self._plans.pop('ap', None)         # the AP pass groups by label; the split pass does not
+
+    def _device_codes(self, kind):
+        """The matches of one pass through otal_eval_match: (plan, int32 codes (nthr, N) over the plan's sorted positions).
+        Plans and their uploads are kept: the split pass's for the evaluator's life, the AP pass's until the labels change."""
+        if 'videos' not in self._plans:
+            self._plans['videos'] = match.video_codes(self.ground_truth['video-id'], self.prediction['video-id'])
+        if kind not in self._plans:
+            self._plans[kind] = match.plan_split(self.prediction, self.ground_truth, self._plans['videos']) if kind == 'split' \
+                else match.plan_ap(self.prediction, self.ground_truth, self.activity_index.values(), self._plans['videos'])
+        plan = self._plans[kind]
+        return plan, match.match_device(*plan.arrays(), self.tiou_thresholds, plan=plan)
 
     @staticmethod
     def _rows(table, mask):
@@ -124,6 +154,10 @@ class ANETdetection(object):
     def wrapper_compute_average_precision(self):
         """eval_detection.py:236-261.  One column per entry of activity_index; in the open-set protocol the
         '__unknown__' entry (index 0) lands in the LAST column (`ap[:, cidx - 1]` with cidx = 0), as in the reference."""
+        if self.device == 'cuda':
+            plan, codes = self._device_codes('ap')
+            return match.average_precision(plan, plan.unsort(codes), self.activity_index.values(), len(self.tiou_thresholds),
+                                           interpolated_prec_rec)
         ap = np.zeros((len(self.tiou_thresholds), len(self.activity_index)))
         for cidx in self.activity_index.values():
             gt = self._rows(self.ground_truth, self.ground_truth['label'] == cidx)
@@ -134,6 +168,10 @@ class ANETdetection(object):
         return ap
 
     def pre_evaluate(self):
+        if self.device == 'cuda':
+            plan, codes = self._device_codes('split')
+            self.eval_data = match.split_lists(plan, codes, self.prediction, self.ground_truth, len(self.tiou_thresholds))
+            return
         unique_videos = sorted(set(self.video_lst))
         self.eval_data = split_results_by_gt(self.prediction, self.ground_truth, unique_videos, self.tiou_thresholds)
 

@@ -5,7 +5,7 @@ reference's format, and mean +- 1.96 sigma / sqrt(n) over the splits.
 
     python -m opental_amd.thumos14.eval_open output/opental/split_{id:d}/detection_results.json \\
         datasets/thumos14/annotations_open/split_{id:d}/known_gt.json --cls_idx_known .../action_known.txt \\
-        --all_splits 0 1 2 --open_set --ood_scoring uncertainty_actionness
+        --all_splits 0 1 2 --open_set --ood_scoring uncertainty_actionness [--device cuda]
 """
 import argparse
 import os
@@ -38,9 +38,10 @@ def get_mean_std(data, axis=0):
 
 
 def evaluate_split(pred_file, gt_file, cls_idx_known, tious, subset, open_set, ood_scoring='confidence', dataset='thumos14',
-                   write=True):
+                   write=True, device='cpu'):
     det = ANETdetection(ground_truth_filename=gt_file, prediction_filename=pred_file, cls_idx_detection=cls_idx_known,
-                        subset=subset, openset=open_set, ood_scoring=ood_scoring, tiou_thresholds=tious, dataset=dataset)
+                        subset=subset, openset=open_set, ood_scoring=ood_scoring, tiou_thresholds=tious, dataset=dataset,
+                        device=device)
     if open_set:
         det.pre_evaluate()
         auc_ROC, auc_PR, far_95 = det.evaluate(type='AUC')
@@ -64,6 +65,8 @@ def main(argv=None):
     parser.add_argument('--dataset', type=str, default='thumos14', choices=['thumos14', 'thumos_anet'])
     parser.add_argument('--ood_scoring', type=str, default='confidence',
                         choices=['uncertainty', 'confidence', 'uncertainty_actionness', 'a_by_inv_u', 'u_by_inv_a', 'half_au'])
+    parser.add_argument('--device', type=str, default='cpu', choices=['cpu', 'cuda'],
+                        help='cuda: the matching passes run through the device kernel (evaluation/match.py)')
     args = parser.parse_args(argv)
     tious = np.linspace(0.5, 0.95, 10) if args.dataset == 'thumos_anet' else [0.3, 0.4, 0.5, 0.6, 0.7]
     subset = ['test', 'validation'] if args.dataset == 'thumos_anet' else ['test']
@@ -71,7 +74,7 @@ def main(argv=None):
     for split in args.all_splits:
         gt_file = args.gt_json if args.open_set else args.gt_json.format(id=split)
         per_split.append(evaluate_split(args.output_json.format(id=split), gt_file, args.cls_idx_known.format(id=split),
-                                        tious, subset, args.open_set, args.ood_scoring, args.dataset))
+                                        tious, subset, args.open_set, args.ood_scoring, args.dataset, device=args.device))
     names = (('far_95', 'FAR@95'), ('auc_roc', 'AUC_ROC'), ('auc_pr', 'AUC_PR'), ('osdr', 'OSDR')) if args.open_set else (('mAP', 'mAP'),)
     for key, title in names:
         mean, std = get_mean_std([r[key] for r in per_split])
