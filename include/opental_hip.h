@@ -393,6 +393,25 @@ int otal_softnms_classes_ws(const float* seg, const float* score, const float* u
                             int A, int K, float sigma, int top_k, float score_threshold, float* out,
                             int* counts, int* out_index, int out_cols, void* scratch, size_t scratch_bytes,
                             int total_clips, void* stream);
+/* otal_detection_table (csrc/dettable.hip): the rows / counts of otal_softnms_classes_ws as one compact table, i.e. the
+ * host loops get_video_prediction (AFSD/anet/test.py:159-200) and get_video_detections (AFSD/thumos14/test.py:165-200) plus
+ * the known-ness scores of threshold.py:128-147, on the device.  The rule is stated in opental_amd/common/det_table.py
+ * (table_reference).  rows (V, K, top_k, cols) fp32, cols 3..5 = [start, end, score(, uncertainty)(, actionness)];
+ * counts (V, K) int32; durations (V) fp64 seconds or NULL.  Row (v, c, i) is valid when i < counts[v][c] and score > 0
+ * (a NaN score is not); with durations or drop_empty also start = max(0, (double)r0), end = min(durations[v], (double)r1)
+ * (without durations end = (double)r1) and the row is dropped when end <= start, compared in fp64.  Rows at and past
+ * counts[v][c] are never read.  Outputs, each with room for V * K * top_k rows, filled for the N valid rows in (v, c, i)
+ * ascending order and left untouched beyond: video, cls (0-based) int32; seg (., 2) fp64; sup (., 3) fp32 = score,
+ * uncertainty, actionness (0.0f for a column the rows do not carry); known fp64 = 1 - ood under `scoring` (0..5 in the
+ * order of thumos14/test.py: OOD_SCORES: uncertainty, confidence, uncertainty_actionness, a_by_inv_u, u_by_inv_a, half_au),
+ * in fp64 from the widened fp32 columns with the operations and their order of the Python lambdas;
+ * list_start (V * K + 1) int32 = exclusive prefix of the valid rows per (v, c), list_start[V * K] = N.
+ * Three launches on `stream` (count, prefix, fill), no allocation, no synchronisation, no atomic: the table is the same
+ * from run to run.  NULL pointer: OTAL_E_NULL; V, K, top_k < 1 or cols outside 3..5: OTAL_E_SHAPE; scoring outside 0..5 or
+ * V * K * top_k >= 2^31: OTAL_E_UNSUPPORTED.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_detection_table(const float* rows, const int* counts, const double* durations, int V, int K, int top_k, int cols,
+                         int drop_empty, int scoring, int* video, int* cls, double* seg, float* sup, double* known,
+                         int* list_start, void* stream);
 
 /* ------------------------------------------------------------------ OpenMax baseline (csrc/openmax.hip) ----
  * Added under ABI 26 (new symbols only).  Feature rows are addressed by ELEMENT strides: row n (0 <= n < N), channel d at

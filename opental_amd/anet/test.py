@@ -6,7 +6,8 @@ is a batch of clips: the network runs on them together and the same two launches
 otal_decode_clips (refine + decode + Dirichlet scores + thresholds, for every clip; otal_decode_clips_ex for the closed-set
 Softmax and EDL heads) and otal_softnms_classes (one workgroup per (video, class)).  Differences from the THUMOS14 file
 that are kept: short videos are padded with 127.5 (mid-grey), the confidence threshold is 0.001, proposals are clipped to
-[0, duration] and empty ones dropped.
+[0, duration] and empty ones dropped.  `detect_rows` ends after the two launches, with the Soft-NMS rows on the device
+(anet/threshold.py turns them into a table there); `detect_batch` adds the host loop that builds the proposal dicts.
 """
 import torch
 
@@ -76,10 +77,10 @@ def get_video_prediction(rows, counts, duration, idx_to_class=None):
 
 
 @torch.no_grad()
-def detect_batch(net, videos, sample_fps, durations, idx_to_class=None, clip_length=CLIP_LENGTH, conf_thresh=0.001,
-                 top_k=5000, nms_sigma=0.85, batch_clips=4):
-    """videos: list of uint8 (C,T,96,96) device tensors (centre-cropped).  Returns {index: proposal list}.  The network's
-    head (os_head, use_edl, evidence) picks the decode."""
+def detect_rows(net, videos, sample_fps, clip_length=CLIP_LENGTH, conf_thresh=0.001, top_k=5000, nms_sigma=0.85, batch_clips=4):
+    """videos: list of uint8 (C,T,96,96) device tensors (centre-cropped).  Returns the Soft-NMS output of the batch, rows
+    (V,K,min(top_k,A),cols) and counts (V,K), on the device: the network, one decode launch, one Soft-NMS launch.  The
+    network's head (os_head, use_edl, evidence) picks the decode."""
     os_head, use_edl, evidence = _t.head_mode(net)
     outs = []
     for i in range(0, len(videos), batch_clips):
@@ -91,6 +92,13 @@ def detect_batch(net, videos, sample_fps, durations, idx_to_class=None, clip_len
     fps = [float(f) for f in sample_fps]
     dec = decode_clips(merged, fps, clip_length, conf_thresh, os_head=os_head, use_edl=use_edl, evidence=evidence)
     rows, counts, _ = _t.softnms_classes(dec, list(range(len(videos) + 1)), top_k, nms_sigma)
+    return rows, counts
+
+
+def detect_batch(net, videos, sample_fps, durations, idx_to_class=None, clip_length=CLIP_LENGTH, conf_thresh=0.001,
+                 top_k=5000, nms_sigma=0.85, batch_clips=4):
+    """detect_rows, then the host loop: returns {index: proposal list} clipped to the videos' durations."""
+    rows, counts = detect_rows(net, videos, sample_fps, clip_length, conf_thresh, top_k, nms_sigma, batch_clips)
     return {v: get_video_prediction(rows[v], counts[v], durations[v], idx_to_class) for v in range(len(videos))}
 
 

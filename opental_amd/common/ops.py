@@ -1935,3 +1935,47 @@ def eval_match(pred_seg, pred_start, gt_seg, gt_start, thresholds):
     L.check(L.lib().otal_eval_match(L.ptr(pred_seg), L.ptr(pred_start), L.ptr(gt_seg), L.ptr(gt_start), L.ptr(thresholds),
                                     ngroups, nthr, L.ptr(out), L.ptr(nonfinite), L.stream()), "otal_eval_match")
     return out, nonfinite
+
+
+def detection_table(rows, counts, durations=None, drop_empty=False, scoring='uncertainty', out=None):
+    """The Soft-NMS output of softnms_classes as one compact table (otal_detection_table, csrc/dettable.hip; the rule:
+    common/det_table.py): rows (V, K, top_k, cols) fp32 with cols 3..5, counts (V, K) int32, durations (V) seconds (a
+    sequence or an fp64 device tensor) or None.  -> dict(video, cls int32; seg fp64 (., 2); sup fp32 (., 3); known fp64;
+    list_start int32 (V*K + 1); n = list_start[-1] as a 0-dim device tensor).  The row arrays have room for V*K*top_k rows
+    and hold the n valid ones in (video, class, row) order; nothing is written past them.  No synchronisation.
+    `out`: a dict of these arrays to write into instead of allocating them."""
+    from .det_table import SCORINGS
+    L.require_device(rows, counts)
+    if rows.dtype != torch.float32 or counts.dtype != torch.int32:
+        raise RuntimeError("detection_table: rows in float32, counts in int32")
+    if rows.dim() != 4 or tuple(counts.shape) != tuple(rows.shape[:2]):
+        raise RuntimeError("detection_table: rows (V, K, top_k, cols), counts (V, K)")
+    if scoring not in SCORINGS:
+        raise NotImplementedError(scoring)
+    V, K, top_k, cols = rows.shape
+    dev = rows.device
+    dur = None
+    if durations is not None:
+        dur = torch.as_tensor(durations, dtype=torch.float64).to(dev).contiguous()
+        if dur.numel() != V:
+            raise RuntimeError("detection_table: one duration per video")
+    cap = V * K * top_k
+    if out is None:
+        out = dict(video=torch.empty(cap, dtype=torch.int32, device=dev), cls=torch.empty(cap, dtype=torch.int32, device=dev),
+                   seg=torch.empty((cap, 2), dtype=torch.float64, device=dev), sup=torch.empty((cap, 3), device=dev),
+                   known=torch.empty(cap, dtype=torch.float64, device=dev),
+                   list_start=torch.empty(V * K + 1, dtype=torch.int32, device=dev))
+    else:
+        want = dict(video=((cap,), torch.int32), cls=((cap,), torch.int32), seg=((cap, 2), torch.float64),
+                    sup=((cap, 3), torch.float32), known=((cap,), torch.float64), list_start=((V * K + 1,), torch.int32))
+        for k, (shape, dtype) in want.items():
+            L.require_device(out[k])
+            if tuple(out[k].shape) != shape or out[k].dtype != dtype:
+                raise RuntimeError(f"detection_table: out[{k!r}] must be {shape} {dtype}")
+        out = {k: out[k] for k in want}
+    L.check(L.lib().otal_detection_table(L.ptr(rows), L.ptr(counts), None if dur is None else L.ptr(dur), V, K, top_k, cols,
+                                         int(bool(drop_empty)), SCORINGS.index(scoring), L.ptr(out['video']), L.ptr(out['cls']),
+                                         L.ptr(out['seg']), L.ptr(out['sup']), L.ptr(out['known']), L.ptr(out['list_start']),
+                                         L.stream()), "otal_detection_table")
+    out['n'] = out['list_start'][-1]
+    return out

@@ -55,6 +55,18 @@ def evaluate_split(pred_file, gt_file, cls_idx_known, tious, subset, open_set, o
     return {'mAP': mAPs, 'average_mAP': average_mAP}
 
 
+def print_summary(per_split, tious, open_set):
+    """Mean and confidence half-width over the splits, per tIoU and of the per-split averages; shared with
+    opental_amd.anet.eval_open."""
+    names = (('far_95', 'FAR@95'), ('auc_roc', 'AUC_ROC'), ('auc_pr', 'AUC_PR'), ('osdr', 'OSDR')) if open_set else (('mAP', 'mAP'),)
+    for key, title in names:
+        mean, std = get_mean_std([r[key] for r in per_split])
+        avg_mean, avg_std = get_mean_std([np.mean(r[key]) for r in per_split])
+        for tiou, m, s in zip(tious, mean, std):
+            print(f"{title}(tIoU={tiou}): mean={m:.5f}, std={s:.5f}")
+        print(f"Average {title} = {avg_mean:.5f} ({avg_std:.5f})\n")
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('output_json', type=str)
@@ -75,13 +87,7 @@ def main(argv=None):
         gt_file = args.gt_json if args.open_set else args.gt_json.format(id=split)
         per_split.append(evaluate_split(args.output_json.format(id=split), gt_file, args.cls_idx_known.format(id=split),
                                         tious, subset, args.open_set, args.ood_scoring, args.dataset, device=args.device))
-    names = (('far_95', 'FAR@95'), ('auc_roc', 'AUC_ROC'), ('auc_pr', 'AUC_PR'), ('osdr', 'OSDR')) if args.open_set else (('mAP', 'mAP'),)
-    for key, title in names:
-        mean, std = get_mean_std([r[key] for r in per_split])
-        avg_mean, avg_std = get_mean_std([np.mean(r[key]) for r in per_split])
-        for tiou, m, s in zip(tious, mean, std):
-            print(f"{title}(tIoU={tiou}): mean={m:.5f}, std={s:.5f}")
-        print(f"Average {title} = {avg_mean:.5f} ({avg_std:.5f})\n")
+    print_summary(per_split, tious, args.open_set)
     return per_split
 
 
