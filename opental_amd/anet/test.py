@@ -6,12 +6,14 @@ is a batch of clips: the network runs on them together and the same two launches
 otal_decode_clips (refine + decode + Dirichlet scores + thresholds, for every clip; otal_decode_clips_ex for the closed-set
 Softmax and EDL heads) and otal_softnms_classes (one workgroup per (video, class)).  Differences from the THUMOS14 file
 that are kept: short videos are padded with 127.5 (mid-grey), the confidence threshold is 0.001, proposals are clipped to
-[0, duration] and empty ones dropped.  `detect_rows` ends after the two launches, with the Soft-NMS rows on the device
+[0, duration] and empty ones dropped.  The pipeline itself is common/detect.py's (one window per video), shared with
+THUMOS14.  `detect_rows` ends after the two launches, with the Soft-NMS rows on the device
 (anet/threshold.py turns them into a table there); `detect_batch` adds the host loop that builds the proposal dicts.
 """
 import torch
 
-from ..thumos14 import test as _t
+from ..common import detect as _d
+from ..common.detect import prepare_data                   # anet/test.py:71-80 reads the .npy as thumos14/test.py does
 
 CLIP_LENGTH = 768
 
@@ -35,64 +37,42 @@ def _heads(output_dict):
 
 def decode_clips(output_dict, fps, clip_length=CLIP_LENGTH, conf_thresh=0.001, os_head=True, use_edl=True, evidence='exp'):
     """Batched decode_prediction + the threshold masks of filtering for n videos (offset 0).  os_head / use_edl / evidence:
-    the network's head (thumos14.test.head_mode).  The closed-set heads (os_head False: anet_softmax.yaml with softmax
+    the network's head (common.detect.head_mode).  The closed-set heads (os_head False: anet_softmax.yaml with softmax
     scores, anet_edl.yaml with Dirichlet scores) leave the background logit out of score / flag, so row c is the
     reference's class c + 1, and apply no actionness factor or mask (anet/test.py:95-156 with os_head False)."""
     n = output_dict['loc'].shape[0]
-    return _t.decode_clips(_heads(output_dict), [0.0] * n, fps, clip_length, conf_thresh, os_head=os_head,
+    return _d.decode_clips(_heads(output_dict), [0.0] * n, fps, clip_length, conf_thresh, os_head=os_head,
                            use_edl=use_edl, evidence=evidence)
 
 
 def decode_prediction(output_dict, idx=0, sample_fps=1.0, clip_length=CLIP_LENGTH, os_head=True, use_edl=True, evidence='exp'):
     """Single-clip view: decoded_segments (A,2) in SECONDS (the reference divides by fps in filtering), conf_scores
     (K,A), uncertainty (A,) or None without use_edl, actionness (A,) or None without os_head."""
-    return _t.decode_predictions(_heads(output_dict), idx, 0.0, sample_fps, clip_length, os_head=os_head, use_edl=use_edl,
+    return _d.decode_predictions(_heads(output_dict), idx, 0.0, sample_fps, clip_length, os_head=os_head, use_edl=use_edl,
                                  evidence=evidence)
 
 
 def filtering(decoded_segments, conf_score_cls, uncertainty, actionness, conf_thresh=0.001, use_edl=True, os_head=True):
-    return _t.filtering(decoded_segments, conf_score_cls, uncertainty, actionness, conf_thresh, use_edl=use_edl,
+    return _d.filtering(decoded_segments, conf_score_cls, uncertainty, actionness, conf_thresh, use_edl=use_edl,
                         os_head=os_head)
 
 
 def get_video_prediction(rows, counts, duration, idx_to_class=None):
     """anet/test.py:159-200: the proposal list of one video from its suppressed rows (K,top_k,cols), clipped to
-    [0, duration]; proposals that end before they start are dropped.  cols is 5 for the OpenTAL head, 4 for the closed-set
-    EDL head and 3 for the Softmax head: 'uncertainty' / 'actionness' are 0.0 where the column is absent (:197-198)."""
-    rows, counts = rows.cpu().numpy(), counts.cpu().numpy()
-    proposal_list = []
-    for cl in range(rows.shape[0]):
-        name = idx_to_class[cl + 1] if idx_to_class is not None else cl + 1
-        for i in range(int(counts[cl])):
-            r = rows[cl, i]
-            if not r[2] > 0:
-                continue
-            start, end = max(0, float(r[0])), min(duration, float(r[1]))
-            if end <= start:
-                continue
-            proposal_list.append({'label': name, 'score': float(r[2]), 'segment': [start, end],
-                                  'uncertainty': float(r[3]) if len(r) > 3 else 0.0,
-                                  'actionness': float(r[4]) if len(r) > 4 else 0.0})
-    return proposal_list
+    [0, duration]; proposals that end before they start are dropped."""
+    return _d.get_video_detections(rows, counts, idx_to_class, duration=duration)
 
 
-@torch.no_grad()
 def detect_rows(net, videos, sample_fps, clip_length=CLIP_LENGTH, conf_thresh=0.001, top_k=5000, nms_sigma=0.85, batch_clips=4):
     """videos: list of uint8 (C,T,96,96) device tensors (centre-cropped).  Returns the Soft-NMS output of the batch, rows
-    (V,K,min(top_k,A),cols) and counts (V,K), on the device: the network, one decode launch, one Soft-NMS launch.  The
-    network's head (os_head, use_edl, evidence) picks the decode."""
-    os_head, use_edl, evidence = _t.head_mode(net)
-    outs = []
-    for i in range(0, len(videos), batch_clips):
-        # one launch per forward pass; same values as prepare_clip per video (127.5 padded before the normalisation IS 0.0)
-        batch = _t.prepare_windows(videos, [(j, 0) for j in range(i, min(i + batch_clips, len(videos)))], clip_length)
-        outs.append(net(batch))
+    (V,K,min(top_k,A),cols) and counts (V,K), on the device: the network, one decode launch, one Soft-NMS launch
+    (common/detect.py's `detect` with one window per video).  The network's head (os_head, use_edl, evidence) picks the
+    decode.  The windows hold the same values as prepare_clip per video (127.5 padded before the normalisation IS 0.0)."""
+    os_head, use_edl, evidence = _d.head_mode(net)
     keys = ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'priors') + (('act', 'prop_act') if os_head else ())
-    merged = {k: (torch.cat([o[k] for o in outs], 0) if k != 'priors' else outs[0][k]) for k in keys}
-    fps = [float(f) for f in sample_fps]
-    dec = decode_clips(merged, fps, clip_length, conf_thresh, os_head=os_head, use_edl=use_edl, evidence=evidence)
-    rows, counts, _ = _t.softnms_classes(dec, list(range(len(videos) + 1)), top_k, nms_sigma)
-    return rows, counts
+    decode = lambda merged, offsets, fps: decode_clips(merged, fps, clip_length, conf_thresh, os_head=os_head,
+                                                       use_edl=use_edl, evidence=evidence)
+    return _d.detect(net, videos, sample_fps, decode, keys, clip_length, None, top_k, nms_sigma, batch_clips)[:2]
 
 
 def detect_batch(net, videos, sample_fps, durations, idx_to_class=None, clip_length=CLIP_LENGTH, conf_thresh=0.001,
@@ -103,11 +83,6 @@ def detect_batch(net, videos, sample_fps, durations, idx_to_class=None, clip_len
 
 
 # ----------------------------------------------------------------------------- the driver (anet/test.py:203-348)
-def prepare_data(npy_path, video_name, crop_size=96, device='cuda'):
-    """anet/test.py:71-80: <npy dir>/<name>.npy uint8 (T,H,W,3) -> centre-cropped planar (3,T,crop,crop) uint8 on the device."""
-    return _t.prepare_data(npy_path, video_name, crop_size, device)
-
-
 def get_class_names(class_info_path):
     """anet/test.py:54-59: one class name per line -> {1..K: name}."""
     with open(class_info_path) as f:
@@ -141,11 +116,9 @@ def main(argv=None):
     import os
     import sys
     from ..common import config as C
-    from ..common import ops
+    from ..common.driver import device_setup, load_net, split_flags, write_json
     from .BDNet import BDNet, model_cfg_from
-    argv = list(sys.argv[1:] if argv is None else argv)
-    random_init = '--random_init' in argv
-    argv = [a for a in argv if a != '--random_init']
+    own, argv = split_flags(list(sys.argv[1:] if argv is None else argv), ('--random_init',))
     config = C.set_config(C.get_config(argv))
     te, md, ds = config['testing'], config['model'], config['dataset']
     t = ds['testing']
@@ -159,27 +132,19 @@ def main(argv=None):
             if len(json.load(f)['results']) == len(video_list):
                 print(f'Result file exist and it is complete! \n{out_file}')
                 return out_file
-    rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
-    dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
-    torch.cuda.set_device(dev)
-    ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
-    net = BDNet(in_channels=md['in_channels'], training=False, frame_num=t['clip_length'], use_edl=md.get('use_edl', False),
-                cfg=model_cfg_from(config))
-    if not random_init:
-        net.load_state_dict(torch.load(te['checkpoint_path'], map_location='cpu'))
-    net = net.to(dev).eval()
+    rank, world, dev = device_setup()
+    net = load_net(BDNet, dev, own['--random_init'], te['checkpoint_path'], in_channels=md['in_channels'],
+                   frame_num=t['clip_length'], use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
     idx_to_class = None
     if ds.get('class_info_path') and os.path.exists(ds['class_info_path']):
         idx_to_class = get_class_names(ds['class_info_path'])
     res = testing(net, video_list, infos, t['video_mp4_path'], idx_to_class, t['clip_length'], t['crop_size'], te['conf_thresh'],
                   te['top_k'], te['nms_sigma'], rank=rank, world=world, device=dev)
-    res = _t.gather_results(res, [n[2:] for n in video_list], rank, world, dev)
+    res = _d.gather_results(res, [n[2:] for n in video_list], rank, world, dev)
     if res is None:
         return None
     assert len(res) == len(video_list), "Incomplete testing results!"
-    os.makedirs(te['output_path'], exist_ok=True)
-    with open(out_file, 'w') as f:
-        json.dump(_t.results_json(res, version="ActivityNet-v1.3"), f)
+    write_json(out_file, _d.results_json(res, version="ActivityNet-v1.3"))
     print(f"{len(res)} videos, {sum(len(v) for v in res.values())} detections -> {out_file}")
     return out_file
 

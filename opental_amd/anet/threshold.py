@@ -27,7 +27,8 @@ import sys
 import torch
 
 from ..common.det_table import detection_table, proposals_from_table, threshold_from_scores
-from ..thumos14 import test as _t
+from ..common.detect import gather_results, results_json
+from ..common.driver import device_setup, load_net, split_flags, write_json
 from . import test as T
 
 
@@ -67,18 +68,14 @@ def gather_scores(scores, rank, world, device=None):
     return None.  One rank: the column itself."""
     if world == 1:
         return scores
-    parts = _t.gather_results({rank: scores.cpu().numpy()}, list(range(world)), rank, world, device)
+    parts = gather_results({rank: scores.cpu().numpy()}, list(range(world)), rank, world, device)
     return None if parts is None else merge_scores(list(parts.values()))
 
 
 def write_threshold_file(output_file, threshold, results=None):
-    """Written under a temporary name and moved into place, so that a reader (or the re-use test of `main`) never sees half
-    a file."""
-    os.makedirs(os.path.dirname(os.path.abspath(output_file)), exist_ok=True)
-    tmp = f"{output_file}.tmp{os.getpid()}"
-    with open(tmp, 'w') as f:
-        json.dump(_t.results_json(results or {}, threshold=threshold, version="ActivityNet-v1.3"), f)
-    os.replace(tmp, output_file)
+    """The file of this pass: the threshold, and the detections when they were kept (driver.write_json: the re-use test of
+    `main` never sees half a file)."""
+    write_json(output_file, results_json(results or {}, threshold=threshold, version="ActivityNet-v1.3"))
 
 
 def read_threshold_file(output_file):
@@ -101,7 +98,7 @@ def thresholding(net, video_list, video_infos, npy_path, output_file, idx_to_cla
                                    idx_to_class)
     scores = gather_scores(scores, rank, world, device)
     if keep_detections:
-        results = _t.gather_results(results, [n[2:] for n in video_list], rank, world, device)
+        results = gather_results(results, [n[2:] for n in video_list], rank, world, device)
     if scores is None:
         return None
     thr = threshold_from_scores(scores)
@@ -111,9 +108,7 @@ def thresholding(net, video_list, video_infos, npy_path, output_file, idx_to_cla
 
 def main(argv=None):
     from ..common import config as C
-    argv = list(sys.argv[1:] if argv is None else argv)
-    random_init, keep = '--random_init' in argv, '--keep_detections' in argv
-    argv = [a for a in argv if a not in ('--random_init', '--keep_detections')]
+    own, argv = split_flags(list(sys.argv[1:] if argv is None else argv), ('--random_init', '--keep_detections'))
     args = C.build_parser().parse_args(argv)
     config = C.set_config(C.get_config(argv))
     te, md, ds = config['testing'], config['model'], config['dataset']
@@ -123,25 +118,18 @@ def main(argv=None):
         print(f'Thresholding result file already exist at {output_file}!')
         print(f'The threshold is: {thr:.12f}')
         return output_file, thr
-    from ..common import ops
     from .BDNet import BDNet, model_cfg_from
-    rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
-    dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
-    torch.cuda.set_device(dev)
-    ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
+    rank, world, dev = device_setup()
     tr, t = ds['training'], ds['testing']
-    net = BDNet(in_channels=md['in_channels'], training=False, frame_num=t['clip_length'], use_edl=md.get('use_edl', False),
-                cfg=model_cfg_from(config))
-    if not random_init:
-        net.load_state_dict(torch.load(te['checkpoint_path'], map_location='cpu'))
-    net = net.to(dev).eval()
+    net = load_net(BDNet, dev, own['--random_init'], te['checkpoint_path'], in_channels=md['in_channels'],
+                   frame_num=t['clip_length'], use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
     video_list, infos = select_videos(tr['video_info_path'], tr['video_mp4_path'])
     idx_to_class = None
     if ds.get('class_info_path') and os.path.exists(ds['class_info_path']):
         idx_to_class = T.get_class_names(ds['class_info_path'])
     thr = thresholding(net, video_list, infos, tr['video_mp4_path'], output_file, idx_to_class, args.ood_scoring,
                        t['clip_length'], t['crop_size'], te['conf_thresh'], te['top_k'], te['nms_sigma'], rank=rank,
-                       world=world, device=dev, keep_detections=keep)
+                       world=world, device=dev, keep_detections=own['--keep_detections'])
     if thr is not None:
         print(f'{len(video_list)} training videos -> {output_file}')
         print(f'The threshold is: {thr:.12f}')

@@ -1,8 +1,8 @@
 """The detections of a batch of videos as one table instead of one dict per detection.
 
-The inference drivers turn the Soft-NMS output (rows (V, K, top_k, cols), counts (V, K); thumos14.test.softnms_classes) into
-proposal dicts by walking every row in Python (anet.test.get_video_prediction, thumos14.test.get_video_detections), and the
-open-set threshold (thumos14.test.ood_threshold) walks all the dicts again.  This module states that walk once as a rule over
+The inference drivers turn the Soft-NMS output (rows (V, K, top_k, cols), counts (V, K); common.detect.softnms_classes) into
+proposal dicts by walking every row in Python (anet.test.get_video_prediction, common.detect.get_video_detections), and the
+open-set threshold (common.detect.ood_threshold) walks all the dicts again.  This module states that walk once as a rule over
 arrays:
 
   * `table_reference` -- the rule in plain numpy loops: the oracle of otal_detection_table (csrc/dettable.hip) and the form
@@ -20,7 +20,7 @@ rows mean anything."""
 import numpy as np
 import torch
 
-from ..thumos14.test import OOD_SCORES
+from .detect import OOD_SCORES
 
 SCORINGS = tuple(OOD_SCORES)        # the kernel's `scoring` argument is the index into this tuple
 
@@ -82,7 +82,7 @@ def _host(a, n):
 
 def proposals_from_table(table, names, idx_to_class=None):
     """{names[v]: [proposal dict, ...]} of a table over len(names) videos: what anet.test.get_video_prediction /
-    thumos14.test.get_video_detections build from the same rows (a clipped start is 0.0 where those give the int 0).
+    common.detect.get_video_detections build from the same rows (a clipped start is 0.0 where those give the int 0).
     The columns come to the host once and become Python numbers by tolist()."""
     n = int(table['n'])
     starts = _host(table['list_start'], None).tolist()
@@ -105,7 +105,7 @@ def threshold_index(n):
 
 
 def threshold_from_scores(scores):
-    """thumos14.test.ood_threshold over a column of known-ness scores (fp64; a device or host tensor, or an array)."""
+    """common.detect.ood_threshold over a column of known-ness scores (fp64; a device or host tensor, or an array)."""
     scores = torch.as_tensor(scores, dtype=torch.float64).reshape(-1)
     n = scores.numel()
     if n == 0:

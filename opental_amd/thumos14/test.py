@@ -1,32 +1,18 @@
-"""Inference path of OpenTAL/AFSD on MI355X, with the reference's function names
-(AFSD/thumos14/test.py): get_offsets (:48-56), prepare_clip (:67-76), parse_output (:79-109),
-decode_predictions (:112-140), filtering (:143-162), get_video_detections (:165-200).
+"""Inference path of OpenTAL/AFSD on MI355X for THUMOS14, with the reference's function names (AFSD/thumos14/test.py):
+prepare_clip (:67-76), the RPL / GCPL flags of :268-269, test (:203-252) and the driver (:255-288).
 
-`detect_batch` is the MI355X-first entry point: all sliding windows of a batch of videos go through
-the network in large batches (the reference runs b=1, test.py:227-235), then TWO launches do the
-rest -- otal_decode_clips (decode + per-class threshold for every clip) and otal_softnms_classes
-(gather + Soft-NMS for every (video, class)) -- with no host synchronisation until the final copy.
-The head decides the decode (test.py:79-162): the OpenTAL head (os_head + use_edl: Dirichlet scores x actionness) and the
-closed-set Softmax / EDL baselines (os_head false: softmax or Dirichlet scores over C = classes + 1 logits, the background
-class dropped, no actionness; otal_decode_clips_ex).
-Multi-GPU: shard the video list across ranks (as the reference's unused AFSD/anet/test.py:248-273
-sketches); there is no collective on this path.
+`detect_batch` is the MI355X-first entry point: common/detect.py's `detect` (batched sliding windows, ONE decode launch, ONE
+Soft-NMS launch, no host synchronisation until the final copy) with the decode the THUMOS14 head asks for (test.py:79-162):
+the OpenTAL head (os_head + use_edl: Dirichlet scores x actionness; otal_decode_clips) and the closed-set Softmax / EDL
+baselines (os_head false: softmax or Dirichlet scores over C = classes + 1 logits, the background class dropped, no
+actionness; otal_decode_clips_ex).  Everything that does not depend on the dataset lives in common/detect.py and is
+imported here under the names it has always had in this module.
 """
-import ctypes
-
 import torch
 
-from .. import _lib as L
-
-
-def get_offsets(sample_count, clip_length, stride):
-    """test.py:48-56 with the video's sample count passed in."""
-    if sample_count < clip_length:
-        return [0]
-    out = list(range(0, sample_count - clip_length + 1, stride))
-    if (sample_count - clip_length) % stride:
-        out += [sample_count - clip_length]
-    return out
+from ..common.detect import (OOD_SCORES, _decode_clips_ex, decode_clips, decode_predictions, detect, filtering,  # noqa: F401
+                             fuse_outputs, gather_results, get_offsets, get_video_detections, head_mode, ood_threshold,
+                             prepare_data, prepare_windows, results_json, rpl_logits, softnms_classes)
 
 
 def prepare_clip(data, offset, clip_length):
@@ -39,39 +25,6 @@ def prepare_clip(data, offset, clip_length):
     return clip.unsqueeze(0)
 
 
-_WINDOW_DTYPE = None
-
-
-def prepare_windows(videos, windows, clip_length):
-    """All windows of one forward pass in ONE launch (otal_prepare_windows): videos = uint8 (C,Tv,H,W) device tensors,
-    windows = [(video index, offset)].  Bit-identical to torch.cat([prepare_clip(videos[v], o, clip_length) ...])."""
-    import numpy as np
-    global _WINDOW_DTYPE
-    if _WINDOW_DTYPE is None:
-        _WINDOW_DTYPE = np.dtype([("src", "<u8"), ("chan_stride4", "<i4"), ("valid_t", "<i4")])
-    C, _, H, W = videos[windows[0][0]].shape
-    recs = np.zeros(len(windows), _WINDOW_DTYPE)
-    for i, (v, o) in enumerate(windows):
-        d = videos[v]
-        if d.dtype != torch.uint8 or not d.is_cuda or not d.is_contiguous() or tuple(d.shape[2:]) != (H, W) or d.shape[0] != C:
-            raise RuntimeError("videos must be contiguous uint8 (C,T,H,W) device tensors of one frame size")
-        if (H * W) % 4 or d.data_ptr() % 4 or not 0 <= o < d.shape[1]:
-            raise RuntimeError("otal_prepare_windows needs H*W % 4 == 0, 4-byte aligned videos and offsets inside the video")
-        recs[i] = (d.data_ptr() + o * H * W, d.shape[1] * H * W // 4, min(clip_length, d.shape[1] - o))
-    dev = videos[windows[0][0]].device
-    params = torch.from_numpy(recs.view(np.uint8).copy()).to(dev, non_blocking=True)
-    out = torch.empty((len(windows), C, clip_length, H, W), dtype=torch.float32, device=dev)
-    L.check(L.lib().otal_prepare_windows(L.ptr(params), L.ptr(out), len(windows), C, clip_length, H, W, L.stream()),
-            "otal_prepare_windows")
-    return out
-
-
-def head_mode(net):
-    """(os_head, use_edl, evidence) of a THUMOS14 BDNet: which decode its outputs need.  A network that does not say is
-    taken for the OpenTAL head (os_head, use_edl, exp evidence)."""
-    return bool(getattr(net, 'os_head', True)), bool(getattr(net, 'use_edl', True)), getattr(net, 'evidence', 'exp')
-
-
 def rpl_flags(config):
     """(use_rpl, use_gcpl) of a parsed config, as test.py:268-269 reads them: the distance head of the RPL / GCPL baselines
     and whether its scores are the softmax of the NEGATED distances."""
@@ -80,161 +33,6 @@ def rpl_flags(config):
     return use_rpl, bool(use_rpl and rc.get('gcpl', False))
 
 
-def rpl_logits(output_dict, use_gcpl=False):
-    """The classification maps the closed-set softmax decode reads for the distance head (parse_output, test.py:85-87): the
-    distances themselves for RPL, their negation for GCPL.  Host or device tensors.
-    Applied to the (fused) maps: both streams' maps are distances, so a two-stream GCPL run scores softmax(-(rgb + flow) / 2).
-    Reference hazard: its parse_output negates the rgb stream BEFORE the average and leaves the flow stream as it is
-    (test.py:85-87 then :96-99), i.e. softmax((flow - rgb) / 2) -- pinned in tests/golden/rpl.npz (dec_gcpl_fus1_*) and
-    reproduced in tests/test_rpl_gpu.py, not adopted.  Single-stream runs are unaffected."""
-    if not use_gcpl:
-        return output_dict
-    return dict(output_dict, conf=-output_dict['conf'], prop_conf=-output_dict['prop_conf'])
-
-
-def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01, os_head=True, use_edl=True, evidence='exp',
-                 use_gcpl=False):
-    """Batched parse_output + decode_predictions + threshold masks.  output_dict: model outputs for
-    `n` clips; offsets/fps: per-clip tensors or lists.  Returns dict(seg, score, unct, actn, flag).
-    os_head / use_edl / evidence: the network's head (head_mode).  The closed-set head (os_head False) has a background
-    logit, which score / flag leave out (K - 1 classes); unct is None without use_edl, actn None without os_head."""
-    if use_edl and evidence != 'exp':
-        raise NotImplementedError(f"evidence {evidence!r}: the decode kernel computes exp evidence only")
-    if os_head and not use_edl:
-        raise NotImplementedError("an actionness head with softmax scores is not a THUMOS14 configuration")
-    if use_gcpl and (os_head or use_edl):
-        raise NotImplementedError("use_gcpl belongs to the closed-set softmax decode of the distance head")
-    output_dict = rpl_logits(output_dict, use_gcpl)
-    loc = output_dict['loc'].contiguous()
-    n, A, _ = loc.shape
-    K = output_dict['conf'].shape[-1]
-    if not os_head:
-        return _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, use_edl)
-    dev = loc.device
-    offs = torch.as_tensor(offsets, dtype=torch.float32, device=dev).contiguous()
-    fpst = torch.as_tensor(fps, dtype=torch.float32, device=dev).contiguous()
-    if fpst.numel() == 1:
-        fpst = fpst.expand(n).contiguous()
-    seg = torch.empty((n, A, 2), device=dev)
-    score = torch.empty((n, K, A), device=dev)
-    unct = torch.empty((n, A), device=dev)
-    actn = torch.empty((n, A), device=dev)
-    flag = torch.empty((n, K, A), dtype=torch.uint8, device=dev)
-    t = lambda k: output_dict[k].contiguous()
-    L.check(L.lib().otal_decode_clips(L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(output_dict['priors'].contiguous()),
-                                      L.ptr(t('conf')), L.ptr(t('prop_conf')), L.ptr(t('center')), L.ptr(t('act')),
-                                      L.ptr(t('prop_act')), L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score),
-                                      L.ptr(unct), L.ptr(actn), L.ptr(flag), n, A, K, ctypes.c_float(clip_length),
-                                      ctypes.c_float(conf_thresh), L.stream()), "otal_decode_clips")
-    return dict(seg=seg, score=score, unct=unct, actn=actn, flag=flag)
-
-
-def _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, use_edl):
-    """The closed-set head: otal_decode_clips_ex with softmax (score_fn 1) or Dirichlet (0) scores, class 0 dropped and
-    no actionness (test.py:112-162 with os_head False)."""
-    n, A, _ = loc.shape
-    K = output_dict['conf'].shape[-1]
-    dev = loc.device
-    offs = torch.as_tensor(offsets, dtype=torch.float32, device=dev).contiguous()
-    fpst = torch.as_tensor(fps, dtype=torch.float32, device=dev).contiguous()
-    if fpst.numel() == 1:
-        fpst = fpst.expand(n).contiguous()
-    seg = torch.empty((n, A, 2), device=dev)
-    score = torch.empty((n, K - 1, A), device=dev)
-    unct = torch.empty((n, A), device=dev) if use_edl else None
-    flag = torch.empty((n, K - 1, A), dtype=torch.uint8, device=dev)
-    t = lambda k: output_dict[k].contiguous()
-    L.check(L.lib().otal_decode_clips_ex(L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(output_dict['priors'].contiguous()),
-                                         L.ptr(t('conf')), L.ptr(t('prop_conf')), L.ptr(t('center')), None, None,
-                                         L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score),
-                                         None if unct is None else L.ptr(unct), None, L.ptr(flag), n, A, K,
-                                         ctypes.c_float(clip_length), ctypes.c_float(conf_thresh), 0 if use_edl else 1, 1,
-                                         L.stream()), "otal_decode_clips_ex")
-    return dict(seg=seg, score=score, unct=unct, actn=None, flag=flag)
-
-
-def decode_predictions(output_dict, idx, offset, sample_fps, clip_length=256, os_head=True, use_edl=True, evidence='exp',
-                       use_gcpl=False):
-    """Single-clip view with the reference's return values (test.py:112-140):
-    decoded_segments (A,2), conf_scores (K,A), uncertainty (A,) or None, actionness (A,) or None.
-    Closed-set heads: conf_scores holds the K - 1 non-background classes (row c = reference row c + 1)."""
-    one = {k: (v[idx:idx + 1] if (v is not None and k != 'priors') else v) for k, v in output_dict.items()}
-    d = decode_clips(one, [float(offset)], [float(sample_fps)], clip_length, os_head=os_head, use_edl=use_edl,
-                     evidence=evidence, use_gcpl=use_gcpl)
-    first = lambda v: None if v is None else v[0]
-    return d['seg'][0], d['score'][0], first(d['unct']), first(d['actn'])
-
-
-def filtering(decoded_segments, conf_score_cls, uncertainty, actionness, conf_thresh, use_edl=True, os_head=True):
-    """test.py:143-162 for one class: (n, 3 + use_edl + os_head) rows [start,end,score(,unct)(,act)] or None."""
-    m = conf_score_cls > conf_thresh
-    if os_head:
-        m = m & (actionness > 0.5)
-    if int(m.sum()) == 0:
-        return None
-    cols = [decoded_segments[m], conf_score_cls[m, None]]
-    if use_edl:
-        cols.append(uncertainty[m, None])
-    if os_head:
-        cols.append(actionness[m, None])
-    return torch.cat(cols, -1)
-
-
-def softnms_classes(dec, clip_start, top_k=5000, sigma=0.5, score_threshold=0.001):
-    """All (video, class) Soft-NMS problems in one launch.  clip_start: per-video clip ranges (V+1).
-    Returns rows (V,K,top_k,cols), counts (V,K), index (V,K,top_k); cols = 3 + use_edl + os_head, i.e. 5 for the OpenTAL
-    head ([start,end,score,unct,act]), 4 for the closed-set EDL and 3 for the Softmax baseline."""
-    cols = 3 + (dec.get('unct') is not None) + (dec.get('actn') is not None)
-    if dec.get('actn') is not None and dec.get('unct') is None:
-        raise NotImplementedError("actionness rows without uncertainty")
-    n, K, A = dec['score'].shape
-    dev = dec['score'].device
-    cs = torch.as_tensor(clip_start, dtype=torch.int32, device=dev).contiguous()
-    V = cs.numel() - 1
-    starts = [int(v) for v in clip_start]
-    max_clips = max(b - a for a, b in zip(starts[:-1], starts[1:]))
-    tk = min(int(top_k), max_clips * A)
-    out = torch.zeros((V, K, tk, cols), device=dev)
-    counts = torch.zeros((V, K), dtype=torch.int32, device=dev)
-    index = torch.zeros((V, K, tk), dtype=torch.int32, device=dev)
-    lib = L.lib()
-    lib.otal_softnms_scratch_bytes.restype = ctypes.c_size_t
-    nbytes = int(lib.otal_softnms_scratch_bytes(int(n), int(max_clips), int(A), int(K)))   # > 0: a video exceeds the LDS working set
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    opt = lambda v: None if v is None else L.ptr(v)
-    L.check(lib.otal_softnms_classes_ws(L.ptr(dec['seg']), L.ptr(dec['score']), opt(dec.get('unct')),
-                                        opt(dec.get('actn')), L.ptr(dec['flag']), L.ptr(cs), V, max_clips, A, K,
-                                        ctypes.c_float(sigma), tk, ctypes.c_float(score_threshold), L.ptr(out),
-                                        L.ptr(counts), L.ptr(index), cols, L.ptr(scratch), ctypes.c_size_t(nbytes), int(n),
-                                        L.stream()), "otal_softnms_classes_ws")
-    return out, counts, index
-
-
-def get_video_detections(rows, counts, idx_to_class=None, top_k=5000, duration=None, drop_empty=False):
-    """test.py:165-200: per-video proposal list from the suppressed rows of one video (K,top_k,cols).  Rows of 3 or 4
-    columns (closed-set heads) give 'uncertainty' / 'actionness' 0.0 where the column is absent (test.py:197-198).
-    With `duration` (seconds) the cross-dataset variant, test_cross_data.py:178-215: segments are clipped to
-    [0, duration] and the ones left empty are dropped (`drop_empty` alone: that script's THUMOS14 leg, which passes
-    no duration but still drops empty segments)."""
-    rows, counts = rows.cpu().numpy(), counts.cpu().numpy()
-    proposal_list = []
-    for cl in range(rows.shape[0]):
-        name = idx_to_class[cl + 1] if idx_to_class is not None else cl + 1
-        for i in range(int(counts[cl])):
-            r = rows[cl, i]
-            if r[2] > 0:
-                start, end = float(r[0]), float(r[1])
-                if duration is not None or drop_empty:
-                    start, end = max(0, start), (min(duration, end) if duration is not None else end)
-                    if end <= start:
-                        continue
-                proposal_list.append({'label': name, 'score': float(r[2]), 'segment': [start, end],
-                                      'uncertainty': float(r[3]) if len(r) > 3 else 0.0,
-                                      'actionness': float(r[4]) if len(r) > 4 else 0.0})
-    return proposal_list
-
-
-@torch.no_grad()
 def detect_batch(net, videos, sample_fps, clip_length=256, stride=128, conf_thresh=0.01, top_k=5000, nms_sigma=0.5,
                  batch_clips=32, flow_net=None, flow_videos=None):
     """videos: list of uint8 (C,T,96,96) device tensors (already centre-cropped).  Returns the
@@ -247,87 +45,19 @@ def detect_batch(net, videos, sample_fps, clip_length=256, stride=128, conf_thre
     if flow_net is not None and head_mode(flow_net) != (os_head, use_edl, evidence):
         raise RuntimeError(f"detect_batch: the rgb and flow networks have different heads "
                            f"({(os_head, use_edl, evidence)} vs {head_mode(flow_net)})")
-    clips, offsets, fps, clip_start = [], [], [], [0]
-    for v, data in enumerate(videos):
-        offs = get_offsets(data.shape[1], clip_length, stride)
-        for o in offs:
-            clips.append((v, o))
-        offsets += [float(o) for o in offs]
-        fps += [float(sample_fps[v] if hasattr(sample_fps, '__len__') else sample_fps)] * len(offs)
-        clip_start.append(clip_start[-1] + len(offs))
-    outs = []
-    # 32 windows per forward pass: past that the first feature maps leave the 32-bit buffer offsets of the vector-gather
-    # kernels (64 windows: Conv3d_1a's output is 4.8 GB) and the generic kernels take over at half the speed
-    batch_clips = max(1, min(int(batch_clips), 32))
-    for i in range(0, len(clips), batch_clips):
-        out = net(prepare_windows(videos, clips[i:i + batch_clips], clip_length))
-        if flow_net is not None:
-            out = fuse_outputs(out, flow_net(prepare_windows(flow_videos, clips[i:i + batch_clips], clip_length)))
-        outs.append(out)
     keys = ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'priors') + (('act', 'prop_act') if os_head else ()) + \
         (('unct', 'prop_unct') if flow_net is not None and use_edl else ())
-    merged = {k: (torch.cat([o[k] for o in outs], 0) if k != 'priors' else outs[0][k]) for k in keys}
-    dec = decode_clips(merged, offsets, fps, clip_length, conf_thresh, os_head=os_head, use_edl=use_edl, evidence=evidence,
-                       use_gcpl=bool(getattr(net, 'use_gcpl', False)))
-    if flow_net is not None and use_edl:
-        # the decode kernel derives the uncertainty from the (fused) logits; the reference averages the two networks'
-        # OWN uncertainties instead (parse_output :105-108, decode_predictions :122) -- not the same number
-        dec['unct'] = ((merged['unct'] + merged['prop_unct']) / 2.0).contiguous()
-    return softnms_classes(dec, clip_start, top_k, nms_sigma) + (dec,)
 
-
-# ----------------------------------------------------------------------------- result files (test.py:246-252, threshold.py:128-150)
-OOD_SCORES = {
-    'uncertainty': lambda p: p['uncertainty'],
-    'confidence': lambda p: 1 - p['score'],
-    'uncertainty_actionness': lambda p: p['uncertainty'] * p['actionness'],
-    'a_by_inv_u': lambda p: p['actionness'] / (1 - p['uncertainty'] + 1e-6),
-    'u_by_inv_a': lambda p: p['uncertainty'] / (1 - p['actionness'] + 1e-6),
-    'half_au': lambda p: 0.5 * (p['actionness'] + 1) * p['uncertainty'],
-}
-
-
-def results_json(result_dict, threshold=None, version="THUMOS14"):
-    """The result-file layout AFSD/evaluation reads: {'version', 'results': {video: [proposal, ...]}, 'external_data'}."""
-    ext = {} if threshold is None else {'threshold': float(threshold)}
-    return {"version": version, "results": dict(result_dict), "external_data": ext}
-
-
-def ood_threshold(result_dict, scoring='uncertainty'):
-    """The known/unknown operating point of AFSD/thumos14/threshold.py:128-150: run the detector over the TRAINING
-    videos, turn every detection into a known-ness score (1 - its OOD score) and take the value that 95 % of the
-    detections exceed."""
-    import numpy as np
-    score = OOD_SCORES[scoring]
-    all_scores = [1 - score(p) for props in result_dict.values() for p in props]
-    n = len(all_scores)
-    if n == 0:
-        raise ValueError("no detections to threshold")
-    return float(np.sort(all_scores)[n - int(n * 0.95) - 1])
-
-
-# ----------------------------------------------------------------------------- the inference driver (test.py:203-288)
-def prepare_data(data_path, video_name, crop_size, device='cuda'):
-    """test.py:59-64: <video>.npy uint8 (T,H,W,3) -> centre-cropped planar (3,T,crop,crop) uint8 on the device."""
-    import os
-    import numpy as np
-    data = np.load(os.path.join(data_path, video_name + '.npy'))
-    data = np.transpose(data, [3, 0, 1, 2])
-    h, w = data.shape[2:]
-    i, j = int(np.round((h - crop_size) / 2.)), int(np.round((w - crop_size) / 2.))
-    return torch.from_numpy(np.ascontiguousarray(data[:, :, i:i + crop_size, j:j + crop_size])).to(device)
-
-
-def fuse_outputs(rgb_out, flow_out):
-    """Two-stream fusion by averaging the two networks' RAW outputs before decoding (parse_output, test.py:90-108): loc,
-    conf, prop_loc, prop_conf, center, the actionness logits and -- with use_edl -- the two uncertainty maps.
-    Reference hazard (H11): with os_head its parse_output squeezes the rgb actionness to (126,) but not the flow one
-    ((126,1)), so `act + flow_act` broadcasts to (126,126) and decode_predictions fails on the OpenTAL configuration; the
-    elementwise average it evidently means is what is computed here."""
-    keys = ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'act', 'prop_act', 'unct', 'prop_unct')
-    fused = {k: (rgb_out[k] + flow_out[k]) / 2.0 for k in keys if rgb_out.get(k) is not None and flow_out.get(k) is not None}
-    fused['priors'] = rgb_out['priors']
-    return fused
+    def decode(merged, offsets, fps):
+        dec = decode_clips(merged, offsets, fps, clip_length, conf_thresh, os_head=os_head, use_edl=use_edl,
+                           evidence=evidence, use_gcpl=bool(getattr(net, 'use_gcpl', False)))
+        if flow_net is not None and use_edl:
+            # the decode kernel derives the uncertainty from the (fused) logits; the reference averages the two networks'
+            # OWN uncertainties instead (parse_output :105-108, decode_predictions :122) -- not the same number
+            dec['unct'] = ((merged['unct'] + merged['prop_unct']) / 2.0).contiguous()
+        return dec
+    return detect(net, videos, sample_fps, decode, keys, clip_length, stride, top_k, nms_sigma, batch_clips, flow_net,
+                  flow_videos)
 
 
 def test(net, video_infos, npy_data_path, idx_to_class=None, clip_length=256, stride=128, crop_size=96, conf_thresh=0.01,
@@ -349,79 +79,35 @@ def test(net, video_infos, npy_data_path, idx_to_class=None, clip_length=256, st
     return result_dict
 
 
-def gather_results(result_dict, names, rank, world, device=None):
-    """Several ranks (video list sharded): every rank's result dict travels to rank 0, which returns the merged
-    dict in the video list's order (the pattern sketched in AFSD/anet/test.py:248-273, with a collective instead of
-    multiprocessing queues); the other ranks return None.  One rank: the dict itself."""
-    if world == 1:
-        return result_dict
-    import torch.distributed as dist
-    if not dist.is_initialized():
-        import os
-        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
-        os.environ.setdefault('MASTER_PORT', '29534')
-        if device is not None and torch.device(device).type == 'cuda':
-            dist.init_process_group(backend='nccl', rank=rank, world_size=world, device_id=torch.device(device))
-        else:
-            dist.init_process_group(backend='gloo', rank=rank, world_size=world)
-    parts = [None] * world if rank == 0 else None
-    dist.gather_object(result_dict, parts, dst=0)
-    if rank != 0:
-        return None
-    merged = {}
-    for part in parts:
-        merged.update(part)
-    return {n: merged[n] for n in names if n in merged}
-
-
 def main(argv=None):
     """python -m opental_amd.thumos14.test <yaml> --open_set --split 0 [--random_init] [--evaluate GT.json KNOWN.txt]
 
     The reference's test driver (AFSD/thumos14/test.py:203-288): config -> model + checkpoint -> sliding windows over
     every test video -> result JSON at <output_path>/<output_json>; `--evaluate` then runs the open-set evaluation of
     opental_amd.thumos14.eval_open on it."""
-    import json
     import os
     import sys
     from ..common import config as C
-    from ..common import ops
+    from ..common.driver import device_setup, load_net, split_flags, write_json
     from ..common.thumos_dataset import get_class_index_map, get_video_info
     from .BDNet import BDNet, model_cfg_from
-    argv = list(sys.argv[1:] if argv is None else argv)
-    random_init, evaluate, rest, i = False, None, [], 0
-    while i < len(argv):
-        if argv[i] == '--random_init':
-            random_init = True
-        elif argv[i] == '--evaluate':
-            evaluate = (argv[i + 1], argv[i + 2]); i += 2
-        else:
-            rest.append(argv[i])
-        i += 1
+    own, rest = split_flags(list(sys.argv[1:] if argv is None else argv), ('--random_init',), {'--evaluate': (2, None)})
+    random_init, evaluate = own['--random_init'], own['--evaluate']
     config = C.set_config(C.get_config(rest))
     te, md, ds = config['testing'], config['model'], config['dataset']['testing']
-    rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
-    dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
-    torch.cuda.set_device(dev)
-    ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
+    rank, world, dev = device_setup()
     flow_net, data_path, flow_path = None, ds['video_data_path'], None
     use_rpl, use_gcpl = rpl_flags(config)
+    kw = dict(use_edl=md.get('use_edl', False), use_rpl=use_rpl, cfg=model_cfg_from(config))
     if te.get('fusion', False):             # build_model(fusion=True), test.py:24-40: rgb + flow networks, their own checkpoints
-        net = BDNet(in_channels=3, training=False, use_edl=md.get('use_edl', False), use_rpl=use_rpl,
-                    cfg=model_cfg_from(config))
-        flow_net = BDNet(in_channels=2, training=False, use_edl=md.get('use_edl', False), use_rpl=use_rpl,
-                    cfg=model_cfg_from(config))
-        if not random_init:
-            net.load_state_dict(torch.load(te.get('rgb_checkpoint_path', './models/thumos14/checkpoint-15.ckpt'), map_location='cpu'))
-            flow_net.load_state_dict(torch.load(te.get('flow_checkpoint_path', './models/thumos14_flow/checkpoint-16.ckpt'), map_location='cpu'))
-        flow_net = flow_net.to(dev).eval()
+        net = load_net(BDNet, dev, random_init, te.get('rgb_checkpoint_path', './models/thumos14/checkpoint-15.ckpt'),
+                       in_channels=3, **kw)
+        flow_net = load_net(BDNet, dev, random_init, te.get('flow_checkpoint_path', './models/thumos14_flow/checkpoint-16.ckpt'),
+                            in_channels=2, **kw)
         data_path = te.get('rgb_data_path', './datasets/thumos14/test_npy/')
         flow_path = te.get('flow_data_path', './datasets/thumos14/test_flow_npy/')
     else:
-        net = BDNet(in_channels=md['in_channels'], training=False, use_edl=md.get('use_edl', False), use_rpl=use_rpl,
-                    cfg=model_cfg_from(config))
-        if not random_init:
-            net.load_state_dict(torch.load(te['checkpoint_path'], map_location='cpu'))
-    net = net.to(dev).eval()
+        net = load_net(BDNet, dev, random_init, te['checkpoint_path'], in_channels=md['in_channels'], **kw)
     net.use_gcpl = use_gcpl                 # GCPL: scores are the softmax of the negated distances (detect_batch)
     video_infos = get_video_info(config['dataset']['testing']['video_info_path'])
     _, idx_to_class = get_class_index_map(config['dataset']['class_info_path'])
@@ -431,10 +117,8 @@ def main(argv=None):
     results = gather_results(results, list(video_infos.keys()), rank, world, dev)
     if results is None:
         return None, None           # ranks > 0: their detections went to rank 0
-    os.makedirs(te['output_path'], exist_ok=True)
     out_file = os.path.join(te['output_path'], te['output_json'])
-    with open(out_file, 'w') as f:
-        json.dump(results_json(results), f)
+    write_json(out_file, results_json(results))
     print(f"{len(results)} videos, {sum(len(v) for v in results.values())} detections -> {out_file}")
     if evaluate is not None:
         from .eval_open import evaluate_split

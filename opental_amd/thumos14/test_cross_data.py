@@ -11,6 +11,7 @@ prefix, and videos annotated with a class THUMOS14 also has are left out before 
 """
 import torch
 
+from ..common.detect import gather_results, get_video_detections, prepare_data, results_json
 from . import test as T
 
 
@@ -36,9 +37,9 @@ def test_anet(net, videos, video_infos, idx_to_class=None, clip_length=256, stri
         rows, counts, _, _ = T.detect_batch(net, [videos[n] for n in part], [float(video_infos[n]['fps']) for n in part],
                                             clip_length, stride, conf_thresh, top_k, nms_sigma, batch_clips)
         for v, n in enumerate(part):
-            result_dict[n[2:]] = T.get_video_detections(rows[v], counts[v], idx_to_class, top_k,
-                                                        duration=video_infos[n]['duration'])
-    return T.results_json(result_dict)
+            result_dict[n[2:]] = get_video_detections(rows[v], counts[v], idx_to_class, top_k,
+                                                      duration=video_infos[n]['duration'])
+    return results_json(result_dict)
 
 
 def exclude_overlapping(anet_out, video_infos, excluded_classes):
@@ -49,7 +50,7 @@ def exclude_overlapping(anet_out, video_infos, excluded_classes):
     for name, preds in anet_out['results'].items():
         if not any(ann['label'] in excluded for ann in video_infos['v_' + name]['annotations']):
             kept[name] = preds
-    return T.results_json(kept)
+    return results_json(kept)
 
 
 def merge_results(thumos_out, anet_out):
@@ -57,15 +58,10 @@ def merge_results(thumos_out, anet_out):
     (test_cross_data.py:433-441; an ActivityNet key equal to a THUMOS one replaces it, as dict.update does)."""
     merged = dict(thumos_out['results'])
     merged.update(anet_out['results'])
-    return T.results_json(merged)
+    return results_json(merged)
 
 
 # ----------------------------------------------------------------------------- the driver (test_cross_data.py:219-262, :336-447)
-def load_anet_video(npy_path, name, crop_size=96, device='cuda'):
-    """<npy dir>/<name>.npy uint8 (T,H,W,3) -> centre-cropped planar (3,T,crop,crop) uint8 on the device (:244-250)."""
-    return T.prepare_data(npy_path, name, crop_size, device)
-
-
 def get_anet_video_info(video_info_path, subset='validation'):
     """test_cross_data.py:381-391: the ActivityNet video_info_train_val.json rows of one subset."""
     import json
@@ -89,40 +85,24 @@ def main(argv=None):
     import os
     import sys
     from ..common import config as C
-    from ..common import ops
+    from ..common.driver import device_setup, load_net, split_flags, write_json
     from ..common.thumos_dataset import get_class_index_map, get_video_info
     from .BDNet import BDNet, model_cfg_from
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = {'--anet_info': 'datasets/activitynet/annotations/video_info_train_val.json',
-            '--anet_npy': 'datasets/activitynet/train_val_npy_112',
-            '--anet_overlap': 'datasets/activitynet/overlapping_classes_in_thumos.txt'}
-    random_init, rest, i = False, [], 0
-    while i < len(argv):
-        if argv[i] == '--random_init':
-            random_init = True
-        elif argv[i] in opts:
-            opts[argv[i]] = argv[i + 1]; i += 1
-        else:
-            rest.append(argv[i])
-        i += 1
+    own, rest = split_flags(list(sys.argv[1:] if argv is None else argv), ('--random_init',), {
+        '--anet_info': (1, 'datasets/activitynet/annotations/video_info_train_val.json'),
+        '--anet_npy': (1, 'datasets/activitynet/train_val_npy_112'),
+        '--anet_overlap': (1, 'datasets/activitynet/overlapping_classes_in_thumos.txt')})
     config = C.set_config(C.get_config(rest))
     te, md, ds = config['testing'], config['model'], config['dataset']
-    rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
-    dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
-    torch.cuda.set_device(dev)
-    ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
-    net = BDNet(in_channels=md['in_channels'], training=False, use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
-    if not random_init:
-        net.load_state_dict(torch.load(te['checkpoint_path'], map_location='cpu'))
-    net = net.to(dev).eval()
+    rank, world, dev = device_setup()
+    net = load_net(BDNet, dev, own['--random_init'], te['checkpoint_path'], in_channels=md['in_channels'],
+                   use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
     _, idx_to_class = get_class_index_map(ds['class_info_path'])
     t = ds['testing']
-    os.makedirs(te['output_path'], exist_ok=True)
 
     def cached(path, run, expected):
         """A result file of an earlier run is re-used only when it parses AND holds exactly the videos this run would
-        produce (a killed run leaves truncated or partial files; anet/test.py checks its file the same way); new files are
-        written next to their place and moved in (os.replace is atomic)."""
+        produce (a killed run leaves truncated or partial files; anet/test.py checks its file the same way)."""
         if os.path.exists(path):
             try:
                 with open(path) as f:
@@ -134,21 +114,18 @@ def main(argv=None):
                 print(f"{path}: unreadable -- recomputed")
         out = run()
         if out is not None:
-            tmp = path + '.tmp'
-            with open(tmp, 'w') as f:
-                json.dump(out, f)
-            os.replace(tmp, path)
+            write_json(path, out)
         return out
 
     def run_thumos():
         infos = get_video_info(t['video_info_path'])
         res = T.test(net, infos, t['video_data_path'], idx_to_class, t['clip_length'], t['clip_stride'], t['crop_size'],
                      te['conf_thresh'], te['top_k'], te['nms_sigma'], rank=rank, world=world, device=dev)
-        res = T.gather_results(res, list(infos.keys()), rank, world, dev)
-        return None if res is None else T.results_json(res)
+        res = gather_results(res, list(infos.keys()), rank, world, dev)
+        return None if res is None else results_json(res)
 
-    anet_infos = get_anet_video_info(opts['--anet_info'], 'validation')
-    on_disk = {f[:-4] for f in os.listdir(opts['--anet_npy']) if f.endswith('.npy')}
+    anet_infos = get_anet_video_info(own['--anet_info'], 'validation')
+    on_disk = {f[:-4] for f in os.listdir(own['--anet_npy']) if f.endswith('.npy')}
     anet_names = [n for n in anet_infos if n in on_disk]
 
     def run_anet():
@@ -156,12 +133,12 @@ def main(argv=None):
         res = {}
         for j in range(0, len(mine), 8):            # eight videos' windows per forward batch, loaded as they are needed
             part = mine[j:j + 8]
-            vids = {n: load_anet_video(opts['--anet_npy'], n, t['crop_size'], dev) for n in part}
+            vids = {n: prepare_data(own['--anet_npy'], n, t['crop_size'], dev) for n in part}
             out = test_anet(net, vids, {n: anet_infos[n] for n in part}, idx_to_class, t['clip_length'], t['clip_stride'],
                             te['conf_thresh'], te['top_k'], te['nms_sigma'])
             res.update(out['results'])
-        res = T.gather_results(res, [n[2:] for n in anet_names], rank, world, dev)
-        return None if res is None else T.results_json(res)
+        res = gather_results(res, [n[2:] for n in anet_names], rank, world, dev)
+        return None if res is None else results_json(res)
 
     thumos_out = cached(os.path.join(te['output_path'], 'thumos14_open_rgb.json'), run_thumos,
                         list(get_video_info(t['video_info_path']).keys()))
@@ -169,13 +146,12 @@ def main(argv=None):
     if thumos_out is None or anet_out is None:
         return None                                  # ranks > 0
     print(f"Number of thumos videos: {len(thumos_out['results'])}; anet videos (before filtering): {len(anet_out['results'])}")
-    with open(opts['--anet_overlap']) as f:
+    with open(own['--anet_overlap']) as f:
         anet_out = exclude_overlapping(anet_out, anet_infos, f.readlines())
     print(f"Number of anet videos (after filtering): {len(anet_out['results'])}")
     merged = merge_results(thumos_out, anet_out)
     out_file = os.path.join(te['output_path'], te['output_json'])
-    with open(out_file, 'w') as f:
-        json.dump(merged, f)
+    write_json(out_file, merged)
     print(f"Number of all merged videos: {len(merged['results'])} -> {out_file}")
     return out_file
 

@@ -6,7 +6,8 @@ OpenMax runs on the checkpoint of the closed-set Softmax baseline (configs/thumo
 thumos14_softmax.yaml only in paths): no training.  The statistics pass sends every training clip through the eval-mode
 network with get_feat=True, collects the 512-d tower features of the positive anchors per class and stage, and writes per
 class <output_path>/mav_dist/<class name>.npz with the reference's keys (mav, dist, mav_prop, dist_prop), so the files are
-interchangeable with the reference's.  Inference is detect_batch_openmax: the network, ONE OpenMax decode launch
+interchangeable with the reference's.  Inference is detect_batch_openmax (common/detect.py's pipeline with the OpenMax
+decode): the network, ONE OpenMax decode launch
 (otal_decode_clips_openmax: both stages' recalibration, the average, the centre factor, segments and threshold flags) and ONE
 Soft-NMS launch, with no host synchronisation before the final copy.  The reference instead loops on the host over every
 anchor and class (openmax.py:76-86), twice per clip.
@@ -21,7 +22,8 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from . import test as T
+from ..common.detect import clip_scalars, detect, get_video_detections, head_mode, prepare_data, prepare_windows, results_json, \
+    windows_per_pass
 from .openmax import OpenMax, class_means, compute_eucos_dist, weibull_fit_high
 
 
@@ -71,7 +73,7 @@ def get_matched_targets(targets, loc_data, priors, clip_length, tiou_thresh=0.5)
 def _train_video(data_path, name, crop_size, clip_length, device):
     """prepare_train_data (test_openmax.py:66-79): the centre-cropped planar uint8 video; one shorter than a clip is padded
     with ZERO frames before normalisation (they become -1.0, unlike the test path's padding with 0.0)."""
-    data = T.prepare_data(data_path, name, crop_size, device)
+    data = prepare_data(data_path, name, crop_size, device)
     if data.shape[1] < clip_length:
         pad = torch.zeros((data.shape[0], clip_length - data.shape[1]) + tuple(data.shape[2:]), dtype=torch.uint8, device=device)
         data = torch.cat([data, pad], 1).contiguous()
@@ -84,7 +86,7 @@ def collect_features(net, samples, video_infos, data_path, clip_length, crop_siz
     and 0-based class indices of the positive anchors of both stages -> (feat (N, D), labels (N,), prop_feat, prop_labels)."""
     from ..common.thumos_dataset import annos_transform
     feats, labels, pfeats, plabels = [], [], [], []
-    batch_clips = max(1, min(int(batch_clips), 32))
+    batch_clips = windows_per_pass(batch_clips)
     order = sorted(range(len(samples)), key=lambda i: samples[i]['video_name'])       # one video on the device at a time
     cache = {}
     for i in range(0, len(order), batch_clips):
@@ -92,7 +94,7 @@ def collect_features(net, samples, video_infos, data_path, clip_length, crop_siz
         names = sorted({s['video_name'] for s in part})
         cache = {n: cache[n] if n in cache else _train_video(data_path, n, crop_size, clip_length, device) for n in names}
         vids = [cache[n] for n in names]
-        out = net(T.prepare_windows(vids, [(names.index(s['video_name']), int(s['offset'])) for s in part], clip_length),
+        out = net(prepare_windows(vids, [(names.index(s['video_name']), int(s['offset'])) for s in part], clip_length),
                   get_feat=True)
         targets = [torch.tensor(annos_transform(s['annos'], clip_length), dtype=torch.float32).reshape(-1, 3) for s in part]
         _, conf_t, _, prop_conf_t = get_matched_targets(targets, out['loc'], out['priors'], clip_length, tiou_thresh)
@@ -177,10 +179,7 @@ def decode_clips_openmax(output_dict, offsets, fps, openmax_layer, openmax_prop_
     if openmax_layer.rank != openmax_prop_layer.rank:
         raise RuntimeError("the two OpenMax layers must use the same rank")
     dev = loc.device
-    offs = torch.as_tensor(offsets, dtype=torch.float32, device=dev).contiguous()
-    fpst = torch.as_tensor(fps, dtype=torch.float32, device=dev).contiguous()
-    if fpst.numel() == 1:
-        fpst = fpst.expand(n).contiguous()
+    offs, fpst = clip_scalars(offsets, fps, n, dev)
     feat, prop_feat = output_dict['conf_feat'], output_dict['prop_conf_feat'] if refined_feature else None
     D = feat.shape[-1]
     strides = lambda t: (ctypes.c_int64 * 3)(*[int(s) for s in t.stride()])
@@ -203,29 +202,17 @@ def decode_clips_openmax(output_dict, offsets, fps, openmax_layer, openmax_prop_
     return dict(seg=seg, score=score, unct=None, actn=None, flag=flag, unknown=unknown)
 
 
-@torch.no_grad()
 def detect_batch_openmax(net, videos, sample_fps, openmax_layer, openmax_prop_layer, clip_length=256, stride=128,
                          conf_thresh=0.01, top_k=5000, nms_sigma=0.5, batch_clips=32, refined_feature=False):
     """detect_batch (thumos14/test.py) for the OpenMax baseline: every sliding window of `videos` through the network with
-    get_feat=True, then the OpenMax decode launch and the Soft-NMS launch; nothing synchronises with the host before the
-    caller copies the rows.  Returns (rows, counts, index, dec)."""
-    if T.head_mode(net)[0]:
+    get_feat=True, then the OpenMax decode launch and the Soft-NMS launch (common/detect.py's `detect`); nothing synchronises
+    with the host before the caller copies the rows.  Returns (rows, counts, index, dec)."""
+    if head_mode(net)[0]:
         raise NotImplementedError("OpenMax runs on the closed-set Softmax network (os_head false)")
-    clips, offsets, fps, clip_start = [], [], [], [0]
-    for v, data in enumerate(videos):
-        offs = T.get_offsets(data.shape[1], clip_length, stride)
-        clips += [(v, o) for o in offs]
-        offsets += [float(o) for o in offs]
-        fps += [float(sample_fps[v] if hasattr(sample_fps, '__len__') else sample_fps)] * len(offs)
-        clip_start.append(clip_start[-1] + len(offs))
-    batch_clips = max(1, min(int(batch_clips), 32))
-    outs = [net(T.prepare_windows(videos, clips[i:i + batch_clips], clip_length), get_feat=True)
-            for i in range(0, len(clips), batch_clips)]
-    keys = ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'conf_feat', 'prop_conf_feat')
-    merged = {k: (torch.cat([o[k] for o in outs], 0) if len(outs) > 1 else outs[0][k]) for k in keys}
-    merged['priors'] = outs[0]['priors']
-    dec = decode_clips_openmax(merged, offsets, fps, openmax_layer, openmax_prop_layer, clip_length, conf_thresh, refined_feature)
-    return T.softnms_classes(dec, clip_start, top_k, nms_sigma) + (dec,)
+    keys = ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'conf_feat', 'prop_conf_feat', 'priors')
+    decode = lambda merged, offsets, fps: decode_clips_openmax(merged, offsets, fps, openmax_layer, openmax_prop_layer,
+                                                               clip_length, conf_thresh, refined_feature)
+    return detect(net, videos, sample_fps, decode, keys, clip_length, stride, top_k, nms_sigma, batch_clips, get_feat=True)
 
 
 def test(net, video_infos, npy_data_path, openmax_layer, openmax_prop_layer, idx_to_class=None, clip_length=256, stride=128,
@@ -236,12 +223,12 @@ def test(net, video_infos, npy_data_path, openmax_layer, openmax_prop_layer, idx
     result_dict = {}
     for i in range(0, len(names), batch_videos):
         part = names[i:i + batch_videos]
-        vids = [T.prepare_data(npy_data_path, n, crop_size, device) for n in part]
+        vids = [prepare_data(npy_data_path, n, crop_size, device) for n in part]
         rows, counts, _, _ = detect_batch_openmax(net, vids, [float(video_infos[n]['sample_fps']) for n in part], openmax_layer,
                                                   openmax_prop_layer, clip_length, stride, conf_thresh, top_k, nms_sigma,
                                                   batch_clips, refined_feature)
         for v, n in enumerate(part):
-            result_dict[n] = T.get_video_detections(rows[v], counts[v], idx_to_class, top_k)
+            result_dict[n] = get_video_detections(rows[v], counts[v], idx_to_class, top_k)
     return result_dict
 
 
@@ -253,33 +240,20 @@ def main(argv=None):
     two OpenMax layers (rank 1) -> sliding windows over every test video -> result JSON at <output_path>/<output_json>
     ('uncertainty' and 'actionness' 0.0, as for the Softmax baseline); `--evaluate` then runs the open-set evaluation with
     `ood_scoring: confidence`."""
-    import json
     import sys
     from ..common import config as C
-    from ..common import ops
+    from ..common.driver import device_setup, load_net, split_flags, write_json
     from ..common.thumos_dataset import get_class_index_map, get_video_anno, get_video_info
     from .BDNet import BDNet, model_cfg_from
-    argv = list(sys.argv[1:] if argv is None else argv)
-    random_init, evaluate, rest, i = False, None, [], 0
-    while i < len(argv):
-        if argv[i] == '--random_init':
-            random_init = True
-        elif argv[i] == '--evaluate':
-            evaluate = (argv[i + 1], argv[i + 2]); i += 2
-        else:
-            rest.append(argv[i])
-        i += 1
+    own, rest = split_flags(list(sys.argv[1:] if argv is None else argv), ('--random_init',), {'--evaluate': (2, None)})
+    evaluate = own['--evaluate']
     config = C.set_config(C.get_config(rest))
     te, md, ds, dtr = config['testing'], config['model'], config['dataset']['testing'], config['dataset']['training']
-    dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
-    torch.cuda.set_device(dev)
-    ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
-    net = BDNet(in_channels=md['in_channels'], training=False, use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
-    if T.head_mode(net)[0] or T.head_mode(net)[1]:
+    _, _, dev = device_setup()
+    net = load_net(BDNet, dev, own['--random_init'], te['checkpoint_path'], in_channels=md['in_channels'],
+                   use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
+    if head_mode(net)[0] or head_mode(net)[1]:
         raise NotImplementedError("OpenMax runs on the closed-set Softmax network (model.os_head and model.use_edl false)")
-    if not random_init:
-        net.load_state_dict(torch.load(te['checkpoint_path'], map_location='cpu'))
-    net = net.to(dev).eval()
     _, idx_to_class = get_class_index_map(config['dataset']['class_info_path'])
     mav_dist_dir = os.path.join(te['output_path'], 'mav_dist')
     if not files_are_ready(mav_dist_dir, idx_to_class):
@@ -292,10 +266,8 @@ def main(argv=None):
     results = test(net, video_infos, ds['video_data_path'], OpenMax(weibull_model), OpenMax(weibull_prop_model), idx_to_class,
                    ds['clip_length'], ds['clip_stride'], ds['crop_size'], te['conf_thresh'], te['top_k'], te['nms_sigma'],
                    device=dev)
-    os.makedirs(te['output_path'], exist_ok=True)
     out_file = os.path.join(te['output_path'], te['output_json'])
-    with open(out_file, 'w') as f:
-        json.dump(T.results_json(results), f)
+    write_json(out_file, results_json(results))
     print(f"{len(results)} videos, {sum(len(v) for v in results.values())} detections -> {out_file}")
     if evaluate is not None:
         from .eval_open import evaluate_split

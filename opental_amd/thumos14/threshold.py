@@ -11,8 +11,8 @@ import json
 import os
 import sys
 
-import torch
-
+from ..common.detect import gather_results, ood_threshold, results_json
+from ..common.driver import device_setup, load_net, split_flags, write_json
 from . import test as T
 
 
@@ -22,24 +22,19 @@ def thresholding(net, video_infos, npy_data_path, output_file, idx_to_class=None
     """threshold.py:71-150.  Returns the threshold on rank 0 (None on the other ranks)."""
     results = T.test(net, video_infos, npy_data_path, idx_to_class, clip_length, stride, crop_size, conf_thresh, top_k, nms_sigma,
                      rank=rank, world=world, device=device, flow_net=flow_net, flow_data_path=flow_data_path)
-    results = T.gather_results(results, list(video_infos.keys()), rank, world, device)
+    results = gather_results(results, list(video_infos.keys()), rank, world, device)
     if results is None:
         return None
-    thr = T.ood_threshold(results, scoring)
-    os.makedirs(os.path.dirname(os.path.abspath(output_file)), exist_ok=True)
-    with open(output_file, 'w') as f:
-        json.dump(T.results_json(results, threshold=thr), f)
+    thr = ood_threshold(results, scoring)
+    write_json(output_file, results_json(results, threshold=thr))
     return thr
 
 
 def main(argv=None):
     from ..common import config as C
-    from ..common import ops
     from ..common.thumos_dataset import get_class_index_map, get_video_info
     from .BDNet import BDNet, model_cfg_from
-    argv = list(sys.argv[1:] if argv is None else argv)
-    random_init = '--random_init' in argv
-    argv = [a for a in argv if a != '--random_init']
+    own, argv = split_flags(list(sys.argv[1:] if argv is None else argv), ('--random_init',))
     args = C.build_parser().parse_args(argv)
     config = C.set_config(C.get_config(argv))
     te, md, ds = config['testing'], config['model'], config['dataset']
@@ -52,17 +47,11 @@ def main(argv=None):
             print(f'Thresholding result file already exist at {output_file}!')
             print(f'The threshold is: {thr:.12f}')
             return output_file, thr
-    rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
-    dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
-    torch.cuda.set_device(dev)
-    ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
+    rank, world, dev = device_setup()
     use_rpl, use_gcpl = T.rpl_flags(config)
-    net = BDNet(in_channels=md['in_channels'], training=False, use_edl=md.get('use_edl', False), use_rpl=use_rpl,
-                cfg=model_cfg_from(config))
+    net = load_net(BDNet, dev, own['--random_init'], te['checkpoint_path'], in_channels=md['in_channels'],
+                   use_edl=md.get('use_edl', False), use_rpl=use_rpl, cfg=model_cfg_from(config))
     net.use_gcpl = use_gcpl                 # GCPL: scores are the softmax of the negated distances
-    if not random_init:
-        net.load_state_dict(torch.load(te['checkpoint_path'], map_location='cpu'))
-    net = net.to(dev).eval()
     video_infos = get_video_info(ds['training']['video_info_path'])          # the TRAINING list (:73)
     _, idx_to_class = get_class_index_map(ds['class_info_path'])
     t = ds['testing']

@@ -85,6 +85,47 @@ def test_threshold_file_is_written_whole(tmp_path):
     assert read_threshold_file(str(tmp_path / 'plain.json')) is None    # a detection file of anet.test carries no threshold
 
 
+def test_write_json_replaces_the_file_whole(tmp_path):
+    from opental_amd.common.driver import write_json
+    out = tmp_path / 'not' / 'there' / 'yet' / 'res.json'
+    obj = {"version": "THUMOS14", "results": {"v": [{"label": "A", "score": 0.5, "segment": [0.0, 1.5]}]}, "external_data": {}}
+    write_json(str(out), obj)
+    assert json.loads(out.read_text()) == obj
+    assert os.listdir(out.parent) == ['res.json']                   # no temporary file is left behind
+    write_json(str(out), {"results": {}})                           # an existing file is replaced
+    assert json.loads(out.read_text()) == {"results": {}}
+    assert os.listdir(out.parent) == ['res.json']
+
+
+def test_split_flags_on_each_drivers_flag_set():
+    from opental_amd.common.driver import split_flags
+    base = ['cfg.yaml', '--open_set', '--split', '0']
+    # thumos14.test / test_openmax: --random_init and --evaluate GT KNOWN, anywhere on the line
+    flags, options = ('--random_init',), {'--evaluate': (2, None)}
+    found, rest = split_flags(['cfg.yaml', '--evaluate', 'gt.json', 'known.txt', '--open_set', '--random_init', '--split', '0'],
+                              flags, options)
+    assert found == {'--random_init': True, '--evaluate': ('gt.json', 'known.txt')} and rest == base
+    assert split_flags(base, flags, options) == ({'--random_init': False, '--evaluate': None}, base)
+    for line in (base + ['--evaluate'], base + ['--evaluate', 'gt.json']):
+        with pytest.raises(ValueError, match='--evaluate takes 2 values'):
+            split_flags(line, flags, options)
+    # thumos14.test_cross_data: three valued options with defaults
+    options = {'--anet_info': (1, 'info.json'), '--anet_npy': (1, 'npy'), '--anet_overlap': (1, 'overlap.txt')}
+    found, rest = split_flags(base[:1] + ['--anet_npy', '/data/npy', '--random_init'] + base[1:] + ['--anet_overlap', 'o.txt'],
+                              flags, options)
+    assert found == {'--random_init': True, '--anet_info': 'info.json', '--anet_npy': '/data/npy', '--anet_overlap': 'o.txt'}
+    assert rest == base
+    with pytest.raises(ValueError, match='--anet_info takes 1 value'):
+        split_flags(base + ['--anet_info'], flags, options)
+    # thumos14.threshold / anet.test: one flag; what the config parser reads (--ood_scoring S) passes through
+    line = base + ['--ood_scoring', 'uncertainty', '--output_json', 'thr.json']
+    assert split_flags(line + ['--random_init'], ('--random_init',)) == ({'--random_init': True}, line)
+    # anet.threshold: two flags
+    found, rest = split_flags(['--keep_detections'] + line, ('--random_init', '--keep_detections'))
+    assert found == {'--random_init': False, '--keep_detections': True} and rest == line
+    assert split_flags([], ('--random_init',)) == ({'--random_init': False}, [])
+
+
 def test_existing_threshold_is_reused_without_the_gpu(tmp_path, monkeypatch, capsys):
     sys.path.insert(0, os.path.join(REPO, 'tools'))
     try:

@@ -49,6 +49,28 @@ def test_exclude_overlapping_and_merge():
     assert thumos['results']['b'] == [{'label': 'old'}]        # inputs untouched
 
 
+def test_enumerate_windows():
+    """The window list every driver's pipeline starts from (common.detect.enumerate_windows), on videos shorter than a clip,
+    exactly one clip, with a tail window, exactly two strides and one frame more; the offsets are get_offsets' (test.py:48-56)
+    written out."""
+    from opental_amd.common.detect import enumerate_windows, get_offsets
+    frames = (200, 256, 300, 384, 385)
+    per_video = [[0], [0], [0, 44], [0, 128], [0, 128, 129]]
+    assert [get_offsets(f, 256, 128) for f in frames] == per_video
+    videos = [torch.zeros((3, f, 2, 2), dtype=torch.uint8) for f in frames]
+    clips, offsets, fps, clip_start = enumerate_windows(videos, 10.0, 256, 128)
+    assert clips == [(0, 0), (1, 0), (2, 0), (2, 44), (3, 0), (3, 128), (4, 0), (4, 128), (4, 129)]
+    assert offsets == [0.0, 0.0, 0.0, 44.0, 0.0, 128.0, 0.0, 128.0, 129.0] and all(type(o) is float for o in offsets)
+    assert fps == [10.0] * 9
+    assert clip_start == [0, 1, 2, 4, 6, 9]
+    each = enumerate_windows(videos, [10.0, 11.0, 12.5, 13.0, 14.0], 256, 128)
+    assert each[2] == [10.0, 11.0, 12.5, 12.5, 13.0, 13.0, 14.0, 14.0, 14.0]
+    assert (each[0], each[1], each[3]) == (clips, offsets, clip_start)
+    # stride None: a video is one clip (the ActivityNet recipe), whatever its length
+    clips, offsets, fps, clip_start = enumerate_windows(videos[2:4], [5.0, 6.0], 768, None)
+    assert (clips, offsets, fps, clip_start) == ([(0, 0), (1, 0)], [0.0, 0.0], [5.0, 6.0], [0, 1, 2])
+
+
 @pytest.mark.gpu
 def test_test_anet_matches_per_window_order(golden_dir):
     """The batched driver (videos batched, all windows decoded and suppressed in two launches) against the reference's
