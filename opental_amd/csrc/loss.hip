@@ -564,7 +564,8 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
         for (int i = t; i < n2; i += LT) {
             unsigned hi = 0xffffffffu;
             if (i < A && !(a.scratch[(size_t)i * SCR + 2 + pass] > 0.f)) {
-                const unsigned u = __float_as_uint(pred[i]);
+                unsigned u = __float_as_uint(pred[i]);
+                if (u == 0x80000000u) u = 0u;                         // -0.0 == +0.0: one key, the index decides (as the ActivityNet kernel's `==`)
                 hi = u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
                 if (hi == 0xffffffffu) hi = 0xfffffffeu;             // keep the sentinel unique to non-negatives
             }

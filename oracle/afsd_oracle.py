@@ -545,7 +545,7 @@ def actionness_loss(logit, label, weight=0.0, margin=1.0):
     top_m = min(npos, nneg) - 1
     use_pred, use_label = pred, label
     if top_m > 0:
-        order = neg.sort()[1][:top_m]
+        order = neg.sort(stable=True)[1][:top_m]       # equal scores: the lower index first
         use_pred = torch.cat([pos, neg[order]])
         use_label = torch.cat([torch.ones(npos), torch.zeros(top_m)])
         nneg = top_m
