@@ -715,6 +715,17 @@ int otal_bmp_bwd_levels_from(const float* grad_out, int64_t pooled_bs, const flo
 int otal_eval_match(const double* pred_seg, const int* pred_start, const double* gt_seg, const int* gt_start,
                     const double* thresholds, int ngroups, int nthr, int* out, int* nonfinite, void* stream);
 
+/* The labelled matching of the Wilderness-Impact pass (compute_wilderness_impact :604-728; the rule: match_labeled_reference
+ * in opental_amd/evaluation/match.py).  As otal_eval_match, with pred_label (N) and gt_label (M) in the rows' order and these
+ * differences: the ground truth that prediction i matches becomes taken only where gt_label == pred_label[i] (a true
+ * positive); a false positive leaves it open for later predictions, so out[t][i] >= 0 can name the same row more than once.
+ * -1 and -2 as above, "taken" read as "taken by a true positive".  max_tiou (N): the largest tIoU of prediction i over its
+ * group's ground truths, whatever the threshold; 0 for a group without ground truth.  *nonfinite, the argument checks and
+ * the return codes are otal_eval_match's; max_tiou is discarded with `out`.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_eval_match_labeled(const double* pred_seg, const int* pred_label, const int* pred_start, const double* gt_seg,
+                            const int* gt_label, const int* gt_start, const double* thresholds, int ngroups, int nthr, int* out,
+                            double* max_tiou, int* nonfinite, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,10 @@ def lib():
         # otal_eval_match (csrc/eval.hip): five device arrays, ngroups, nthr, out, the non-finite counter, the stream
         L.otal_eval_match.restype = ctypes.c_int
         L.otal_eval_match.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3
+        # otal_eval_match_labeled: seven device arrays (labels after each segment array), ngroups, nthr, out, max_tiou, the
+        # counter, the stream
+        L.otal_eval_match_labeled.restype = ctypes.c_int
+        L.otal_eval_match_labeled.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 4
         # otal_detection_table (csrc/dettable.hip): rows, counts, durations, V, K, top_k, cols, drop_empty, scoring, the six
         # output arrays, the stream
         L.otal_detection_table.restype = ctypes.c_int

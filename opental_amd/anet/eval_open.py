@@ -6,10 +6,12 @@
     python -m opental_amd.anet.eval_open output/anet/opental/split_{id:d}/detection_results.json \\
         datasets/activitynet/annotations_open/split_{id:d}/known_gt.json \\
         --cls_idx_known datasets/activitynet/annotations_open/split_{id:d}/action_known.txt \\
-        --all_splits 0 1 2 --open_set --ood_scoring uncertainty_actionness [--device cuda] [--tious 0.1 0.2 0.3 0.4 0.5]
+        --all_splits 0 1 2 --open_set --ood_scoring uncertainty_actionness [--device cuda] [--tious 0.1 0.2 0.3 0.4 0.5] \\
+        [--wi] [--stats_json FILE] [--ood_threshold THR]
 
 Differences from the THUMOS14 driver: dataset 'anet' (one class name per line), the `validation` subset, a ground-truth path
-formatted with the split id in both protocols (:39), and --tious.  The default list is ActivityNet's
+formatted with the split id in both protocols (:39), and --tious (--wi, --stats_json and --ood_threshold are the THUMOS14
+driver's).  The default list is ActivityNet's
 np.linspace(0.5, 0.95, 10) (anet/eval.py:11); the reference's open-set script carries 0.1 .. 0.5 (:16), a leftover of the
 THUMOS14 file it was copied from, which --tious selects.  That script also unpacks two values from evaluate('AUC'), which
 returns three (:64), so it does not run as shipped; the text files therefore have the line format of the THUMOS14 driver, the
@@ -18,7 +20,7 @@ import argparse
 
 import numpy as np
 
-from ..thumos14.eval_open import evaluate_split, print_summary
+from ..thumos14.eval_open import add_wi_arguments, check_wi_arguments, evaluate_split, finish_wi, print_summary
 
 SUBSET = ['validation']
 
@@ -40,13 +42,17 @@ def main(argv=None):
                         help='cuda: the matching passes run through the device kernel (evaluation/match.py)')
     parser.add_argument('--tious', nargs='+', type=float, default=None,
                         help='tIoU thresholds; default: 0.5 .. 0.95 in ten steps')
+    add_wi_arguments(parser)
     args = parser.parse_args(argv)
+    check_wi_arguments(parser, args)
     tious = default_tious() if args.tious is None else np.array(args.tious, dtype=np.float64)
     per_split = []
     for split in args.all_splits:
         per_split.append(evaluate_split(args.output_json.format(id=split), args.gt_json.format(id=split),
                                         args.cls_idx_known.format(id=split), tious, SUBSET, args.open_set, args.ood_scoring,
-                                        'anet', device=args.device))
+                                        'anet', device=args.device, wi=args.wi or bool(args.stats_json),
+                                        ood_threshold=args.ood_threshold))
+    finish_wi(per_split, args)
     print_summary(per_split, tious, args.open_set)
     return per_split
 

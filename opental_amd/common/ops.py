@@ -1937,6 +1937,35 @@ def eval_match(pred_seg, pred_start, gt_seg, gt_start, thresholds):
     return out, nonfinite
 
 
+def eval_match_labeled(pred_seg, pred_label, pred_start, gt_seg, gt_label, gt_start, thresholds):
+    """The labelled matching of the Wilderness-Impact pass for every video and tIoU threshold in one launch
+    (otal_eval_match_labeled, csrc/eval.hip; the rule: evaluation/match.py, match_labeled_reference).  Arrays as eval_match's,
+    plus pred_label (N) / gt_label (M) int32 in the rows' order.  A matched ground truth is taken only where the labels agree.
+    -> (out (nthr, N) int32: the matched row of gt_seg, -1 or -2; max_tiou (N) fp64: each prediction's largest tIoU over its
+    group; nonfinite (1,) int32: non-zero = discard both)."""
+    L.require_device(pred_seg, pred_label, pred_start, gt_seg, gt_label, gt_start, thresholds)
+    if pred_seg.dtype != torch.float64 or gt_seg.dtype != torch.float64 or thresholds.dtype != torch.float64 \
+            or any(t.dtype != torch.int32 for t in (pred_start, gt_start, pred_label, gt_label)):
+        raise RuntimeError("eval_match_labeled: segments and thresholds in float64, offsets and labels in int32")
+    if pred_seg.dim() != 2 or pred_seg.shape[1] != 2 or gt_seg.dim() != 2 or gt_seg.shape[1] != 2 \
+            or pred_start.dim() != 1 or pred_start.shape != gt_start.shape or pred_start.numel() < 1 or thresholds.dim() != 1 \
+            or pred_label.shape != pred_seg.shape[:1] or gt_label.shape != gt_seg.shape[:1]:
+        raise RuntimeError("eval_match_labeled: pred_seg (N, 2), pred_label (N), gt_seg (M, 2), gt_label (M), "
+                           "pred_start / gt_start (ngroups + 1), thresholds (nthr,)")
+    N, ngroups, nthr = pred_seg.shape[0], pred_start.numel() - 1, thresholds.numel()
+    out = torch.empty((nthr, N), dtype=torch.int32, device=pred_seg.device)
+    max_tiou = torch.zeros(N, dtype=torch.float64, device=pred_seg.device)
+    nonfinite = torch.zeros(1, dtype=torch.int32, device=pred_seg.device)
+    if N == 0 or ngroups == 0:
+        return out, max_tiou, nonfinite
+    if gt_seg.shape[0] == 0:        # an empty tensor has no address to pass; the offsets say that no row of it is read
+        gt_seg, gt_label = gt_seg.new_zeros((1, 2)), gt_label.new_zeros(1)
+    L.check(L.lib().otal_eval_match_labeled(L.ptr(pred_seg), L.ptr(pred_label), L.ptr(pred_start), L.ptr(gt_seg), L.ptr(gt_label),
+                                            L.ptr(gt_start), L.ptr(thresholds), ngroups, nthr, L.ptr(out), L.ptr(max_tiou),
+                                            L.ptr(nonfinite), L.stream()), "otal_eval_match_labeled")
+    return out, max_tiou, nonfinite
+
+
 def detection_table(rows, counts, durations=None, drop_empty=False, scoring='uncertainty', out=None):
     """The Soft-NMS output of softnms_classes as one compact table (otal_detection_table, csrc/dettable.hip; the rule:
     common/det_table.py): rows (V, K, top_k, cols) fp32 with cols 3..5, counts (V, K) int32, durations (V) seconds (a

@@ -1,16 +1,22 @@
 """Detection evaluation of OpenTAL: closed-set mAP and the open-set metrics AUROC / AUPR / FAR@95 / OSDR from a
 result JSON (reference AFSD/evaluation/eval_detection.py: ANETdetection :26-320, compute_average_precision_detection
-:323-402, split_results_by_gt :405-456, compute_auc_scores :459-491, compute_osdr_scores :494-510).  SURVEY 8f rank 3.
+:323-402, split_results_by_gt :405-456, compute_auc_scores :459-491, compute_osdr_scores :494-510,
+compute_wilderness_impact :604-728).  SURVEY 8f rank 3.
 
 Same class name, constructor arguments and `evaluate(type=...)` results as the reference, on plain numpy arrays
 instead of pandas frames + joblib (the reference walks data frames row by row; here a prediction row is an index into
 parallel arrays).  Pinned against the imported reference by oracle/pin_evaluation.py -> tests/golden/eval_*.json.
 
-`device='cuda'` routes the two matching passes (pre_evaluate, evaluate('AP')) through the device kernel of match.py /
-csrc/eval.hip; None or 'cpu' is the numpy code below.  The metric arithmetic stays on the host in fp64 either way.
+`device='cuda'` routes the matching passes (pre_evaluate, evaluate('AP'), evaluate('WI')) through the device kernels of
+match.py / csrc/eval.hip; None or 'cpu' is the numpy code below.  The metric arithmetic stays on the host in fp64 either way.
 
-Not restated: the Wilderness-Impact variant (`evaluate('WI')`) -- the reference's own drivers have it commented out
-(thumos14/eval_open.py:77-80) -- and the plotting helpers (save_curve_data).
+evaluate('WI') is the Wilderness Impact and the open-set error breakdown `self.stats` (tools/pin_wilderness.py ->
+tests/golden/eval_wi.json).  Its matching is match.py's labelled rule on both paths -- the numpy statement for None / 'cpu',
+the kernel for 'cuda' -- and two things are defined where the reference leaves them to chance: videos are visited in the order
+of sorted(set(videos)) (the reference: list(set(...)), hash order; the WI value depends on it, the outcome of a detection does
+not), and equal tIoU go to the lowest ground-truth row.
+
+Not restated: the plotting helpers (save_curve_data) and the older compute_wilderness_impact1.
 """
 import json
 
@@ -136,15 +142,19 @@ class ANETdetection(object):
         self.prediction['label'] = label
         self._plans.pop('ap', None)         # the AP pass groups by label; the split pass does not
 
-    def _device_codes(self, kind):
-        """The matches of one pass through otal_eval_match: (plan, int32 codes (nthr, N) over the plan's sorted positions).
-        Plans and their uploads are kept: the split pass's for the evaluator's life, the AP pass's until the labels change."""
+    def _plan(self, kind):
+        """The group-sorted arrays of the split pass ('split', also the WI pass's) or of the AP pass ('ap').  Plans and their
+        uploads are kept: the split pass's for the evaluator's life, the AP pass's until the labels change."""
         if 'videos' not in self._plans:
             self._plans['videos'] = match.video_codes(self.ground_truth['video-id'], self.prediction['video-id'])
         if kind not in self._plans:
             self._plans[kind] = match.plan_split(self.prediction, self.ground_truth, self._plans['videos']) if kind == 'split' \
                 else match.plan_ap(self.prediction, self.ground_truth, self.activity_index.values(), self._plans['videos'])
-        plan = self._plans[kind]
+        return self._plans[kind]
+
+    def _device_codes(self, kind):
+        """The matches of one pass through otal_eval_match: (plan, int32 codes (nthr, N) over the plan's sorted positions)."""
+        plan = self._plan(kind)
         return plan, match.match_device(*plan.arrays(), self.tiou_thresholds, plan=plan)
 
     @staticmethod
@@ -166,6 +176,26 @@ class ANETdetection(object):
             pred = self._rows(self.prediction, self.prediction['label'] == cidx)
             ap[:, cidx - 1] = compute_average_precision_detection(gt, pred, self.tiou_thresholds)
         return ap
+
+    def wrapper_compute_wilderness_impact(self):
+        """eval_detection.py:279-289 -> wi (nthr, K); sets self.stats.  Detections are numbered video by video in the order
+        of sorted(set(videos)), file order inside: the sorted positions of the split pass's plan."""
+        assert '__unknown__' in self.activity_index
+        plan = self._plan('split')
+        pred_seg, pred_start, gt_seg, gt_start = plan.arrays()
+        pred_label, gt_label = self.prediction['label'][plan.order], self.ground_truth['label'][plan.gt_order]
+        if self.device == 'cuda':
+            codes, max_tiou = match.match_labeled_device(pred_seg, pred_label, pred_start, gt_seg, gt_label, gt_start,
+                                                         self.tiou_thresholds, plan=plan)
+        else:
+            codes, max_tiou = match.match_labeled_reference(pred_seg, pred_label, pred_start, gt_seg, gt_label, gt_start,
+                                                            self.tiou_thresholds)
+        n_known = len(self.activity_index) - 1
+        flags = match.wi_outcomes(codes, pred_label, gt_label, n_known)
+        num_gt = np.bincount(gt_label, minlength=n_known + 1).astype(np.float32)
+        wi, self.stats = compute_wilderness_impact(flags, num_gt, self.prediction['ood_score'][plan.order],
+                                                   self.prediction['score'][plan.order], max_tiou)
+        return wi
 
     def pre_evaluate(self):
         if self.device == 'cuda':
@@ -189,7 +219,43 @@ class ANETdetection(object):
             pred_scores, pred_labels, gt_labels = self.eval_data
             self.osdr, _ = compute_osdr_scores(pred_scores, pred_labels, gt_labels, self.tiou_thresholds)
             return self.osdr
+        if type == 'WI':
+            assert self.openset, 'Wilderness Impact Cannot be Evaluated for Closed Set!'
+            self.wi = self.wrapper_compute_wilderness_impact()
+            self.mWI = self.wi.mean(axis=1)
+            self.average_mWI = self.mWI.mean()
+            return self.mWI, self.average_mWI, self.wi
         raise NotImplementedError(type)
+
+
+def compute_wilderness_impact(flags, num_gt, ood_scores, scores, max_tious):
+    """The arithmetic of compute_wilderness_impact (eval_detection.py:694-728) on the outcome flags of match.wi_outcomes,
+    in fp64: -> (wi (nthr, K), stats).  Detections along the last axis are in the pass's order, which the cumulative sums
+    follow.  num_gt (K + 1,) float32: ground truths per label, 0 = unknown.
+
+    stats has the reference's keys: the seven flag arrays, 'ood_scores', 'scores', 'max_tious' (fp64 arrays where the
+    reference has lists) and 'num_gt'.  As in the reference, stats holds the very arrays that :712-713 fold in place
+    (`fp_k2u += fp_bg2u`, `fp_k2k += fp_bg2k`): a background detection is flagged in 'fp_bg2u' / 'fp_bg2k' AND in
+    'fp_k2u' / 'fp_k2k', which is what the reference pickles and its analyze_stats.py counts."""
+    stats = dict(flags, ood_scores=np.asarray(ood_scores, dtype=np.float64), scores=np.asarray(scores, dtype=np.float64),
+                 max_tious=np.asarray(max_tious, dtype=np.float64), num_gt=num_gt)
+    tp_u2u, tp_k2k, fp_u2k, fp_k2k, fp_k2u = (flags[k] for k in ('tp_u2u', 'tp_k2k', 'fp_u2k', 'fp_k2k', 'fp_k2u'))
+    # the background detections (small tIoU) are taken to come from the background class, a known class
+    fp_k2u += flags['fp_bg2u']
+    fp_k2k += flags['fp_bg2k']
+    nthr, n_known = tp_k2k.shape[:2]
+    wi = np.zeros((nthr, n_known))
+    # impact on the recall ratio, (nthr, N)
+    tp_u2u_cumsum = np.cumsum(tp_u2u, axis=-1).astype(float)
+    recall_ratio_cumsum = num_gt[1:].sum() / (num_gt[1:].sum() + num_gt[0] - tp_u2u_cumsum)
+    for cidx in range(n_known):                 # class by class: the reference's (nthr, K, N) temporaries, one K at a time
+        tp_k2k_cumsum = np.cumsum(tp_k2k[:, cidx], axis=-1).astype(float)
+        fp_u2k_cumsum = np.cumsum(fp_u2k[:, cidx], axis=-1).astype(float)
+        fp_k2k_cumsum = np.cumsum(fp_k2k[:, cidx], axis=-1).astype(float)
+        precision_ratio_cumsum = (tp_k2k_cumsum + fp_k2k_cumsum) / (tp_k2k_cumsum + fp_k2k_cumsum + fp_u2k_cumsum + 1e-6)
+        for tidx in range(nthr):
+            wi[tidx, cidx] = interpolated_prec_rec(precision_ratio_cumsum[tidx, :], recall_ratio_cumsum[tidx, :])
+    return wi, stats
 
 
 def compute_average_precision_detection(ground_truth, prediction, tiou_thresholds=np.linspace(0.5, 0.95, 10)):

@@ -17,7 +17,27 @@ Thresholds are independent problems with their own taken-sets.  Ties: the CPU lo
 
 match_reference is the executable statement of the rule in numpy (the oracle of the GPU tests and the fallback),
 match_device the same through otal_eval_match (csrc/eval.hip).  plan_split / plan_ap turn the evaluator's column arrays
-into group-sorted arrays and map the results back; they are vectorised, no per-row Python."""
+into group-sorted arrays and map the results back; they are vectorised, no per-row Python.
+
+Labelled matching (the Wilderness-Impact pass, compute_wilderness_impact :604-728) is a second rule beside it.  A group is a
+video: its predictions in file order, its ground truths of ALL classes, the unknown label 0 included; predictions and ground
+truths carry labels.  For prediction i with label lp:
+
+  * MATCH as above: among the ground truths that are not locked and satisfy `not (tiou_j < thr)` the one with the largest
+    tIoU, the lowest row among equal tIoU; the result is its row;
+  * LOCK: that ground truth becomes locked only where lp == label_j, a true positive (:676-681 writes lock_gt in the TP
+    branch alone).  A false positive leaves it open for later predictions -- the one difference from the rule above;
+  * without a candidate the result is -1 where some tiou_j < thr (the background break, :662-667) and -2 where every ground
+    truth clears the threshold and is locked (the reference sets no flag for such a prediction); a group without ground
+    truth gives -1 (the reference cannot have one, the planner can);
+  * once per prediction, whatever the threshold: max_tiou = the largest tIoU over the group's ground truths (:656), 0 for a
+    group without ground truth.
+
+Ties are decided as above, by the lowest row, where the reference's `argsort()[::-1]` leaves them to the numpy build; they
+arise only between ground truths with equal tIoU at or above the threshold, that is duplicated ground-truth segments.
+match_labeled_reference is this rule in numpy, match_labeled_device the same through otal_eval_match_labeled; plan_split's
+Plan serves both rules (group = video, file order) and its order / gt_order carry the labels.  wi_outcome_codes / wi_outcomes
+turn result codes and the two labels into the pass's seven outcomes, on the host."""
 import warnings
 
 import numpy as np
@@ -50,6 +70,75 @@ def match_reference(pred_seg, pred_start, gt_seg, gt_start, thresholds):
             hit = cand.any(axis=1)
             out[:, i] = np.where(hit, g0 + best, np.where(below.any(axis=1), -1, -2))
             taken[hit, best[hit]] = True
+    return out
+
+
+def match_labeled_reference(pred_seg, pred_label, pred_start, gt_seg, gt_label, gt_start, thresholds):
+    """The labelled rule (module docstring).  Arrays as match_reference's, pred_label (N) / gt_label (M) integer labels in
+    the rows' order -> (int32 codes (nthr, N): the matched row of gt_seg, -1 or -2; fp64 max_tiou (N))."""
+    pred_seg = np.asarray(pred_seg, dtype=np.float64).reshape(-1, 2)
+    gt_seg = np.asarray(gt_seg, dtype=np.float64).reshape(-1, 2)
+    pred_label, gt_label = np.asarray(pred_label).reshape(-1), np.asarray(gt_label).reshape(-1)
+    thr = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    out = np.full((len(thr), len(pred_seg)), -1, dtype=np.int32)
+    max_tiou = np.zeros(len(pred_seg), dtype=np.float64)
+    for g in range(len(pred_start) - 1):
+        g0, g1 = int(gt_start[g]), int(gt_start[g + 1])
+        if g1 == g0:
+            continue
+        segs, labels = gt_seg[g0:g1], gt_label[g0:g1]
+        locked = np.zeros((len(thr), g1 - g0), dtype=bool)
+        for i in range(int(pred_start[g]), int(pred_start[g + 1])):
+            with np.errstate(invalid='ignore', divide='ignore'):
+                tiou = segment_iou(pred_seg[i], segs)
+                below = tiou[None, :] < thr[:, None]
+            max_tiou[i] = tiou.max()
+            cand = ~below & ~locked
+            # np.argmax returns the first maximum: the lowest row among equal tIoU
+            best = np.where(cand, tiou[None, :], -np.inf).argmax(axis=1)
+            hit = cand.any(axis=1)
+            out[:, i] = np.where(hit, g0 + best, np.where(below.any(axis=1), -1, -2))
+            tp = hit & (labels[best] == pred_label[i])
+            locked[tp, best[tp]] = True
+    return out, max_tiou
+
+
+WI_OUTCOMES = ('tp_u2u', 'tp_k2k', 'fp_u2k', 'fp_k2k', 'fp_k2u', 'fp_bg2u', 'fp_bg2k')
+WI_PER_CLASS = ('tp_k2k', 'fp_u2k', 'fp_k2k', 'fp_bg2k')       # (T, K, N) arrays, the class = the PREDICTION's label - 1
+
+
+def wi_outcome_codes(codes, pred_label, gt_label):
+    """Result codes (nthr, N) of the labelled rule, pred_label (N) and gt_label (M; codes >= 0 index it) -> int8 (nthr, N):
+    the index into WI_OUTCOMES of each prediction's outcome (compute_wilderness_impact :662-689), -1 for none (code -2).
+    Label 0 is '__unknown__'."""
+    codes = np.asarray(codes)
+    lp = np.asarray(pred_label, dtype=np.int64).reshape(1, -1)
+    gt_label = np.asarray(gt_label, dtype=np.int64).reshape(-1)
+    lg = gt_label[np.maximum(codes, 0)] if len(gt_label) else np.zeros(codes.shape, dtype=np.int64)
+    matched = codes >= 0
+    fp = np.where(lg == 0, 2, np.where(lp == 0, 4, 3))                          # fp_u2k, fp_k2u, fp_k2k
+    outcome = np.where(matched, np.where(lp == lg, np.where(lg == 0, 0, 1), fp),
+                       np.where(codes == -1, np.where(lp == 0, 5, 6), -1))
+    return outcome.astype(np.int8)
+
+
+def wi_outcomes(codes, pred_label, gt_label, n_known):
+    """The seven outcome arrays of compute_wilderness_impact in its shapes, as 0 / 1 in fp64: dict of WI_OUTCOMES ->
+    (nthr, N), or (nthr, n_known, N) for WI_PER_CLASS.  A prediction has at most one flag, none for code -2; these are the
+    flags as the pass sets them, before it folds the background ones into fp_k2u / fp_k2k (:712-713)."""
+    outcome = wi_outcome_codes(codes, pred_label, gt_label)
+    lp = np.asarray(pred_label, dtype=np.int64).reshape(-1)
+    nthr, n = outcome.shape
+    out = {}
+    for idx, key in enumerate(WI_OUTCOMES):
+        mask = outcome == idx
+        if key in WI_PER_CLASS:
+            arr = np.zeros((nthr, n_known, n))
+            t, i = np.nonzero(mask)
+            arr[t, lp[i] - 1, i] = 1.0
+        else:
+            arr = mask.astype(np.float64)
+        out[key] = arr
     return out
 
 
@@ -178,6 +267,20 @@ def average_precision(plan, codes, classes, nthr, interpolated_prec_rec):
     return ap
 
 
+def _uploads(pred_seg, pred_start, gt_seg, gt_start, plan):
+    """The four arrays on the current device: (pred_seg (N, 2), pred_start, gt_seg (M, 2), gt_start); made once per plan."""
+    import torch
+    dev = plan.device if plan is not None else None
+    if dev is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+        dev = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)
+                    for a, dt in ((pred_seg, np.float64), (pred_start, np.int32), (gt_seg, np.float64), (gt_start, np.int32)))
+        dev = (dev[0].reshape(-1, 2), dev[1], dev[2].reshape(-1, 2), dev[3])
+        if plan is not None:
+            plan.device = dev
+    return dev
+
+
 def match_device(pred_seg, pred_start, gt_seg, gt_start, thresholds, plan=None):
     """match_reference through the kernel (ops.eval_match).  With `plan` (a Plan whose arrays the first four arguments
     are) the uploaded segments and offsets are kept on it and reused by later calls.  A result whose non-finite counter is
@@ -187,14 +290,7 @@ def match_device(pred_seg, pred_start, gt_seg, gt_start, thresholds, plan=None):
     thr = np.asarray(thresholds, dtype=np.float64).reshape(-1)
     if not 1 <= len(thr) <= MAX_THRESHOLDS:
         raise ValueError("1 .. %d tIoU thresholds, got %d" % (MAX_THRESHOLDS, len(thr)))
-    dev = plan.device if plan is not None else None
-    if dev is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-        dev = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)
-                    for a, dt in ((pred_seg, np.float64), (pred_start, np.int32), (gt_seg, np.float64), (gt_start, np.int32)))
-        dev = (dev[0].reshape(-1, 2), dev[1], dev[2].reshape(-1, 2), dev[3])
-        if plan is not None:
-            plan.device = dev
+    dev = _uploads(pred_seg, pred_start, gt_seg, gt_start, plan)
     out, nonfinite = ops.eval_match(dev[0], dev[1], dev[2], dev[3], torch.from_numpy(thr).to(dev[0].device))
     result = out.cpu().numpy()              # the read-back waits for the kernel; the counter is final after it
     if int(nonfinite.item()) != 0:
@@ -202,6 +298,28 @@ def match_device(pred_seg, pred_start, gt_seg, gt_start, thresholds, plan=None):
                       "matching on the CPU instead")
         return match_reference(pred_seg, pred_start, gt_seg, gt_start, thr)
     return result
+
+
+def match_labeled_device(pred_seg, pred_label, pred_start, gt_seg, gt_label, gt_start, thresholds, plan=None):
+    """match_labeled_reference through the kernel (ops.eval_match_labeled), with match_device's conventions: the uploaded
+    segments and offsets are kept on `plan` -- the very uploads match_device makes, so the split pass and this one share
+    them; the labels are uploaded per call (set_ood_threshold changes them).  A result whose counter is non-zero is
+    discarded for match_labeled_reference's, with a warning."""
+    import torch
+    from ..common import ops
+    thr = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    if not 1 <= len(thr) <= MAX_THRESHOLDS:
+        raise ValueError("1 .. %d tIoU thresholds, got %d" % (MAX_THRESHOLDS, len(thr)))
+    dev = _uploads(pred_seg, pred_start, gt_seg, gt_start, plan)
+    labels = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32).reshape(-1)).to(dev[0].device) for a in (pred_label, gt_label)]
+    out, top, nonfinite = ops.eval_match_labeled(dev[0], labels[0], dev[1], dev[2], labels[1], dev[3],
+                                                 torch.from_numpy(thr).to(dev[0].device))
+    result, max_tiou = out.cpu().numpy(), top.cpu().numpy()     # the read-back waits for the kernel; the counter is final
+    if int(nonfinite.item()) != 0:
+        warnings.warn("eval_match_labeled: non-finite tIoU (zero-length segments) or a group with too many ground truths; "
+                      "matching on the CPU instead")
+        return match_labeled_reference(pred_seg, pred_label, pred_start, gt_seg, gt_label, gt_start, thr)
+    return result, max_tiou
 
 
 def plan_ap(prediction, ground_truth, classes, codes=None):

@@ -8,7 +8,10 @@ thresholds 0.3 .. 0.7, open-set protocol.  Times, with the JSON files already pa
   (b) ANETdetection(device='cuda'): the same two calls on a fresh evaluator -- host planners, uploads, kernel and read-back
       included -- after one tiny warm-up evaluation that loads the library and creates the device context;
 and for (b) where the time goes.  Both paths must give the same lists and AP values (asserted).  (c), the kernel alone, is
-what the kernel trace shows:  tools/kernel_time.sh 4 -- python tools/micro_eval.py --cuda-only"""
+what the kernel trace shows:  tools/kernel_time.sh 4 -- python tools/micro_eval.py --cuda-only
+  (d) evaluate('WI') with ood_threshold 0.5 on the same set: the labelled matching on the device (upload of the labels, kernel,
+      read-back; the segments are the split pass's uploads) against match_labeled_reference, the CPU rule, and the host part
+      common to both (outcome flags, cumulative sums, interpolation).  Both must give the same stats and WI (asserted)."""
 import argparse
 import json
 import os
@@ -85,6 +88,7 @@ def main():
         if not os.path.exists(os.path.join(f, "done")):
             write_set(f, *shape)
     timed(evaluator(tiny, "cuda"))                      # warm-up: library, device context, first launch
+    evaluator(tiny, "cuda").evaluate(type="WI")         # and the labelled kernel's first launch
     t0 = time.perf_counter()
     det = evaluator(folder, "cuda")
     t_import = time.perf_counter() - t0
@@ -111,8 +115,27 @@ def main():
     print("    video codes %.3f s | split: planner %.3f, upload + kernel + read-back %.3f, lists %.3f | "
           "AP: planner %.3f, upload + kernel + read-back %.3f, cumsum + interpolation %.3f"
           % (t_codes, t_plan_s, t_dev_s, t_lists, t_plan_a, t_dev_a, t_ap))
+    # (d) the Wilderness-Impact pass on the evaluator whose split plan is already uploaded
+    det.set_ood_threshold(0.5)
+    plan = det._plan("split")
+    labels = (det.prediction["label"][plan.order], det.ground_truth["label"][plan.gt_order])
+    pseg, pstart, gseg, gstart = plan.arrays()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    d_codes, d_top = match.match_labeled_device(pseg, labels[0], pstart, gseg, labels[1], gstart, TIOUS, plan=plan)
+    t_wi_dev = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    wi = det.evaluate(type="WI")
+    t_wi_all = time.perf_counter() - t0
+    print("(d) WI, device='cuda': labelled matching (labels up, kernel, read-back) %.3f s; evaluate('WI') in all %.3f s   "
+          "(average WI %.6f)" % (t_wi_dev, t_wi_all, wi[1]))
     if args.cuda_only:
         return
+    t0 = time.perf_counter()
+    c_codes, c_top = match.match_labeled_reference(pseg, labels[0], pstart, gseg, labels[1], gstart, TIOUS)
+    t_wi_cpu = time.perf_counter() - t0
+    assert np.array_equal(c_codes, d_codes) and np.array_equal(c_top, d_top), "the labelled rule: device and CPU differ"
+    print("(d) WI, CPU rule: match_labeled_reference %.3f s; CPU / device = %.1f" % (t_wi_cpu, t_wi_cpu / t_wi_dev))
     cpu = evaluator(folder, "cpu")
     csplit_s, cap_s, cres = timed(cpu)
     print("(a) device='cpu':  pre_evaluate %.3f s + evaluate('AP') %.3f s = %.3f s   (average mAP %.6f)"
