@@ -412,6 +412,36 @@ int otal_softnms_classes_ws(const float* seg, const float* score, const float* u
 int otal_detection_table(const float* rows, const int* counts, const double* durations, int V, int K, int top_k, int cols,
                          int drop_empty, int scoring, int* video, int* cls, double* seg, float* sup, double* known,
                          int* list_start, void* stream);
+/* otal_anchor_stats (csrc/anchorstats.hip): the anchor diagnostics of a THUMOS14 detector before decoding and Soft-NMS -- per
+ * anchor and stage (0 coarse, 1 refined) the matched label, one score and the EDL gradient, and their histograms
+ * (experiments/analyze_actionness.py:226-339, experiments/analyze_gradnorm.py:173-189,:248-262).  The rule is stated in
+ * opental_amd/common/anchor_stats.py (anchor_stats_reference).  Layouts of otal_detection_loss: loc (B,K,2) frames; conf,
+ * prop_conf (B,K,C) logits; center (B,K); act, prop_act (B,K) or both NULL; priors (K); gt (B,G,3) = [start, end, label]
+ * in units of the clip, padded; gvalid (B,G) uint8.
+ *   labels   coarse = the loss's matching (first minimum of left + right over the valid ground truths that contain the
+ *            anchor, 0 when none does); refined = coarse, 0 where the IoU of loc with the matched target is < overlap_thresh.
+ *            fp32, the operations and order of the loss kernel.
+ *   groups   0 known (1 <= label <= n_known), 1 unknown (label > n_known), 2 background (label 0).
+ *   score    `target` 0..4 = uncertainty C/S, actionness sigmoid(act), confidence max_k alpha_k/S * sigmoid(center) (times the
+ *            actionness with os_head), uncertainty * actionness, 0.5 (actionness + 1) uncertainty; alpha = exp(clamp(z, +-10))
+ *            + 1 of the stage's logits, the actionness of the stage's map.
+ *   gradient 1/alpha_y - C/S at the label's column: with os_head the anchors labelled 1..C at column label - 1, without it
+ *            every anchor at column label (0 = background); a label outside the C columns gives no row; 0 where no row.
+ * Outputs: hist_score int64 (2, 3, score_bins), bin min((int)floorf(v * score_bins), score_bins - 1), a NaN score counted
+ * nowhere; hist_grad int64 (2, grad_bins) over |gradient| of the rows that count, edges i / grad_bins with 1e-6 added to the
+ * last (the bins of reweight 2).  Both are ADDED to: a dataset accumulates over launches.  label int32, value fp32, grad fp32,
+ * each (B,K,2) and each nullable (not written).
+ * One launch on `stream`, one workgroup per sample, no allocation, no synchronisation; the counts are integers, so the result
+ * is identical from run to run.  Checked before any read or launch: a NULL required pointer (everything but act, prop_act,
+ * label, value, grad): OTAL_E_NULL; B, K, C, G, score_bins or grad_bins < 1: OTAL_E_SHAPE; target outside 0..4, a target that
+ * uses the actionness without both maps (1, 3, 4, and 2 with os_head), one map without the other, n_known < 1, or
+ * 6 score_bins + 2 grad_bins > 16384 (the histograms of a workgroup live in LDS): OTAL_E_UNSUPPORTED.
+ * An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_anchor_stats(const float* loc, const float* conf, const float* prop_conf, const float* center, const float* act,
+                      const float* prop_act, const float* priors, const float* gt, const unsigned char* gvalid, int B, int K,
+                      int C, int G, float clip_length, float overlap_thresh, int os_head, int n_known, int target,
+                      int score_bins, int grad_bins, long long* hist_score, long long* hist_grad, int* label, float* value,
+                      float* grad, void* stream);
 
 /* ------------------------------------------------------------------ OpenMax baseline (csrc/openmax.hip) ----
  * Added under ABI 26 (new symbols only).  Feature rows are addressed by ELEMENT strides: row n (0 <= n < N), channel d at

@@ -40,6 +40,11 @@ def lib():
         # output arrays, the stream
         L.otal_detection_table.restype = ctypes.c_int
         L.otal_detection_table.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 7
+        # otal_anchor_stats (csrc/anchorstats.hip): eight fp32 arrays and gvalid, B, K, C, G, clip_length, overlap_thresh,
+        # os_head, n_known, target, score_bins, grad_bins, the two histograms, label / value / grad, the stream
+        L.otal_anchor_stats.restype = ctypes.c_int
+        L.otal_anchor_stats.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int] * 5 \
+            + [ctypes.c_void_p] * 6
         _lib = L
     return _lib
 

@@ -2008,3 +2008,50 @@ def detection_table(rows, counts, durations=None, drop_empty=False, scoring='unc
                                          L.stream()), "otal_detection_table")
     out['n'] = out['list_start'][-1]
     return out
+
+
+def anchor_stats(loc, conf, prop_conf, center, act, prop_act, priors, gt, gvalid, clip_length, overlap_thresh, os_head, n_known,
+                 target, score_bins=100, grad_bins=100, out=None, rows=True):
+    """The anchor diagnostics of a batch of windows in one launch (otal_anchor_stats, csrc/anchorstats.hip; the rule:
+    common/anchor_stats.py): head outputs in the layouts of the detection loss -- loc (B, K, 2), conf / prop_conf (B, K, C),
+    center (B, K), act / prop_act (B, K) or both None, priors (K), gt (B, G, 3) padded, gvalid (B, G).
+    -> dict(hist_score int64 (2, 3, score_bins), hist_grad int64 (2, grad_bins), label int32 / value fp32 / grad fp32
+    (B, K, 2)).  The histograms are ADDED to.  `out`: a dict with the caller's hist_score and hist_grad (a dataset accumulates
+    in them over launches) and any of label / value / grad; a row array it does not hold is allocated when `rows` is true and
+    left out (NULL to the kernel, None in the result) otherwise.  No synchronisation."""
+    from .anchor_stats import TARGETS, check_mode
+    check_mode(target, os_head, have_act=act is not None and prop_act is not None)
+    B, K, C = conf.shape
+    G = gt.shape[1]
+    f32 = lambda t: None if t is None else t.contiguous().float()
+    loc, conf, prop_conf, center, act, prop_act, priors, gt = (f32(t) for t in (loc, conf, prop_conf, center, act, prop_act,
+                                                                                  priors, gt))
+    gv = gvalid.contiguous().to(torch.uint8)
+    L.require_device(*[t for t in (loc, conf, prop_conf, center, act, prop_act, priors, gt, gv) if t is not None])
+    want = dict(loc=(loc, B * K * 2), prop_conf=(prop_conf, B * K * C), center=(center, B * K), priors=(priors, K),
+                gt=(gt, B * G * 3), gvalid=(gv, B * G), act=(act, B * K), prop_act=(prop_act, B * K))
+    for name, (t, n) in want.items():
+        if t is not None and t.numel() != n:
+            raise RuntimeError(f"anchor_stats: {name} has {t.numel()} elements, {n} expected for B, K, C, G = {(B, K, C, G)}")
+    dev = conf.device
+    shapes = dict(hist_score=((2, 3, int(score_bins)), torch.int64), hist_grad=((2, int(grad_bins)), torch.int64),
+                  label=((B, K, 2), torch.int32), value=((B, K, 2), torch.float32), grad=((B, K, 2), torch.float32))
+    res = {}
+    for k, (shape, dtype) in shapes.items():
+        if out is not None and out.get(k) is not None:
+            L.require_device(out[k])
+            if tuple(out[k].shape) != shape or out[k].dtype != dtype:
+                raise RuntimeError(f"anchor_stats: out[{k!r}] must be {shape} {dtype}")
+            res[k] = out[k]
+        elif k.startswith('hist'):
+            if out is not None:
+                raise RuntimeError(f"anchor_stats: out must hold {k}")
+            res[k] = torch.zeros(shape, dtype=dtype, device=dev)
+        else:
+            res[k] = torch.empty(shape, dtype=dtype, device=dev) if rows else None
+    L.check(L.lib().otal_anchor_stats(L.ptr(loc), L.ptr(conf), L.ptr(prop_conf), L.ptr(center), _opt(act), _opt(prop_act),
+                                      L.ptr(priors), L.ptr(gt), L.ptr(gv), B, K, C, G, float(clip_length), float(overlap_thresh),
+                                      int(bool(os_head)), int(n_known), TARGETS.index(target), int(score_bins), int(grad_bins),
+                                      L.ptr(res['hist_score']), L.ptr(res['hist_grad']), _opt(res['label']), _opt(res['value']),
+                                      _opt(res['grad']), L.stream()), "otal_anchor_stats")
+    return res
