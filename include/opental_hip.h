@@ -679,6 +679,15 @@ int otal_prepare_clips(const unsigned char* frames, const void* params, float* o
  * on the host.  `out` or `out_ssl` may be null (not both); frame_map is required with out_ssl. */
 int otal_prepare_clips_map(const unsigned char* frames, const void* params, const int* frame_map, float* out,
                            float* out_ssl, int B, int T, int Hs, int Ws, int Ho, int Wo, void* stream);
+/* otal_prepare_clips_map for source frames (T',Hs,Ws,C_src) written as C_out planes: out / out_ssl are (B,C_out,T,Ho,Wo).
+ * Planes c < C_src are ((float)px / 255.0f) * 2.0f - 1.0f as above; planes C_src <= c < C_out are +0.0f everywhere, padding
+ * frames included.  C_src = 2, C_out = 3 is how a 2-channel optical-flow clip is trained: Conv3d_1a multiplies the third
+ * plane with an all-zero weight slice (common/i3d_backbone.py).  The same 24-byte records, flip bits and frame map; frame0
+ * counts bytes of the C_src-channel buffer.  Supported: C_src in {2, 3} with C_src <= C_out <= 3 (else OTAL_E_UNSUPPORTED);
+ * C_src = C_out = 3 gives otal_prepare_clips_map's result bit for bit.  Null and shape errors as above, answered before any
+ * launch.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_prepare_clips_ch(const unsigned char* frames, const void* params, const int* frame_map, float* out, float* out_ssl,
+                          int B, int C_src, int C_out, int T, int Hs, int Ws, int Ho, int Wo, void* stream);
 
 /* Sliding windows of the inference path: B windows cut out of planar uint8 videos (C,Tv,H,W) resident on the device
  * -> normalised fp32 batch (B,C,T,H,W) in one pass.  Replaces AFSD/thumos14/test.py:67-76 prepare_clip per window

@@ -71,6 +71,11 @@ def build_training(config, device, random_init=False, dist_group=None, **trainer
     from .BDNet import BDNet, model_cfg_from
     from .multisegment_loss import MultiSegmentLoss
     tr, md = config['training'], config['model']
+    if int(md['in_channels']) != 3:
+        # the optical-flow stream is trained for THUMOS14 only (opental_amd.thumos14.train): anet/test.py has no fusion, and
+        # the ActivityNet loader reads rgb frames
+        raise RuntimeError(f"opental_amd.anet.train: model.in_channels is {md['in_channels']}; ActivityNet trains the rgb "
+                           "stream only (in_channels: 3) -- flow training is opental_amd.thumos14.train")
     net = BDNet(in_channels=md['in_channels'], backbone_model=md.get('backbone_model'), training=not random_init,
                 frame_num=config['dataset']['training']['clip_length'], use_edl=md.get('use_edl', False), cfg=model_cfg_from(config))
     if random_init:                 # no pretrained I3D file (synthetic runs): the architecture's glorot initialisation

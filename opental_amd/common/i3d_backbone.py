@@ -103,6 +103,58 @@ _ENDPOINTS = (
 )
 
 
+class ExtendWeightFunction(Function):
+    """A (Cout,2,kt,kh,kw) weight as the (Cout,3,kt,kh,kw) weight whose third input slice is zero: the zero-plane rule of the
+    optical-flow stream.  A flow batch lives on the device as three planes, the third +0.0 (otal_prepare_clips_ch), so
+    Conv3d_1a of a 2-channel network runs the kernels of the 3-channel layer -- every product with the extra plane is
+    0 * 0, the result is the 2-channel convolution -- and the weight gradient's third slice, sum dy * 0 = 0, is dropped.
+
+    forward(w2, buf): copies w2 into slices 0..1 of `buf`, a persistent buffer whose slice 2 was zeroed when it was made
+    (InceptionI3d._extended_weight) and is never written, and returns an alias of it.  backward: the first two slices of
+    the incoming gradient -- written into w2's slice of a running trainer's gradient arena where there is one (ops.grad_slot),
+    so the step has two 176 KB copies more than the rgb step and nothing else."""
+
+    @staticmethod
+    def forward(ctx, w2, buf):
+        if w2.dim() != 5 or w2.shape[1] != 2 or tuple(buf.shape) != (w2.shape[0], 3) + tuple(w2.shape[2:]) \
+                or buf.dtype != w2.dtype or buf.device != w2.device:
+            raise RuntimeError("ExtendWeightFunction: a (Cout,2,kt,kh,kw) weight and a (Cout,3,kt,kh,kw) buffer of its dtype / device")
+        buf[:, :2].copy_(w2.detach())
+        ctx.w2 = w2
+        return buf.detach()         # a new tensor on the buffer's storage: the graph hangs on it, not on the persistent buffer
+
+    @staticmethod
+    def backward(ctx, g3):
+        w2, ctx.w2 = ctx.w2, None
+        slot = ops.grad_slot(w2) if g3.is_cuda else None
+        if slot is not None:
+            slot.copy_(g3[:, :2])
+            return slot, None
+        return g3[:, :2].contiguous(), None
+
+
+def check_clip_planes(weight_channels, x):
+    """The planes of a clip batch against the first layer's input slices.  A 2-channel (optical-flow) network takes 2-plane
+    clips, or 3-plane clips that their producer flagged as zero-plane batches (input_pipeline.mark_zero_plane: ClipStager,
+    prepare_clips); anything else is refused -- rgb frames must never train a flow network through a coincidence of shapes,
+    nor flow frames an rgb network.  Returns True when the zero-plane path applies."""
+    from .input_pipeline import is_zero_plane
+    planes = int(x.shape[1])
+    if weight_channels == 2 and planes == 3:
+        if not is_zero_plane(x):
+            raise RuntimeError("a 2-channel (optical-flow) network was handed a 3-plane clip batch that is not flagged as a "
+                               "zero-plane flow batch (rgb frames?): flow batches come from ClipStager(channels=2) / "
+                               "prepare_clips on (T,H,W,2) frames")
+        return True
+    if is_zero_plane(x) and weight_channels != 2:
+        raise RuntimeError(f"a zero-plane optical-flow batch was handed to a network with {weight_channels} input channels "
+                           "(in_channels must be 2)")
+    if planes != weight_channels:
+        raise RuntimeError(f"clip batch has {planes} planes, the network's first layer takes {weight_channels} "
+                           "(rgb clips have 3, optical-flow clips 2)")
+    return False
+
+
 class InceptionI3d(nn.Module):
     VALID_ENDPOINTS = tuple(n for n, _, _ in _ENDPOINTS) + ('Logits', 'Predictions')
 
@@ -155,6 +207,7 @@ class InceptionI3d(nn.Module):
         if self._plan is None:
             self._plan = self._make_plan()
         plan, units = self._plan
+        zero_plane = check_clip_planes(int(units[0].conv3d.weight.shape[1]), x)
         for u in units:
             if u.bn.training or (torch.is_grad_enabled() and u.bn.weight.requires_grad):
                 raise NotImplementedError("I3D BatchNorm must be frozen (freeze_bn + freeze_bn_affine, BDNet.py:39-49)")
@@ -171,6 +224,10 @@ class InceptionI3d(nn.Module):
             self._fold_key = key
         scale, shift, offs = self._fold
         weights = [u.conv3d.weight for u in units]
+        if zero_plane:
+            # the flow stream: Conv3d_1a's 2-slice weight extended by a zero slice.  Not a parameter and not in a trainer's
+            # arena: its gradient comes back from the node as a tensor and reaches the 2-slice parameter through autograd.
+            weights[0] = ExtendWeightFunction.apply(weights[0], self._extended_weight(weights[0]))
         cut = self._stem_cut(plan, endpoints) if self.split_backward else 0
         if cut:
             # Two autograd nodes instead of one, cut behind MaxPool3d_4a: a data-parallel trainer runs the backward pass
@@ -191,6 +248,19 @@ class InceptionI3d(nn.Module):
             self.stem_out = None
             outs = I3DFeaturesFunction.apply(x, plan, tuple(endpoints), scale, shift, offs, *weights)
         return dict(zip(endpoints, outs))
+
+    _w3 = None                  # the persistent (64,3,7,7,7) buffer of the zero-plane path (ExtendWeightFunction)
+
+    def _extended_weight(self, w2):
+        buf = self._w3
+        if buf is None or buf.device != w2.device or buf.dtype != w2.dtype:
+            # slice 2 is zeroed HERE, once; every forward pass overwrites slices 0..1 only
+            if w2.is_cuda and torch.cuda.is_current_stream_capturing():
+                # (a buffer born inside a capture would live in the graph's memory pool and die with the graph)
+                raise RuntimeError("the zero-plane weight buffer cannot be created inside a graph capture: run one eager "
+                                   "forward pass of the flow network first")
+            buf = self._w3 = torch.zeros((w2.shape[0], 3) + tuple(w2.shape[2:]), dtype=w2.dtype, device=w2.device)
+        return buf
 
     split_backward = False      # set by a trainer that wants the two-phase backward (see extract_features)
     detach_cut = False          # ... and, while it captures the two phases, the autograd graph broken at the cut

@@ -31,17 +31,49 @@ def sample_crop_flip(h, w, crop, training, rng=random):
 _PARAM_DTYPE = np.dtype([("frame0", "<i8"), ("valid_t", "<i4"), ("crop_i", "<i4"), ("crop_j", "<i4"), ("flip", "<i4")])
 
 
+ZERO_PLANE_ATTR = "otal_zero_plane"
+
+
+def mark_zero_plane(clips):
+    """Flag a (B,3,T,H,W) batch whose planes 0 and 1 are the two optical-flow channels and whose plane 2 is +0.0 everywhere
+    (otal_prepare_clips_ch with C_src 2, C_out 3).  A 2-channel network takes a 3-plane batch only with this flag
+    (common/i3d_backbone.py): real rgb frames must never train a flow network through a coincidence of shapes.  The flag
+    lives on the tensor OBJECT; whoever copies such a batch into another tensor carries it over (`carry_zero_plane`)."""
+    setattr(clips, ZERO_PLANE_ATTR, True)
+    return clips
+
+
+def is_zero_plane(clips):
+    return bool(getattr(clips, ZERO_PLANE_ATTR, False))
+
+
+def carry_zero_plane(src, dst):
+    if is_zero_plane(src):
+        mark_zero_plane(dst)
+    return dst
+
+
+def clip_channels(video, what="videos"):
+    """2 (optical flow) or 3 (rgb): the channel count of a uint8 (T,H,W,C) video, refusing everything else."""
+    if video.dtype != torch.uint8 or video.dim() != 4 or int(video.shape[3]) not in (2, 3):
+        raise RuntimeError(f"{what} must be uint8 (T,H,W,3) rgb or (T,H,W,2) optical-flow frames, got "
+                           f"{tuple(video.shape)} {video.dtype}")
+    return int(video.shape[3])
+
+
 def prepare_clips(videos, offsets, clip_length=256, crop=96, training=True, device="cuda", rng=random, decisions=None):
-    """videos: list of uint8 arrays (T_i,H,W,3) (numpy or torch); offsets: first frame of each clip.
-    Returns the fp32 batch (B,3,clip_length,crop,crop) on `device` and the list of (i, j, flip) decisions used."""
+    """videos: list of uint8 arrays (T_i,H,W,C) (numpy or torch), C = 3 (rgb) or 2 (optical flow), one C per batch; offsets:
+    first frame of each clip.  Returns the fp32 batch (B,3,clip_length,crop,crop) on `device` -- for C = 2 with an all-zero
+    third plane and the zero-plane flag (`mark_zero_plane`) -- and the list of (i, j, flip) decisions used."""
     B = len(videos)
     H, W = int(videos[0].shape[1]), int(videos[0].shape[2])
+    C = clip_channels(torch.as_tensor(videos[0]))
     chunks, recs, used = [], np.zeros(B, _PARAM_DTYPE), []
     pos = 0
     for b, (v, off) in enumerate(zip(videos, offsets)):
         v = torch.as_tensor(v)
-        if v.dtype != torch.uint8 or v.dim() != 4 or v.shape[3] != 3 or tuple(v.shape[1:3]) != (H, W):
-            raise RuntimeError("videos must be uint8 (T,H,W,3) with one frame size per batch")
+        if v.dtype != torch.uint8 or v.dim() != 4 or tuple(v.shape[1:]) != (H, W, C):
+            raise RuntimeError("videos must be uint8 (T,H,W,3) or (T,H,W,2) with one frame size and channel count per batch")
         sl = v[off: off + clip_length].contiguous()
         i, j, flip = decisions[b] if decisions is not None else sample_crop_flip(H, W, crop, training, rng)
         used.append((i, j, flip))
@@ -52,8 +84,13 @@ def prepare_clips(videos, offsets, clip_length=256, crop=96, training=True, devi
     params = torch.from_numpy(recs.view(np.uint8).copy()).to(device, non_blocking=True)
     out = torch.empty((B, 3, clip_length, crop, crop), dtype=torch.float32, device=device)
     L.require_device(frames, params, out)
-    L.check(L.lib().otal_prepare_clips(L.ptr(frames), L.ptr(params), L.ptr(out), B, clip_length, H, W, crop, crop,
-                                       L.stream()), "otal_prepare_clips")
+    if C == 3:
+        L.check(L.lib().otal_prepare_clips(L.ptr(frames), L.ptr(params), L.ptr(out), B, clip_length, H, W, crop, crop,
+                                           L.stream()), "otal_prepare_clips")
+    else:
+        L.check(L.lib().otal_prepare_clips_ch(L.ptr(frames), L.ptr(params), None, L.ptr(out), None, B, C, 3, clip_length,
+                                              H, W, crop, crop, L.stream()), "otal_prepare_clips_ch")
+        mark_zero_plane(out)
     return out, used
 
 

@@ -5,13 +5,15 @@ Same names and the same host-side arithmetic as the reference -- `get_class_inde
 `THUMOS_Dataset` :144-275 (incl. the self-supervised clip splice `augment_` :187-228) -- but no pixel is touched on
 the host:
 
-  * `load_video_data` keeps the uint8 frames as stored, (T,H,W,3), in PINNED host memory;
+  * `load_video_data` keeps the uint8 frames as stored, (T,H,W,3) rgb or (T,H,W,2) optical flow, in PINNED host memory;
   * a sample is a list of DECISIONS -- clip offset, crop corner, flip, and for the ssl branch a 256-entry frame map --
     taken with the reference's exact sequence of `random` calls, so a seeded run draws the same numbers;
   * `ClipStager` slices the clips' uint8 frames straight out of the pinned videos with asynchronous copies on a copy
     stream into one of two device staging buffers (double buffering: batch k+1 travels over PCIe while step k runs), and
     `otal_prepare_clips_map` (csrc/input.hip) writes the normalised (B,3,T,96,96) batch AND the spliced ssl batch from the
     same upload.  The reference builds both clips in numpy / torch-CPU per sample and uploads 2 x 28 MB of fp32.
+    Optical-flow frames (`ClipStager(channels=2)`) go through `otal_prepare_clips_ch` and come out as three planes, the
+    third all zero, flagged as a zero-plane batch (input_pipeline.mark_zero_plane; common/i3d_backbone.py takes it from there).
 """
 import ctypes
 import math
@@ -22,7 +24,8 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from .input_pipeline import _PARAM_DTYPE, LabelRecord, max_target_count, sample_crop_flip  # noqa: F401
+from .input_pipeline import (_PARAM_DTYPE, LabelRecord, clip_channels, mark_zero_plane, max_target_count,  # noqa: F401
+                             sample_crop_flip)
 
 
 def get_class_index_map(class_info_path='datasets/thumos14/annotations/Class_Index_Detection.txt'):
@@ -111,13 +114,13 @@ def split_videos(video_infos, video_annos, clip_length=256, stride=30):
 
 
 def load_video_data(video_infos, npy_data_path, pin=True):
-    """uint8 (T,H,W,3) frames per video, as stored on disk, in pinned host memory (asynchronous H2D copies need it;
-    the reference transposes to (3,T,H,W) here, thumos_dataset.py:137 -- the device kernel does that instead)."""
+    """uint8 (T,H,W,3) rgb or (T,H,W,2) optical-flow frames per video, as stored on disk, in pinned host memory
+    (asynchronous H2D copies need it; the reference transposes to (C,T,H,W) here, thumos_dataset.py:137 -- the device kernel
+    does that instead)."""
     data_dict = {}
     for video_name in video_infos.keys():
         t = torch.from_numpy(np.load(os.path.join(npy_data_path, video_name + '.npy')))
-        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
-            raise RuntimeError(f"{video_name}.npy: expected uint8 (T,H,W,3)")
+        clip_channels(t, video_name + ".npy")
         data_dict[video_name] = t.pin_memory() if (pin and torch.cuda.is_available()) else t
     return data_dict
 
@@ -206,18 +209,24 @@ class ClipStager:
     otherwise pair batch k's frames with batch k+2's decisions.  That wait is over long before it is reached unless
     the host really is that far ahead."""
 
-    def __init__(self, batch, clip_length, H, W, crop, device="cuda", max_targets=None, score_rows=2, copy_stream=None):
-        """`max_targets` (input_pipeline.max_target_count(dataset)): the batch's labels -- targets padded to that row count,
+    def __init__(self, batch, clip_length, H, W, crop, device="cuda", max_targets=None, score_rows=2, copy_stream=None,
+                 channels=3):
+        """`channels`: 3 (rgb frames) or 2 (optical flow: the batches handed out still have three planes, the third all
+        zero and the batch flagged so, input_pipeline.mark_zero_plane).
+        `max_targets` (input_pipeline.max_target_count(dataset)): the batch's labels -- targets padded to that row count,
         boundary masks, ssl segments -- travel with the frames as ONE fixed-shape record per slot (LabelRecord): one pinned
         buffer, one asynchronous copy; `labels()` hands out the device record of the batch collected last."""
         self.B, self.T, self.H, self.W, self.crop = batch, clip_length, H, W, crop
+        if channels not in (2, 3):
+            raise RuntimeError("ClipStager: channels must be 3 (rgb) or 2 (optical flow)")
+        self.channels = int(channels)
         self.device = torch.device(device)
         self.labels_host = self.labels_dev = None
         if max_targets is not None:
             self.labels_host = [LabelRecord(batch, max_targets, score_rows, clip_length, pin=True) for _ in range(2)]
             self.labels_dev = [LabelRecord(batch, max_targets, score_rows, clip_length, device=self.device) for _ in range(2)]
         self._last = None
-        self.frame_bytes = H * W * 3
+        self.frame_bytes = H * W * self.channels
         self.stage = [torch.empty(batch * clip_length * self.frame_bytes, dtype=torch.uint8, device=self.device) for _ in range(2)]
         self.params_host = [torch.empty(batch * _PARAM_DTYPE.itemsize, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.maps_host = [torch.empty(batch * clip_length, dtype=torch.int32).pin_memory() for _ in range(2)]
@@ -250,8 +259,8 @@ class ClipStager:
             pos = 0
             for b, smp in enumerate(samples):
                 v, off = smp['video'], int(smp['offset'])
-                if tuple(v.shape[1:]) != (self.H, self.W, 3) or v.dtype != torch.uint8:
-                    raise RuntimeError("ClipStager: videos must be uint8 (T,H,W,3) of the configured frame size")
+                if tuple(v.shape[1:]) != (self.H, self.W, self.channels) or v.dtype != torch.uint8:
+                    raise RuntimeError(f"ClipStager: videos must be uint8 (T,H,W,{self.channels}) of the configured frame size")
                 sl = v[off: off + min(self.T, int(smp.get('valid', self.T)))]     # contiguous frame range of the pinned video
                 n = sl.shape[0] * self.frame_bytes
                 self.stage[s][pos: pos + n].copy_(sl.reshape(-1), non_blocking=True)
@@ -287,10 +296,18 @@ class ClipStager:
             raise RuntimeError("ClipStager.collect: `out` must be a contiguous fp32 (B,3,T,crop,crop) tensor")
         clips = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else out
         ssl = torch.empty(shape, dtype=torch.float32, device=self.device) if (any_ssl if want_ssl is None else want_ssl) else None
-        L.check(L.lib().otal_prepare_clips_map(L.ptr(self.stage[s]), L.ptr(self.params_dev[s]),
-                                               L.ptr(self.maps_dev[s]) if ssl is not None else None, L.ptr(clips),
-                                               L.ptr(ssl) if ssl is not None else None, self.B, self.T, self.H, self.W,
-                                               self.crop, self.crop, L.stream()), "otal_prepare_clips_map")
+        fmap, ssl_ptr = (L.ptr(self.maps_dev[s]), L.ptr(ssl)) if ssl is not None else (None, None)
+        if self.channels == 3:
+            L.check(L.lib().otal_prepare_clips_map(L.ptr(self.stage[s]), L.ptr(self.params_dev[s]), fmap, L.ptr(clips), ssl_ptr,
+                                                   self.B, self.T, self.H, self.W, self.crop, self.crop, L.stream()),
+                    "otal_prepare_clips_map")
+        else:       # optical flow: two source channels, three planes out, the third +0.0 (the zero-plane rule)
+            L.check(L.lib().otal_prepare_clips_ch(L.ptr(self.stage[s]), L.ptr(self.params_dev[s]), fmap, L.ptr(clips), ssl_ptr,
+                                                  self.B, self.channels, 3, self.T, self.H, self.W, self.crop, self.crop,
+                                                  L.stream()), "otal_prepare_clips_ch")
+            mark_zero_plane(clips)
+            if ssl is not None:
+                mark_zero_plane(ssl)
         self.consumed[s].record(cur)
         self._last = s
         return clips, ssl

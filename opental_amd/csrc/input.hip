@@ -86,6 +86,98 @@ __global__ __launch_bounds__(256) void prepare_clips_map_kernel(const unsigned c
     }
 }
 
+// The map kernel's preparation for CS source channels written as CO >= CS output planes (otal_prepare_clips_ch): planes
+// c < CS are the normalised pixels, planes CS <= c < CO are +0.0f everywhere, padding frames included -- a 2-channel
+// optical-flow clip becomes the 3-plane batch whose third plane the first layer multiplies with an all-zero weight slice.
+// HBM-bound: CS bytes read + 4 CO written per pixel (flow: 2 + 12).  V pixels per thread: V = 4 where a crop row is a whole
+// number of 16-byte groups (three 16-byte stores per thread, each wave instruction one contiguous 1 KB run per plane),
+// V = 1 for any other shape (dword stores, coalesced along idx as in the kernels above).  A 2-channel pixel is ONE 16-bit
+// load where the clip's first byte sits at an even address (every pixel offset is even; the same answer for a whole workgroup).
+template <int CS>
+__device__ __forceinline__ void load_pixel(const unsigned char* px, bool pair, float* v) {
+    unsigned c0, c1, c2 = 0;
+    if (CS == 2 && pair) {
+        const unsigned w = *reinterpret_cast<const unsigned short*>(px);
+        c0 = w & 0xffu;
+        c1 = w >> 8;
+    } else {
+        c0 = px[0];
+        c1 = px[1];
+        if (CS == 3) c2 = px[2];
+    }
+    v[0] = ((float)c0 / 255.0f) * 2.0f - 1.0f;      // the operation order of the kernels above (no fma: -ffp-contract=off)
+    v[1] = ((float)c1 / 255.0f) * 2.0f - 1.0f;
+    if (CS == 3) v[2] = ((float)c2 / 255.0f) * 2.0f - 1.0f;
+}
+
+template <int CS, int CO, int V>
+__global__ __launch_bounds__(256) void prepare_clips_ch_kernel(const unsigned char* __restrict__ frames,
+                                                               const ClipParams* __restrict__ params,
+                                                               const int* __restrict__ fmap, float* __restrict__ out,
+                                                               float* __restrict__ out_ssl, int T, int Hs, int Ws, int Ho, int Wo) {
+    static_assert(CS >= 2 && CS <= 3 && CO >= CS && CO <= 3 && (V == 1 || V == 4), "unsupported plane counts");
+    const int b = blockIdx.y;
+    const ClipParams p = params[b];
+    const int plane = Ho * Wo;
+    const long long vol = (long long)T * plane;
+    const long long groups = vol / V;                   // V == 4 only with Wo % 4 == 0: a group never leaves its row
+    const unsigned char* src = frames + p.frame0;
+    const bool pair = (reinterpret_cast<unsigned long long>(src) & 1ull) == 0;
+    const float pad = (((p.flip & 2) ? 127.5f : 0.0f) / 255.0f) * 2.0f - 1.0f;
+    for (int pass = 0; pass < 2; ++pass) {
+        float* dst = pass == 0 ? out : out_ssl;
+        if (!dst) continue;
+        float* ob = dst + (long long)b * CO * vol;
+        for (long long gi = (long long)blockIdx.x * 256 + threadIdx.x; gi < groups; gi += (long long)gridDim.x * 256) {
+            const long long idx = gi * V;
+            const int t = (int)(idx / plane);
+            const int r = (int)(idx - (long long)t * plane);
+            const int y = r / Wo, x = r - y * Wo;
+            const int ts = (pass == 1 && fmap) ? fmap[b * T + t] : t;
+            float v[V][3];
+            if (ts >= 0 && ts < p.valid_t) {
+                const unsigned char* row = src + (((long long)ts * Hs + (p.crop_i + y)) * Ws + p.crop_j) * CS;
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const int xo = (p.flip & 1) ? Wo - 1 - (x + j) : x + j;
+                    load_pixel<CS>(row + xo * CS, pair, v[j]);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < V; ++j) v[j][0] = v[j][1] = v[j][2] = pad;
+            }
+#pragma unroll
+            for (int c = 0; c < CO; ++c) {
+                float* o = ob + c * vol + idx;
+                if constexpr (V == 4) {
+                    *reinterpret_cast<float4*>(o) = c < CS ? make_float4(v[0][c], v[1][c], v[2][c], v[3][c])
+                                                           : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                } else {
+                    *o = c < CS ? v[0][c] : 0.0f;
+                }
+            }
+        }
+    }
+}
+
+template <int CS, int CO>
+int launch_prepare_clips_ch(const unsigned char* frames, const ClipParams* params, const int* frame_map, float* out,
+                            float* out_ssl, int B, int T, int Hs, int Ws, int Ho, int Wo, hipStream_t stream) {
+    const long long vol = (long long)T * Ho * Wo;
+    const bool vec = Wo % 4 == 0 && ((reinterpret_cast<unsigned long long>(out) | reinterpret_cast<unsigned long long>(out_ssl)) & 15ull) == 0;
+    const long long groups = vec ? vol / 4 : vol;
+    // a streaming kernel: about eight workgroups per CU over the whole grid (256 CUs), the rest by grid stride
+    const long long cap = 2048 / B > 0 ? 2048 / B : 1;
+    const int bx = (int)((groups + 255) / 256 < cap ? (groups + 255) / 256 : cap);
+    if (vec)
+        hipLaunchKernelGGL((prepare_clips_ch_kernel<CS, CO, 4>), dim3(bx, B), dim3(256), 0, stream, frames, params, frame_map, out,
+                           out_ssl, T, Hs, Ws, Ho, Wo);
+    else
+        hipLaunchKernelGGL((prepare_clips_ch_kernel<CS, CO, 1>), dim3(bx, B), dim3(256), 0, stream, frames, params, frame_map, out,
+                           out_ssl, T, Hs, Ws, Ho, Wo);
+    return otal_launch_status();
+}
+
 struct WindowParams {    // one per inference window, device array (16 bytes)
     unsigned long long src;  // device address of frame `offset` of channel 0 of the window's video (planar uint8 (C,Tv,H,W))
     int chan_stride4;        // Tv * H * W / 4: distance between the channels of that video, in 4-byte words
@@ -157,4 +249,18 @@ extern "C" int otal_prepare_clips_map(const unsigned char* frames, const void* p
     hipLaunchKernelGGL(prepare_clips_map_kernel, dim3(bx, B), dim3(256), 0, (hipStream_t)stream, frames,
                        static_cast<const ClipParams*>(params), frame_map, out, out_ssl, T, Hs, Ws, Ho, Wo);
     return otal_launch_status();
+}
+
+extern "C" int otal_prepare_clips_ch(const unsigned char* frames, const void* params, const int* frame_map, float* out,
+                                     float* out_ssl, int B, int C_src, int C_out, int T, int Hs, int Ws, int Ho, int Wo,
+                                     void* stream) {
+    if (!frames || !params || (!out && !out_ssl)) return OTAL_E_NULL;
+    if (out_ssl && !frame_map) return OTAL_E_NULL;
+    if (B <= 0 || T <= 0 || Hs <= 0 || Ws <= 0 || Ho <= 0 || Wo <= 0 || Ho > Hs || Wo > Ws) return OTAL_E_SHAPE;
+    if (B > 65535 || C_src < 2 || C_src > 3 || C_out < C_src || C_out > 3) return OTAL_E_UNSUPPORTED;
+    const ClipParams* cp = static_cast<const ClipParams*>(params);
+    hipStream_t st = (hipStream_t)stream;
+    if (C_src == 3) return launch_prepare_clips_ch<3, 3>(frames, cp, frame_map, out, out_ssl, B, T, Hs, Ws, Ho, Wo, st);
+    if (C_out == 3) return launch_prepare_clips_ch<2, 3>(frames, cp, frame_map, out, out_ssl, B, T, Hs, Ws, Ho, Wo, st);
+    return launch_prepare_clips_ch<2, 2>(frames, cp, frame_map, out, out_ssl, B, T, Hs, Ws, Ho, Wo, st);
 }

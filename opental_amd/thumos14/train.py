@@ -25,7 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..common import ops
-from ..common.input_pipeline import PaddedTargets
+from ..common.input_pipeline import PaddedTargets, carry_zero_plane, is_zero_plane
 
 
 def calc_bce_loss(start, end, scores):
@@ -132,7 +132,7 @@ def _clone_inputs(clips, targets, scores):
         if flat is None:
             return t.clone()
         return torch.empty(0, dtype=t.dtype, device=t.device).set_(flat.untyped_storage(), t.storage_offset(), t.shape, t.stride())
-    c = one(clips)
+    c = carry_zero_plane(clips, one(clips))     # (an optical-flow batch stays flagged as one: common/i3d_backbone.py)
     if isinstance(targets, PaddedTargets):
         tg = PaddedTargets(one(targets.gt), one(targets.valid))
     elif isinstance(targets, (list, tuple)):
@@ -863,6 +863,10 @@ class DetectorTrainer:
         dsts, srcs = _flatten_inputs(*static), _flatten_inputs(*given)
         if len(dsts) != len(srcs):
             raise RuntimeError("captured step replayed with a different batch; call capture_step again")
+        if is_zero_plane(dsts[0]) != is_zero_plane(srcs[0]):
+            # a replay runs no forward check: rgb frames must not reach a captured optical-flow step (or the reverse)
+            raise RuntimeError("captured step replayed with a clip batch of the other kind (rgb frames / zero-plane "
+                               "optical-flow batch)")
         key = tuple((d.data_ptr(), g.data_ptr()) for d, g in zip(dsts, srcs))
         plan = self._copy_plans.get(key)
         if plan is None:
@@ -1083,6 +1087,18 @@ def build_training(config, device, as_shipped=False, random_init=False, dist_gro
     return net, crit, trainer
 
 
+def check_stream_channels(config, video):
+    """The channel count of the run's frames -- 3: rgb, 2: optical flow (`model.in_channels: 2`, configs/
+    thumos14_opental_flow.yaml) -- which must be the network's: a flow network is never fed rgb frames, nor the reverse."""
+    want, have = int(config['model']['in_channels']), int(video.shape[3])
+    if want not in (2, 3):
+        raise SystemExit(f"model.in_channels is {want}: 3 (rgb) or 2 (optical flow)")
+    if want != have:
+        raise SystemExit(f"model.in_channels is {want} but the videos under dataset.training.video_data_path have {have} "
+                         "channels (rgb .npy files are (T,H,W,3), optical-flow ones (T,H,W,2))")
+    return have
+
+
 def rank_batches(every, rank, world):
     """The batches of one epoch that rank `rank` of `world` runs: every world-th one of a list truncated to a multiple of
     `world` -- drop_last across ranks.  Every rank must run the SAME number of steps (each step's bucket / IBM / used-mask
@@ -1223,6 +1239,8 @@ def main(argv=None):
       --log_every N           per-step loss line every N steps through asynchronous D2H copies (StepLog; 0 = epoch lines only)
       --launch lanes|eager    lanes (default): plain steps replay captured HIP graphs on two streams (DetectorTrainer.
                               capture_step(lanes=True)) from fixed-shape label records; eager: one launch at a time
+    A yaml with `model.in_channels: 2` (configs/thumos14_opental_flow.yaml) trains the optical-flow stream on uint8 (T,H,W,2)
+    frames: the stager hands out three-plane batches with an all-zero third plane (ClipStager(channels=2)).
     One process per GPU; under torchrun the ranks all-reduce gradients over RCCL (DetectorTrainer)."""
     import os
     import sys
@@ -1266,10 +1284,11 @@ def main(argv=None):
     dataset = D.THUMOS_Dataset(data, infos, annos, clip_length=ds_cfg['clip_length'], crop_size=ds_cfg['crop_size'],
                                stride=ds_cfg['clip_stride'])
     any_video = next(iter(data.values()))
+    channels = check_stream_channels(config, any_video)
     stager = D.ClipStager(tr['batch_size'], ds_cfg['clip_length'], int(any_video.shape[1]), int(any_video.shape[2]),
                           ds_cfg['crop_size'], device=dev, max_targets=D.max_target_count(dataset), score_rows=2,
-                          copy_stream=ops.side_wgrads(dev).side)       # the next batch crosses PCIe on the weight-gradient
-                                                                        # lane's stream, idle during the forward pass (ClipStager)
+                          copy_stream=ops.side_wgrads(dev).side,       # the next batch crosses PCIe on the weight-gradient
+                          channels=channels)                            # lane's stream, idle during the forward pass (ClipStager)
     trainer.launch = extra['launch']
     checkpoint_path = tr['checkpoint_path']
     train_state_path = os.path.join(checkpoint_path, 'training')
