@@ -311,6 +311,7 @@ int otal_convert_storage(const void* src, int64_t src_bs, int64_t src_cs, void* 
  *   modes[i] 0: the permute(0,2,1).contiguous() only;
  *            1: ScaleExp per pyramid level, exp(scales[l] * x) * level_strides[l] (level_strides null = 1: THUMOS14);
  *            2: permute + DirichletLayer.compute_uncertainty with evidence 'exp' into unct[i] (B, N).
+ *            3, 4: mode 2 with evidence 'relu' / 'softplus' (BDNet.py:541-549; backward: 0 at z <= 0 / sigmoid(z), 1 above 20).
  * lev[0..nlev]: anchor ranges of the levels along N.  _bwd: draw[i] (B, C, N) from dout[i] (B, N, C) and dunct[i] (B, N)
  * (either may be null = zero) and dscales[nlev] (deterministic single-workgroup reduction). */
 int otal_head_outputs_fwd(int n_items, const int* channels, const int* modes, const float* const* raw, float* const* out,
@@ -371,6 +372,16 @@ int otal_decode_clips_ex(const float* loc, const float* prop_loc, const float* p
                          const float* offsets, const float* fps, float* seg, float* score, float* unct,
                          float* actn, unsigned char* flag, int nclips, int A, int K, float clip_length,
                          float conf_thresh, int score_fn, int first_class, void* stream);
+/* otal_decode_clips_ev: otal_decode_clips_ex plus `evidence`, the evidence function of the Dirichlet scores and of the
+ * uncertainty when score_fn is 0 (DirichletLayer.evidence_func, AFSD/thumos14/BDNet.py:541-549; model.evidence of the yaml):
+ * 0 exp(clamp(z, +-10)), 1 relu, 2 softplus (beta 1, threshold 20); alpha = evidence + 1.  score_fn 1 ignores it.
+ * evidence 0 == otal_decode_clips_ex(...) bit for bit; another value: OTAL_E_UNSUPPORTED.  An additive entry:
+ * OTAL_ABI_VERSION is unchanged. */
+int otal_decode_clips_ev(const float* loc, const float* prop_loc, const float* priors, const float* conf,
+                         const float* prop_conf, const float* center, const float* act, const float* prop_act,
+                         const float* offsets, const float* fps, float* seg, float* score, float* unct,
+                         float* actn, unsigned char* flag, int nclips, int A, int K, float clip_length,
+                         float conf_thresh, int score_fn, int first_class, int evidence, void* stream);
 /* otal_softnms_classes: for every (video, class) gather the flagged candidates of the video's clips
  * [clip_start[v], clip_start[v+1]) in clip-major / anchor-minor order and run softnms_v2
  * (AFSD/common/segment_utils.py:128-162; get_video_detections, test.py:165-200).
@@ -442,6 +453,15 @@ int otal_anchor_stats(const float* loc, const float* conf, const float* prop_con
                       int C, int G, float clip_length, float overlap_thresh, int os_head, int n_known, int target,
                       int score_bins, int grad_bins, long long* hist_score, long long* hist_grad, int* label, float* value,
                       float* grad, void* stream);
+/* otal_anchor_stats_ev: otal_anchor_stats with the network's evidence function (grad_edl reads the model's evidence,
+ * experiments/analyze_gradnorm.py:164-184): alpha = evidence(z) + 1 with evidence 0 exp, 1 relu, 2 softplus in S, in the
+ * scores and in the gradient.  evidence 0 == otal_anchor_stats(...); another value: OTAL_E_UNSUPPORTED.  An additive entry:
+ * OTAL_ABI_VERSION is unchanged. */
+int otal_anchor_stats_ev(const float* loc, const float* conf, const float* prop_conf, const float* center, const float* act,
+                         const float* prop_act, const float* priors, const float* gt, const unsigned char* gvalid, int B,
+                         int K, int C, int G, float clip_length, float overlap_thresh, int os_head, int n_known, int target,
+                         int score_bins, int grad_bins, long long* hist_score, long long* hist_grad, int* label,
+                         float* value, float* grad, int evidence, void* stream);
 
 /* ------------------------------------------------------------------ OpenMax baseline (csrc/openmax.hip) ----
  * Added under ABI 26 (new symbols only).  Feature rows are addressed by ELEMENT strides: row n (0 <= n < N), channel d at
@@ -602,6 +622,25 @@ int otal_detection_loss_ex(const float* loc, const float* conf, const float* pro
                            float clip_length, float overlap_thresh, int ibm_active, int num_bins, float momentum,
                            int iou_aware, int cls_mode, float focal_alpha, int reweight, float rw_gamma, float* losses,
                            float* grads, float* scratch, void* stream);
+/* otal_detection_loss_ev: otal_detection_loss_ex for cls_mode 0 and 2 with the other standard EDL settings of the reference
+ * (AFSD/thumos14/cls_loss.py:171-190 get_loss_func / evidence_func, :193-209 mse_loss, :281-285 loglikelihood_loss;
+ * training.edl_config.evidence and .loss_type of the yaml).  The arithmetic is csrc/evidence.h:
+ *   evidence  0 exp(clamp(z, +-10)) (backward: exp(z) inside the closed interval, else 0), 1 relu (backward 0 at z == 0),
+ *             2 softplus, beta 1, threshold 20 (backward 1 above the threshold, else sigmoid(z)); alpha = evidence + 1;
+ *   loss_type 0 log S - log alpha_y, 1 digamma(S) - digamma(alpha_y) (fp32 recurrence up to 6, then the asymptotic series),
+ *             2 mse: sum_k (y_k - alpha_k / S)^2 + sum_k alpha_k (S - alpha_k) / (S^2 (S + 1)).
+ * The re-weighting rules (ibm_active, reweight 1..3) apply to loss_type 0 and 1 with the detached weights |1/alpha_y - C/S|
+ * of the selected evidence; focal-EDL's weight carries gradient through d alpha / d z.  The reference's mse_loss applies no
+ * rule: loss_type 2 with ibm_active or reweight != 0 is OTAL_E_UNSUPPORTED.  The IoU calibration uses u = C / S of the
+ * selected evidence and no clamp: a relu row whose logits are all <= 0 has u = 1 and gives -inf, as the reference does.
+ * (evidence, loss_type) = (0, 0) == otal_detection_loss_ex(...) bit for bit.  cls_mode 1 / 3, a kind out of range:
+ * OTAL_E_UNSUPPORTED, before any read or launch.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_detection_loss_ev(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                           const float* center, const float* act, const float* prop_act, const float* priors,
+                           const float* gt, const unsigned char* gvalid, float* weight_accum, int B, int K, int C, int G,
+                           float clip_length, float overlap_thresh, int ibm_active, int num_bins, float momentum,
+                           int iou_aware, int cls_mode, float focal_alpha, int reweight, float rw_gamma, int evidence,
+                           int loss_type, float* losses, float* grads, float* scratch, void* stream);
 
 /* The same for the ActivityNet1.3 recipe (ABI 22): AFSD/anet/multisegment_loss.py:87-301 with anet/cls_loss.py:78-246
  * (EvidenceLoss 'log', exp evidence, the closed-form influence-balanced weight 1 / (|z|_1 exp(ibm_coeff g) + 1e-10) whose

@@ -131,12 +131,27 @@ def score_bin(v, bins):
     return np.where(np.isnan(v), -1, b)
 
 
+def alpha_of(z, evidence='exp'):
+    """alpha = evidence(z) + 1 in float32 (DirichletLayer.evidence_func; csrc/evidence.h)."""
+    z = np.asarray(z, np.float32)
+    one = np.float32(1)
+    if evidence == 'exp':
+        return (np.exp(np.clip(z, np.float32(-10), np.float32(10))) + one).astype(np.float32)
+    if evidence == 'relu':
+        return (np.maximum(z, np.float32(0)) + one).astype(np.float32)
+    if evidence == 'softplus':
+        with np.errstate(over='ignore'):
+            return (np.where(z > np.float32(20), z, np.log1p(np.exp(z))) + one).astype(np.float32)
+    raise NotImplementedError(f"evidence {evidence!r}")
+
+
 def anchor_stats_reference(loc, conf, prop_conf, center, act, prop_act, priors, gt, gvalid, clip_length, overlap_thresh,
                            os_head, n_known, target, score_bins=100, grad_bins=100, use_edl=True, hist_score=None,
-                           hist_grad=None):
+                           hist_grad=None, evidence='exp'):
     """The rule on host arrays -> dict(label int32, value fp32, grad fp32, counts bool (B, K, 2): the rows of the gradient;
     group int32 (B, K, 2): GROUPS index; hist_score, hist_grad int64 (added to the arrays passed in, or fresh); iou, area_gap:
-    match_reference's margins).  Sums over the classes run in float32 in the order of the columns, as the kernel's."""
+    match_reference's margins).  Sums over the classes run in float32 in the order of the columns, as the kernel's.
+    evidence: the network's evidence function ('exp', 'relu', 'softplus'; grad_edl, analyze_gradnorm.py:164-184)."""
     check_mode(target, os_head, use_edl, have_act=act is not None and prop_act is not None)
     if int(n_known) < 1 or score_bins < 1 or grad_bins < 1:
         raise ValueError("n_known, score_bins and grad_bins are at least 1")
@@ -151,7 +166,7 @@ def anchor_stats_reference(loc, conf, prop_conf, center, act, prop_act, priors, 
     hist_grad = np.zeros((2, grad_bins), np.int64) if hist_grad is None else hist_grad
     group = group_of(label, n_known)
     for s, (z, a) in enumerate(((conf, act), (prop_conf, prop_act))):
-        alpha = (np.exp(np.clip(z, np.float32(-10), np.float32(10))) + np.float32(1)).astype(np.float32)
+        alpha = alpha_of(z, evidence)
         S = np.zeros((B, K), np.float32)
         for k in range(C):
             S = S + alpha[:, :, k]
@@ -187,20 +202,21 @@ def anchor_stats_reference(loc, conf, prop_conf, center, act, prop_act, priors, 
 
 
 def anchor_stats(loc, conf, prop_conf, center, act, prop_act, priors, gt, gvalid, clip_length, overlap_thresh, os_head, n_known,
-                 target, score_bins=100, grad_bins=100, use_edl=True, out=None, rows=True):
-    """The statistics of a batch of windows: device tensors go through otal_anchor_stats (`out`, `rows`: ops.anchor_stats),
-    host tensors through `anchor_stats_reference` (returned as host tensors; out['hist_score'] / out['hist_grad'] are added to)."""
+                 target, score_bins=100, grad_bins=100, use_edl=True, out=None, rows=True, evidence='exp'):
+    """The statistics of a batch of windows: device tensors go through otal_anchor_stats / otal_anchor_stats_ev (`out`, `rows`:
+    ops.anchor_stats), host tensors through `anchor_stats_reference` (returned as host tensors; out['hist_score'] /
+    out['hist_grad'] are added to).  evidence: the network's evidence function."""
     check_mode(target, os_head, use_edl, have_act=act is not None and prop_act is not None)
     if conf.is_cuda:
         from . import ops
         return ops.anchor_stats(loc, conf, prop_conf, center, act, prop_act, priors, gt, gvalid, clip_length, overlap_thresh,
-                                os_head, n_known, target, score_bins, grad_bins, out=out, rows=rows)
+                                os_head, n_known, target, score_bins, grad_bins, out=out, rows=rows, evidence=evidence)
     npy = lambda t: None if t is None else t.detach().numpy()
     hs = None if out is None else out['hist_score'].numpy()
     hg = None if out is None else out['hist_grad'].numpy()
     ref = anchor_stats_reference(npy(loc), npy(conf), npy(prop_conf), npy(center), npy(act), npy(prop_act), npy(priors), npy(gt),
                                  npy(gvalid), clip_length, overlap_thresh, os_head, n_known, target, score_bins, grad_bins,
-                                 hist_score=hs, hist_grad=hg)
+                                 hist_score=hs, hist_grad=hg, evidence=evidence)
     keys = ('hist_score', 'hist_grad') + (('label', 'value', 'grad') if rows else ())
     res = {k: torch.as_tensor(ref[k]) for k in keys}
     for k in ('label', 'value', 'grad'):

@@ -15,6 +15,7 @@ import ctypes
 import torch
 
 from .. import _lib as L
+from .ops import EVIDENCE
 
 
 def get_offsets(sample_count, clip_length, stride):
@@ -87,9 +88,13 @@ def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01, o
     """Batched parse_output + decode_predictions + threshold masks.  output_dict: model outputs for
     `n` clips; offsets/fps: per-clip tensors or lists.  Returns dict(seg, score, unct, actn, flag).
     os_head / use_edl / evidence: the network's head (head_mode).  The closed-set head (os_head False) has a background
-    logit, which score / flag leave out (K - 1 classes); unct is None without use_edl, actn None without os_head."""
-    if use_edl and evidence != 'exp':
-        raise NotImplementedError(f"evidence {evidence!r}: the decode kernel computes exp evidence only")
+    logit, which score / flag leave out (K - 1 classes); unct is None without use_edl, actn None without os_head.
+    Evidence other than 'exp' goes through otal_decode_clips_ev."""
+    if use_edl and evidence not in EVIDENCE:
+        raise NotImplementedError(f"evidence {evidence!r}: the decode kernel computes {', '.join(EVIDENCE)} evidence")
+    if use_edl and evidence != 'exp' and not output_dict['loc'].is_cuda:
+        # otal_decode_clips_ev reads device memory: a host pointer must not reach it, and there is no host form of this decode
+        raise NotImplementedError(f"evidence {evidence!r} on host tensors: otal_decode_clips_ev decodes device tensors only")
     if os_head and not use_edl:
         raise NotImplementedError("an actionness head with softmax scores is not a THUMOS14 configuration")
     if use_gcpl and (os_head or use_edl):
@@ -99,7 +104,7 @@ def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01, o
     n, A, _ = loc.shape
     K = output_dict['conf'].shape[-1]
     if not os_head:
-        return _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, use_edl)
+        return _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, use_edl, evidence)
     dev = loc.device
     offs, fpst = clip_scalars(offsets, fps, n, dev)
     seg = torch.empty((n, A, 2), device=dev)
@@ -108,17 +113,19 @@ def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01, o
     actn = torch.empty((n, A), device=dev)
     flag = torch.empty((n, K, A), dtype=torch.uint8, device=dev)
     t = lambda k: output_dict[k].contiguous()
-    L.check(L.lib().otal_decode_clips(L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(output_dict['priors'].contiguous()),
-                                      L.ptr(t('conf')), L.ptr(t('prop_conf')), L.ptr(t('center')), L.ptr(t('act')),
-                                      L.ptr(t('prop_act')), L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score),
-                                      L.ptr(unct), L.ptr(actn), L.ptr(flag), n, A, K, ctypes.c_float(clip_length),
-                                      ctypes.c_float(conf_thresh), L.stream()), "otal_decode_clips")
+    head = (L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(output_dict['priors'].contiguous()), L.ptr(t('conf')), L.ptr(t('prop_conf')),
+            L.ptr(t('center')), L.ptr(t('act')), L.ptr(t('prop_act')), L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score),
+            L.ptr(unct), L.ptr(actn), L.ptr(flag), n, A, K, ctypes.c_float(clip_length), ctypes.c_float(conf_thresh))
+    if evidence == 'exp':
+        L.check(L.lib().otal_decode_clips(*head, L.stream()), "otal_decode_clips")
+    else:
+        L.check(L.lib().otal_decode_clips_ev(*head, 0, 0, EVIDENCE[evidence], L.stream()), "otal_decode_clips_ev")
     return dict(seg=seg, score=score, unct=unct, actn=actn, flag=flag)
 
 
-def _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, use_edl):
+def _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, use_edl, evidence='exp'):
     """The closed-set head: otal_decode_clips_ex with softmax (score_fn 1) or Dirichlet (0) scores, class 0 dropped and
-    no actionness (test.py:112-162 with os_head False)."""
+    no actionness (test.py:112-162 with os_head False); Dirichlet scores of relu / softplus evidence: otal_decode_clips_ev."""
     n, A, _ = loc.shape
     K = output_dict['conf'].shape[-1]
     dev = loc.device
@@ -128,12 +135,14 @@ def _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, u
     unct = torch.empty((n, A), device=dev) if use_edl else None
     flag = torch.empty((n, K - 1, A), dtype=torch.uint8, device=dev)
     t = lambda k: output_dict[k].contiguous()
-    L.check(L.lib().otal_decode_clips_ex(L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(output_dict['priors'].contiguous()),
-                                         L.ptr(t('conf')), L.ptr(t('prop_conf')), L.ptr(t('center')), None, None,
-                                         L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score),
-                                         None if unct is None else L.ptr(unct), None, L.ptr(flag), n, A, K,
-                                         ctypes.c_float(clip_length), ctypes.c_float(conf_thresh), 0 if use_edl else 1, 1,
-                                         L.stream()), "otal_decode_clips_ex")
+    head = (L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(output_dict['priors'].contiguous()), L.ptr(t('conf')), L.ptr(t('prop_conf')),
+            L.ptr(t('center')), None, None, L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score),
+            None if unct is None else L.ptr(unct), None, L.ptr(flag), n, A, K, ctypes.c_float(clip_length),
+            ctypes.c_float(conf_thresh), 0 if use_edl else 1, 1)
+    if use_edl and evidence != 'exp':
+        L.check(L.lib().otal_decode_clips_ev(*head, EVIDENCE[evidence], L.stream()), "otal_decode_clips_ev")
+    else:
+        L.check(L.lib().otal_decode_clips_ex(*head, L.stream()), "otal_decode_clips_ex")
     return dict(seg=seg, score=score, unct=unct, actn=None, flag=flag)
 
 

@@ -1432,15 +1432,21 @@ def adam_flat_dev(p, g, m, v, bias_corr, lr, beta1=0.9, beta2=0.999, eps=1e-8, w
 
 
 # ----------------------------------------------------------------------------- fused detection loss
+EVIDENCE = {'exp': 0, 'relu': 1, 'softplus': 2}         # the evidence kinds and loss types of csrc/evidence.h, by their yaml names
+LOSS_TYPE = {'log': 0, 'digamma': 1, 'mse': 2}
+HEAD_UNCT_MODE = {'exp': 2, 'relu': 3, 'softplus': 4}   # the Dirichlet-uncertainty item of otal_head_outputs_fwd per evidence kind
+
+
 class DetectionLossFunction(torch.autograd.Function):
     """The seven loss terms of MultiSegmentLoss (EDL recipe) from ONE launch that also produces every gradient
     (csrc/loss.hip); backward only scales the stored gradients by the incoming scalars.  act / prop_act may be None
-    (closed-set cls_mode 2 / 3): the kernel gets NULL, and their gradients are None."""
+    (closed-set cls_mode 2 / 3): the kernel gets NULL, and their gradients are None.  evidence / loss_type (EVIDENCE,
+    LOSS_TYPE) other than exp / log go through otal_detection_loss_ev (cls_mode 0 and 2)."""
 
     @staticmethod
     def forward(ctx, loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt, gvalid, weight_accum,
                 clip_length, overlap, ibm_active, num_bins, momentum, iou_aware, cls_mode=0, focal_alpha=0.25, reweight=0,
-                rw_gamma=0.0):
+                rw_gamma=0.0, evidence=0, loss_type=0):
         B, K, C = conf.shape
         G = gt.shape[1]
         tens = [None if t is None else t.contiguous().float()
@@ -1459,7 +1465,10 @@ class DetectionLossFunction(torch.autograd.Function):
             L.ptr(gv), L.ptr(weight_accum), B, K, C, G, ctypes.c_float(clip_length), ctypes.c_float(overlap), int(ibm_active),
             int(num_bins), ctypes.c_float(momentum), int(iou_aware), int(cls_mode), ctypes.c_float(focal_alpha)]
         tail = [L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream()]
-        if int(reweight) != 0 or (int(cls_mode) == 2 and ibm_active):
+        if int(evidence) != 0 or int(loss_type) != 0:
+            L.check(lib.otal_detection_loss_ev(*head, int(reweight), ctypes.c_float(rw_gamma), int(evidence), int(loss_type), *tail),
+                    "otal_detection_loss_ev")
+        elif int(reweight) != 0 or (int(cls_mode) == 2 and ibm_active):
             # a re-weighting rule of the loss ablations, or IBM over a closed set (noACT): the extended entry
             L.check(lib.otal_detection_loss_ex(*head, int(reweight), ctypes.c_float(rw_gamma), *tail), "otal_detection_loss_ex")
         else:
@@ -1489,7 +1498,7 @@ class DetectionLossFunction(torch.autograd.Function):
         d_cen, d_act, d_pact = take(A, (B, K)), take(A, (B, K)), take(A, (B, K))
         if not getattr(ctx, 'has_act', True):        # (AnetDetectionLossFunction shares this backward)
             d_act = d_pact = None
-        return (d_loc, d_conf, d_pl, d_pconf, d_cen, d_act, d_pact) + (None,) * 14
+        return (d_loc, d_conf, d_pl, d_pconf, d_cen, d_act, d_pact) + (None,) * 16
 
 
 class AnetDetectionLossFunction(torch.autograd.Function):
@@ -1586,7 +1595,7 @@ class HeadOutputsFunction(torch.autograd.Function):
     apply(levels, level_strides, modes, *scales_then_raws): the nlev one-element ScaleExp parameters (separate tensors, so
     that each receives its own 16-byte-aligned gradient: a 4-byte-offset view would push the trainer's whole multi-tensor
     gradient copy onto its unvectorised path), then raws[i] (B,C_i,N) -> outs[i] (B,N,C_i) for every item, followed by
-    the uncertainty maps (B,N) of the mode-2 items."""
+    the uncertainty maps (B,N) of the Dirichlet items (mode 2, 3, 4: exp, relu, softplus evidence; HEAD_UNCT_MODE)."""
 
     @staticmethod
     def forward(ctx, levels, level_strides, modes, *tensors):
@@ -1600,7 +1609,7 @@ class HeadOutputsFunction(torch.autograd.Function):
         B, _, N = raws[0].shape
         n = len(raws)
         outs = [torch.empty((B, N, r.shape[1]), dtype=torch.float32, device=r.device) for r in raws]
-        uncts = [torch.empty((B, N), dtype=torch.float32, device=raws[0].device) if m == 2 else None for m in modes]
+        uncts = [torch.empty((B, N), dtype=torch.float32, device=raws[0].device) if m >= 2 else None for m in modes]
         VP = ctypes.c_void_p * n
         arr = lambda ts: VP(*[None if t is None else t.data_ptr() for t in ts])
         strides = None if level_strides is None else (ctypes.c_float * len(level_strides))(*level_strides)
@@ -1618,7 +1627,7 @@ class HeadOutputsFunction(torch.autograd.Function):
         scales, raws, outs, us = saved[0], saved[1:1 + n], saved[1 + n:1 + 2 * n], list(saved[1 + 2 * n:])
         uncts, dunct, k = [], [], 0
         for m in ctx.modes:
-            if m == 2:
+            if m >= 2:
                 uncts.append(us[k]); dunct.append(grads[n + k]); k += 1
             else:
                 uncts.append(None); dunct.append(None)
@@ -2011,8 +2020,9 @@ def detection_table(rows, counts, durations=None, drop_empty=False, scoring='unc
 
 
 def anchor_stats(loc, conf, prop_conf, center, act, prop_act, priors, gt, gvalid, clip_length, overlap_thresh, os_head, n_known,
-                 target, score_bins=100, grad_bins=100, out=None, rows=True):
-    """The anchor diagnostics of a batch of windows in one launch (otal_anchor_stats, csrc/anchorstats.hip; the rule:
+                 target, score_bins=100, grad_bins=100, out=None, rows=True, evidence='exp'):
+    """The anchor diagnostics of a batch of windows in one launch (otal_anchor_stats, or otal_anchor_stats_ev for relu / softplus
+    `evidence`; csrc/anchorstats.hip; the rule:
     common/anchor_stats.py): head outputs in the layouts of the detection loss -- loc (B, K, 2), conf / prop_conf (B, K, C),
     center (B, K), act / prop_act (B, K) or both None, priors (K), gt (B, G, 3) padded, gvalid (B, G).
     -> dict(hist_score int64 (2, 3, score_bins), hist_grad int64 (2, grad_bins), label int32 / value fp32 / grad fp32
@@ -2049,9 +2059,16 @@ def anchor_stats(loc, conf, prop_conf, center, act, prop_act, priors, gt, gvalid
             res[k] = torch.zeros(shape, dtype=dtype, device=dev)
         else:
             res[k] = torch.empty(shape, dtype=dtype, device=dev) if rows else None
-    L.check(L.lib().otal_anchor_stats(L.ptr(loc), L.ptr(conf), L.ptr(prop_conf), L.ptr(center), _opt(act), _opt(prop_act),
-                                      L.ptr(priors), L.ptr(gt), L.ptr(gv), B, K, C, G, float(clip_length), float(overlap_thresh),
-                                      int(bool(os_head)), int(n_known), TARGETS.index(target), int(score_bins), int(grad_bins),
-                                      L.ptr(res['hist_score']), L.ptr(res['hist_grad']), _opt(res['label']), _opt(res['value']),
-                                      _opt(res['grad']), L.stream()), "otal_anchor_stats")
+    if evidence not in EVIDENCE:
+        raise NotImplementedError(f"evidence {evidence!r}")
+    head = (L.ptr(loc), L.ptr(conf), L.ptr(prop_conf), L.ptr(center), _opt(act), _opt(prop_act), L.ptr(priors), L.ptr(gt),
+            L.ptr(gv), B, K, C, G, float(clip_length), float(overlap_thresh), int(bool(os_head)), int(n_known),
+            TARGETS.index(target), int(score_bins), int(grad_bins), L.ptr(res['hist_score']), L.ptr(res['hist_grad']),
+            _opt(res['label']), _opt(res['value']), _opt(res['grad']))
+    if evidence == 'exp':
+        L.check(L.lib().otal_anchor_stats(*head, L.stream()), "otal_anchor_stats")
+    else:
+        fn = L.lib().otal_anchor_stats_ev           # otal_anchor_stats's prototype (_lib.py) with the kind in front of the stream
+        fn.argtypes = L.lib().otal_anchor_stats.argtypes[:-1] + [ctypes.c_int, ctypes.c_void_p]
+        L.check(fn(*head, EVIDENCE[evidence], L.stream()), "otal_anchor_stats_ev")
     return res

@@ -13,6 +13,7 @@
 // adds and is identical from run to run, and the global arrays accumulate over launches.
 // The library is built with -ffp-contract=off and nothing here calls fma.
 #include "common.h"
+#include "evidence.h"
 
 namespace {
 
@@ -27,6 +28,7 @@ struct AnchorStatsArgs {
     int K, C, G;
     float clip, overlap;
     int os_head, n_known, target, score_bins, grad_bins;
+    int evidence;                                               // EV instance (otal_anchor_stats_ev): the kind of csrc/evidence.h
     unsigned long long *hist_score, *hist_grad;
     int* label;
     float *value, *grad;
@@ -46,6 +48,9 @@ __device__ int as_grad_bin(float g, int num_bins) {
     return (b >= 0 && b < num_bins && g >= edge(b) && g < edge(b + 1)) ? b : -1;
 }
 
+// EV: alpha = evidence(z) + 1 with the caller's evidence function (grad_edl with the network's evidence, analyze_gradnorm.py:
+// 164-184); false is the exp code as it was.
+template <bool EV>
 __global__ __launch_bounds__(AS_THREADS) void anchor_stats_kernel(const AnchorStatsArgs a) {
     extern __shared__ unsigned int s_hist[];        // [2][3][score_bins] then [2][grad_bins]
     const int b = blockIdx.x, t = threadIdx.x;
@@ -89,7 +94,9 @@ __global__ __launch_bounds__(AS_THREADS) void anchor_stats_kernel(const AnchorSt
             const int col = a.os_head ? y[s] - 1 : y[s];                        // os_head: rows 1..C count, at column y - 1
             float S = 0.f, amax = 0.f, ay = 1.f;
             for (int q = 0; q < C; ++q) {
-                const float al = expf(fminf(fmaxf(z[q], -10.f), 10.f)) + 1.f;
+                float al;
+                if constexpr (EV) al = otal_ev::alpha(z[q], a.evidence);
+                else al = expf(fminf(fmaxf(z[q], -10.f), 10.f)) + 1.f;
                 S += al;
                 amax = fmaxf(amax, al);
                 if (q == col) ay = al;
@@ -127,16 +134,16 @@ __global__ __launch_bounds__(AS_THREADS) void anchor_stats_kernel(const AnchorSt
         if (s_grad[e]) atomicAdd(&a.hist_grad[e], (unsigned long long)s_grad[e]);
 }
 
-}  // namespace
-
-extern "C" int otal_anchor_stats(const float* loc, const float* conf, const float* prop_conf, const float* center,
+int anchor_stats_entry(const float* loc, const float* conf, const float* prop_conf, const float* center,
                                  const float* act, const float* prop_act, const float* priors, const float* gt,
                                  const unsigned char* gvalid, int B, int K, int C, int G, float clip_length, float overlap_thresh,
                                  int os_head, int n_known, int target, int score_bins, int grad_bins, long long* hist_score,
-                                 long long* hist_grad, int* label, float* value, float* grad, void* stream) {
+                                 long long* hist_grad, int* label, float* value, float* grad, bool ev, int evidence,
+                                 void* stream) {
     if (!loc || !conf || !prop_conf || !center || !priors || !gt || !gvalid || !hist_score || !hist_grad) return OTAL_E_NULL;
     if (B < 1 || K < 1 || C < 1 || G < 1 || score_bins < 1 || grad_bins < 1) return OTAL_E_SHAPE;
     if (target < 0 || target > 4 || n_known < 1) return OTAL_E_UNSUPPORTED;
+    if (ev && (evidence < 0 || evidence >= otal_ev::EV_KINDS)) return OTAL_E_UNSUPPORTED;
     const bool uses_act = target == 1 || target == 3 || target == 4 || (target == 2 && os_head);
     if (uses_act && (!act || !prop_act)) return OTAL_E_UNSUPPORTED;
     if ((act == nullptr) != (prop_act == nullptr)) return OTAL_E_UNSUPPORTED;
@@ -151,6 +158,33 @@ extern "C" int otal_anchor_stats(const float* loc, const float* conf, const floa
     a.hist_score = reinterpret_cast<unsigned long long*>(hist_score);
     a.hist_grad = reinterpret_cast<unsigned long long*>(hist_grad);
     a.label = label; a.value = value; a.grad = grad;
-    hipLaunchKernelGGL(anchor_stats_kernel, dim3(B), dim3(AS_THREADS), (size_t)lds, (hipStream_t)stream, a);
+    a.evidence = evidence;
+    if (ev) hipLaunchKernelGGL(anchor_stats_kernel<true>, dim3(B), dim3(AS_THREADS), (size_t)lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(anchor_stats_kernel<false>, dim3(B), dim3(AS_THREADS), (size_t)lds, (hipStream_t)stream, a);
     return otal_launch_status();
+}
+
+}  // namespace
+
+extern "C" int otal_anchor_stats(const float* loc, const float* conf, const float* prop_conf, const float* center,
+                                 const float* act, const float* prop_act, const float* priors, const float* gt,
+                                 const unsigned char* gvalid, int B, int K, int C, int G, float clip_length, float overlap_thresh,
+                                 int os_head, int n_known, int target, int score_bins, int grad_bins, long long* hist_score,
+                                 long long* hist_grad, int* label, float* value, float* grad, void* stream) {
+    return anchor_stats_entry(loc, conf, prop_conf, center, act, prop_act, priors, gt, gvalid, B, K, C, G, clip_length,
+                              overlap_thresh, os_head, n_known, target, score_bins, grad_bins, hist_score, hist_grad, label, value,
+                              grad, false, 0, stream);
+}
+
+// otal_anchor_stats with the network's evidence function (0 exp, 1 relu, 2 softplus): alpha_k = evidence(z_k) + 1 in S, in
+// the scores and in the EDL gradient.  evidence 0 gives what otal_anchor_stats gives.
+extern "C" int otal_anchor_stats_ev(const float* loc, const float* conf, const float* prop_conf, const float* center,
+                                    const float* act, const float* prop_act, const float* priors, const float* gt,
+                                    const unsigned char* gvalid, int B, int K, int C, int G, float clip_length,
+                                    float overlap_thresh, int os_head, int n_known, int target, int score_bins, int grad_bins,
+                                    long long* hist_score, long long* hist_grad, int* label, float* value, float* grad,
+                                    int evidence, void* stream) {
+    return anchor_stats_entry(loc, conf, prop_conf, center, act, prop_act, priors, gt, gvalid, B, K, C, G, clip_length,
+                              overlap_thresh, os_head, n_known, target, score_bins, grad_bins, hist_score, hist_grad, label, value,
+                              grad, true, evidence, stream);
 }

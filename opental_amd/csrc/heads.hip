@@ -4,11 +4,13 @@
 // Replaces, per pyramid level and head, AFSD/thumos14/BDNet.py:337-353,:399-412 (and AFSD/anet/BDNet.py:307-320,:366-376):
 //   loc      = ScaleExp_l(conv)            .view(b,2,-1).permute(0,2,1).contiguous()   [* fpn_stride_l in the ANet model]
 //   conf/act/prop_*/center = conv          .view(b,C,-1).permute(0,2,1).contiguous()
-// and DirichletLayer.compute_uncertainty (BDNet.py:538-556): u = K / sum_k (exp(clamp(z_k, -10, 10)) + 1)
+// and DirichletLayer.compute_uncertainty (BDNet.py:538-556): u = K / sum_k (exp(clamp(z_k, -10, 10)) + 1); modes 3 and 4 are the
+// same item with relu and softplus evidence (csrc/evidence.h)
 // -- ~25 ATen launches forward (exp, mul, 7 permute copies, 2 x {clamp, exp, add, sum, div}) and as many backward.
 // The maps are small ((B, C <= 150, 126..189)): one thread per (item, sample, anchor) walks the channels; reads are
 // coalesced along the anchors, the channel-last writes are 4..600 bytes per thread (L2-resident).
 #include "common.h"
+#include "evidence.h"
 
 namespace {
 
@@ -16,10 +18,11 @@ constexpr int MAX_ITEMS = 8;
 struct HeadItems {
     int n_items;
     int C[MAX_ITEMS];
-    int mode[MAX_ITEMS];               // 0 permute, 1 exp(scale_l * x) * stride_l, 2 permute + Dirichlet uncertainty
+    int mode[MAX_ITEMS];               // 0 permute, 1 exp(scale_l * x) * stride_l, 2 permute + Dirichlet uncertainty (exp evidence),
+                                       // 3 / 4 the same with relu / softplus evidence
     const float* raw[MAX_ITEMS];       // (B, C, N)
     float* out[MAX_ITEMS];             // (B, N, C)
-    float* unct[MAX_ITEMS];            // (B, N) for mode 2
+    float* unct[MAX_ITEMS];            // (B, N) for modes 2, 3, 4
     // backward
     const float* dout[MAX_ITEMS];      // (B, N, C) or null
     const float* dunct[MAX_ITEMS];     // (B, N) or null
@@ -53,8 +56,9 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(HeadItems it, HeadLevels
         const float v = x[(size_t)c * N];
         y[c] = v;
         if (mode == 2) sum += expf(fminf(fmaxf(v, -10.f), 10.f)) + 1.f;
+        else if (mode > 2) sum += otal_ev::alpha(v, mode - 2);
     }
-    if (mode == 2) it.unct[i][(size_t)b * N + n] = (float)C / sum;
+    if (mode >= 2) it.unct[i][(size_t)b * N + n] = (float)C / sum;
 }
 
 // grid: (ceil(N / 256), B, n_items) + one extra z-slice (z == n_items) of a single workgroup for the ScaleExp gradients
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(HeadItems it, HeadLevels
     }
     float coef = 0.f;                    // d unct / d z_c = -K / S^2 * exp(z_c) inside the clamp, 0 outside
     const float* x = it.raw[i] + (size_t)b * C * N + n;
-    if (mode == 2 && it.dunct[i]) {
+    if (mode >= 2 && it.dunct[i]) {
         const float u = it.unct[i][(size_t)b * N + n];          // K / S
         coef = -it.dunct[i][(size_t)b * N + n] * u * u / (float)C;
     }
@@ -108,7 +112,8 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(HeadItems it, HeadLevels
         float g = dy ? dy[c] : 0.f;
         if (coef != 0.f) {
             const float v = x[(size_t)c * N];
-            if (v > -10.f && v < 10.f) g += coef * expf(v);
+            if (mode > 2) g += coef * otal_ev::dalpha(v, mode - 2);
+            else if (v > -10.f && v < 10.f) g += coef * expf(v);
         }
         dx[(size_t)c * N] = g;
     }
@@ -121,7 +126,7 @@ int fill(HeadItems& it, HeadLevels& L, int n_items, const int* channels, const i
     it = HeadItems{};
     it.n_items = n_items;
     for (int i = 0; i < n_items; ++i) {
-        if (channels[i] <= 0 || modes[i] < 0 || modes[i] > 2) return OTAL_E_SHAPE;
+        if (channels[i] <= 0 || modes[i] < 0 || modes[i] > 4) return OTAL_E_SHAPE;
         it.C[i] = channels[i]; it.mode[i] = modes[i];
     }
     L.nlev = nlev;
@@ -141,7 +146,7 @@ extern "C" int otal_head_outputs_fwd(int n_items, const int* channels, const int
     HeadLevels L;
     if (int e = fill(it, L, n_items, channels, modes, B, N, nlev, lev, level_strides)) return e;
     for (int i = 0; i < n_items; ++i) {
-        if (!raw[i] || !out[i] || (modes[i] == 2 && !unct[i]) || (modes[i] == 1 && !scales)) return OTAL_E_NULL;
+        if (!raw[i] || !out[i] || (modes[i] >= 2 && !unct[i]) || (modes[i] == 1 && !scales)) return OTAL_E_NULL;
         it.raw[i] = raw[i]; it.out[i] = out[i]; it.unct[i] = unct[i];
     }
     hipLaunchKernelGGL(heads_fwd_kernel, dim3((N + 255) / 256, B, n_items), dim3(256), 0, (hipStream_t)stream, it, L, scales, B, N);
@@ -158,7 +163,7 @@ extern "C" int otal_head_outputs_bwd(int n_items, const int* channels, const int
     if (int e = fill(it, L, n_items, channels, modes, B, N, nlev, lev, level_strides)) return e;
     bool any_exp = false;
     for (int i = 0; i < n_items; ++i) {
-        if (!raw[i] || !out[i] || !draw[i] || (modes[i] == 2 && !unct[i])) return OTAL_E_NULL;
+        if (!raw[i] || !out[i] || !draw[i] || (modes[i] >= 2 && !unct[i])) return OTAL_E_NULL;
         it.raw[i] = raw[i]; it.out[i] = const_cast<float*>(out[i]); it.unct[i] = const_cast<float*>(unct[i]);
         it.dout[i] = dout[i]; it.dunct[i] = dunct[i]; it.draw[i] = draw[i];
         any_exp = any_exp || modes[i] == 1;

@@ -4,6 +4,7 @@
 //                         head (Dirichlet scores x actionness);
 //   otal_decode_clips_ex: the same with the score function (Dirichlet / softmax), the background class and the
 //                         actionness heads chosen by the caller -- the closed-set Softmax and EDL baselines;
+//   otal_decode_clips_ev: the same with the evidence function of the Dirichlet scores (exp / relu / softplus, csrc/evidence.h);
 //   otal_softnms_classes: per (video, class) gather of the surviving candidates in the reference's
 //                         order (clip-major, anchor-minor) followed by Gaussian Soft-NMS
 //                         (softnms_v2, AFSD/common/segment_utils.py:128-162) -- one workgroup per
@@ -18,6 +19,7 @@
 // original index order with the decayed scores.  Latency-bound (min(top_k, N) dependent rounds), so
 // the figure of merit is candidates/s, not bytes.
 #include "common.h"
+#include "evidence.h"
 
 namespace {
 
@@ -30,15 +32,16 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf
 // SOFTMAX false: Dirichlet mean with exp evidence (BDNet.py DirichletLayer); true: softmax, exp(z - max) / sum (nn.Softmax).
 // first_class 1 drops class 0 (the closed-set background) from score / flag.  act / prop_act NULL (no actionness heads):
 // no actionness factor and flag = score > conf_thresh.  unct / actn NULL: not written; with SOFTMAX or without act the
-// absent quantity is written as 0.
-template <bool SOFTMAX>
+// absent quantity is written as 0.  EV (SOFTMAX false): alpha = evidence(z) + 1 of csrc/evidence.h with the caller's evidence kind;
+// false is the exp code as it was.
+template <bool SOFTMAX, bool EV = false>
 __global__ __launch_bounds__(128) void decode_clips_kernel(
         const float* __restrict__ loc, const float* __restrict__ prop_loc, const float* __restrict__ priors,
         const float* __restrict__ conf, const float* __restrict__ prop_conf, const float* __restrict__ center,
         const float* __restrict__ act, const float* __restrict__ prop_act, const float* __restrict__ offsets,
         const float* __restrict__ fps, float* __restrict__ seg, float* __restrict__ score, float* __restrict__ unct,
         float* __restrict__ actn, unsigned char* __restrict__ flag, int A, int K, float clip_length,
-        float conf_thresh, int first_class) {
+        float conf_thresh, int first_class, int evidence) {
     const int c = blockIdx.x;
     const int KO = K - first_class;
     const bool has_act = act != nullptr;
@@ -61,6 +64,11 @@ __global__ __launch_bounds__(128) void decode_clips_kernel(
             M = cf[0]; PM = pf[0];
             for (int k = 1; k < K; ++k) { M = fmaxf(M, cf[k]); PM = fmaxf(PM, pf[k]); }
             for (int k = 0; k < K; ++k) { S += expf(cf[k] - M); PS += expf(pf[k] - PM); }
+        } else if constexpr (EV) {
+            for (int k = 0; k < K; ++k) {
+                S += otal_ev::alpha(cf[k], evidence);
+                PS += otal_ev::alpha(pf[k], evidence);
+            }
         } else {
             // Dirichlet mean + uncertainty (BDNet.py:538-561), evidence = exp(clamp(logit, +-10))
             for (int k = 0; k < K; ++k) {
@@ -77,6 +85,9 @@ __global__ __launch_bounds__(128) void decode_clips_kernel(
             if constexpr (SOFTMAX) {
                 a0 = expf(cf[k] - M) / S;
                 a1 = expf(pf[k] - PM) / PS;
+            } else if constexpr (EV) {
+                a0 = otal_ev::alpha(cf[k], evidence) / S;
+                a1 = otal_ev::alpha(pf[k], evidence) / PS;
             } else {
                 a0 = (expf(fminf(fmaxf(cf[k], -10.f), 10.f)) + 1.0f) / S;
                 a1 = (expf(fminf(fmaxf(pf[k], -10.f), 10.f)) + 1.0f) / PS;
@@ -252,26 +263,55 @@ __global__ __launch_bounds__(NMS_THREADS) void softnms_classes_kernel(
 
 }  // namespace
 
+namespace {
+int decode_clips_entry(const float* loc, const float* prop_loc, const float* priors, const float* conf,
+                                    const float* prop_conf, const float* center, const float* act,
+                                    const float* prop_act, const float* offsets, const float* fps, float* seg,
+                                    float* score, float* unct, float* actn, unsigned char* flag, int nclips, int A,
+                                    int K, float clip_length, float conf_thresh, int score_fn, int first_class,
+                                    bool ev, int evidence, void* stream) {
+    if (!loc || !prop_loc || !priors || !conf || !prop_conf || !center || (!act) != (!prop_act) || !offsets || !fps ||
+        !seg || !score || !flag) return OTAL_E_NULL;
+    if (nclips <= 0 || A <= 0 || K <= 0) return OTAL_E_SHAPE;
+    if (score_fn < 0 || score_fn > 1 || first_class < 0 || first_class > 1) return OTAL_E_UNSUPPORTED;
+    if (K - first_class <= 0) return OTAL_E_SHAPE;
+    if (ev && (evidence < 0 || evidence >= otal_ev::EV_KINDS)) return OTAL_E_UNSUPPORTED;
+    if (score_fn == 1)
+        hipLaunchKernelGGL(decode_clips_kernel<true>, dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc, priors,
+                           conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
+                           clip_length, conf_thresh, first_class, 0);
+    else if (ev)
+        hipLaunchKernelGGL((decode_clips_kernel<false, true>), dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc,
+                           priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
+                           clip_length, conf_thresh, first_class, evidence);
+    else
+        hipLaunchKernelGGL(decode_clips_kernel<false>, dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc, priors,
+                           conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
+                           clip_length, conf_thresh, first_class, 0);
+    return otal_launch_status();
+}
+}  // namespace
+
 extern "C" int otal_decode_clips_ex(const float* loc, const float* prop_loc, const float* priors, const float* conf,
                                     const float* prop_conf, const float* center, const float* act,
                                     const float* prop_act, const float* offsets, const float* fps, float* seg,
                                     float* score, float* unct, float* actn, unsigned char* flag, int nclips, int A,
                                     int K, float clip_length, float conf_thresh, int score_fn, int first_class,
                                     void* stream) {
-    if (!loc || !prop_loc || !priors || !conf || !prop_conf || !center || (!act) != (!prop_act) || !offsets || !fps ||
-        !seg || !score || !flag) return OTAL_E_NULL;
-    if (nclips <= 0 || A <= 0 || K <= 0) return OTAL_E_SHAPE;
-    if (score_fn < 0 || score_fn > 1 || first_class < 0 || first_class > 1) return OTAL_E_UNSUPPORTED;
-    if (K - first_class <= 0) return OTAL_E_SHAPE;
-    if (score_fn == 1)
-        hipLaunchKernelGGL(decode_clips_kernel<true>, dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc, priors,
-                           conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
-                           clip_length, conf_thresh, first_class);
-    else
-        hipLaunchKernelGGL(decode_clips_kernel<false>, dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc, priors,
-                           conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
-                           clip_length, conf_thresh, first_class);
-    return otal_launch_status();
+    return decode_clips_entry(loc, prop_loc, priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn,
+                              flag, nclips, A, K, clip_length, conf_thresh, score_fn, first_class, false, 0, stream);
+}
+
+// otal_decode_clips_ex with the evidence function of the Dirichlet scores and uncertainty (score_fn 0): 0 exp, 1 relu,
+// 2 softplus.  evidence 0 gives bit for bit what otal_decode_clips_ex gives; a kind out of range: OTAL_E_UNSUPPORTED.
+extern "C" int otal_decode_clips_ev(const float* loc, const float* prop_loc, const float* priors, const float* conf,
+                                    const float* prop_conf, const float* center, const float* act,
+                                    const float* prop_act, const float* offsets, const float* fps, float* seg,
+                                    float* score, float* unct, float* actn, unsigned char* flag, int nclips, int A,
+                                    int K, float clip_length, float conf_thresh, int score_fn, int first_class,
+                                    int evidence, void* stream) {
+    return decode_clips_entry(loc, prop_loc, priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn,
+                              flag, nclips, A, K, clip_length, conf_thresh, score_fn, first_class, true, evidence, stream);
 }
 
 extern "C" int otal_decode_clips(const float* loc, const float* prop_loc, const float* priors, const float* conf,

@@ -15,16 +15,22 @@
 // Latency-bound by construction (SURVEY 8d puts the losses under "launch latency"); the win is 400 launches -> 1.
 //
 // Supported configurations: the final recipe -- evidence 'exp', loss_type 'log', os_head, size_average False, actionness
-// rank-term weight 0 -- and, with cls_mode = 1, the as-shipped THUMOS14 dispatch (train.py:27-31 overwrites 'edl' with
+// rank-term weight 0 -- and the other standard EDL settings of the reference (evidence 'relu' / 'softplus', loss_type
+// 'digamma' / 'mse'; cls_loss.py:171-209,:281-285) through otal_detection_loss_ev for cls_mode 0 and 2: the GEN instances of
+// the kernel, whose evidence and loss arithmetic is csrc/evidence.h ('mse' with IBM or a re-weighting rule is refused: the
+// reference's mse_loss applies none).  With cls_mode = 1, the as-shipped THUMOS14 dispatch (train.py:27-31 overwrites 'edl' with
 // 'focal'): FocalLoss_Ori(balance_index 0, alpha 0.25, gamma 2) on softmax scores (cls_loss.py:6-78) instead
 // of the evidential terms (no IBM, no IoU calibration).  Two closed-set baselines (os_head false: C = K + 1 logits, class 0
 // = background, EVERY anchor is classified against its matched label, multisegment_loss.py:196-231 without os_head):
-// cls_mode 2 = EvidenceLoss 'log' / exp (no IBM; IoU calibration as in mode 0), cls_mode 3 = FocalLoss_Ori on softmax scores.
+// cls_mode 2 = EvidenceLoss (no IBM through otal_detection_loss; IoU calibration as in mode 0), cls_mode 3 = FocalLoss_Ori on
+// softmax scores.
 // Modes 2 and 3 have no actionness heads: act / prop_act may be NULL, losses 5 and 6 and their gradient slots are 0.
 // The ActivityNet1.3 form (detection_loss_anet_kernel, below) takes the same cls_mode numbers for its OpenTAL recipe (0)
 // and its two closed-set baselines (2, 3) through otal_detection_loss_anet_ex.
-// Everything else stays on the torch formulation.
+// The ActivityNet1.3 form stays exp / log.  Everything else (soft_label, size_average, 'mse' with a re-weighting rule) stays on
+// the torch formulation.
 #include "common.h"
+#include "evidence.h"
 
 namespace {
 
@@ -53,6 +59,7 @@ struct LossArgs {
     int gcpl;                       // 0: RPL, cross-entropy on dist / T; 1: GCPL, on -dist / T
     float temperature, weight_pl, radius;
     float rw_gamma;                 // focal-EDL (RW 1): the exponent of (1 - max_k alpha_k / S)
+    int evidence, loss_type;        // GEN instances (otal_detection_loss_ev): the kinds of csrc/evidence.h; the others are exp / log
 };
 constexpr int SCR = 12;             // loc_t0, loc_t1, conf_t, prop_conf_t, iou, prop_loc_t0, prop_loc_t1, ghat, slot, binpos, per, used
 
@@ -127,6 +134,23 @@ __device__ Edl edl_row(const float* z, int C, int y, int num_bins) {
     return e;
 }
 
+// the same statistics for any evidence function and loss type (csrc/evidence.h); with (exp, log) the operations and their order
+// are those of edl_row.  The detached weights keep |1 / alpha_y - u| whatever the loss function (cls_loss.py:228-270).
+__device__ Edl edl_row_gen(const float* z, int C, int y, int num_bins, int evidence, int loss_type) {
+    Edl e;
+    const otal_ev::ClsRow r = otal_ev::cls_row(z, C, y, evidence, loss_type);
+    e.S = r.S; e.ay = r.ay; e.per = r.per;
+    const float u = (float)C / r.S;
+    const float gnorm = fabsf(1.f / r.ay - u);
+    e.ghat = gnorm * r.l1; e.gnorm = gnorm;
+    const long bins = (long)ceilf(gnorm * (float)num_bins);
+    e.binpos = bins > 0 ? 1 : 0;
+    long sl = (bins - 1) % num_bins;
+    if (sl < 0) sl += num_bins;
+    e.slot = (int)sl;
+    return e;
+}
+
 // GHM (cls_loss.py:99-104,:228-249): the bin of a gradient length, edges[b] <= g < edges[b + 1] with edges[b] = b / num_bins in
 // double rounded to float (the reference compares a float tensor with python floats) and 1e-6 added to the last one; -1: none
 __device__ int ghm_bin(float g, int num_bins) {
@@ -155,8 +179,12 @@ __device__ int ghm_bin(float g, int num_bins) {
 // the two classification passes are a softmax cross-entropy on +-dist / T of EVERY anchor against its matched label plus a
 // regulariser on d_i = dist[i][y_i] -- (feats - centers[y]).pow(2).mean(1) IS d_i, so the 512-wide features are never read and
 // their gradient (and the centres') flows through d dist.  Everything else is the closed-set form of the kernel.
-template <bool ST, bool RPL = false, int RW = 0>
+// GEN (otal_detection_loss_ev; EvidenceLoss modes only): the evidence function and the loss type are a.evidence / a.loss_type,
+// uniform over the workgroup, and every piece of evidence / loss arithmetic is a call into csrc/evidence.h.  GEN false is the
+// exp / log code as it was.
+template <bool ST, bool RPL = false, int RW = 0, bool GEN = false>
 __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
+    static_assert(!(GEN && RPL), "the distance losses take no evidence");
     extern __shared__ __attribute__((aligned(16))) float zl[];       // ST: A * C floats (logits, then gradients, of the current pass)
     __shared__ float red[LT];
     __shared__ float wacc[MAX_BINS];
@@ -306,7 +334,10 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
             float* s = a.scratch + (size_t)i * SCR;
             const int tgt = (int)s[2 + pass];
             const int y = closed ? tgt : max(tgt - 1, 0);
-            const Edl e = edl_row(staged ? zl + (size_t)i * C : logits + (size_t)i * C, C, y, a.num_bins);
+            const float* zrow = staged ? zl + (size_t)i * C : logits + (size_t)i * C;
+            Edl e;
+            if constexpr (GEN) e = edl_row_gen(zrow, C, y, a.num_bins, a.evidence, a.loss_type);
+            else e = edl_row(zrow, C, y, a.num_bins);
             s[7] = e.ghat; s[8] = (float)e.slot; s[9] = (float)e.binpos; s[10] = e.per;
             if constexpr (RW == 2) {
                 const int gb = ghm_bin(e.gnorm, a.num_bins);
@@ -385,6 +416,13 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
                 const int y = closed ? tgt : tgt - 1;
                 float S = 0.f, ay = 1.f, amax = 0.f;
                 int kmax = 0;
+                otal_ev::ClsRow row{};
+                if constexpr (GEN) {
+                    if (cnt || cal) {
+                        row = otal_ev::cls_row(z, C, y, a.evidence, a.loss_type);
+                        S = row.S; ay = row.ay; amax = row.amax; kmax = row.kmax;
+                    }
+                } else
                 if (cnt || cal) {
                     for (int k = 0; k < C; ++k) {
                         const float al = expf(fminf(fmaxf(z[k], -10.f), 10.f)) + 1.f;
@@ -415,12 +453,19 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
                 }
                 for (int k = 0; k < C; ++k) {
                     const float zk = z[k];
-                    const float da = (zk >= -10.f && zk <= 10.f) ? expf(zk) : 0.f;      // clamp backward is inclusive
+                    float da, dk;               // d alpha_k / d z_k (clamp backward is inclusive) and d per / d alpha_k
+                    if constexpr (GEN) {
+                        da = otal_ev::dalpha(zk, a.evidence);
+                        dk = cnt ? otal_ev::cls_dalpha(row, otal_ev::alpha(zk, a.evidence), k == y, a.loss_type) : 0.f;
+                    } else {
+                        da = (zk >= -10.f && zk <= 10.f) ? expf(zk) : 0.f;
+                        dk = 1.f / S - (k == y ? 1.f / ay : 0.f);
+                    }
                     float gk;
                     if constexpr (RW == 1)      // d alpha_kmax / S / d alpha_k = ((k == kmax) - p) / S
-                        gk = cnt ? (wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) + fq * ((k == kmax ? 1.f : 0.f) - fp)) * da / norm : 0.f;
+                        gk = cnt ? (wgt * dk + fq * ((k == kmax ? 1.f : 0.f) - fp)) * da / norm : 0.f;
                     else
-                        gk = cnt ? wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) * da / norm : 0.f;
+                        gk = cnt ? wgt * dk * da / norm : 0.f;
                     if (cal) gk += cg * da / (float)A;
                     z[k] = gk;
                 }
@@ -437,6 +482,11 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
                 const int y = closed ? tgt : tgt - 1;
                 float S = 0.f, ay = 1.f, amax = 0.f;
                 int kmax = 0;
+                otal_ev::ClsRow row{};
+                if constexpr (GEN) {
+                    row = otal_ev::cls_row(z, C, y, a.evidence, a.loss_type);
+                    S = row.S; ay = row.ay; amax = row.amax; kmax = row.kmax;
+                } else
                 for (int k = 0; k < C; ++k) {
                     const float al = expf(fminf(fmaxf(z[k], -10.f), 10.f)) + 1.f;
                     S += al;
@@ -453,11 +503,18 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
                 }
                 for (int k = 0; k < C; ++k) {
                     const float zk = z[k];
-                    const float da = (zk >= -10.f && zk <= 10.f) ? expf(zk) : 0.f;      // clamp backward is inclusive
+                    float da, dk;               // as in the staged form
+                    if constexpr (GEN) {
+                        da = otal_ev::dalpha(zk, a.evidence);
+                        dk = otal_ev::cls_dalpha(row, otal_ev::alpha(zk, a.evidence), k == y, a.loss_type);
+                    } else {
+                        da = (zk >= -10.f && zk <= 10.f) ? expf(zk) : 0.f;      // clamp backward is inclusive
+                        dk = 1.f / S - (k == y ? 1.f / ay : 0.f);
+                    }
                     if constexpr (RW == 1)
-                        gz[k] = (wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) + fq * ((k == kmax ? 1.f : 0.f) - fp)) * da / norm;
+                        gz[k] = (wgt * dk + fq * ((k == kmax ? 1.f : 0.f) - fp)) * da / norm;
                     else
-                        gz[k] = wgt * (1.f / S - (k == y ? 1.f / ay : 0.f)) * da / norm;
+                        gz[k] = wgt * dk * da / norm;
                 }
             } else {
                 for (int k = 0; k < C; ++k) gz[k] = 0.f;
@@ -484,14 +541,19 @@ __global__ __launch_bounds__(LT) void detection_loss_kernel(const LossArgs a) {
             if (iou < 0.f) iou = 1e-3f;
             const float* z = a.prop_conf + (size_t)j * C;
             float S = 0.f;
-            for (int k = 0; k < C; ++k) S += expf(fminf(fmaxf(z[k], -10.f), 10.f)) + 1.f;
+            for (int k = 0; k < C; ++k) {
+                if constexpr (GEN) S += otal_ev::alpha(z[k], a.evidence);
+                else S += expf(fminf(fmaxf(z[k], -10.f), 10.f)) + 1.f;
+            }
             const float u = (float)C / S;
             part += -iou * logf(1.f - u) - (1.f - iou) * logf(u);
             const float dreg_du = iou / (1.f - u) - (1.f - iou) / u;
             float* gz = g_pconf + (size_t)j * C;
             for (int k = 0; k < C; ++k) {
                 const float zk = z[k];
-                const float da = (zk >= -10.f && zk <= 10.f) ? expf(zk) : 0.f;
+                float da;
+                if constexpr (GEN) da = otal_ev::dalpha(zk, a.evidence);
+                else da = (zk >= -10.f && zk <= 10.f) ? expf(zk) : 0.f;
                 gz[k] += dreg_du * (-(float)C / (S * S)) * da / (float)A;
             }
         }
@@ -1043,8 +1105,8 @@ extern "C" size_t otal_detection_loss_grad_floats(int B, int K, int C) {
 }
 
 namespace {
-// one launch of detection_loss_kernel<., false, RW>: the staged form when the pass's logits fit the dynamic LDS
-template <int RW>
+// one launch of detection_loss_kernel<., false, RW, GEN>: the staged form when the pass's logits fit the dynamic LDS
+template <int RW, bool GEN = false>
 int launch_detection_loss(const LossArgs& a, bool edl, hipStream_t stream) {
     // staged logits: EvidenceLoss modes (0, 2) and A * C floats within the dynamic LDS this kernel may add to its ~40 KB of static
     // arrays (C = 16: up to 1536 anchors, B * 126 anchors for B <= 12); 40 + 96 KB stays inside the 160 KB of a gfx950 compute unit
@@ -1053,25 +1115,27 @@ int launch_detection_loss(const LossArgs& a, bool edl, hipStream_t stream) {
     static int staged_ok = -1;          // -1: not asked yet; the attribute is set once per process (and per instance)
     if (edl && stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE")) {
         if (staged_ok < 0)
-            staged_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(detection_loss_kernel<true, false, RW>),
+            staged_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(detection_loss_kernel<true, false, RW, GEN>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAGE_MAX) == hipSuccess ? 1 : 0;
         if (staged_ok == 1) {
-            hipLaunchKernelGGL((detection_loss_kernel<true, false, RW>), dim3(1), dim3(LT), stage, stream, a);
+            hipLaunchKernelGGL((detection_loss_kernel<true, false, RW, GEN>), dim3(1), dim3(LT), stage, stream, a);
             return otal_launch_status();
         }
         (void)hipGetLastError();
     }
-    hipLaunchKernelGGL((detection_loss_kernel<false, false, RW>), dim3(1), dim3(LT), 0, stream, a);
+    hipLaunchKernelGGL((detection_loss_kernel<false, false, RW, GEN>), dim3(1), dim3(LT), 0, stream, a);
     return otal_launch_status();
 }
 
 // ex: otal_detection_loss_ex (the re-weighting rules of the loss ablations, and IBM over a closed set)
+// gen: otal_detection_loss_ev (evidence / loss_type of csrc/evidence.h, EvidenceLoss modes 0 and 2 only; implies ex)
 int detection_loss_entry(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
                          const float* center, const float* act, const float* prop_act, const float* priors,
                          const float* gt, const unsigned char* gvalid, float* weight_accum, int B, int K,
                          int C, int G, float clip_length, float overlap_thresh, int ibm_active, int num_bins,
                          float momentum, int iou_aware, int cls_mode, float focal_alpha, int reweight, float rw_gamma,
-                         bool ex, float* losses, float* grads, float* scratch, void* stream) {
+                         bool ex, float* losses, float* grads, float* scratch, void* stream, bool gen = false,
+                         int evidence = 0, int loss_type = 0) {
     const bool closed = cls_mode == 2 || cls_mode == 3;        // closed-set modes: no actionness heads
     if (!loc || !conf || !prop_loc || !prop_conf || !center || (!closed && (!act || !prop_act)) || !priors || !gt || !gvalid ||
         !weight_accum || !losses || !grads || !scratch) return OTAL_E_NULL;
@@ -1081,6 +1145,13 @@ int detection_loss_entry(const float* loc, const float* conf, const float* prop_
     if (reweight < 0 || reweight > 3) return OTAL_E_UNSUPPORTED;
     if (reweight != 0 && ((cls_mode != 0 && cls_mode != 2) || ibm_active)) return OTAL_E_UNSUPPORTED;
     if (reweight == 2 && !(momentum >= 0.f)) return OTAL_E_UNSUPPORTED;
+    if (gen) {
+        if (cls_mode != 0 && cls_mode != 2) return OTAL_E_UNSUPPORTED;           // the focal modes take no evidence
+        if (evidence < 0 || evidence >= otal_ev::EV_KINDS || loss_type < 0 || loss_type >= otal_ev::LOSS_TYPES)
+            return OTAL_E_UNSUPPORTED;
+        // the reference's mse_loss applies no re-weighting rule (cls_loss.py:193-209): that combination is not this kernel's
+        if (loss_type == otal_ev::LOSS_MSE && (ibm_active || reweight != 0)) return OTAL_E_UNSUPPORTED;
+    }
     LossArgs a{};
     a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
     a.prop_act = prop_act; a.priors = priors; a.gt = gt; a.gvalid = gvalid; a.weight_accum = weight_accum;
@@ -1090,7 +1161,16 @@ int detection_loss_entry(const float* loc, const float* conf, const float* prop_
     a.ibm_active = (cls_mode == 0 || closed_ibm) ? ibm_active : 0; a.num_bins = num_bins;
     a.iou_aware = (cls_mode == 0 || cls_mode == 2) ? iou_aware : 0;
     a.momentum = momentum; a.cls_mode = cls_mode; a.focal_alpha = focal_alpha; a.rw_gamma = rw_gamma;
+    a.evidence = evidence; a.loss_type = loss_type;
     const bool edl = cls_mode == 0 || cls_mode == 2;
+    if (gen)
+        switch (closed_ibm ? 4 : reweight) {
+            case 1: return launch_detection_loss<1, true>(a, edl, (hipStream_t)stream);
+            case 2: return launch_detection_loss<2, true>(a, edl, (hipStream_t)stream);
+            case 3: return launch_detection_loss<3, true>(a, edl, (hipStream_t)stream);
+            case 4: return launch_detection_loss<4, true>(a, edl, (hipStream_t)stream);
+            default: return launch_detection_loss<0, true>(a, edl, (hipStream_t)stream);
+        }
     switch (closed_ibm ? 4 : reweight) {
         case 1: return launch_detection_loss<1>(a, edl, (hipStream_t)stream);
         case 2: return launch_detection_loss<2>(a, edl, (hipStream_t)stream);
@@ -1123,6 +1203,21 @@ extern "C" int otal_detection_loss_ex(const float* loc, const float* conf, const
                                 reweight, rw_gamma, true, losses, grads, scratch, stream);
 }
 
+// The other standard EDL settings (model.evidence / training.edl_config.evidence relu | softplus, loss_type digamma | mse;
+// cls_loss.py:171-190): otal_detection_loss_ex for cls_mode 0 and 2 with the evidence function (0 exp, 1 relu, 2 softplus) and
+// the loss type (0 log, 1 digamma, 2 mse) chosen by the caller.  (0, 0) gives bit for bit what otal_detection_loss_ex gives.
+// mse with ibm_active or reweight != 0, a kind out of range and the focal modes: OTAL_E_UNSUPPORTED, nothing is written.
+extern "C" int otal_detection_loss_ev(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                                      const float* center, const float* act, const float* prop_act, const float* priors,
+                                      const float* gt, const unsigned char* gvalid, float* weight_accum, int B, int K,
+                                      int C, int G, float clip_length, float overlap_thresh, int ibm_active, int num_bins,
+                                      float momentum, int iou_aware, int cls_mode, float focal_alpha, int reweight,
+                                      float rw_gamma, int evidence, int loss_type, float* losses, float* grads, float* scratch,
+                                      void* stream) {
+    return detection_loss_entry(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt, gvalid, weight_accum, B, K, C,
+                                G, clip_length, overlap_thresh, ibm_active, num_bins, momentum, iou_aware, cls_mode, focal_alpha,
+                                reweight, rw_gamma, true, losses, grads, scratch, stream, true, evidence, loss_type);
+}
 
 // The RPL / GCPL baselines (thumos14_open_rpl.yaml, thumos14_open_gcpl.yaml): the closed-set form of the kernel above with
 // the distance classification terms.  conf / prop_conf are the (B, K, C) distance maps of otal_rpl_head_fwd.

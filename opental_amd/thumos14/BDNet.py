@@ -151,7 +151,8 @@ class CoarsePyramid(nn.Module):
         self.num_classes = num_cls
         self.os_head = os_head
         self.fpn_strides = fpn_strides
-        self.dirichlet_exp = False      # set by BDNet: uncertainty maps come out of the head-tail launch (evidence 'exp')
+        self.dirichlet_mode = 0         # set by BDNet (use_edl): the head-tail item that also gives the uncertainty map, by evidence
+                                        # kind (ops.HEAD_UNCT_MODE: 2 exp, 3 relu, 4 softplus); 0 = no uncertainty maps
         self.projection_inputs = tuple(ep for ep, _ in projections)
         self.pyramids = nn.ModuleList()
         self.loc_heads = nn.ModuleList()
@@ -289,7 +290,7 @@ class CoarsePyramid(nn.Module):
         # the permute(0,2,1).contiguous() of every map and the Dirichlet uncertainty -- are one launch per stage
         # (csrc/heads.hip): the coarse stage here, the refined stage after the proposal branches.
         scales = [h.scale for h in self.loc_heads]
-        um = 2 if self.dirichlet_exp else 0
+        um = self.dirichlet_mode
         # the skinny heads of a stage: one fused launch (csrc/headconv.hip) where it applies, else head by head
         stage = [(loc_feat, self.loc_head), (self._drop(conf_feat), self.conf_head)]
         if self.os_head:
@@ -298,7 +299,7 @@ class CoarsePyramid(nn.Module):
         res = ops.HeadOutputsFunction.apply(tuple(lev), self.fpn_strides, (1, um, 0)[:len(raws)], *scales, *raws)
         loc, conf = res[0], res[1]
         act = res[2] if self.os_head else None
-        unct = res[len(raws)] if self.dirichlet_exp else None
+        unct = res[len(raws)] if um else None
         with torch.no_grad():
             segments, frame_segments = ops.proposal_windows(loc.detach(), lev, float(self.frame_num))
         from ..prop_pooling import boundary_pooling_op as _bp
@@ -331,7 +332,7 @@ class CoarsePyramid(nn.Module):
         res = ops.HeadOutputsFunction.apply(tuple(lev), None, (0, um, 0, 0)[:len(raws)], *[h.detach() for h in scales], *raws)
         prop_loc, prop_conf, center = res[0], res[1], res[2]
         prop_act = res[3] if self.os_head else None
-        fused_unct = (unct, res[len(raws)]) if self.dirichlet_exp else None
+        fused_unct = (unct, res[len(raws)]) if um else None
         priors = self._priors_on(loc.device)
         outs = (loc, conf, prop_loc, prop_conf, center, priors, start, end,
                 start_loc_prop, end_loc_prop, start_conf_prop, end_conf_prop, act, prop_act)
@@ -387,7 +388,7 @@ class BDNet(nn.Module):
         self.evidence = cfg['evidence']
         if self.use_edl:
             self.out_layer = DirichletLayer(self.evidence, dim=-1)
-        self.coarse_pyramid_detection.dirichlet_exp = bool(self.use_edl and self.evidence == 'exp')
+        self.coarse_pyramid_detection.dirichlet_mode = ops.HEAD_UNCT_MODE[self.evidence] if self.use_edl else 0
         self.use_rpl = use_rpl
 
     @staticmethod

@@ -75,8 +75,6 @@ def analyze(net, windows, npy_data_path, target, overlap_thresh, n_known, clip_l
     forward passes in chunks of `batch_clips`, then one otal_anchor_stats launch."""
     os_head, use_edl, evidence = head_mode(net)
     check_mode(target, os_head, use_edl)
-    if evidence != 'exp':
-        raise NotImplementedError(f"evidence {evidence!r}: the statistics are those of exp evidence")
     names = list(dict.fromkeys(w['video_name'] for w in windows))
     hists = dict(hist_score=torch.zeros((2, 3, score_bins), dtype=torch.int64, device=device),
                  hist_grad=torch.zeros((2, grad_bins), dtype=torch.int64, device=device))
@@ -91,7 +89,7 @@ def analyze(net, windows, npy_data_path, target, overlap_thresh, n_known, clip_l
         gt, gvalid = pad_targets([windows[j]['annos'] for j in idx], clip_length, device)
         res = anchor_stats(heads['loc'], heads['conf'], heads['prop_conf'], heads['center'], heads.get('act'),
                            heads.get('prop_act'), heads['priors'], gt, gvalid, clip_length, overlap_thresh, os_head, n_known,
-                           target, score_bins, grad_bins, out=hists, rows=keep_rows)
+                           target, score_bins, grad_bins, out=hists, rows=keep_rows, evidence=evidence)
         if keep_rows:
             for k in rows:
                 rows[k].append(res[k])

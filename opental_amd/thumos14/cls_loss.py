@@ -57,8 +57,9 @@ class EvidenceLoss(nn.Module):
     """EDL loss ('log' / 'digamma' / 'mse', evidence exp / relu / softplus) with influence-balanced (IBM) re-weighting from
     a 50-bin EMA (cls_loss.py:186-285) and the IoU-calibration term (cls_loss.py:120-129), and the three re-weightings of the
     loss ablations for 'log' / 'digamma' (cls_loss.py:221-256): focal-EDL, GHM and the closed-form influence-balanced loss.
-    The exp / log combinations run inside the single-launch HIP loss (csrc/loss.hip); the other kinds use this masked torch
-    formulation on the device."""
+    Every evidence / loss_type combination runs inside the single-launch HIP loss (csrc/loss.hip, arithmetic in
+    csrc/evidence.h) except 'mse' with a re-weighting rule or IBM configured; this masked torch formulation is the host form
+    of the same rule and what the kernels are tested against."""
 
     def __init__(self, num_cls, cfg, size_average=False):
         super(EvidenceLoss, self).__init__()

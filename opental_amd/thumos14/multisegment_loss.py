@@ -5,7 +5,10 @@ synchronisation: anchor<->GT matching runs for all clips at once on padded targe
 
 The loss ablations of the paper (configs/ablations/thumos14_opental_{focal,ghm,ib,hardmib,noMIB,noIoUC,noACT}.yaml) differ from
 the final recipe only in model.os_head and training.edl_config; all seven run through the single-launch loss (otal_detection_loss_ex
-for the focal / ghm / ib re-weightings and for noACT = closed-set EDL with IBM).
+for the focal / ghm / ib re-weightings and for noACT = closed-set EDL with IBM).  So do the other standard EDL settings,
+edl_config.evidence relu / softplus and loss_type digamma / mse (otal_detection_loss_ev, csrc/evidence.h); only mse with a
+re-weighting rule or IBM configured keeps the torch formulation (the reference's mse_loss ignores the rules, and the kernel
+refuses the combination).
 
 os_head=False is the closed-set variant of the Softmax and EDL baselines (configs thumos14_softmax.yaml,
 thumos14_open_edl.yaml): C = classes + 1 logits with class 0 = background, EVERY anchor is classified against its matched
@@ -164,9 +167,11 @@ class MultiSegmentLoss(nn.Module):
 
     def _cls_mode(self, loc):
         """cls_mode of otal_detection_loss for this criterion, or None when the kernel does not cover it:
-        0 = EDL with actionness (OpenTAL), 1 = focal with actionness (as-shipped dispatch), 2 = closed-set EDL ('log', exp;
-        with IBM it is the noACT ablation), 3 = closed-set focal.  'rpl' is an entry of its own (otal_detection_loss_rpl): 'rpl'.
-        The loss ablations (with_focal / with_ghm / with_ibloss) are modes 0 and 2 with the `reweight` of _reweight()."""
+        0 = EDL with actionness (OpenTAL), 1 = focal with actionness (as-shipped dispatch), 2 = closed-set EDL (with IBM it
+        is the noACT ablation), 3 = closed-set focal.  'rpl' is an entry of its own (otal_detection_loss_rpl): 'rpl'.
+        The loss ablations (with_focal / with_ghm / with_ibloss) are modes 0 and 2 with the `reweight` of _reweight(); the
+        evidence function and the loss type of modes 0 and 2 are those of _kinds() (anything but exp / log:
+        otal_detection_loss_ev).  'mse' with a re-weighting rule or IBM configured is not the kernel's: None."""
         cl = self.cls_loss
         common = (FUSED and loc.is_cuda and loc.dtype == torch.float32 and loc.shape[0] * loc.shape[1] <= 2048
                   and not self.size_average and not cl.size_average)
@@ -178,9 +183,18 @@ class MultiSegmentLoss(nn.Module):
             return 'rpl' if float(cl.temp) > 0 else None
         if self.cls_loss_type == 'focal':       # the as-shipped THUMOS14 dispatch (train.py:27-31) / thumos14_softmax.yaml
             return (1 if self.os_head else 3) if self._focal_alpha0 is not None else None
-        if self.cls_loss_type != 'edl' or cl.loss_type != 'log' or cl.evidence != 'exp' or cl.num_bins > 64:
+        if self.cls_loss_type != 'edl' or cl.num_bins > 64:
+            return None
+        if cl.evidence not in ('exp', 'relu', 'softplus') or cl.loss_type not in ('log', 'digamma', 'mse'):
+            return None
+        if cl.loss_type == 'mse' and (cl.with_focal or cl.with_ghm or cl.with_ibloss or cl.with_ibm):
             return None
         return 0 if self.os_head else 2
+
+    def _kinds(self):
+        """(evidence, loss_type) of otal_detection_loss_ev for this criterion's EvidenceLoss."""
+        from ..common.ops import EVIDENCE, LOSS_TYPE
+        return EVIDENCE[self.cls_loss.evidence], LOSS_TYPE[self.cls_loss.loss_type]
 
     def _reweight(self):
         """(ibm_active, reweight, rw_gamma, focal_alpha, state) of otal_detection_loss_ex for this call: the rule EvidenceLoss.
@@ -216,12 +230,15 @@ class MultiSegmentLoss(nn.Module):
                     self._no_ibm = torch.ones(1, dtype=torch.float32, device=loc.device)    # unused EMA slot of the ABI
                 wacc, nb, fa = self._no_ibm, 1, self._focal_alpha0
                 ibm, rw, gamma, mom = False, 0, 0.0, 0.0
+                ev, lt = 0, 0
             else:
                 ibm, rw, gamma, fa, wacc = self._reweight()
                 nb, mom = cl.num_bins, float(cl.momentum) if (ibm or rw) else 0.0
+                ev, lt = self._kinds()
             out = DetectionLossFunction.apply(
                 loc, conf, prop_loc, prop_conf, center.reshape(B, K), None, None, priors[:, 0], gt, valid, wacc,
-                float(self.clip_length), float(self.overlap_thresh), ibm, nb, mom, bool(self.iou_aware), mode, fa, rw, gamma)
+                float(self.clip_length), float(self.overlap_thresh), ibm, nb, mom, bool(self.iou_aware), mode, fa, rw, gamma,
+                ev, lt)
             return out[:5] + (None, None)
         if mode is not None:
             from ..common.ops import DetectionLossFunction
@@ -238,7 +255,7 @@ class MultiSegmentLoss(nn.Module):
             return DetectionLossFunction.apply(
                 loc, conf, prop_loc, prop_conf, center.reshape(B, K), act.reshape(B, K), prop_act.reshape(B, K),
                 priors[:, 0], gt, valid, state, float(self.clip_length), float(self.overlap_thresh),
-                ibm, cl.num_bins, float(cl.momentum), bool(self.iou_aware), 0, fa, rw, gamma)
+                ibm, cl.num_bins, float(cl.momentum), bool(self.iou_aware), 0, fa, rw, gamma, *self._kinds())
         loc_t, conf_t, prop_loc_t, prop_conf_t, iou_pred = self.match(loc.detach(), priors, targets)
         pos, prop_pos = conf_t > 0, prop_conf_t > 0
         zero = loc.new_zeros(())

@@ -581,7 +581,9 @@ class DetectorTrainer:
             ibm = (bool(getattr(cl, 'with_ibm', False)), int(cl.epoch) >= int(getattr(cl, 'ibm_start', 0)),
                    float(getattr(cl, 'annealing_coef', 0.0)) if hasattr(cl, 'annealing_coef') else None,
                    # the re-weighting rule in force (focal / ghm / ib / ibm): crossing ghm_start or ib_start re-captures
-                   cl.reweight() if hasattr(cl, 'reweight') else None)
+                   cl.reweight() if hasattr(cl, 'reweight') else None,
+                   # the evidence function and loss type the loss launch is given (otal_detection_loss_ev)
+                   getattr(cl, 'evidence', None), getattr(cl, 'loss_type', None))
         return (float(self.lr), float(self._base_lr), tuple(float(g) for _, _, g in self._group_ranges), float(self.wd),
                 tuple(self.betas), float(self.eps), self.world, bool(self.collectives), ibm,
                 tuple(sorted((k, float(v)) for k, v in self.w.items())))
