@@ -436,17 +436,17 @@ extern "C" int otal_head_convs_bwd_parts(int n_heads, int n_inputs, const int* i
         if (!w[h] || !dw[h]) return OTAL_E_NULL;
         a.w[h] = w[h]; a.dy[h] = dy[h]; a.dw[h] = dw[h]; a.db[h] = db[h];
     }
-    if (any_dx && (parts & 1)) {
-        const size_t lds = ((size_t)maxrows * (N + 2) + (size_t)maxrows * 48) * 4;
-        if (lds > HC_LDS_MAX) return OTAL_E_UNSUPPORTED;
-        if (int e = allow_lds(head_convs_dgrad_kernel, lds)) return e;
-        hipLaunchKernelGGL(head_convs_dgrad_kernel, dim3(C / 16, B, n_inputs), dim3(256), lds, (hipStream_t)stream, a);
+    // both launches are sized and allowed before the first is issued: a refusal has launched nothing
+    const bool do_dx = any_dx && (parts & 1), do_dw = parts & 2;
+    const size_t lds_dx = ((size_t)maxrows * (N + 2) + (size_t)maxrows * 48) * 4, lds_dw = wgrad_lds(a);
+    if ((do_dx && lds_dx > HC_LDS_MAX) || (do_dw && lds_dw > HC_LDS_MAX)) return OTAL_E_UNSUPPORTED;
+    if (do_dx) if (int e = allow_lds(head_convs_dgrad_kernel, lds_dx)) return e;
+    if (do_dw) if (int e = allow_lds(head_convs_wgrad_kernel, lds_dw)) return e;
+    if (do_dx) {
+        hipLaunchKernelGGL(head_convs_dgrad_kernel, dim3(C / 16, B, n_inputs), dim3(256), lds_dx, (hipStream_t)stream, a);
         if (int e = otal_launch_status()) return e;
     }
-    if (!(parts & 2)) return 0;
-    const size_t lds = wgrad_lds(a);
-    if (lds > HC_LDS_MAX) return OTAL_E_UNSUPPORTED;
-    if (int e = allow_lds(head_convs_wgrad_kernel, lds)) return e;
-    hipLaunchKernelGGL(head_convs_wgrad_kernel, dim3(C / 4, 1, n_inputs), dim3(256), lds, (hipStream_t)stream, a);
+    if (!do_dw) return 0;
+    hipLaunchKernelGGL(head_convs_wgrad_kernel, dim3(C / 4, 1, n_inputs), dim3(256), lds_dw, (hipStream_t)stream, a);
     return otal_launch_status();
 }

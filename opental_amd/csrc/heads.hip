@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(HeadItems it, HeadLevels
         for (int c = 0; c < C; ++c) dx[(size_t)c * N] = dy ? dy[c] * y[c] * s : 0.f;
         return;
     }
-    float coef = 0.f;                    // d unct / d z_c = -K / S^2 * exp(z_c) inside the clamp, 0 outside
+    float coef = 0.f;                    // d unct / d z_c = -K / S^2 * d alpha_c / d z_c (evidence.h)
     const float* x = it.raw[i] + (size_t)b * C * N + n;
     if (mode >= 2 && it.dunct[i]) {
         const float u = it.unct[i][(size_t)b * N + n];          // K / S
@@ -112,8 +112,7 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(HeadItems it, HeadLevels
         float g = dy ? dy[c] : 0.f;
         if (coef != 0.f) {
             const float v = x[(size_t)c * N];
-            if (mode > 2) g += coef * otal_ev::dalpha(v, mode - 2);
-            else if (v > -10.f && v < 10.f) g += coef * expf(v);
+            g += coef * otal_ev::dalpha(v, mode - 2);           // exp evidence: clamp's backward, closed at +-10
         }
         dx[(size_t)c * N] = g;
     }
