@@ -674,6 +674,27 @@ int otal_detection_loss_anet_ex(const float* loc, const float* conf, const float
                                 float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
                                 int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
                                 int cls_mode, float focal_alpha, float* losses, float* grads, float* scratch, void* stream);
+/* otal_detection_loss_anet_ev: otal_detection_loss_anet_ex for cls_mode 0 and 2 with the other standard EDL settings of the
+ * reference's ActivityNet1.3 EvidenceLoss (AFSD/anet/cls_loss.py:153-172 get_loss_func / evidence_func, :175-191 mse_loss,
+ * :242-246 loglikelihood_loss; training.edl_config.evidence and .loss_type of the yaml), numbered and computed as for
+ * otal_detection_loss_ev (csrc/evidence.h; the four lanes of an anchor share its row through row_part / mse_part / row_finish):
+ *   evidence  0 exp, 1 relu, 2 softplus; loss_type 0 log, 1 digamma, 2 mse (err + var, both summed).
+ * ibm_active applies to loss_type 0 and 1: w = 1 / (|z|_1 exp(ibm_coeff g) + 1e-10) with the detached g = |1/alpha_y - C/S| of
+ * the selected evidence, whatever the loss function; |z|_1 carries gradient.  Unlike _ex, cls_mode 2 takes ibm_active too
+ * (the reference's with_ibm does not depend on os_head): every anchor, y = its matched label (0 = background), |z|_1 over all
+ * C logits.  The reference's mse_loss applies no weight: loss_type 2 with ibm_active is OTAL_E_UNSUPPORTED.  The IoU
+ * calibration uses u = C / S of the selected evidence and no clamp (a relu row with all logits <= 0 gives -inf, as the
+ * reference does).  (evidence, loss_type) = (0, 0) == otal_detection_loss_anet_ex(...) bit for bit wherever that entry accepts
+ * the call (it launches the same kernel instances).  cls_mode other than 0 or 2, a kind out of range, K > 1024, nlev > 8:
+ * OTAL_E_UNSUPPORTED, before any read or launch; the null and shape checks are those of _ex.  An additive entry:
+ * OTAL_ABI_VERSION is unchanged. */
+int otal_detection_loss_anet_ev(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                                const float* center, const float* act, const float* prop_act, const float* priors2,
+                                const float* gt, const unsigned char* gvalid, int B, int K, int C, int G,
+                                float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
+                                int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
+                                int cls_mode, float focal_alpha, int evidence, int loss_type, float* losses, float* grads,
+                                float* scratch, void* stream);
 
 /* otal_detection_loss_rpl: the closed-set form of otal_detection_loss for the RPL and GCPL baselines (thumos14_open_rpl.yaml,
  * thumos14_open_gcpl.yaml; AFSD/thumos14/cls_loss.py:342-378 RPLoss, multisegment_loss.py:101-105,:201-204,:225-228).

@@ -49,7 +49,7 @@ class EvidenceLoss(nn.Module):
         if other:
             raise NotImplementedError(f"edl_config keys of the THUMOS14 EvidenceLoss, which the ActivityNet1.3 recipe does "
                                       f"not have: {other}")
-        if self.loss_type not in ('log', 'digamma'):
+        if self.loss_type not in ('log', 'digamma', 'mse'):
             raise NotImplementedError(self.loss_type)
         self.iou_aware = cfg.get('iou_aware', False)
         self.with_ibm = cfg.get('with_ibm', False)
@@ -71,8 +71,16 @@ class EvidenceLoss(nn.Module):
 
     def forward(self, logit, target, mask):
         """logit (B,K,C), target (B,K) class ids (any valid id where mask is False), mask (B,K) -> (B,)."""
-        func = torch.log if self.loss_type == 'log' else torch.digamma
         alpha = self.evidence_func(logit) + 1
+        if self.loss_type == 'mse':
+            # mse_loss + loglikelihood_loss (:175-191, :242-246): err + var per row, both summed; no re-weighting (with_ibm is
+            # not read on this branch of the reference either)
+            S = alpha.sum(dim=-1, keepdim=True)
+            y = F.one_hot(target, alpha.shape[-1]).to(alpha.dtype)
+            per = ((y - alpha / S) ** 2).sum(-1) + (alpha * (S - alpha) / (S * S * (S + 1))).sum(-1)
+            per = torch.where(mask, per, torch.zeros_like(per))
+            return per.sum(-1) / mask.sum(-1).clamp(min=1) if self.size_average else per.sum(-1)
+        func = torch.log if self.loss_type == 'log' else torch.digamma
         S = alpha.sum(dim=-1)
         a_y = alpha.gather(-1, target.unsqueeze(-1)).squeeze(-1)
         per = func(S) - func(a_y)                      # sum_k y_k (f(S) - f(alpha_k)) with one-hot y

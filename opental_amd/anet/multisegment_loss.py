@@ -19,7 +19,7 @@ from ..thumos14.multisegment_loss import _tiou, as_padded, iou_loss, pad_targets
 from .cls_loss import ActionnessLoss, EvidenceLoss, FocalLoss_Ori
 
 bounds = [[0, 30], [15, 60], [30, 120], [60, 240], [96, 768], [256, 768]]
-FUSED = True      # one workgroup per sample (csrc/loss.hip) for the recipe's settings; False forces the torch formulation
+FUSED = True      # one workgroup per sample (csrc/loss.hip) for the EDL and focal settings; False forces the torch formulation
 
 
 class MultiSegmentLoss(nn.Module):
@@ -98,28 +98,49 @@ class MultiSegmentLoss(nn.Module):
     def _fused_ok(self, loc, conf, priors):
         return self._cls_mode(loc, conf, priors) is not None
 
+    def fused_route(self):
+        """Which HIP entry of this recipe (csrc/loss.hip) this criterion's SETTINGS select -- no tensors are read -- or None
+        where the torch formulation below runs.  -> (entry, cls_mode, kinds, ibm_active):
+          entry     'anet_ex' (otal_detection_loss_anet_ex: what the three shipped configs launch) or 'anet_ev'
+                    (otal_detection_loss_anet_ev);
+          cls_mode  0 = EDL with actionness (configs/anet_opental.yaml), 2 = closed-set EDL (anet_edl.yaml), 3 = closed-set
+                    focal (anet_softmax.yaml);
+          kinds     None with 'anet_ex', else (evidence, loss_type) numbered as csrc/evidence.h;
+          ibm_active  the influence-balanced weight at the criterion's current epoch.
+        (exp, log) goes to 'anet_ex' unless it is closed-set with IBM configured, which that entry refuses; every other pair goes
+        to 'anet_ev'.  The reference's mse_loss applies no weight, and the kernel refuses mse with IBM: an mse config that has
+        `with_ibm` keeps the torch formulation (which ignores the flag, as the reference does)."""
+        from ..common.ops import EVIDENCE, LOSS_TYPE
+        cl = self.cls_loss
+        if not FUSED or cl.size_average or self.size_average:
+            return None
+        if self.cls_loss_type == 'focal':
+            if self.os_head or self._focal_alpha0 is None:
+                return None
+            return 'anet_ex', 3, None, False
+        if self.cls_loss_type != 'edl' or cl.evidence not in EVIDENCE or cl.loss_type not in LOSS_TYPE:
+            return None
+        if self.os_head and self.act_loss.size_average:
+            return None
+        if cl.loss_type == 'mse' and cl.with_ibm:
+            return None
+        mode = 0 if self.os_head else 2
+        ibm = bool(cl.with_ibm and cl.epoch >= cl.ibm_start)
+        if (cl.evidence, cl.loss_type) == ('exp', 'log') and (self.os_head or not cl.with_ibm):
+            return 'anet_ex', mode, None, ibm
+        return 'anet_ev', mode, (EVIDENCE[cl.evidence], LOSS_TYPE[cl.loss_type]), ibm
+
     def _cls_mode(self, loc, conf, priors):
-        """cls_mode of the HIP loss of this recipe (csrc/loss.hip, otal_detection_loss_anet_ex) for this criterion, or None
-        where the torch formulation below runs: 0 = what configs/anet_opental.yaml trains with (EDL with actionness),
-        2 = closed-set EDL ('log', exp, no IBM; anet_edl.yaml), 3 = closed-set focal (anet_softmax.yaml)."""
+        """cls_mode of fused_route() for these tensors, or None where the torch formulation below runs."""
         cl = self.cls_loss
         if not (FUSED and loc.is_cuda and loc.dtype == torch.float32 and priors.shape[0] <= 1024 and priors.shape[1] == 2
                 and conf.shape[-1] == self.num_classes and self.num_classes < 32768 and not cl.size_average
                 and self.level_bounds.shape[0] <= 8):        # (the kernel keeps labels in 16 bits and <= MAX_LEVELS_A = 8 levels)
             return None
-        if self.os_head:
-            if not (self.cls_loss_type == 'edl' and cl.loss_type == 'log' and cl.evidence == 'exp'
-                    and not self.act_loss.size_average):
-                return None
-            mode = 0
-        elif self.cls_loss_type == 'focal':
-            if self._focal_alpha0 is None:
-                return None
-            mode = 3
-        elif cl.loss_type == 'log' and cl.evidence == 'exp' and not cl.with_ibm:
-            mode = 2
-        else:
+        route = self.fused_route()
+        if route is None:
             return None
+        mode = route[1]
         # the kernel clamps a prior's level id into the table; the torch path would raise on an out-of-range one: keep the
         # torch path's behaviour for such priors (checked once per priors tensor -- one host read, not one per step)
         key = (priors.data_ptr(), priors._version, tuple(priors.shape))
@@ -132,23 +153,31 @@ class MultiSegmentLoss(nn.Module):
         loc, conf, prop_loc, prop_conf, center, priors, act, prop_act = predictions
         B, K = loc.shape[0], priors.shape[0]
         mode = self._cls_mode(loc, conf, priors)
-        if mode is not None and not self.os_head:
+        if mode is not None:
             from ..common.ops import AnetDetectionLossFunction
+            _, _, kinds, ibm = self.fused_route()
+            kinds = () if kinds is None else (mode, 0.25) + kinds      # (the kinds follow cls_mode and focal_alpha)
+        if mode is not None and not self.os_head:
             gt, valid = as_padded(targets, loc.device)
             iou_aware = mode == 2 and self.iou_aware
+            if kinds:
+                out = AnetDetectionLossFunction.apply(
+                    loc, conf, prop_loc, prop_conf, center.reshape(B, K), None, None, priors, gt, valid, self._bounds_list(),
+                    float(self.clip_length), float(self.overlap_thresh), ibm, float(self.cls_loss.coeff), bool(iou_aware), 0.0,
+                    0.0, *kinds)
+                return out[:5] + (None, None)
             out = AnetDetectionLossFunction.apply(
                 loc, conf, prop_loc, prop_conf, center.reshape(B, K), None, None, priors, gt, valid, self._bounds_list(),
                 float(self.clip_length), float(self.overlap_thresh), False, 0.0, bool(iou_aware), 0.0, 0.0, mode,
                 0.25 if mode == 2 else self._focal_alpha0)
             return out[:5] + (None, None)
         if mode is not None:
-            from ..common.ops import AnetDetectionLossFunction
             gt, valid = as_padded(targets, loc.device)
             cl = self.cls_loss
             return AnetDetectionLossFunction.apply(
                 loc, conf, prop_loc, prop_conf, center.reshape(B, K), act.reshape(B, K), prop_act.reshape(B, K), priors, gt, valid,
-                self._bounds_list(), float(self.clip_length), float(self.overlap_thresh), bool(cl.with_ibm and cl.epoch >= cl.ibm_start),
-                float(cl.coeff), bool(self.iou_aware), float(self.act_loss.weight), float(self.act_loss.margin))
+                self._bounds_list(), float(self.clip_length), float(self.overlap_thresh), ibm,
+                float(cl.coeff), bool(self.iou_aware), float(self.act_loss.weight), float(self.act_loss.margin), *kinds)
         loc_t, conf_t, prop_loc_t, prop_conf_t, iou_pred = self.match(loc.detach(), priors, targets)
         pos, prop_pos = conf_t > 0, prop_conf_t > 0
         zero = loc.new_zeros(())

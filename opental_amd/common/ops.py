@@ -1505,11 +1505,13 @@ class AnetDetectionLossFunction(torch.autograd.Function):
     """The seven terms of the ActivityNet1.3 MultiSegmentLoss (per-sample normalisation) and all their gradients from one
     workgroup per sample + a seven-sum launch (csrc/loss.hip: otal_detection_loss_anet_ex); backward = the shared
     otal_detection_loss_bwd.  cls_mode 0 is the OpenTAL recipe, 2 / 3 the closed-set EDL / Softmax baselines, whose act /
-    prop_act are None: the kernel gets NULL, and their gradients are None."""
+    prop_act are None: the kernel gets NULL, and their gradients are None.  evidence / loss_type (EVIDENCE, LOSS_TYPE), when
+    given, go through otal_detection_loss_anet_ev (cls_mode 0 and 2; with them cls_mode 2 takes ibm_active too)."""
 
     @staticmethod
     def forward(ctx, loc, conf, prop_loc, prop_conf, center, act, prop_act, priors2, gt, gvalid, level_bounds,
-                clip_length, overlap, ibm_active, ibm_coeff, iou_aware, act_weight, act_margin, cls_mode=0, focal_alpha=0.25):
+                clip_length, overlap, ibm_active, ibm_coeff, iou_aware, act_weight, act_margin, cls_mode=0, focal_alpha=0.25,
+                evidence=None, loss_type=None):
         B, K, C = conf.shape
         G = gt.shape[1]
         tens = [None if t is None else t.contiguous().float()
@@ -1524,12 +1526,15 @@ class AnetDetectionLossFunction(torch.autograd.Function):
         scratch = torch.empty(8 * B, dtype=torch.float32, device=loc.device)
         nlev = len(level_bounds)
         lbs = (ctypes.c_float * (2 * nlev))(*[float(v) for row in level_bounds for v in row])
-        L.check(lib.otal_detection_loss_anet_ex(*[None if t is None else L.ptr(t) for t in tens], L.ptr(gv), B, K, C, G,
-                                                ctypes.c_float(clip_length), ctypes.c_float(overlap), lbs, nlev, int(ibm_active),
-                                                ctypes.c_float(ibm_coeff), int(iou_aware), ctypes.c_float(act_weight),
-                                                ctypes.c_float(act_margin), int(cls_mode), ctypes.c_float(focal_alpha),
-                                                L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream()),
-                "otal_detection_loss_anet_ex")
+        head = [None if t is None else L.ptr(t) for t in tens] + [
+            L.ptr(gv), B, K, C, G, ctypes.c_float(clip_length), ctypes.c_float(overlap), lbs, nlev, int(ibm_active),
+            ctypes.c_float(ibm_coeff), int(iou_aware), ctypes.c_float(act_weight), ctypes.c_float(act_margin), int(cls_mode),
+            ctypes.c_float(focal_alpha)]
+        tail = [L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream()]
+        if evidence is None and loss_type is None:
+            L.check(lib.otal_detection_loss_anet_ex(*head, *tail), "otal_detection_loss_anet_ex")
+        else:
+            L.check(lib.otal_detection_loss_anet_ev(*head, int(evidence), int(loss_type), *tail), "otal_detection_loss_anet_ev")
         ctx.save_for_backward(grads)
         ctx.dims = (B, K, C)
         ctx.has_act = act is not None
@@ -1537,7 +1542,7 @@ class AnetDetectionLossFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gs):
-        return DetectionLossFunction.backward(ctx, *gs)[:7] + (None,) * 13
+        return DetectionLossFunction.backward(ctx, *gs)[:7] + (None,) * 15
 
 
 class RPLDetectionLossFunction(torch.autograd.Function):

@@ -3,7 +3,9 @@
 // digamma / trigamma for arguments >= 1, and the per-row classification term of the three loss types (cls_loss.py:193-285)
 // with its derivative with respect to alpha_k.  Shared by loss.hip, heads.hip, infer.hip and anchorstats.hip (the kernels
 // that take an evidence kind call these functions and nothing else for evidence and loss arithmetic) and by a plain-C++ CPU
-// harness (tests/cpu_evidence.cpp) that compares them against float64.  No HIP types in here.
+// harness (tests/cpu_evidence.cpp) that compares them against float64.  No HIP types in here.  The ActivityNet loss kernel,
+// whose anchors have four lanes each, evaluates a row through the lane-share functions at the end of this file
+// (tests/cpu_evidence_lanes.cpp).
 //
 //   evidence   0 exp       e = exp(clamp(z, -10, 10));   de/dz = exp(z) for -10 <= z <= 10 (inclusive, clamp's backward), else 0
 //              1 relu      e = max(z, 0);                de/dz = 1 for z > 0, else 0 (0 at z == 0)
@@ -109,6 +111,63 @@ OTAL_EV_FN ClsRow cls_row(const float* z, int C, int y, int evidence, int loss_t
         const float T = p2 - ay / S;
         r.c1 = 2.f / (S * (S + 1.f));                                   // 2 / S^2 - 2 / (S^2 (S + 1))
         r.dS = (2.f / (S * (S + 1.f)) - 2.f * T / S) - (1.f - p2) * (3.f * S + 2.f) / (S * (S + 1.f) * (S + 1.f));
+        r.dY = 2.f / S;
+    }
+    return r;
+}
+
+// ---- one row evaluated in lane shares: its classes dealt out as c = sub, sub + nsub, ... to nsub cooperating lanes (the
+// ActivityNet loss kernel: four lanes per anchor).  Each lane makes a partial pass over its classes, the caller combines the
+// partials (S, l1, ay: sums -- a lane that does not own class y leaves ay 0, and alpha >= 1, so a combined 0 means "row not
+// classified"; amax: maximum), and row_finish gives cls_row's fields.  mse needs a second partial pass once the combined S is
+// known (err, var, sum p^2: sums).  With nsub = 1 the operations and their order are cls_row's: the same bits.  kmax is not
+// tracked across lanes (-1).
+struct RowPart { float S, l1, ay, amax; };
+struct MsePart { float err, var, p2; };
+
+OTAL_EV_FN RowPart row_part(const float* z, int C, int y, int evidence, int sub, int nsub) {
+    RowPart p;
+    p.S = 0.f; p.l1 = 0.f; p.ay = 0.f; p.amax = 0.f;
+    for (int k = sub; k < C; k += nsub) {
+        const float a = alpha(z[k], evidence);
+        p.S += a;
+        p.l1 += fabsf(z[k]);
+        if (k == y) p.ay = a;
+        if (a > p.amax) p.amax = a;
+    }
+    return p;
+}
+
+// S: the row's combined sum of alpha
+OTAL_EV_FN MsePart mse_part(const float* z, int C, int y, int evidence, float S, int sub, int nsub) {
+    MsePart m;
+    m.err = 0.f; m.var = 0.f; m.p2 = 0.f;
+    const float den = S * S * (S + 1.f);
+    for (int k = sub; k < C; k += nsub) {
+        const float a = alpha(z[k], evidence), p = a / S, d = (k == y ? 1.f : 0.f) - p;
+        m.err += d * d;
+        m.var += a * (S - a) / den;
+        m.p2 += p * p;
+    }
+    return m;
+}
+
+// t, m: the combined partials (m is read for mse only)
+OTAL_EV_FN ClsRow row_finish(const RowPart& t, const MsePart& m, int loss_type) {
+    ClsRow r;
+    const float S = t.S, ay = t.ay > 0.f ? t.ay : 1.f;
+    r.S = S; r.ay = ay; r.l1 = t.l1; r.amax = t.amax; r.kmax = -1; r.c1 = 0.f;
+    if (loss_type == LOSS_LOG) {
+        r.per = logf(S) - logf(ay);
+        r.dS = 1.f / S; r.dY = 1.f / ay;
+    } else if (loss_type == LOSS_DIGAMMA) {
+        r.per = digammaf_(S) - digammaf_(ay);
+        r.dS = trigammaf_(S); r.dY = trigammaf_(ay);
+    } else {                            // the formulas of cls_row
+        r.per = m.err + m.var;
+        const float T = m.p2 - ay / S;
+        r.c1 = 2.f / (S * (S + 1.f));
+        r.dS = (2.f / (S * (S + 1.f)) - 2.f * T / S) - (1.f - m.p2) * (3.f * S + 2.f) / (S * (S + 1.f) * (S + 1.f));
         r.dY = 2.f / S;
     }
     return r;

@@ -27,7 +27,8 @@
 // Modes 2 and 3 have no actionness heads: act / prop_act may be NULL, losses 5 and 6 and their gradient slots are 0.
 // The ActivityNet1.3 form (detection_loss_anet_kernel, below) takes the same cls_mode numbers for its OpenTAL recipe (0)
 // and its two closed-set baselines (2, 3) through otal_detection_loss_anet_ex.
-// The ActivityNet1.3 form stays exp / log.  Everything else (soft_label, size_average, 'mse' with a re-weighting rule) stays on
+// Its GEN instances (otal_detection_loss_anet_ev, modes 0 and 2) take the other evidence kinds and loss types, and IBM over
+// the closed set.  Everything else (soft_label, size_average, 'mse' with a re-weighting rule) stays on
 // the torch formulation.
 #include "common.h"
 #include "evidence.h"
@@ -727,6 +728,7 @@ struct AnetLossArgs {
     float lb[MAX_LEVELS_A], rb[MAX_LEVELS_A];
     int nlev;
     float focal_alpha;              // mode 3: FocalLoss_Ori alpha of class 0; 1 - focal_alpha for the others
+    int evidence, loss_type;        // GEN instances (otal_detection_loss_anet_ev): the kinds of csrc/evidence.h, uniform over the workgroup
 };
 
 __device__ __forceinline__ float quad_sum(float v) {        // sum over the four lanes of an anchor (same wave)
@@ -772,9 +774,15 @@ __device__ float bmaxA(float v, int idx, float* red, int* redi, int* arg) {
     return r;
 }
 
-template <int MODE>         // cls_mode: 0 (OpenTAL), 2 (closed-set EDL), 3 (closed-set focal)
+// GEN (otal_detection_loss_anet_ev, modes 0 and 2): the two classification passes and the IoU calibration take the evidence
+// function and the loss type of csrc/evidence.h (a.evidence, a.loss_type) through its lane-share row functions -- each of an
+// anchor's four lanes makes row_part / mse_part over its classes c = sub, sub + 4, ..., quad_sum combines, row_finish gives the
+// term and its derivative -- and mode 2 takes the influence-balanced weight too (every anchor, y = matched label, |z|_1 over all
+// C logits).  GEN = false is the source as it was before that parameter existed.
+template <int MODE, bool GEN = false>   // cls_mode: 0 (OpenTAL), 2 (closed-set EDL), 3 (closed-set focal)
 __global__ __launch_bounds__(LA) void detection_loss_anet_kernel(const AnetLossArgs a) {
     static_assert(MODE == 0 || MODE == 2 || MODE == 3, "cls_mode 0, 2 or 3");
+    static_assert(!GEN || MODE != 3, "the focal mode takes no evidence");
     __shared__ float red[LA];
     __shared__ int redi[LA];
     __shared__ float s_lt0[MAX_KA], s_lt1[MAX_KA], s_iou[MAX_KA], s_pl0[MAX_KA], s_pl1[MAX_KA], s_pred[MAX_KA];
@@ -837,7 +845,7 @@ __global__ __launch_bounds__(LA) void detection_loss_anet_kernel(const AnetLossA
     // ---- classification: EvidenceLoss 'log' with exp evidence (anet/cls_loss.py:120-141), per sample
     float loss_cls[2];
     // closed set (modes 2, 3): every anchor against its matched label y (0 = background), normalised by N / PN
-    for (int pass = 0; pass < (MODE == 0 ? 0 : 2); ++pass) {
+    for (int pass = 0; pass < (GEN || MODE == 0 ? 0 : 2); ++pass) {
         const float* logits = pass == 0 ? a.conf : a.prop_conf;
         float* gout = pass == 0 ? g_conf : g_pconf;
         const float norm = (pass == 0 ? Nf : PNf) * (float)a.B;
@@ -897,7 +905,7 @@ __global__ __launch_bounds__(LA) void detection_loss_anet_kernel(const AnetLossA
         loss_cls[pass] = bsumA(part, red) / (pass == 0 ? Nf : PNf);
     }
     // OpenTAL (mode 0): the positives only, y = label - 1
-    for (int pass = 0; pass < (MODE == 0 ? 2 : 0); ++pass) {
+    for (int pass = 0; pass < (!GEN && MODE == 0 ? 2 : 0); ++pass) {
         const float* logits = pass == 0 ? a.conf : a.prop_conf;
         float* gout = pass == 0 ? g_conf : g_pconf;
         const float norm = (pass == 0 ? Nf : PNf) * (float)a.B;
@@ -942,6 +950,54 @@ __global__ __launch_bounds__(LA) void detection_loss_anet_kernel(const AnetLossA
         loss_cls[pass] = bsumA(part, red) / (pass == 0 ? Nf : PNf);
     }
 
+    // GEN: either form with the kinds of csrc/evidence.h (mode 0: the positives, y = label - 1; mode 2: every anchor, y = label)
+    for (int pass = 0; pass < (GEN ? 2 : 0); ++pass) {
+        const float* logits = pass == 0 ? a.conf : a.prop_conf;
+        float* gout = pass == 0 ? g_conf : g_pconf;
+        const float norm = (pass == 0 ? Nf : PNf) * (float)a.B;
+        const int ev = a.evidence, lt = a.loss_type;
+        float part = 0.f;
+        for (int k0 = 0; k0 < K; k0 += LQ) {            // (uniform trip count: the shuffles below need all four lanes)
+            const int k = k0 + q4;
+            const bool live = k < K;
+            const int i = b * K + (live ? k : 0);
+            const int tgt = !live ? 0 : (pass == 0 ? (int)s_ct[k] : (int)s_pct[k]);
+            const bool on = MODE == 0 ? tgt > 0 : live;                 // quad-uniform: the four lanes share k
+            const int y = MODE == 0 ? tgt - 1 : tgt;
+            const float* z = logits + (size_t)i * C;
+            float* gz = gout + (size_t)i * C;
+            const int Cq = on ? C : 0;                                  // a dead quad makes empty passes and reaches the shuffles
+            otal_ev::RowPart p = otal_ev::row_part(z, Cq, y, ev, sub, 4);
+            p.S = quad_sum(p.S); p.l1 = quad_sum(p.l1); p.ay = quad_sum(p.ay);
+            otal_ev::MsePart m;
+            m.err = m.var = m.p2 = 0.f;
+            if (lt == otal_ev::LOSS_MSE) {                              // workgroup-uniform
+                m = otal_ev::mse_part(z, Cq, y, ev, p.S, sub, 4);
+                m.err = quad_sum(m.err); m.var = quad_sum(m.var); m.p2 = quad_sum(m.p2);
+            }
+            if (on) {
+                const otal_ev::ClsRow r = otal_ev::row_finish(p, m, lt);
+                float invD = 1.f, dfn = 0.f;            // per = per0 * invD;  d per / d |z|_1 = dfn
+                if (a.ibm_active) {
+                    const float e = expf(a.coeff * fabsf(1.f / r.ay - (float)C / r.S));   // exp(coeff * g), g detached
+                    const float D = r.l1 * e + 1e-10f;
+                    invD = 1.f / D;
+                    dfn = -r.per * e / (D * D);
+                }
+                if (lead) part += r.per * invD;
+                for (int c = sub; c < C; c += 4) {
+                    const float zc = z[c];
+                    const float sg = zc > 0.f ? 1.f : (zc < 0.f ? -1.f : 0.f);
+                    const float dper = otal_ev::cls_dalpha(r, otal_ev::alpha(zc, ev), c == y, lt) * otal_ev::dalpha(zc, ev);
+                    gz[c] = (dper * invD + dfn * sg) / norm;
+                }
+            } else if (live) {
+                for (int c = sub; c < C; c += 4) gz[c] = 0.f;
+            }
+        }
+        loss_cls[pass] = bsumA(part, red) / (pass == 0 ? Nf : PNf);
+    }
+
     // ---- IoU calibration on prop_conf: this sample's mean over its K anchors (anet/multisegment_loss.py:259-261)
     if (a.iou_aware) {
         float part = 0.f;
@@ -954,8 +1010,12 @@ __global__ __launch_bounds__(LA) void detection_loss_anet_kernel(const AnetLossA
             if (iou < 0.f) iou = 1e-3f;
             const float* z = a.prop_conf + (size_t)i * C;
             float S = 0.f;
-            if (live)
-                for (int c = sub; c < C; c += 4) S += expf(fminf(fmaxf(z[c], -10.f), 10.f)) + 1.f;
+            if constexpr (GEN) {
+                S = otal_ev::row_part(z, live ? C : 0, -1, a.evidence, sub, 4).S;
+            } else {
+                if (live)
+                    for (int c = sub; c < C; c += 4) S += expf(fminf(fmaxf(z[c], -10.f), 10.f)) + 1.f;
+            }
             S = quad_sum(S);
             if (live) {
                 const float u = (float)C / S;
@@ -964,7 +1024,7 @@ __global__ __launch_bounds__(LA) void detection_loss_anet_kernel(const AnetLossA
                 float* gz = g_pconf + (size_t)i * C;
                 for (int c = sub; c < C; c += 4) {
                     const float zc = z[c];
-                    const float da = (zc >= -10.f && zc <= 10.f) ? expf(zc) : 0.f;
+                    const float da = GEN ? otal_ev::dalpha(zc, a.evidence) : ((zc >= -10.f && zc <= 10.f) ? expf(zc) : 0.f);
                     gz[c] += dreg_du * (-(float)C / (S * S)) * da / norm;
                 }
             }
@@ -1255,28 +1315,45 @@ extern "C" int otal_detection_loss_rpl(const float* loc, const float* conf, cons
 }
 
 
-extern "C" int otal_detection_loss_anet_ex(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
-                                           const float* center, const float* act, const float* prop_act, const float* priors2,
-                                           const float* gt, const unsigned char* gvalid, int B, int K, int C, int G,
-                                           float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
-                                           int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
-                                           int cls_mode, float focal_alpha, float* losses, float* grads, float* scratch,
-                                           void* stream) {
+namespace {
+// gen: otal_detection_loss_anet_ev (evidence / loss_type of csrc/evidence.h, EvidenceLoss modes 0 and 2 only; mode 2 with IBM)
+int detection_loss_anet_entry(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                              const float* center, const float* act, const float* prop_act, const float* priors2,
+                              const float* gt, const unsigned char* gvalid, int B, int K, int C, int G,
+                              float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
+                              int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
+                              int cls_mode, float focal_alpha, bool gen, int evidence, int loss_type, float* losses,
+                              float* grads, float* scratch, void* stream) {
     const bool closed = cls_mode == 2 || cls_mode == 3;        // closed-set modes: no actionness heads
     if (!loc || !conf || !prop_loc || !prop_conf || !center || (!closed && (!act || !prop_act)) || !priors2 || !gt ||
         !gvalid || !level_bounds || !losses || !grads || !scratch) return OTAL_E_NULL;
     if (B <= 0 || K <= 0 || C <= 0 || G <= 0 || nlev <= 0) return OTAL_E_SHAPE;
     if (K > MAX_KA || nlev > MAX_LEVELS_A || !(cls_mode == 0 || closed)) return OTAL_E_UNSUPPORTED;
-    if (cls_mode == 2 && ibm_active) return OTAL_E_UNSUPPORTED;    // closed-set EDL: no influence-balanced re-weighting
+    if (!gen && cls_mode == 2 && ibm_active) return OTAL_E_UNSUPPORTED;    // closed-set EDL with IBM: otal_detection_loss_anet_ev only
+    if (gen) {
+        if (cls_mode != 0 && cls_mode != 2) return OTAL_E_UNSUPPORTED;           // the focal mode takes no evidence
+        if (evidence < 0 || evidence >= otal_ev::EV_KINDS || loss_type < 0 || loss_type >= otal_ev::LOSS_TYPES)
+            return OTAL_E_UNSUPPORTED;
+        // the reference's mse_loss applies no re-weighting (anet/cls_loss.py:175-191): that combination is not this kernel's
+        if (loss_type == otal_ev::LOSS_MSE && ibm_active) return OTAL_E_UNSUPPORTED;
+    }
     AnetLossArgs a;
     a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
     a.prop_act = prop_act; a.priors = priors2; a.gt = gt; a.gvalid = gvalid; a.terms = scratch; a.grads = grads;
     a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
-    a.ibm_active = cls_mode == 0 ? ibm_active : 0; a.iou_aware = cls_mode == 3 ? 0 : iou_aware;
+    a.ibm_active = (cls_mode == 0 || gen) ? ibm_active : 0; a.iou_aware = cls_mode == 3 ? 0 : iou_aware;
     a.coeff = ibm_coeff; a.act_weight = act_weight; a.act_margin = act_margin;
     a.nlev = nlev; a.focal_alpha = focal_alpha;
+    a.evidence = evidence; a.loss_type = loss_type;
+    // (exp, log) without closed-set IBM is what the instances without GEN compute: launch those, so that the pair gives the bits
+    // of otal_detection_loss_anet_ex by construction and the shipped configs run the code they ran
+    const bool general = gen && (evidence != otal_ev::EV_EXP || loss_type != otal_ev::LOSS_LOG || (cls_mode == 2 && ibm_active));
     for (int l = 0; l < MAX_LEVELS_A; ++l) { a.lb[l] = l < nlev ? level_bounds[2 * l] : 0.f; a.rb[l] = l < nlev ? level_bounds[2 * l + 1] : 0.f; }
-    if (cls_mode == 0)
+    if (general && cls_mode == 0)
+        hipLaunchKernelGGL((detection_loss_anet_kernel<0, true>), dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
+    else if (general)
+        hipLaunchKernelGGL((detection_loss_anet_kernel<2, true>), dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
+    else if (cls_mode == 0)
         hipLaunchKernelGGL(detection_loss_anet_kernel<0>, dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
     else if (cls_mode == 2)
         hipLaunchKernelGGL(detection_loss_anet_kernel<2>, dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
@@ -1285,6 +1362,36 @@ extern "C" int otal_detection_loss_anet_ex(const float* loc, const float* conf, 
     if (int e = otal_launch_status()) return e;
     hipLaunchKernelGGL(detection_loss_anet_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scratch, losses, B);
     return otal_launch_status();
+}
+}  // namespace
+
+extern "C" int otal_detection_loss_anet_ex(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                                           const float* center, const float* act, const float* prop_act, const float* priors2,
+                                           const float* gt, const unsigned char* gvalid, int B, int K, int C, int G,
+                                           float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
+                                           int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
+                                           int cls_mode, float focal_alpha, float* losses, float* grads, float* scratch,
+                                           void* stream) {
+    return detection_loss_anet_entry(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors2, gt, gvalid, B, K, C, G,
+                                     clip_length, overlap_thresh, level_bounds, nlev, ibm_active, ibm_coeff, iou_aware, act_weight,
+                                     act_margin, cls_mode, focal_alpha, false, 0, 0, losses, grads, scratch, stream);
+}
+
+// The other standard EDL settings for the ActivityNet1.3 recipe (edl_config.evidence relu | softplus, loss_type digamma | mse;
+// AFSD/anet/cls_loss.py:153-246), and the influence-balanced weight over the closed set: otal_detection_loss_anet_ex for
+// cls_mode 0 and 2 with the evidence function (0 exp, 1 relu, 2 softplus) and the loss type (0 log, 1 digamma, 2 mse) chosen
+// by the caller.  (0, 0) gives bit for bit what otal_detection_loss_anet_ex gives wherever that entry accepts the call.  mse
+// with ibm_active, a kind out of range and cls_mode 3: OTAL_E_UNSUPPORTED, nothing is read or written.
+extern "C" int otal_detection_loss_anet_ev(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
+                                           const float* center, const float* act, const float* prop_act, const float* priors2,
+                                           const float* gt, const unsigned char* gvalid, int B, int K, int C, int G,
+                                           float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
+                                           int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
+                                           int cls_mode, float focal_alpha, int evidence, int loss_type, float* losses,
+                                           float* grads, float* scratch, void* stream) {
+    return detection_loss_anet_entry(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors2, gt, gvalid, B, K, C, G,
+                                     clip_length, overlap_thresh, level_bounds, nlev, ibm_active, ibm_coeff, iou_aware, act_weight,
+                                     act_margin, cls_mode, focal_alpha, true, evidence, loss_type, losses, grads, scratch, stream);
 }
 
 extern "C" int otal_detection_loss_anet(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
