@@ -507,6 +507,35 @@ int otal_decode_clips_openmax(const float* loc, const float* prop_loc, const flo
                               int nclips, int A, int C, int first_class, int D, int R, int refined_feature,
                               float clip_length, float conf_thresh, void* stream);
 
+/* ------------------------------------------------------------------ OpenMax for up to 256 classes (csrc/openmax_wide.hip) ----
+ * The ActivityNet1.3 OpenMax baseline has K = 150 classes: no MAV table fits in LDS.  Only the R largest logits of a row get a
+ * non-zero alpha (openmax.py:42-73), every other class keeps its logit exactly and adds exactly 0 to the unknown sum, so a
+ * row needs R distances: the R MAV rows are gathered from memory, O(R D + K) per row.  Feature view, MAVs, wb, ranking of
+ * equal logits, w-score form and softmax as documented above.  Limits: 1 <= K <= 256, 16 <= D <= 512, D % 16 == 0,
+ * 1 <= R <= K, MAVs 16-byte aligned; beyond them OTAL_E_UNSUPPORTED before any read or launch.  All sums over D run in fp32
+ * in one fixed order (64 partial sums: channel d in partial d % 64; then a tree), independent of the feature's layout; no
+ * atomics; every output element is written exactly once.
+ *
+ * otal_openmax_dist_wide: dist (N), row n against MAV labels[n]; -1 where the label is outside [0, K).  labels is required
+ * (the all-pairs form at wide K has no user).  An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_openmax_dist_wide(const float* feat, int N, int rows_per_batch, int64_t sb, int64_t sr, int64_t sc, const float* mav,
+                           int K, int D, const int* labels, float* dist, void* stream);
+/* otal_openmax_probs_wide: otal_openmax_probs for K <= 256.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_openmax_probs_wide(const float* logits, int64_t ldl, const float* feat, int N, int rows_per_batch, int64_t sb,
+                            int64_t sr, int64_t sc, const float* mav, const float* wb, int K, int D, int R, float* probs,
+                            void* stream);
+/* otal_decode_clips_openmax_wide: the arguments and outputs of otal_decode_clips_openmax for K = C - first_class <= 256, in one
+ * launch; no (N, K + 1) intermediate is written.  The segments are those of ActivityNet inference (AFSD/anet/test.py:110-115):
+ * priors[i] * clip_length -/+ the refined offsets, clamped to [0, clip_length], (+ offset) / fps -- the narrow decode's
+ * formula; `priors` holds the A centres.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_decode_clips_openmax_wide(const float* loc, const float* prop_loc, const float* priors, const float* conf,
+                                   const float* prop_conf, const float* center, const float* offsets, const float* fps,
+                                   const float* feat, const float* prop_feat, const int64_t* feat_strides,
+                                   const int64_t* prop_feat_strides, const float* mav, const float* mav_prop, const float* wb,
+                                   const float* wb_prop, float* seg, float* score, float* unknown, unsigned char* flag,
+                                   int nclips, int A, int C, int first_class, int D, int R, int refined_feature,
+                                   float clip_length, float conf_thresh, void* stream);
+
 /* ------------------------------------------------------------------ detection-head convolutions ----
  * The skinny Unit1D heads of one CoarsePyramid stage (AFSD/thumos14/BDNet.py:205-272, :337-353, :399-412;
  * AFSD/common/layers.py:178-214: SAME pad + nn.Conv1d(512, cout, k) + bias, cout = 1 / 2 / num_classes, k = 1 / 3) as

@@ -43,9 +43,11 @@ class CoarsePyramid(_thumos.CoarsePyramid):
                                             projections=(('Mixed_5c', [1, 3, 3]),), first_level_t=frame_num // 8,
                                             fpn_strides=tuple(fpn_strides))
 
-    def forward(self, feat_dict, ssl=False):
-        outs = super(CoarsePyramid, self).forward(feat_dict, ssl=ssl)
-        return outs if ssl else outs[:14] + outs[16:]   # the reference returns 14 tensors (anet/BDNet.py:384-391) [+ the extras dict]
+    def forward(self, feat_dict, ssl=False, get_feat=False):
+        outs = super(CoarsePyramid, self).forward(feat_dict, ssl=ssl, get_feat=get_feat)
+        if ssl or get_feat:     # get_feat: the 14 tensors, the two (B,189,512) tower features, the extras dict
+            return outs
+        return outs[:14] + outs[16:]   # the reference returns 14 tensors (anet/BDNet.py:384-391) [+ the extras dict]
 
 
 class BDNet(_thumos.BDNet):
@@ -94,5 +96,7 @@ class BDNet(_thumos.BDNet):
                     torch.nn.init.normal_(layer.weight, mean=0, std=0.01)
                     torch.nn.init.constant_(layer.bias, 0)
 
-    def forward(self, x, proposals=None, ssl=False):
-        return super(BDNet, self).forward(x, proposals=proposals, ssl=ssl)
+    def forward(self, x, proposals=None, ssl=False, get_feat=False):
+        """get_feat (eval mode): the output dict gains conf_feat / prop_conf_feat (n, 189, 512), the inputs of the two
+        classification heads, as the THUMOS14 model returns them (what the OpenMax baseline reads)."""
+        return super(BDNet, self).forward(x, proposals=proposals, ssl=ssl, get_feat=get_feat)

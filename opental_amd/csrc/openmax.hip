@@ -23,23 +23,13 @@
 // ulp of 1e-3 and shape is of order 1e5, so the literal form is off by 2e-3 in w.  The host passes per class, prepared in
 // float64, off = small + (scale - 10000), inv_scale = 1 / scale and shape; with u = (d - off) * inv_scale the translated
 // argument over scale is 1 + u, and  w = -expm1(-exp(shape * log1p(u))),  w = 0 where 1 + u <= 0 (weibull_cdf, weibull.c:79-104).
-#include "common.h"
+#include "openmax_common.h"       // FeatView, stage_feat, w_score, omx_sigmoid: shared with csrc/openmax_wide.hip
 
 namespace {
 
-constexpr int OMX_TR = 16;            // feature rows per workgroup
 constexpr int OMX_KS = 16;            // class slots per row (K <= 16)
-constexpr int OMX_THREADS = OMX_TR * OMX_KS;
-constexpr int OMX_MAXD = 512;
-constexpr int OMX_PAD = 4;            // floats of padding per LDS row
+static_assert(OMX_THREADS == OMX_TR * OMX_KS, "one thread per (row, class slot)");
 constexpr int CM_GROUPS = 16;         // row groups (waves) of a class-means workgroup
-
-// feature rows addressed by element strides: row n, channel d at p + (n / rpb) * sb + (n % rpb) * sr + d * sc
-struct FeatView { const float* p; int rpb; long long sb, sr, sc; };
-
-__device__ __forceinline__ const float* feat_row(const FeatView& f, int n) {
-    return f.p + (long long)(n / f.rpb) * f.sb + (long long)(n % f.rpb) * f.sr;
-}
 
 struct OmxArgs {
     FeatView f0, f1;                  // coarse feature; feature of the second stage (decode; may be the same view)
@@ -55,38 +45,6 @@ struct OmxArgs {
     int N, A, K, D, R, two_feats;
     float clip_length, conf_thresh;
 };
-
-__device__ __forceinline__ float omx_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ bool aligned16(const FeatView& f) {
-    return f.sc == 1 && ((uintptr_t)f.p & 15) == 0 && (f.sb & 3) == 0 && (f.sr & 3) == 0;
-}
-
-// rows n0 .. n0 + OMX_TR - 1 (the first `nvalid` exist, the rest are zero-filled) -> s[r * ld + d]
-__device__ void stage_feat(float* s, int ld, const FeatView& f, int n0, int nvalid, int D) {
-    const int t = threadIdx.x;
-    if (aligned16(f)) {
-        const int q4 = D >> 2, total = OMX_TR * q4;
-#pragma unroll 4
-        for (int i = t; i < total; i += OMX_THREADS) {
-            const int r = i / q4, q = i - r * q4;
-            // unconditional load from a clamped row, then select: a guarded load becomes a branch with a full wait behind it
-            float4 v = *reinterpret_cast<const float4*>(feat_row(f, n0 + min(r, nvalid - 1)) + 4 * q);
-            if (r >= nvalid) v = make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float4*>(s + r * ld + 4 * q) = v;
-        }
-    } else {
-        const int total = OMX_TR * D;
-        const bool rows_fastest = (f.sr < 0 ? -f.sr : f.sr) < (f.sc < 0 ? -f.sc : f.sc);
-#pragma unroll 8
-        for (int i = t; i < total; i += OMX_THREADS) {
-            const int r = rows_fastest ? i % OMX_TR : i / D;
-            const int d = rows_fastest ? i / OMX_TR : i - (i / D) * D;
-            const float v = feat_row(f, n0 + min(r, nvalid - 1))[(long long)d * f.sc];
-            s[r * ld + d] = r < nvalid ? v : 0.f;
-        }
-    }
-}
 
 // (K, D) contiguous, 16-byte aligned (checked by the entry points) -> s[k * ld + d]
 __device__ void stage_mav(float* s, int ld, const float* mav, int K, int D) {
@@ -140,13 +98,6 @@ __device__ __forceinline__ float tree16(const float* v) {
 __device__ __forceinline__ float eucos(const Sums& s) {
     const float ee = (s.ee[0] + s.ee[1]) + (s.ee[2] + s.ee[3]);
     return sqrtf(ee) / 200.0f + (1.0f - tree16(s.fm) / (sqrtf(tree16(s.ff)) * sqrtf(tree16(s.mm))));
-}
-
-// w_score of libMR (MetaRecognition.cpp:141-152 -> weibull_cdf) in the stable fp32 form of the file header
-__device__ __forceinline__ float w_score(float d, const float* wb) {
-    const float u = (d - wb[0]) * wb[1];
-    if (u <= -1.0f) return 0.f;
-    return -expm1f(-expf(wb[2] * log1pf(u)));
 }
 
 // openmax_recalibrate + compute_openmax_prob (openmax.py:21-73) for one row, one lane per class slot j of a 16-lane group

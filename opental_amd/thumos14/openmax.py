@@ -157,6 +157,8 @@ class OpenMax(nn.Module):
     any object with scale / shape / small_score / translate).  forward(logits (N, K), feature (N, D)) -> (N, K + 1) float32 on
     the device, column 0 = P(unknown), in one launch.  rank: how many top logits are recalibrated (1 <= rank <= K; equal
     logits rank the higher index first, as numpy's argsort()[::-1] does)."""
+    # the kernel's limits and its entry point; anet.openmax.OpenMax overrides them with the wide kernel's (same arguments)
+    MAX_CLASSES, MAX_DIM, ENTRY = MAX_CLASSES, MAX_DIM, "otal_openmax_probs"
 
     def __init__(self, weibull_model, rank=1):
         super().__init__()
@@ -168,9 +170,9 @@ class OpenMax(nn.Module):
             raise ValueError("rank must be at least 1")
         mav = np.stack([np.asarray(weibull_model[n]['mean_vec'], np.float32).reshape(-1) for n in self.class_names], 0)
         wb = np.array([_constants(weibull_model[n]['model'][0]) for n in self.class_names], np.float64)
-        if self.num_cls > MAX_CLASSES or mav.shape[1] > MAX_DIM or mav.shape[1] % 16:
-            raise NotImplementedError(f"OpenMax kernel: K <= {MAX_CLASSES}, D <= {MAX_DIM}, D % 16 == 0; got K = {self.num_cls}, "
-                                      f"D = {mav.shape[1]}")
+        if self.num_cls > self.MAX_CLASSES or mav.shape[1] > self.MAX_DIM or mav.shape[1] % 16:
+            raise NotImplementedError(f"OpenMax kernel ({self.ENTRY}): K <= {self.MAX_CLASSES}, D <= {self.MAX_DIM}, D % 16 == 0; "
+                                      f"got K = {self.num_cls}, D = {mav.shape[1]}")
         self.register_buffer('mav', torch.from_numpy(mav), persistent=False)
         self.register_buffer('wb', torch.from_numpy(wb.astype(np.float32)), persistent=False)
 
@@ -190,9 +192,9 @@ class OpenMax(nn.Module):
         if D != mav.shape[1]:
             raise RuntimeError(f"feature dimension {D} != MAV dimension {mav.shape[1]}")
         out = torch.empty((N, K + 1), dtype=torch.float32, device=feature_in.device)
-        L.check(L.lib().otal_openmax_probs(L.ptr(logits), _i64(logits.stride(0)), L.ptr(feature_in), N, rpb, _i64(sb), _i64(sr),
-                                           _i64(sc), L.ptr(mav), L.ptr(wb), K, D, self.rank, L.ptr(out), L.stream()),
-                "otal_openmax_probs")
+        L.check(getattr(L.lib(), self.ENTRY)(L.ptr(logits), _i64(logits.stride(0)), L.ptr(feature_in), N, rpb, _i64(sb), _i64(sr),
+                                             _i64(sc), L.ptr(mav), L.ptr(wb), K, D, self.rank, L.ptr(out), L.stream()),
+                self.ENTRY)
         return out
 
 
