@@ -352,7 +352,10 @@ int otal_proposal_windows(const float* loc, float* seg, float* frame_seg, int B,
  * (AFSD/thumos14/test.py:79-162) for `nclips` clips in one launch.  Inputs are the model outputs
  * (nclips,A,.) as the reference lays them out; offsets/fps: per-clip frame offset and sampling rate.
  * Outputs: seg (nclips,A,2) seconds, score (nclips,K,A), unct/actn (nclips,A), flag (nclips,K,A) uint8
- * = score > conf_thresh && actionness > 0.5. */
+ * = score > conf_thresh && actionness > 0.5.  Both comparisons are strict on the fp32 values: an anchor with act == prop_act == 0
+ * has actionness exactly 0.5 and is never flagged.  The two ends of a segment are clamped to [0, clip_length] independently, so
+ * end < start and zero-width segments can come out; every element of every output is written for any A and K >= 1.  A refused
+ * call (this entry, _ex and _ev) returns its code before any launch and writes nothing. */
 int otal_decode_clips(const float* loc, const float* prop_loc, const float* priors, const float* conf,
                       const float* prop_conf, const float* center, const float* act, const float* prop_act,
                       const float* offsets, const float* fps, float* seg, float* score, float* unct,
@@ -388,7 +391,13 @@ int otal_decode_clips_ev(const float* loc, const float* prop_loc, const float* p
  * out: (nvideos*K, top_k, out_cols) rows [start,end,decayed score,unct,actionness] in original index
  * order; counts: (nvideos*K); out_index (nullable): (nvideos*K, top_k) source row = clip*A + anchor,
  * relative to the video's first clip.  max_clips bounds the clips of one video.  out_cols 3..5: unct may be NULL when
- * out_cols == 3 and actn when out_cols <= 4 (the closed-set rows [start,end,score(,unct)]). */
+ * out_cols == 3 and actn when out_cols <= 4 (the closed-set rows [start,end,score(,unct)]); the narrower rows are the leading
+ * columns of the 5-column rows bit for bit.  A candidate with score == score_threshold takes part, and one whose decayed score
+ * equals it stays; among equal scores the lowest index is taken first; start, end, unct and actn are copied unchanged, and so is
+ * the score of a row that met no overlapping segment.  counts[v][k] <= min(top_k, candidates - 1), 0 for a video without clips;
+ * rows and index entries at and past counts[v][k] are left untouched, so a problem never writes into its neighbours.  Zero-width
+ * and reversed (end < start) candidates take part with the reference's arithmetic (width of the top segment clamped at 1e-5);
+ * nothing is promised for NaN or Inf inputs.  top_k <= 0 or out_cols outside 3..5: OTAL_E_SHAPE; a refused call writes nothing. */
 int otal_softnms_classes(const float* seg, const float* score, const float* unct, const float* actn,
                          const unsigned char* flag, const int* clip_start, int nvideos, int max_clips,
                          int A, int K, float sigma, int top_k, float score_threshold, float* out,
@@ -396,7 +405,8 @@ int otal_softnms_classes(const float* seg, const float* score, const float* unct
 /* A (video, class) problem keeps its candidates in LDS (<= ~7600 rows = 60 THUMOS14 windows).  The reference's host
  * loop has no such limit (test.py:165-200 handles a video of any length), so longer videos run from a caller-owned
  * global scratch: otal_softnms_scratch_bytes returns its size for a batch with `total_clips` clips in all and at most
- * `max_clips` per video (0 when every video fits LDS); otal_softnms_classes_ws = otal_softnms_classes + that scratch.
+ * `max_clips` per video (0 when every video fits LDS: max_clips * A <= 7680 rows, inclusive); otal_softnms_classes_ws =
+ * otal_softnms_classes + that scratch; videos on either side of the limit may share a batch.
  * otal_softnms_classes itself returns OTAL_E_UNSUPPORTED when a scratch would be needed. */
 size_t otal_softnms_scratch_bytes(int total_clips, int max_clips, int A, int K);
 int otal_softnms_classes_ws(const float* seg, const float* score, const float* unct, const float* actn,

@@ -23,9 +23,9 @@ def softnms_v2(segments, sigma=0.5, top_k=1000, score_threshold=0.001, use_edl=F
     if cols < ncol:
         raise RuntimeError(f"segments has {cols} columns, {ncol} expected")
     dev = seg.device
-    if n == 0:
+    if n == 0 or int(top_k) <= 0:           # nothing to keep (the reference's loop needs done.sum() < top_k): no launch
         empty = seg.new_zeros((0, ncol))
-        return (empty, torch.zeros((), dtype=torch.long, device=dev)) + ((torch.zeros(0, dtype=torch.bool, device=dev),) if get_mask else ())
+        return (empty, torch.zeros((), dtype=torch.long, device=dev)) + ((torch.zeros(n, dtype=torch.bool, device=dev),) if get_mask else ())
     # one "video" with one "clip" of n anchors and one class
     se = seg[:, :2].contiguous()
     sc = seg[:, 2].contiguous()
@@ -35,15 +35,15 @@ def softnms_v2(segments, sigma=0.5, top_k=1000, score_threshold=0.001, use_edl=F
     flag = torch.ones(n, dtype=torch.uint8, device=dev)
     clip_start = torch.tensor([0, 1], dtype=torch.int32, device=dev)
     k = min(int(top_k), n)
-    out = torch.empty((1, max(k, 1), 5), device=dev)
+    out = torch.empty((1, k, 5), device=dev)
     counts = torch.zeros(1, dtype=torch.int32, device=dev)
-    idx = torch.empty((1, max(k, 1)), dtype=torch.int32, device=dev)
+    idx = torch.empty((1, k), dtype=torch.int32, device=dev)
     lib = L.lib()
     lib.otal_softnms_scratch_bytes.restype = ctypes.c_size_t
     nbytes = int(lib.otal_softnms_scratch_bytes(1, 1, n, 1))          # > 0 past ~7600 candidates: global working set
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     L.check(lib.otal_softnms_classes_ws(L.ptr(se), L.ptr(sc), L.ptr(c3), L.ptr(c4), L.ptr(flag), L.ptr(clip_start),
-                                        1, 1, n, 1, ctypes.c_float(sigma), max(k, 1), ctypes.c_float(score_threshold),
+                                        1, 1, n, 1, ctypes.c_float(sigma), k, ctypes.c_float(score_threshold),
                                         L.ptr(out), L.ptr(counts), L.ptr(idx), 5, L.ptr(scratch), ctypes.c_size_t(nbytes), 1,
                                         L.stream()), "otal_softnms_classes_ws")
     count = int(counts.item())
