@@ -864,6 +864,30 @@ int otal_eval_match_labeled(const double* pred_seg, const int* pred_label, const
                             const int* gt_label, const int* gt_start, const double* thresholds, int ngroups, int nthr, int* out,
                             double* max_tiou, int* nonfinite, void* stream);
 
+/* otal_average_precision (csrc/ap.hip): the average precision of every (class, tIoU threshold) from the codes of
+ * otal_eval_match, i.e. the tail of compute_average_precision_detection (:388-402) with utils_eval.interpolated_prec_rec
+ * (:20-29), on the device.  The rule is stated in opental_amd/evaluation/table_ap.py (ap_reference).
+ *   codes (nthr, N) int32   out of otal_eval_match over group-sorted positions; >= 0 is a true positive;
+ *   rank_pos (N) int32      the group-sorted position of the r-th row in (class, descending score, row) order;
+ *   class_start (K + 1)     int32 offsets into rank_pos, non-decreasing, class_start[K] <= N (rows past it are in no class);
+ *   gt_count (K) int32      ground truths per class (npos), all > 0;
+ *   ap (nthr, K) fp64       every element is written; a class without rows gets 0.0.
+ * Per (class, threshold): tp_cum_r = the true positives among the class's first r + 1 rows (int32), precision_r = tp_cum_r /
+ * (r + 1), envelope_r = max over j >= r of precision_j, AP = sum over the true positives of (tp_cum_r / npos - (tp_cum_r - 1) /
+ * npos) * envelope_r, all in fp64 with IEEE division.  One workgroup per (class, threshold) walks the class in chunks of
+ * OTAL_AP_TILE rows from the back with carried count and carried maximum; the sum runs in one fixed order (inside a wave a
+ * butterfly, the waves of a chunk in order, the chunks from the last to the first) that depends on OTAL_AP_TILE and the class
+ * sizes alone: no atomic, no scratch, the same bits from run to run.  One launch on `stream`, no allocation, no
+ * synchronisation.  class_start is clamped into 0 .. N and a rank_pos outside 0 .. N - 1 counts as a false positive.
+ * NULL pointer: OTAL_E_NULL; N < 0, K < 1 or nthr < 1: OTAL_E_SHAPE; nthr > 32: OTAL_E_UNSUPPORTED.  The chunk bookkeeping
+ * (int32 row numbers advanced by OTAL_AP_TILE) serves a class of up to OTAL_AP_MAX_CLASS_ROWS rows; no class is larger than
+ * N, so the bound is checked on the host as N > OTAL_AP_MAX_CLASS_ROWS: OTAL_E_UNSUPPORTED, without reading class_start from
+ * the device.  N == 0 writes zeros.  A refused call writes nothing.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+#define OTAL_AP_TILE 256
+#define OTAL_AP_MAX_CLASS_ROWS (2147483647 - OTAL_AP_TILE)
+int otal_average_precision(const int* codes, const int* rank_pos, const int* class_start, const int* gt_count, int N, int K,
+                           int nthr, double* ap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

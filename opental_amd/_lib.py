@@ -45,6 +45,9 @@ def lib():
         L.otal_anchor_stats.restype = ctypes.c_int
         L.otal_anchor_stats.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int] * 5 \
             + [ctypes.c_void_p] * 6
+        # otal_average_precision (csrc/ap.hip): codes, rank_pos, class_start, gt_count, N, K, nthr, ap, the stream
+        L.otal_average_precision.restype = ctypes.c_int
+        L.otal_average_precision.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2
         _lib = L
     return _lib
 

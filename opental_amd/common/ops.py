@@ -1980,6 +1980,39 @@ def eval_match_labeled(pred_seg, pred_label, pred_start, gt_seg, gt_label, gt_st
     return out, max_tiou, nonfinite
 
 
+AP_TILE = 256                               # OTAL_AP_TILE: rows of a class that one pass of the AP kernel's workgroup covers
+AP_MAX_CLASS_ROWS = 2 ** 31 - 1 - AP_TILE   # OTAL_AP_MAX_CLASS_ROWS
+
+
+def average_precision(codes, rank_pos, class_start, gt_count, out=None):
+    """The average precision of every (class, tIoU threshold) in one launch (otal_average_precision, csrc/ap.hip; the rule:
+    evaluation/table_ap.py).  codes (nthr, N) int32 out of eval_match over group-sorted positions, rank_pos (N) int32 the
+    group-sorted position of the r-th row in (class, descending score, row) order, class_start (K + 1) int32 offsets into
+    rank_pos with class_start[K] <= N (rows past it are in no class), gt_count (K) int32 ground truths per class, all > 0;
+    all on the device.
+    -> ap (nthr, K) fp64, every element written (0.0 for a class without rows).  `out`: the array to write into instead of
+    allocating it; a refused call leaves it untouched.  No synchronisation."""
+    L.require_device(codes, rank_pos, class_start, gt_count)
+    if any(t.dtype != torch.int32 for t in (codes, rank_pos, class_start, gt_count)):
+        raise RuntimeError("average_precision: codes, rank_pos, class_start and gt_count in int32")
+    if codes.dim() != 2 or rank_pos.dim() != 1 or rank_pos.shape[0] != codes.shape[1] or class_start.dim() != 1 \
+            or class_start.numel() < 2 or gt_count.dim() != 1 or gt_count.numel() != class_start.numel() - 1:
+        raise RuntimeError("average_precision: codes (nthr, N), rank_pos (N), class_start (K + 1), gt_count (K)")
+    nthr, N = codes.shape
+    K = gt_count.numel()
+    if out is None:
+        out = torch.empty((nthr, K), dtype=torch.float64, device=codes.device)
+    else:
+        L.require_device(out)
+        if tuple(out.shape) != (nthr, K) or out.dtype != torch.float64:
+            raise RuntimeError("average_precision: out must be (nthr, K) float64")
+    if N == 0:          # an empty tensor has no address to pass; class_start says that no row of them is read
+        codes, rank_pos = codes.new_zeros((nthr, 1)), rank_pos.new_zeros(1)
+    L.check(L.lib().otal_average_precision(L.ptr(codes), L.ptr(rank_pos), L.ptr(class_start), L.ptr(gt_count), N, K, nthr,
+                                           L.ptr(out), L.stream()), "otal_average_precision")
+    return out
+
+
 def detection_table(rows, counts, durations=None, drop_empty=False, scoring='uncertainty', out=None):
     """The Soft-NMS output of softnms_classes as one compact table (otal_detection_table, csrc/dettable.hip; the rule:
     common/det_table.py): rows (V, K, top_k, cols) fp32 with cols 3..5, counts (V, K) int32, durations (V) seconds (a

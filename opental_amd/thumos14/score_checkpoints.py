@@ -1,0 +1,51 @@
+"""python -m opental_amd.thumos14.score_checkpoints <yaml> [--open_set --split N] --gt GT.json --known KNOWN.txt \\
+       [--epochs A B ...] [--tious ...] [--random_init]
+
+The mAP of every saved epoch of the THUMOS14 recipe on the test videos, from detection tables on the device
+(common/score_checkpoints.py): the network, batches and thresholds of thumos14/test.py (`test`: batches of 8 videos), the
+`test` subset of the ground truth, tIoU 0.3 .. 0.7."""
+from ..common import ops
+from ..common.detect import prepare_data
+from ..common.driver import load_net
+from ..common.score_checkpoints import Recipe, run
+from ..common.thumos_dataset import get_video_info
+from . import test as T
+
+BATCH_VIDEOS = 8        # thumos14.test.test's default
+
+
+def _build(config, dev):
+    from .BDNet import BDNet, model_cfg_from
+    md = config['model']
+    return load_net(BDNet, dev, True, None, in_channels=md['in_channels'], use_edl=md.get('use_edl', False), use_rpl=False,
+                    cfg=model_cfg_from(config))
+
+
+def _videos(config):
+    infos = get_video_info(config['dataset']['testing']['video_info_path'])
+    return list(infos.keys()), infos
+
+
+def _batches(config, infos):
+    return [list(range(i, min(i + BATCH_VIDEOS, len(infos)))) for i in range(0, len(infos), BATCH_VIDEOS)]
+
+
+def _table(net, config, infos, positions, dev):
+    te, ds = config['testing'], config['dataset']['testing']
+    names = list(infos.keys())
+    part = [names[p] for p in positions]
+    vids = [prepare_data(ds['video_data_path'], n, ds['crop_size'], dev) for n in part]
+    rows, counts, _, _ = T.detect_batch(net, vids, [float(infos[n]['sample_fps']) for n in part], ds['clip_length'],
+                                        ds['clip_stride'], te['conf_thresh'], te['top_k'], te['nms_sigma'])
+    return ops.detection_table(rows, counts)
+
+
+RECIPE = Recipe('thumos14', ['test'], [0.3, 0.4, 0.5, 0.6, 0.7], _build, _videos, _batches, _table)
+
+
+def main(argv=None):
+    return run(RECIPE, argv)
+
+
+if __name__ == '__main__':
+    main()
