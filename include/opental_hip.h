@@ -497,7 +497,8 @@ int otal_openmax_class_means(const float* feat, int N, int rows_per_batch, int64
  * w_score(d) = -expm1(-exp(shape * log1p((d - off) / scale))), 0 where the translated argument is <= 0.  R: the alpha rank,
  * 1 <= R <= K (else OTAL_E_UNSUPPORTED); the i-th largest logit gets alpha (R + 1 - i) / R, equal logits rank the higher
  * index first (numpy `argsort()[::-1]`).  probs (N, K + 1): column 0 is P(unknown).  The softmax subtracts the maximum
- * exponent (same value as the reference, no overflow). */
+ * exponent (same value as the reference, no overflow).  Checks run in the order NULL, SHAPE, UNSUPPORTED, as in
+ * otal_openmax_probs_wide: ldl < K together with K > 16 is OTAL_E_SHAPE. */
 int otal_openmax_probs(const float* logits, int64_t ldl, const float* feat, int N, int rows_per_batch, int64_t sb, int64_t sr,
                        int64_t sc, const float* mav, const float* wb, int K, int D, int R, float* probs, void* stream);
 /* otal_decode_clips_openmax: decode_output + the threshold test of `filtering` (test_openmax.py:141-189) for nclips clips in

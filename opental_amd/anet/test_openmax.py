@@ -18,11 +18,11 @@ Statistics pass.
   * per class and stage, MAV = class_means of its rows and the own-class distances come from the labelled wide distance
     kernel (otal_openmax_dist_wide);
   * files: <output_path>/openmax/mav_dist/<class name>.npz with the keys mav, dist, mav_prop, dist_prop (the layout of the
-    THUMOS14 files).  A class without a positive in either stage raises the ValueError of thumos14's save_mav_dist.  If the
+    THUMOS14 files).  A class without a positive in either stage raises the ValueError of common.openmax.save_mav_dist.  If the
     files are all there the pass is skipped; if they are missing and WORLD_SIZE > 1 the driver raises: the pass reads the
     whole training set once and is to be run once, in one process, before a multi-rank test.
 
-Fits.  thumos14.test_openmax.weibull_fitting with tailsize 20; two anet.openmax.OpenMax layers of rank 1.
+Fits.  common.openmax.weibull_fitting with tailsize 20; two anet.openmax.OpenMax layers of rank 1.
 
 Test pass.  The validation videos as anet.test.main selects them; each rank takes every world-th video;
 common/detect.py's `detect` with the wide decode launch (otal_decode_clips_openmax_wide, get_feat=True) and ONE Soft-NMS
@@ -34,21 +34,22 @@ would otherwise re-use as complete -- as {"version": "ActivityNet-v1.3", "result
 through driver.write_json; 'uncertainty' and 'actionness' are 0.0, as for the Softmax baseline.  It evaluates with
 `python -m opental_amd.anet.eval_open --open_set --ood_scoring confidence`.
 """
-import ctypes
+import functools
 import json
 import os
 import sys
 
 import torch
 
-from .. import _lib as L
 from ..common import detect as _d
+from ..common import openmax as _common
 from ..common.detect import prepare_data
-from ..thumos14.test_openmax import files_are_ready, save_mav_dist, weibull_fitting
+from ..common.openmax import files_are_ready, save_mav_dist, weibull_fitting
 from . import test as T
-from .openmax import OpenMax, class_means, compute_eucos_dist
+from .openmax import OpenMax
 
 TAILSIZE = 20
+mav_and_dist = functools.partial(_common.mav_and_dist, family=OpenMax.FAMILY)
 
 
 def positive_labels(criterion, loc, priors, targets):
@@ -63,7 +64,7 @@ def collect_features(net, criterion, samples, npy_path, clip_length=T.CLIP_LENGT
     """The statistics pass's loop over `samples` (split_videos records): the tower features and 0-based class indices of
     the positive anchors of both stages -> (feat (N, D), labels (N,) int32, prop_feat, prop_labels)."""
     from ..common.anet_dataset import annos_transform
-    feats, labels, pfeats, plabels = [], [], [], []
+    rows = []
     batch_clips = _d.windows_per_pass(batch_clips)
     for i in range(0, len(samples), batch_clips):
         part = samples[i:i + batch_clips]
@@ -71,22 +72,8 @@ def collect_features(net, criterion, samples, npy_path, clip_length=T.CLIP_LENGT
         out = net(_d.prepare_windows(vids, [(v, 0) for v in range(len(part))], clip_length), get_feat=True)
         targets = [torch.tensor(annos_transform(s['annos'], clip_length), dtype=torch.float32).reshape(-1, 3) for s in part]
         conf_t, prop_conf_t = positive_labels(criterion, out['loc'], out['priors'], targets)
-        for ft, lab, fs, ls in ((out['conf_feat'], conf_t, feats, labels), (out['prop_conf_feat'], prop_conf_t, pfeats, plabels)):
-            pos = lab.reshape(-1) > 0
-            fs.append(ft.reshape(-1, ft.shape[-1])[pos])
-            ls.append((lab.reshape(-1)[pos] - 1).to(torch.int32))
-    cat = lambda xs: torch.cat(xs, 0).contiguous()
-    return cat(feats), cat(labels), cat(pfeats), cat(plabels)
-
-
-def mav_and_dist(feat, labels, num_classes):
-    """Per class: MAV = float32 mean of its rows, dist = eucos distance of each of its rows to that MAV, with the class-means
-    kernel and the labelled wide distance kernel.  -> mav (K, D), counts (K,), dist (N,) on the device."""
-    if feat.shape[0] == 0:
-        return (torch.zeros((num_classes, feat.shape[1]), device=feat.device),
-                torch.zeros((num_classes,), dtype=torch.int32, device=feat.device), torch.zeros((0,), device=feat.device))
-    mav, counts = class_means(feat, labels, num_classes)
-    return mav, counts, compute_eucos_dist(mav, feat, labels)
+        rows.append(_common.positive_rows(out, conf_t, prop_conf_t))
+    return _common.cat_rows(rows)
 
 
 def compute_mav_dist(mav_dist_dir, net, idx_to_class, config, batch_clips=4, device='cuda'):
@@ -110,37 +97,9 @@ def decode_clips_openmax(output_dict, fps, openmax_layer, openmax_prop_layer, cl
     output_dict: the closed-set network's outputs with get_feat=True (conf / prop_conf carry the background logit, which is
     dropped; the priors' level column is dropped too).  Returns dict(seg (n, A, 2), score (n, K, A), flag (n, K, A) uint8,
     unknown (n, A), unct None, actn None): the layout of decode_clips, so softnms_classes takes it as it is."""
-    output_dict = T._heads(output_dict)
-    loc = output_dict['loc'].contiguous()
-    n, A, _ = loc.shape
-    C = output_dict['conf'].shape[-1]
-    K = openmax_layer.num_cls
-    if C != K + 1 or openmax_prop_layer.num_cls != K:
-        raise RuntimeError(f"OpenMax decode: {C} logits per anchor for {K} Weibull models (a closed-set head has K + 1)")
-    if openmax_layer.rank != openmax_prop_layer.rank:
-        raise RuntimeError("the two OpenMax layers must use the same rank")
-    dev = loc.device
-    offs, fpst = _d.clip_scalars([0.0] * n, fps, n, dev)
-    feat, prop_feat = output_dict['conf_feat'], output_dict['prop_conf_feat'] if refined_feature else None
-    D = feat.shape[-1]
-    strides = lambda t: (ctypes.c_int64 * 3)(*[int(s) for s in t.stride()])
-    for t in (feat, prop_feat):
-        if t is not None and (t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (n, A, D)):
-            raise RuntimeError("conf_feat / prop_conf_feat must be (n, A, D) float32 device tensors")
-    mav, wb = openmax_layer.tensors(dev)
-    pmav, pwb = openmax_prop_layer.tensors(dev)
-    seg = torch.empty((n, A, 2), device=dev)
-    score = torch.empty((n, K, A), device=dev)
-    unknown = torch.empty((n, A), device=dev)
-    flag = torch.empty((n, K, A), dtype=torch.uint8, device=dev)
-    t = lambda k: output_dict[k].contiguous()
-    L.check(L.lib().otal_decode_clips_openmax_wide(
-        L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(t('priors')), L.ptr(t('conf')), L.ptr(t('prop_conf')), L.ptr(t('center')),
-        L.ptr(offs), L.ptr(fpst), L.ptr(feat), None if prop_feat is None else L.ptr(prop_feat), strides(feat),
-        None if prop_feat is None else strides(prop_feat), L.ptr(mav), L.ptr(pmav), L.ptr(wb), L.ptr(pwb), L.ptr(seg),
-        L.ptr(score), L.ptr(unknown), L.ptr(flag), n, A, C, 1, D, openmax_layer.rank, 1 if refined_feature else 0,
-        ctypes.c_float(clip_length), ctypes.c_float(conf_thresh), L.stream()), "otal_decode_clips_openmax_wide")
-    return dict(seg=seg, score=score, unct=None, actn=None, flag=flag, unknown=unknown)
+    heads = T._heads(output_dict)
+    return _common.decode_clips_openmax(heads, [0.0] * heads['loc'].shape[0], fps, openmax_layer, openmax_prop_layer,
+                                        clip_length, conf_thresh, refined_feature)
 
 
 def detect_rows(net, videos, sample_fps, openmax_layer, openmax_prop_layer, clip_length=T.CLIP_LENGTH, conf_thresh=0.001,

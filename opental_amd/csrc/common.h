@@ -29,6 +29,23 @@ __device__ __forceinline__ void st_f32(bf16_t* p, size_t i, float v) { p[i] = f3
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
+// The late-fusion segment rule of every decode kernel (decode_predictions, AFSD/thumos14/test.py:114-120; anet/test.py:110-115):
+// the refined offsets scale with the coarse width, the segment is clamped to the clip and leaves in seconds.  Anchor i of
+// clip c is row n = c * A + i of loc, prop_loc and seg (n, 2); priors (A) are centres in [0, 1]; offsets and fps are per clip.
+__device__ __forceinline__ void decode_segment(const float* loc, const float* prop_loc, const float* priors,
+                                               const float* offsets, const float* fps, float* seg, size_t n, int i, int c,
+                                               float clip_length) {
+    const float l0 = loc[n * 2], l1 = loc[n * 2 + 1];
+    const float w = l0 + l1;
+    const float r0 = 0.5f * w * prop_loc[n * 2] + l0;
+    const float r1 = 0.5f * w * prop_loc[n * 2 + 1] + l1;
+    const float pc = priors[i] * clip_length;
+    const float s0 = fminf(fmaxf(pc - r0, 0.f), clip_length);
+    const float s1 = fminf(fmaxf(pc + r1, 0.f), clip_length);
+    seg[n * 2] = (s0 + offsets[c]) / fps[c];
+    seg[n * 2 + 1] = (s1 + offsets[c]) / fps[c];
+}
+
 static inline int otal_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;

@@ -48,15 +48,7 @@ __global__ __launch_bounds__(128) void decode_clips_kernel(
     for (int i = threadIdx.x; i < A; i += blockDim.x) {
         const size_t ai = (size_t)c * A + i;
         // decode_predictions (test.py:114-120)
-        const float l0 = loc[ai * 2], l1 = loc[ai * 2 + 1];
-        const float w = l0 + l1;
-        const float r0 = 0.5f * w * prop_loc[ai * 2] + l0;
-        const float r1 = 0.5f * w * prop_loc[ai * 2 + 1] + l1;
-        const float pc = priors[i] * clip_length;
-        float s0 = fminf(fmaxf(pc - r0, 0.f), clip_length);
-        float s1 = fminf(fmaxf(pc + r1, 0.f), clip_length);
-        seg[ai * 2] = (s0 + offsets[c]) / fps[c];
-        seg[ai * 2 + 1] = (s1 + offsets[c]) / fps[c];
+        decode_segment(loc, prop_loc, priors, offsets, fps, seg, ai, i, c, clip_length);
         const float* cf = conf + ai * K;
         const float* pf = prop_conf + ai * K;
         float S = 0.f, PS = 0.f, M = 0.f, PM = 0.f;

@@ -23,28 +23,14 @@
 // ulp of 1e-3 and shape is of order 1e5, so the literal form is off by 2e-3 in w.  The host passes per class, prepared in
 // float64, off = small + (scale - 10000), inv_scale = 1 / scale and shape; with u = (d - off) * inv_scale the translated
 // argument over scale is 1 + u, and  w = -expm1(-exp(shape * log1p(u))),  w = 0 where 1 + u <= 0 (weibull_cdf, weibull.c:79-104).
-#include "openmax_common.h"       // FeatView, stage_feat, w_score, omx_sigmoid: shared with csrc/openmax_wide.hip
+#include "openmax_common.h"       // OmxArgs, FeatView, stage_feat, w_score, omx_tile, omx_launch and the argument checks:
+                                  // shared with csrc/openmax_wide.hip
 
 namespace {
 
 constexpr int OMX_KS = 16;            // class slots per row (K <= 16)
 static_assert(OMX_THREADS == OMX_TR * OMX_KS, "one thread per (row, class slot)");
 constexpr int CM_GROUPS = 16;         // row groups (waves) of a class-means workgroup
-
-struct OmxArgs {
-    FeatView f0, f1;                  // coarse feature; feature of the second stage (decode; may be the same view)
-    const float *mav0, *mav1;         // (K, D)
-    const float *wb0, *wb1;           // (K, 3): off, inv_scale, shape
-    const float *logit0, *logit1;     // row n, class j at logit[n * ldl + j]
-    long long ldl;
-    const int* labels;
-    float* out;                       // dist (N, K) / (N,), probs (N, K + 1)
-    const float *loc, *prop_loc, *priors, *center, *offsets, *fps;
-    float *seg, *score, *unknown;
-    unsigned char* flag;
-    int N, A, K, D, R, two_feats;
-    float clip_length, conf_thresh;
-};
 
 // (K, D) contiguous, 16-byte aligned (checked by the entry points) -> s[k * ld + d]
 __device__ void stage_mav(float* s, int ld, const float* mav, int K, int D) {
@@ -144,17 +130,8 @@ __global__ __launch_bounds__(OMX_THREADS) void openmax_tile_kernel(OmxArgs a) {
     float* sM1 = sM0 + (NS - 1) * K * ld;
     float* sF0 = sM0 + NS * K * ld;
     float* sF1 = (NS == 2 && a.two_feats) ? sF0 + OMX_TR * ld : sF0;
-    int n0, nvalid, clip = 0, row0 = 0;
-    if constexpr (MODE == 3) {
-        const int tiles = (a.A + OMX_TR - 1) / OMX_TR;
-        clip = blockIdx.x / tiles;
-        row0 = (blockIdx.x - clip * tiles) * OMX_TR;
-        n0 = clip * a.A + row0;
-        nvalid = min(OMX_TR, a.A - row0);
-    } else {
-        n0 = blockIdx.x * OMX_TR;
-        nvalid = min(OMX_TR, a.N - n0);
-    }
+    int n0, nvalid, clip, row0;
+    omx_tile<MODE == 3>(a, n0, nvalid, clip, row0);
     stage_mav(sM0, ld, a.mav0, K, D);
     stage_feat(sF0, ld, a.f0, n0, nvalid, D);
     if constexpr (NS == 2) {
@@ -210,16 +187,8 @@ __global__ __launch_bounds__(OMX_THREADS) void openmax_tile_kernel(OmxArgs a) {
             }
             if (j == 0) {
                 a.unknown[n] = (pu0 + pu1) / 2.0f * ct;
-                // late fusion + segments (test_openmax.py:150-156), as otal_decode_clips
-                const float l0 = a.loc[(size_t)n * 2], l1 = a.loc[(size_t)n * 2 + 1];
-                const float w = l0 + l1;
-                const float r0 = 0.5f * w * a.prop_loc[(size_t)n * 2] + l0;
-                const float r1 = 0.5f * w * a.prop_loc[(size_t)n * 2 + 1] + l1;
-                const float pc = a.priors[i] * a.clip_length;
-                const float s0_ = fminf(fmaxf(pc - r0, 0.f), a.clip_length);
-                const float s1_ = fminf(fmaxf(pc + r1, 0.f), a.clip_length);
-                a.seg[(size_t)n * 2] = (s0_ + a.offsets[clip]) / a.fps[clip];
-                a.seg[(size_t)n * 2 + 1] = (s1_ + a.offsets[clip]) / a.fps[clip];
+                // late fusion + segments (test_openmax.py:150-156)
+                decode_segment(a.loc, a.prop_loc, a.priors, a.offsets, a.fps, a.seg, n, i, clip, a.clip_length);
             }
         }
     }
@@ -259,22 +228,11 @@ __global__ __launch_bounds__(CM_GROUPS * 64) void class_means_kernel(FeatView f,
     }
 }
 
-int check_dims(int N, int rpb, int K, int D) {
-    if (N <= 0 || rpb <= 0 || K <= 0 || D <= 0) return OTAL_E_SHAPE;
-    if (K > OMX_KS || D > OMX_MAXD || (D & 15)) return OTAL_E_UNSUPPORTED;
-    return 0;
-}
-
 template <int MODE>
-int launch_tile(const OmxArgs& a, int blocks, int stages, void* stream) {
+int launch_tile(const OmxArgs& a, int blocks, void* stream) {
+    constexpr int stages = MODE == 3 ? 2 : 1;
     const size_t lds = (size_t)(stages * a.K + (1 + (stages == 2 && a.two_feats)) * OMX_TR) * (a.D + OMX_PAD) * sizeof(float);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(openmax_tile_kernel<MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(openmax_tile_kernel<MODE>, dim3(blocks), dim3(OMX_THREADS), lds, (hipStream_t)stream, a);
-    return otal_launch_status();
+    return omx_launch<openmax_tile_kernel<MODE>>(a, blocks, lds, stream);
 }
 
 }  // namespace
@@ -282,13 +240,10 @@ int launch_tile(const OmxArgs& a, int blocks, int stages, void* stream) {
 extern "C" int otal_openmax_dist(const float* feat, int N, int rows_per_batch, int64_t sb, int64_t sr, int64_t sc,
                                  const float* mav, int K, int D, const int* labels, float* dist, void* stream) {
     if (!feat || !mav || !dist) return OTAL_E_NULL;
-    if (int e = check_dims(N, rows_per_batch, K, D)) return e;
-    if ((uintptr_t)mav & 15) return OTAL_E_UNSUPPORTED;
-    OmxArgs a = {};
-    a.f0 = a.f1 = FeatView{feat, rows_per_batch, (long long)sb, (long long)sr, (long long)sc};
-    a.mav0 = mav; a.labels = labels; a.out = dist; a.N = N; a.K = K; a.D = D;
-    const int blocks = (N + OMX_TR - 1) / OMX_TR;
-    return labels ? launch_tile<1>(a, blocks, 1, stream) : launch_tile<0>(a, blocks, 1, stream);
+    OmxArgs a;
+    if (int e = omx_rows_args(feat, N, rows_per_batch, sb, sr, sc, mav, K, D, 1, K, OMX_KS, a)) return e;
+    a.labels = labels; a.out = dist;
+    return labels ? launch_tile<1>(a, omx_tiles(N), stream) : launch_tile<0>(a, omx_tiles(N), stream);
 }
 
 extern "C" int otal_openmax_class_means(const float* feat, int N, int rows_per_batch, int64_t sb, int64_t sr, int64_t sc,
@@ -305,13 +260,10 @@ extern "C" int otal_openmax_probs(const float* logits, int64_t ldl, const float*
                                   int64_t sr, int64_t sc, const float* mav, const float* wb, int K, int D, int R,
                                   float* probs, void* stream) {
     if (!logits || !feat || !mav || !wb || !probs) return OTAL_E_NULL;
-    if (int e = check_dims(N, rows_per_batch, K, D)) return e;
-    if (ldl < K) return OTAL_E_SHAPE;
-    if (R < 1 || R > K || ((uintptr_t)mav & 15)) return OTAL_E_UNSUPPORTED;
-    OmxArgs a = {};
-    a.f0 = a.f1 = FeatView{feat, rows_per_batch, (long long)sb, (long long)sr, (long long)sc};
-    a.mav0 = mav; a.wb0 = wb; a.logit0 = logits; a.ldl = ldl; a.out = probs; a.N = N; a.K = K; a.D = D; a.R = R;
-    return launch_tile<2>(a, (N + OMX_TR - 1) / OMX_TR, 1, stream);
+    OmxArgs a;
+    if (int e = omx_rows_args(feat, N, rows_per_batch, sb, sr, sc, mav, K, D, R, ldl, OMX_KS, a)) return e;
+    a.wb0 = wb; a.logit0 = logits; a.out = probs;
+    return launch_tile<2>(a, omx_tiles(N), stream);
 }
 
 extern "C" int otal_decode_clips_openmax(const float* loc, const float* prop_loc, const float* priors, const float* conf,
@@ -322,27 +274,11 @@ extern "C" int otal_decode_clips_openmax(const float* loc, const float* prop_loc
                                          float* score, float* unknown, unsigned char* flag, int nclips, int A, int C,
                                          int first_class, int D, int R, int refined_feature, float clip_length,
                                          float conf_thresh, void* stream) {
-    if (!loc || !prop_loc || !priors || !conf || !prop_conf || !center || !offsets || !fps || !feat || !feat_strides ||
-        !mav || !mav_prop || !wb || !wb_prop || !seg || !score || !unknown || !flag)
-        return OTAL_E_NULL;
-    if (refined_feature && (!prop_feat || !prop_feat_strides)) return OTAL_E_NULL;
-    if (nclips <= 0 || A <= 0 || C <= 0 || first_class < 0 || C - first_class <= 0) return OTAL_E_SHAPE;
-    if ((long long)nclips * A > 0x7fffffffLL) return OTAL_E_SHAPE;
-    const int K = C - first_class;
-    if (int e = check_dims(nclips * A, A, K, D)) return e;
-    if (R < 1 || R > K || refined_feature < 0 || refined_feature > 1 || ((uintptr_t)mav & 15) || ((uintptr_t)mav_prop & 15))
-        return OTAL_E_UNSUPPORTED;
-    OmxArgs a = {};
-    a.f0 = FeatView{feat, A, (long long)feat_strides[0], (long long)feat_strides[1], (long long)feat_strides[2]};
-    a.f1 = refined_feature ? FeatView{prop_feat, A, (long long)prop_feat_strides[0], (long long)prop_feat_strides[1],
-                                      (long long)prop_feat_strides[2]}
-                           : a.f0;
-    a.two_feats = refined_feature;
-    a.mav0 = mav; a.mav1 = mav_prop; a.wb0 = wb; a.wb1 = wb_prop;
-    a.logit0 = conf + first_class; a.logit1 = prop_conf + first_class; a.ldl = C;
-    a.loc = loc; a.prop_loc = prop_loc; a.priors = priors; a.center = center; a.offsets = offsets; a.fps = fps;
-    a.seg = seg; a.score = score; a.unknown = unknown; a.flag = flag;
-    a.N = nclips * A; a.A = A; a.K = K; a.D = D; a.R = R; a.clip_length = clip_length; a.conf_thresh = conf_thresh;
-    const int tiles = (A + OMX_TR - 1) / OMX_TR;
-    return launch_tile<3>(a, nclips * tiles, 2, stream);
+    OmxArgs a;
+    if (int e = omx_decode_args(loc, prop_loc, priors, conf, prop_conf, center, offsets, fps, feat, prop_feat, feat_strides,
+                                prop_feat_strides, mav, mav_prop, wb, wb_prop, seg, score, unknown, flag, nclips, A, C,
+                                first_class, D, R, refined_feature, clip_length, conf_thresh, OMX_KS, a))
+        return e;
+    return launch_tile<3>(a, nclips * omx_tiles(A), stream);
 }
+

@@ -33,21 +33,6 @@ constexpr int OMW_MAXK = OMW_L * OMW_SLOTS;
 constexpr int OMW_TLD = OMX_TR + 1;   // row length of the (class, anchor) transposition buffer
 static_assert(OMX_THREADS == OMX_TR * OMW_L, "one 16-lane group per row");
 
-struct OmwArgs {
-    FeatView f0, f1;                  // coarse feature; feature of the second stage (decode; may be the same view)
-    const float *mav0, *mav1;         // (K, D)
-    const float *wb0, *wb1;           // (K, 3): off, inv_scale, shape
-    const float *logit0, *logit1;     // row n, class c at logit[n * ldl + c]
-    long long ldl;
-    const int* labels;
-    float* out;                       // dist (N,), probs (N, K + 1)
-    const float *loc, *prop_loc, *priors, *center, *offsets, *fps;
-    float *seg, *score, *unknown;
-    unsigned char* flag;
-    int N, A, K, D, R, two_feats;
-    float clip_length, conf_thresh;
-};
-
 __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
     for (int o = OMW_L / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, OMW_L);
@@ -152,22 +137,13 @@ __device__ __forceinline__ void load_logits(float (&z)[OMW_SLOTS], const float* 
 
 // MODE 1: dist (N,) of each row against the MAV of its label; 2: probs (N, K + 1); 3: decode.
 template <int MODE>
-__global__ __launch_bounds__(OMX_THREADS) void openmax_wide_kernel(OmwArgs a) {
+__global__ __launch_bounds__(OMX_THREADS) void openmax_wide_kernel(OmxArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int K = a.K, D = a.D, ld = D + OMX_PAD;
     float* sF0 = reinterpret_cast<float*>(smem);
     float* sF1 = (MODE == 3 && a.two_feats) ? sF0 + OMX_TR * ld : sF0;
-    int n0, nvalid, clip = 0, row0 = 0;
-    if constexpr (MODE == 3) {
-        const int tiles = (a.A + OMX_TR - 1) / OMX_TR;
-        clip = blockIdx.x / tiles;
-        row0 = (blockIdx.x - clip * tiles) * OMX_TR;
-        n0 = clip * a.A + row0;
-        nvalid = min(OMX_TR, a.A - row0);
-    } else {
-        n0 = blockIdx.x * OMX_TR;
-        nvalid = min(OMX_TR, a.N - n0);
-    }
+    int n0, nvalid, clip, row0;
+    omx_tile<MODE == 3>(a, n0, nvalid, clip, row0);
     stage_feat(sF0, ld, a.f0, n0, nvalid, D);
     if constexpr (MODE == 3)
         if (a.two_feats) stage_feat(sF1, ld, a.f1, n0, nvalid, D);
@@ -208,16 +184,8 @@ __global__ __launch_bounds__(OMX_THREADS) void openmax_wide_kernel(OmwArgs a) {
         if (rv && l == 0) {
             const int i = row0 + r;
             a.unknown[n] = (pu0 + pu1) / 2.0f * ct;
-            // segments (anet/test.py:110-115; the arithmetic of otal_decode_clips_openmax)
-            const float l0 = a.loc[(size_t)n * 2], l1 = a.loc[(size_t)n * 2 + 1];
-            const float w = l0 + l1;
-            const float r0 = 0.5f * w * a.prop_loc[(size_t)n * 2] + l0;
-            const float r1 = 0.5f * w * a.prop_loc[(size_t)n * 2 + 1] + l1;
-            const float pc = a.priors[i] * a.clip_length;
-            const float s0_ = fminf(fmaxf(pc - r0, 0.f), a.clip_length);
-            const float s1_ = fminf(fmaxf(pc + r1, 0.f), a.clip_length);
-            a.seg[(size_t)n * 2] = (s0_ + a.offsets[clip]) / a.fps[clip];
-            a.seg[(size_t)n * 2 + 1] = (s1_ + a.offsets[clip]) / a.fps[clip];
+            // segments (anet/test.py:110-115)
+            decode_segment(a.loc, a.prop_loc, a.priors, a.offsets, a.fps, a.seg, n, i, clip, a.clip_length);
         }
         __syncthreads();
         for (int i = threadIdx.x; i < K * OMX_TR; i += OMX_THREADS) {
@@ -232,24 +200,11 @@ __global__ __launch_bounds__(OMX_THREADS) void openmax_wide_kernel(OmwArgs a) {
     }
 }
 
-int check_dims(int N, int rpb, int K, int D, int R) {
-    if (N <= 0 || rpb <= 0 || K <= 0 || D <= 0) return OTAL_E_SHAPE;
-    if (K > OMW_MAXK || D > OMX_MAXD || (D & 15) || R < 1 || R > K) return OTAL_E_UNSUPPORTED;
-    return 0;
-}
-
 template <int MODE>
-int launch_wide(const OmwArgs& a, int blocks, void* stream) {
+int launch_wide(const OmxArgs& a, int blocks, void* stream) {
     const size_t rows = (size_t)(1 + (MODE == 3 && a.two_feats)) * OMX_TR * (a.D + OMX_PAD) * sizeof(float);
     const size_t trans = MODE == 3 ? (size_t)a.K * OMW_TLD * sizeof(float) : 0;
-    const size_t lds = rows > trans ? rows : trans;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(openmax_wide_kernel<MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(openmax_wide_kernel<MODE>, dim3(blocks), dim3(OMX_THREADS), lds, (hipStream_t)stream, a);
-    return otal_launch_status();
+    return omx_launch<openmax_wide_kernel<MODE>>(a, blocks, rows > trans ? rows : trans, stream);
 }
 
 }  // namespace
@@ -257,25 +212,20 @@ int launch_wide(const OmwArgs& a, int blocks, void* stream) {
 extern "C" int otal_openmax_dist_wide(const float* feat, int N, int rows_per_batch, int64_t sb, int64_t sr, int64_t sc,
                                       const float* mav, int K, int D, const int* labels, float* dist, void* stream) {
     if (!feat || !mav || !labels || !dist) return OTAL_E_NULL;
-    if (int e = check_dims(N, rows_per_batch, K, D, 1)) return e;
-    if ((uintptr_t)mav & 15) return OTAL_E_UNSUPPORTED;
-    OmwArgs a = {};
-    a.f0 = a.f1 = FeatView{feat, rows_per_batch, (long long)sb, (long long)sr, (long long)sc};
-    a.mav0 = mav; a.labels = labels; a.out = dist; a.N = N; a.K = K; a.D = D;
-    return launch_wide<1>(a, (N + OMX_TR - 1) / OMX_TR, stream);
+    OmxArgs a;
+    if (int e = omx_rows_args(feat, N, rows_per_batch, sb, sr, sc, mav, K, D, 1, K, OMW_MAXK, a)) return e;
+    a.labels = labels; a.out = dist;
+    return launch_wide<1>(a, omx_tiles(N), stream);
 }
 
 extern "C" int otal_openmax_probs_wide(const float* logits, int64_t ldl, const float* feat, int N, int rows_per_batch,
                                        int64_t sb, int64_t sr, int64_t sc, const float* mav, const float* wb, int K, int D,
                                        int R, float* probs, void* stream) {
     if (!logits || !feat || !mav || !wb || !probs) return OTAL_E_NULL;
-    if (N <= 0 || rows_per_batch <= 0 || K <= 0 || D <= 0 || ldl < K) return OTAL_E_SHAPE;
-    if (int e = check_dims(N, rows_per_batch, K, D, R)) return e;
-    if ((uintptr_t)mav & 15) return OTAL_E_UNSUPPORTED;
-    OmwArgs a = {};
-    a.f0 = a.f1 = FeatView{feat, rows_per_batch, (long long)sb, (long long)sr, (long long)sc};
-    a.mav0 = mav; a.wb0 = wb; a.logit0 = logits; a.ldl = ldl; a.out = probs; a.N = N; a.K = K; a.D = D; a.R = R;
-    return launch_wide<2>(a, (N + OMX_TR - 1) / OMX_TR, stream);
+    OmxArgs a;
+    if (int e = omx_rows_args(feat, N, rows_per_batch, sb, sr, sc, mav, K, D, R, ldl, OMW_MAXK, a)) return e;
+    a.wb0 = wb; a.logit0 = logits; a.out = probs;
+    return launch_wide<2>(a, omx_tiles(N), stream);
 }
 
 extern "C" int otal_decode_clips_openmax_wide(const float* loc, const float* prop_loc, const float* priors, const float* conf,
@@ -286,27 +236,11 @@ extern "C" int otal_decode_clips_openmax_wide(const float* loc, const float* pro
                                               float* seg, float* score, float* unknown, unsigned char* flag, int nclips, int A,
                                               int C, int first_class, int D, int R, int refined_feature, float clip_length,
                                               float conf_thresh, void* stream) {
-    if (!loc || !prop_loc || !priors || !conf || !prop_conf || !center || !offsets || !fps || !feat || !feat_strides ||
-        !mav || !mav_prop || !wb || !wb_prop || !seg || !score || !unknown || !flag)
-        return OTAL_E_NULL;
-    if (refined_feature && (!prop_feat || !prop_feat_strides)) return OTAL_E_NULL;
-    if (nclips <= 0 || A <= 0 || C <= 0 || first_class < 0 || C - first_class <= 0) return OTAL_E_SHAPE;
-    if ((long long)nclips * A > 0x7fffffffLL) return OTAL_E_SHAPE;
-    const int K = C - first_class;
-    if (int e = check_dims(nclips * A, A, K, D, R)) return e;
-    if (refined_feature < 0 || refined_feature > 1 || ((uintptr_t)mav & 15) || ((uintptr_t)mav_prop & 15))
-        return OTAL_E_UNSUPPORTED;
-    OmwArgs a = {};
-    a.f0 = FeatView{feat, A, (long long)feat_strides[0], (long long)feat_strides[1], (long long)feat_strides[2]};
-    a.f1 = refined_feature ? FeatView{prop_feat, A, (long long)prop_feat_strides[0], (long long)prop_feat_strides[1],
-                                      (long long)prop_feat_strides[2]}
-                           : a.f0;
-    a.two_feats = refined_feature;
-    a.mav0 = mav; a.mav1 = mav_prop; a.wb0 = wb; a.wb1 = wb_prop;
-    a.logit0 = conf + first_class; a.logit1 = prop_conf + first_class; a.ldl = C;
-    a.loc = loc; a.prop_loc = prop_loc; a.priors = priors; a.center = center; a.offsets = offsets; a.fps = fps;
-    a.seg = seg; a.score = score; a.unknown = unknown; a.flag = flag;
-    a.N = nclips * A; a.A = A; a.K = K; a.D = D; a.R = R; a.clip_length = clip_length; a.conf_thresh = conf_thresh;
-    const int tiles = (A + OMX_TR - 1) / OMX_TR;
-    return launch_wide<3>(a, nclips * tiles, stream);
+    OmxArgs a;
+    if (int e = omx_decode_args(loc, prop_loc, priors, conf, prop_conf, center, offsets, fps, feat, prop_feat, feat_strides,
+                                prop_feat_strides, mav, mav_prop, wb, wb_prop, seg, score, unknown, flag, nclips, A, C,
+                                first_class, D, R, refined_feature, clip_length, conf_thresh, OMW_MAXK, a))
+        return e;
+    return launch_wide<3>(a, nclips * omx_tiles(A), stream);
 }
+

@@ -14,17 +14,21 @@ anchor and class (openmax.py:76-86), twice per clip.
 
 As shipped the reference feeds the COARSE feature to the refined stage's OpenMax layer too (test_openmax.py:159), although
 that layer's MAVs were built from the refined features; `refined_feature=True` reads the refined feature instead.
+
+decode_clips_openmax, mav_and_dist, save_mav_dist, files_are_ready and weibull_fitting are common/openmax.py's, shared with
+the ActivityNet1.3 recipe and bound here under the reference's names.
 """
-import ctypes
+import functools
 import os
 
-import numpy as np
 import torch
 
-from .. import _lib as L
-from ..common.detect import clip_scalars, detect, get_video_detections, head_mode, prepare_data, prepare_windows, results_json, \
-    windows_per_pass
-from .openmax import OpenMax, class_means, compute_eucos_dist, weibull_fit_high
+from ..common import openmax as _common
+from ..common.detect import detect, get_video_detections, head_mode, prepare_data, prepare_windows, results_json, windows_per_pass
+from ..common.openmax import decode_clips_openmax, files_are_ready, save_mav_dist, weibull_fitting  # noqa: F401
+from .openmax import OpenMax
+
+mav_and_dist = functools.partial(_common.mav_and_dist, family=OpenMax.FAMILY)
 
 
 def compute_iou(pred, target):
@@ -85,7 +89,7 @@ def collect_features(net, samples, video_infos, data_path, clip_length, crop_siz
     """The loop of compute_mav_dist (test_openmax.py:268-311), `batch_clips` training clips per forward pass: the features
     and 0-based class indices of the positive anchors of both stages -> (feat (N, D), labels (N,), prop_feat, prop_labels)."""
     from ..common.thumos_dataset import annos_transform
-    feats, labels, pfeats, plabels = [], [], [], []
+    rows = []
     batch_clips = windows_per_pass(batch_clips)
     order = sorted(range(len(samples)), key=lambda i: samples[i]['video_name'])       # one video on the device at a time
     cache = {}
@@ -98,46 +102,8 @@ def collect_features(net, samples, video_infos, data_path, clip_length, crop_siz
                   get_feat=True)
         targets = [torch.tensor(annos_transform(s['annos'], clip_length), dtype=torch.float32).reshape(-1, 3) for s in part]
         _, conf_t, _, prop_conf_t = get_matched_targets(targets, out['loc'], out['priors'], clip_length, tiou_thresh)
-        for ft, lab, fs, ls in ((out['conf_feat'], conf_t, feats, labels), (out['prop_conf_feat'], prop_conf_t, pfeats, plabels)):
-            pos = lab.reshape(-1) > 0
-            fs.append(ft.reshape(-1, ft.shape[-1])[pos])
-            ls.append((lab.reshape(-1)[pos] - 1).to(torch.int32))
-    cat = lambda xs: torch.cat(xs, 0).contiguous()
-    return cat(feats), cat(labels), cat(pfeats), cat(plabels)
-
-
-def mav_and_dist(feat, labels, num_classes):
-    """Per class: MAV = float32 mean of its rows, dist = eucos distance of each of its rows to that MAV
-    (test_openmax.py:316-324), with the two statistics kernels.  -> mav (K, D), counts (K,), dist (N,) on the device."""
-    if feat.shape[0] == 0:
-        return (torch.zeros((num_classes, feat.shape[1]), device=feat.device),
-                torch.zeros((num_classes,), dtype=torch.int32, device=feat.device), torch.zeros((0,), device=feat.device))
-    mav, counts = class_means(feat, labels, num_classes)
-    return mav, counts, compute_eucos_dist(mav, feat, labels)
-
-
-def save_mav_dist(mav_dist_dir, idx_to_class, stats, prop_stats):
-    """One <class name>.npz per class with the reference's keys (test_openmax.py:326-327).  stats = (mav, counts, dist,
-    labels) of the coarse stage, prop_stats of the refined one.  A class without a positive anchor raises (the reference
-    fails in np.stack([]))."""
-    os.makedirs(mav_dist_dir, exist_ok=True)
-    host = [[np.asarray(t.cpu().numpy()) for t in s] for s in (stats, prop_stats)]
-    names = [idx_to_class[c] for c in sorted(idx_to_class)]
-    for stage, (_, counts, _, _) in zip(("coarse", "refined"), host):
-        empty = [n for k, n in enumerate(names) if counts[k] == 0]
-        if empty:
-            raise ValueError(f"compute_mav_dist: no positive {stage}-stage anchor for class(es) {', '.join(empty)}: "
-                             "the training split must hold every known class (and, for the refined stage, proposals "
-                             "whose tIoU reaches training.piou)")
-    for k, name in enumerate(names):
-        (mav, _, dist, lab), (pmav, _, pdist, plab) = host
-        np.savez(os.path.join(mav_dist_dir, f'{name}.npz'), mav=mav[k], dist=dist[lab == k], mav_prop=pmav[k],
-                 dist_prop=pdist[plab == k])
-
-
-def files_are_ready(mav_dist_dir, idx_to_class):
-    """test_openmax.py:407-414."""
-    return all(os.path.exists(os.path.join(mav_dist_dir, f'{n}.npz')) for n in idx_to_class.values())
+        rows.append(_common.positive_rows(out, conf_t, prop_conf_t))
+    return _common.cat_rows(rows)
 
 
 def compute_mav_dist(mav_dist_dir, net, idx_to_class, video_infos, video_annos, data_path, clip_length=256, stride=30,
@@ -149,57 +115,6 @@ def compute_mav_dist(mav_dist_dir, net, idx_to_class, video_infos, video_annos, 
     feat, lab, pfeat, plab = collect_features(net, data_list, video_infos, data_path, clip_length, crop_size, tiou_thresh,
                                               batch_clips, device)
     save_mav_dist(mav_dist_dir, idx_to_class, mav_and_dist(feat, lab, K) + (lab,), mav_and_dist(pfeat, plab, K) + (plab,))
-
-
-def weibull_fitting(idx_to_class, mav_dist_dir, tailsize=20):
-    """test_openmax.py:331-354: per class and stage the `tailsize` largest distances -> weibull_fit_high.  Returns the
-    reference's two dicts {name: {'mean_vec', 'model': [fit]}}."""
-    weibull_model, weibull_prop_model = {}, {}
-    for cl in sorted(idx_to_class):
-        name = idx_to_class[cl]
-        data = np.load(os.path.join(mav_dist_dir, f'{name}.npz'), allow_pickle=True)
-        for model, mav, dist in ((weibull_model, data['mav'], data['dist']), (weibull_prop_model, data['mav_prop'], data['dist_prop'])):
-            tail = sorted(dist)[-tailsize:]
-            model[name] = {'mean_vec': mav, 'model': [weibull_fit_high(tail, name)]}
-    return weibull_model, weibull_prop_model
-
-
-def decode_clips_openmax(output_dict, offsets, fps, openmax_layer, openmax_prop_layer, clip_length=256, conf_thresh=0.01,
-                         refined_feature=False):
-    """Batched decode_output (test_openmax.py:141-170) + the threshold test of `filtering` (:173-174) in one launch.
-    output_dict: the closed-set network's outputs for n clips with get_feat=True (conf / prop_conf carry the background
-    logit, which is dropped).  Returns dict(seg (n, A, 2), score (n, K, A), flag (n, K, A) uint8, unknown (n, A), unct None,
-    actn None): the layout of decode_clips, so softnms_classes takes it as it is (3-column rows)."""
-    loc = output_dict['loc'].contiguous()
-    n, A, _ = loc.shape
-    C = output_dict['conf'].shape[-1]
-    K = openmax_layer.num_cls
-    if C != K + 1 or openmax_prop_layer.num_cls != K:
-        raise RuntimeError(f"OpenMax decode: {C} logits per anchor for {K} Weibull models (a closed-set head has K + 1)")
-    if openmax_layer.rank != openmax_prop_layer.rank:
-        raise RuntimeError("the two OpenMax layers must use the same rank")
-    dev = loc.device
-    offs, fpst = clip_scalars(offsets, fps, n, dev)
-    feat, prop_feat = output_dict['conf_feat'], output_dict['prop_conf_feat'] if refined_feature else None
-    D = feat.shape[-1]
-    strides = lambda t: (ctypes.c_int64 * 3)(*[int(s) for s in t.stride()])
-    for t in (feat, prop_feat):
-        if t is not None and (t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (n, A, D)):
-            raise RuntimeError("conf_feat / prop_conf_feat must be (n, A, D) float32 device tensors")
-    mav, wb = openmax_layer.tensors(dev)
-    pmav, pwb = openmax_prop_layer.tensors(dev)
-    seg = torch.empty((n, A, 2), device=dev)
-    score = torch.empty((n, K, A), device=dev)
-    unknown = torch.empty((n, A), device=dev)
-    flag = torch.empty((n, K, A), dtype=torch.uint8, device=dev)
-    t = lambda k: output_dict[k].contiguous()
-    L.check(L.lib().otal_decode_clips_openmax(
-        L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(output_dict['priors'].contiguous()), L.ptr(t('conf')), L.ptr(t('prop_conf')),
-        L.ptr(t('center')), L.ptr(offs), L.ptr(fpst), L.ptr(feat), None if prop_feat is None else L.ptr(prop_feat),
-        strides(feat), None if prop_feat is None else strides(prop_feat), L.ptr(mav), L.ptr(pmav), L.ptr(wb), L.ptr(pwb),
-        L.ptr(seg), L.ptr(score), L.ptr(unknown), L.ptr(flag), n, A, C, 1, D, openmax_layer.rank, 1 if refined_feature else 0,
-        ctypes.c_float(clip_length), ctypes.c_float(conf_thresh), L.stream()), "otal_decode_clips_openmax")
-    return dict(seg=seg, score=score, unct=None, actn=None, flag=flag, unknown=unknown)
 
 
 def detect_batch_openmax(net, videos, sample_fps, openmax_layer, openmax_prop_layer, clip_length=256, stride=128,

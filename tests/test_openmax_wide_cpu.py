@@ -216,6 +216,27 @@ def test_anet_openmax_layer_contract(fx):
         AO.compute_eucos_dist(torch.zeros(K, D), torch.zeros(4, D), torch.zeros(4, dtype=torch.int32))
     with pytest.raises(NotImplementedError):                    # the narrow layer keeps its limit
         TO.OpenMax(model_of(fx, 17))
+    # one statistics pass, one set of file helpers and one decode wrapper serve both recipes
+    from opental_amd.anet import test_openmax as ATO
+    from opental_amd.common import openmax as CO
+    from opental_amd.thumos14 import test_openmax as TTO
+    for mod, family in ((TTO, 'narrow'), (ATO, 'wide')):
+        assert mod.mav_and_dist.func is CO.mav_and_dist and mod.mav_and_dist.keywords == {'family': family}
+        assert mod.save_mav_dist is CO.save_mav_dist and mod.weibull_fitting is CO.weibull_fitting
+        assert mod.files_are_ready is CO.files_are_ready
+    assert TTO.decode_clips_openmax is CO.decode_clips_openmax
+    assert AO.compute_eucos_dist.func is TO.compute_eucos_dist is CO.compute_eucos_dist
+    # a narrow and a wide layer of equal K do not decode together: refused first (their ranks differ too), on host tensors
+    narrow, wide = TO.OpenMax(model_of(fx, 15), rank=1), AO.OpenMax(model_of(fx, 15), rank=3)
+    z = lambda *shape: torch.zeros(shape)
+    host = dict(loc=z(2, A, 2), prop_loc=z(2, A, 2), conf=z(2, A, 16), prop_conf=z(2, A, 16), center=z(2, A, 1),
+                conf_feat=z(2, A, D), prop_conf_feat=z(2, A, D), priors=z(A, 2))
+    with pytest.raises(RuntimeError, match="one kernel family"):
+        CO.decode_clips_openmax(host, [0.0, 0.0], 30.0, narrow, wide, 768, 0.001)
+    with pytest.raises(RuntimeError, match="one kernel family"):                # the recipe's wrapper goes through it
+        ATO.decode_clips_openmax(host, 30.0, wide, narrow)
+    with pytest.raises(RuntimeError, match="same rank"):
+        CO.decode_clips_openmax(host, [0.0, 0.0], 30.0, wide, AO.OpenMax(model_of(fx, 15), rank=1), 768, 0.001)
 
 
 def test_driver_module_imports_without_a_device():
