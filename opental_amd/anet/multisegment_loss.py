@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..thumos14.multisegment_loss import _tiou, as_padded, iou_loss, pad_targets  # noqa: F401  (iou_loss: reference name)
+from ..thumos14.multisegment_loss import _tiou, as_padded, iou_loss, kernel_focal_alpha0, pad_targets  # noqa: F401  (iou_loss: reference name)
 from .cls_loss import ActionnessLoss, EvidenceLoss, FocalLoss_Ori
 
 bounds = [[0, 30], [15, 60], [30, 120], [60, 240], [96, 768], [256, 768]]
@@ -38,10 +38,7 @@ class MultiSegmentLoss(nn.Module):
         self._focal_alpha0 = None
         if cls_loss_type == 'focal':
             self.cls_loss = FocalLoss_Ori(num_classes, balance_index=0, size_average=False, alpha=0.25)
-            al = self.cls_loss.alpha            # still on the host here: decide once whether the HIP kernel's form applies
-            if (self.cls_loss.gamma == 2 and al.numel() >= 2 and bool((al[1:] == al[1]).all())
-                    and abs(float(al[0]) + float(al[1]) - 1.0) < 1e-6):
-                self._focal_alpha0 = float(al[0])
+            self._focal_alpha0 = kernel_focal_alpha0(self.cls_loss)
         elif cls_loss_type == 'edl':
             self.cls_loss = EvidenceLoss(num_classes, edl_config, size_average=False)
         else:
@@ -130,8 +127,8 @@ class MultiSegmentLoss(nn.Module):
             return 'anet_ex', mode, None, ibm
         return 'anet_ev', mode, (EVIDENCE[cl.evidence], LOSS_TYPE[cl.loss_type]), ibm
 
-    def _cls_mode(self, loc, conf, priors):
-        """cls_mode of fused_route() for these tensors, or None where the torch formulation below runs."""
+    def _route(self, loc, conf, priors):
+        """fused_route() where the tensors are what the kernel takes, else None."""
         cl = self.cls_loss
         if not (FUSED and loc.is_cuda and loc.dtype == torch.float32 and priors.shape[0] <= 1024 and priors.shape[1] == 2
                 and conf.shape[-1] == self.num_classes and self.num_classes < 32768 and not cl.size_average
@@ -140,44 +137,44 @@ class MultiSegmentLoss(nn.Module):
         route = self.fused_route()
         if route is None:
             return None
-        mode = route[1]
         # the kernel clamps a prior's level id into the table; the torch path would raise on an out-of-range one: keep the
         # torch path's behaviour for such priors (checked once per priors tensor -- one host read, not one per step)
         key = (priors.data_ptr(), priors._version, tuple(priors.shape))
         if getattr(self, '_lvl_checked', None) != key:
             self._lvl_ok = bool(0 <= int(priors[:, 1].min()) and int(priors[:, 1].max()) < self.level_bounds.shape[0])
             self._lvl_checked = key
-        return mode if self._lvl_ok else None
+        return route if self._lvl_ok else None
+
+    def _cls_mode(self, loc, conf, priors):
+        """cls_mode of fused_route() for these tensors, or None where the torch formulation below runs."""
+        route = self._route(loc, conf, priors)
+        return None if route is None else route[1]
+
+    def _loss_call(self, route):
+        """The host scalars (ops.LossCall) of the launch `route` names."""
+        from ..common.ops import LossCall
+        entry, mode, kinds, ibm = route
+        evidence, loss_type = kinds or (0, 0)
+        # (what an entry's mode does not read is passed as 0: the IBM coefficient of the closed-set modes of 'anet_ex', the
+        # actionness settings without actionness heads)
+        return LossCall(entry=entry, clip_length=float(self.clip_length), overlap_thresh=float(self.overlap_thresh), cls_mode=mode,
+                        focal_alpha=self._focal_alpha0 if mode == 3 else 0.25, ibm_active=ibm, iou_aware=bool(self.iou_aware),
+                        evidence=evidence, loss_type=loss_type, level_bounds=self._bounds_list(),
+                        ibm_coeff=float(self.cls_loss.coeff) if (mode == 0 or entry == 'anet_ev') else 0.0,
+                        act_weight=float(self.act_loss.weight) if self.os_head else 0.0,
+                        act_margin=float(self.act_loss.margin) if self.os_head else 0.0)
 
     def forward(self, predictions, targets, pre_locs=None):
         loc, conf, prop_loc, prop_conf, center, priors, act, prop_act = predictions
         B, K = loc.shape[0], priors.shape[0]
-        mode = self._cls_mode(loc, conf, priors)
-        if mode is not None:
+        route = self._route(loc, conf, priors)
+        if route is not None:
             from ..common.ops import AnetDetectionLossFunction
-            _, _, kinds, ibm = self.fused_route()
-            kinds = () if kinds is None else (mode, 0.25) + kinds      # (the kinds follow cls_mode and focal_alpha)
-        if mode is not None and not self.os_head:
             gt, valid = as_padded(targets, loc.device)
-            iou_aware = mode == 2 and self.iou_aware
-            if kinds:
-                out = AnetDetectionLossFunction.apply(
-                    loc, conf, prop_loc, prop_conf, center.reshape(B, K), None, None, priors, gt, valid, self._bounds_list(),
-                    float(self.clip_length), float(self.overlap_thresh), ibm, float(self.cls_loss.coeff), bool(iou_aware), 0.0,
-                    0.0, *kinds)
-                return out[:5] + (None, None)
-            out = AnetDetectionLossFunction.apply(
-                loc, conf, prop_loc, prop_conf, center.reshape(B, K), None, None, priors, gt, valid, self._bounds_list(),
-                float(self.clip_length), float(self.overlap_thresh), False, 0.0, bool(iou_aware), 0.0, 0.0, mode,
-                0.25 if mode == 2 else self._focal_alpha0)
-            return out[:5] + (None, None)
-        if mode is not None:
-            gt, valid = as_padded(targets, loc.device)
-            cl = self.cls_loss
-            return AnetDetectionLossFunction.apply(
-                loc, conf, prop_loc, prop_conf, center.reshape(B, K), act.reshape(B, K), prop_act.reshape(B, K), priors, gt, valid,
-                self._bounds_list(), float(self.clip_length), float(self.overlap_thresh), ibm,
-                float(cl.coeff), bool(self.iou_aware), float(self.act_loss.weight), float(self.act_loss.margin), *kinds)
+            acts = (act.reshape(B, K), prop_act.reshape(B, K)) if self.os_head else (None, None)
+            out = AnetDetectionLossFunction.apply(loc, conf, prop_loc, prop_conf, center.reshape(B, K), *acts, priors, gt, valid,
+                                                  None, self._loss_call(route))
+            return out if self.os_head else out[:5] + (None, None)
         loc_t, conf_t, prop_loc_t, prop_conf_t, iou_pred = self.match(loc.detach(), priors, targets)
         pos, prop_pos = conf_t > 0, prop_conf_t > 0
         zero = loc.new_zeros(())

@@ -9,6 +9,7 @@ import bisect
 import ctypes
 import os
 import warnings
+from typing import NamedTuple
 
 import torch
 
@@ -1437,55 +1438,75 @@ LOSS_TYPE = {'log': 0, 'digamma': 1, 'mse': 2}
 HEAD_UNCT_MODE = {'exp': 2, 'relu': 3, 'softplus': 4}   # the Dirichlet-uncertainty item of otal_head_outputs_fwd per evidence kind
 
 
-class DetectionLossFunction(torch.autograd.Function):
-    """The seven loss terms of MultiSegmentLoss (EDL recipe) from ONE launch that also produces every gradient
-    (csrc/loss.hip); backward only scales the stored gradients by the incoming scalars.  act / prop_act may be None
-    (closed-set cls_mode 2 / 3): the kernel gets NULL, and their gradients are None.  evidence / loss_type (EVIDENCE,
-    LOSS_TYPE) other than exp / log go through otal_detection_loss_ev (cls_mode 0 and 2)."""
+class LossCall(NamedTuple):
+    """The host scalars of one fused-loss launch, under the names include/opental_hip.h gives the parameters.  A criterion
+    builds it from its fused_route(); what the chosen entry does not take keeps its default and is not passed."""
+    entry: str                  # the route's name of the entry: a key of the Function's ENTRIES
+    clip_length: float
+    overlap_thresh: float
+    cls_mode: int = 0
+    focal_alpha: float = 0.25
+    ibm_active: bool = False
+    iou_aware: bool = False
+    evidence: int = 0           # the _ev entries (EVIDENCE, LOSS_TYPE)
+    loss_type: int = 0
+    num_bins: int = 1           # otal_detection_loss, _ex, _ev
+    momentum: float = 0.0
+    reweight: int = 0           # _ex, _ev (cls_loss.REWEIGHT)
+    rw_gamma: float = 0.0
+    level_bounds: tuple = ()    # otal_detection_loss_anet_ex, _anet_ev: rows (left, right), one per pyramid level
+    ibm_coeff: float = 0.0
+    act_weight: float = 0.0
+    act_margin: float = 0.0
+    gcpl: bool = False          # otal_detection_loss_rpl
+    temperature: float = 1.0
+    weight_pl: float = 0.0
+    radius: float = 0.0
 
-    @staticmethod
-    def forward(ctx, loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt, gvalid, weight_accum,
-                clip_length, overlap, ibm_active, num_bins, momentum, iou_aware, cls_mode=0, focal_alpha=0.25, reweight=0,
-                rw_gamma=0.0, evidence=0, loss_type=0):
-        B, K, C = conf.shape
-        G = gt.shape[1]
-        tens = [None if t is None else t.contiguous().float()
-                for t in (loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt)]
+
+def _cf(*values):
+    return [ctypes.c_float(v) for v in values]
+
+
+class _FusedLossFunction(torch.autograd.Function):
+    """What the three Functions below share: every term and every gradient from one launch of csrc/loss.hip in forward; backward
+    only scales the stored gradients by the incoming scalars.
+    apply(loc, conf, prop_loc, prop_conf, center[, act, prop_act], priors, gt, gvalid, state, call): act / prop_act may be None
+    (the closed-set modes: the kernel gets NULL, and their gradients are None); state is the tensor the kernel carries from call
+    to call (None where the entry has none); call is the LossCall.  A subclass gives ENTRIES (LossCall.entry -> symbol), TERMS and
+    c_args(call, state, B, K, C, G) -> (the entry's arguments between gvalid and losses, its scratch floats)."""
+
+    @classmethod
+    def forward(cls, ctx, *inputs):
+        *maps, gvalid, state, call = inputs
+        B, K, C = maps[1].shape
+        G = maps[-1].shape[1]
+        tens = [None if t is None else t.contiguous().float() for t in maps]
         L.require_device(*[t for t in tens if t is not None])
         gv = gvalid.contiguous().to(torch.uint8)
         lib = L.lib()
-        lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
-        lib.otal_detection_loss_scratch_floats.restype = ctypes.c_size_t
-        ng = lib.otal_detection_loss_grad_floats(B, K, C)
-        ns = lib.otal_detection_loss_scratch_floats(B, K)
-        losses = torch.empty(7, dtype=torch.float32, device=loc.device)
-        grads = torch.empty(ng, dtype=torch.float32, device=loc.device)
-        scratch = torch.empty(ns, dtype=torch.float32, device=loc.device)
-        head = [None if t is None else L.ptr(t) for t in tens] + [
-            L.ptr(gv), L.ptr(weight_accum), B, K, C, G, ctypes.c_float(clip_length), ctypes.c_float(overlap), int(ibm_active),
-            int(num_bins), ctypes.c_float(momentum), int(iou_aware), int(cls_mode), ctypes.c_float(focal_alpha)]
-        tail = [L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream()]
-        if int(evidence) != 0 or int(loss_type) != 0:
-            L.check(lib.otal_detection_loss_ev(*head, int(reweight), ctypes.c_float(rw_gamma), int(evidence), int(loss_type), *tail),
-                    "otal_detection_loss_ev")
-        elif int(reweight) != 0 or (int(cls_mode) == 2 and ibm_active):
-            # a re-weighting rule of the loss ablations, or IBM over a closed set (noACT): the extended entry
-            L.check(lib.otal_detection_loss_ex(*head, int(reweight), ctypes.c_float(rw_gamma), *tail), "otal_detection_loss_ex")
-        else:
-            L.check(lib.otal_detection_loss(*head, *tail), "otal_detection_loss")
+        lib.otal_detection_loss_grad_floats.restype = lib.otal_detection_loss_scratch_floats.restype = ctypes.c_size_t
+        args, nscratch = cls.c_args(call, state, B, K, C, G)
+        dev = maps[0].device
+        losses = torch.empty(7, dtype=torch.float32, device=dev)
+        grads = torch.empty(lib.otal_detection_loss_grad_floats(B, K, C), dtype=torch.float32, device=dev)
+        scratch = torch.empty(nscratch, dtype=torch.float32, device=dev)
+        symbol = cls.ENTRIES[call.entry]
+        L.check(getattr(lib, symbol)(*[None if t is None else L.ptr(t) for t in tens], L.ptr(gv), *args, L.ptr(losses),
+                                     L.ptr(grads), L.ptr(scratch), L.stream()), symbol)
         ctx.save_for_backward(grads)
         ctx.dims = (B, K, C)
-        ctx.has_act = act is not None
-        return tuple(losses[i] for i in range(7))
+        ctx.heads = [t is not None for t in maps[:-2]]
+        return tuple(losses[i] for i in range(cls.TERMS))
 
     @staticmethod
-    def backward(ctx, g_l, g_c, g_pl, g_pc, g_ct, g_a, g_pa):
+    def backward(ctx, *gs):
         (grads,) = ctx.saved_tensors
         B, K, C = ctx.dims
         A = B * K
-        gs = [None if g is None else g.contiguous() for g in (g_l, g_c, g_pl, g_pc, g_ct, g_a, g_pa)]
+        gs = [None if g is None else g.contiguous() for g in gs]
         out = torch.empty(4 * A + 2 * A * C + 3 * A, dtype=torch.float32, device=grads.device)
-        g7 = (ctypes.c_void_p * 7)(*[None if g is None else g.data_ptr() for g in gs])
+        g7 = (ctypes.c_void_p * 7)(*[None if g is None else g.data_ptr() for g in gs])      # (a term the Function lacks: NULL)
         L.check(L.lib().otal_detection_loss_bwd(L.ptr(grads), g7, L.ptr(out), B, K, C, L.stream()), "otal_detection_loss_bwd")
         o = 0
         def take(n, shape):
@@ -1496,87 +1517,57 @@ class DetectionLossFunction(torch.autograd.Function):
         d_loc, d_pl = take(2 * A, (B, K, 2)), take(2 * A, (B, K, 2))
         d_conf, d_pconf = take(A * C, (B, K, C)), take(A * C, (B, K, C))
         d_cen, d_act, d_pact = take(A, (B, K)), take(A, (B, K)), take(A, (B, K))
-        if not getattr(ctx, 'has_act', True):        # (AnetDetectionLossFunction shares this backward)
-            d_act = d_pact = None
-        return (d_loc, d_conf, d_pl, d_pconf, d_cen, d_act, d_pact) + (None,) * 16
+        heads = tuple(d if there else None for d, there in zip((d_loc, d_conf, d_pl, d_pconf, d_cen, d_act, d_pact), ctx.heads))
+        return heads + (None,) * (len(ctx.needs_input_grad) - len(heads))       # the other inputs take no gradient
 
 
-class AnetDetectionLossFunction(torch.autograd.Function):
-    """The seven terms of the ActivityNet1.3 MultiSegmentLoss (per-sample normalisation) and all their gradients from one
-    workgroup per sample + a seven-sum launch (csrc/loss.hip: otal_detection_loss_anet_ex); backward = the shared
-    otal_detection_loss_bwd.  cls_mode 0 is the OpenTAL recipe, 2 / 3 the closed-set EDL / Softmax baselines, whose act /
-    prop_act are None: the kernel gets NULL, and their gradients are None.  evidence / loss_type (EVIDENCE, LOSS_TYPE), when
-    given, go through otal_detection_loss_anet_ev (cls_mode 0 and 2; with them cls_mode 2 takes ibm_active too)."""
+class DetectionLossFunction(_FusedLossFunction):
+    """The seven loss terms of the THUMOS14 MultiSegmentLoss (cls_mode 0 - 3); state is the IBM EMA or the GHM populations, one
+    unused float in the modes without either.  evidence / loss_type other than exp / log go through otal_detection_loss_ev."""
+    ENTRIES = {'plain': 'otal_detection_loss', 'ex': 'otal_detection_loss_ex', 'ev': 'otal_detection_loss_ev'}
+    TERMS = 7
 
     @staticmethod
-    def forward(ctx, loc, conf, prop_loc, prop_conf, center, act, prop_act, priors2, gt, gvalid, level_bounds,
-                clip_length, overlap, ibm_active, ibm_coeff, iou_aware, act_weight, act_margin, cls_mode=0, focal_alpha=0.25,
-                evidence=None, loss_type=None):
-        B, K, C = conf.shape
-        G = gt.shape[1]
-        tens = [None if t is None else t.contiguous().float()
-                for t in (loc, conf, prop_loc, prop_conf, center, act, prop_act, priors2, gt)]
-        L.require_device(*[t for t in tens if t is not None])
-        gv = gvalid.contiguous().to(torch.uint8)
-        lib = L.lib()
-        lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
-        ng = lib.otal_detection_loss_grad_floats(B, K, C)
-        losses = torch.empty(7, dtype=torch.float32, device=loc.device)
-        grads = torch.empty(ng, dtype=torch.float32, device=loc.device)
-        scratch = torch.empty(8 * B, dtype=torch.float32, device=loc.device)
-        nlev = len(level_bounds)
-        lbs = (ctypes.c_float * (2 * nlev))(*[float(v) for row in level_bounds for v in row])
-        head = [None if t is None else L.ptr(t) for t in tens] + [
-            L.ptr(gv), B, K, C, G, ctypes.c_float(clip_length), ctypes.c_float(overlap), lbs, nlev, int(ibm_active),
-            ctypes.c_float(ibm_coeff), int(iou_aware), ctypes.c_float(act_weight), ctypes.c_float(act_margin), int(cls_mode),
-            ctypes.c_float(focal_alpha)]
-        tail = [L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream()]
-        if evidence is None and loss_type is None:
-            L.check(lib.otal_detection_loss_anet_ex(*head, *tail), "otal_detection_loss_anet_ex")
-        else:
-            L.check(lib.otal_detection_loss_anet_ev(*head, int(evidence), int(loss_type), *tail), "otal_detection_loss_anet_ev")
-        ctx.save_for_backward(grads)
-        ctx.dims = (B, K, C)
-        ctx.has_act = act is not None
-        return tuple(losses[i] for i in range(7))
+    def c_args(call, state, B, K, C, G):
+        args = [L.ptr(state), B, K, C, G, *_cf(call.clip_length, call.overlap_thresh), int(call.ibm_active), int(call.num_bins),
+                *_cf(call.momentum), int(call.iou_aware), int(call.cls_mode), *_cf(call.focal_alpha)]
+        if call.entry != 'plain':
+            args += [int(call.reweight), *_cf(call.rw_gamma)]
+        if call.entry == 'ev':
+            args += [int(call.evidence), int(call.loss_type)]
+        return args, L.lib().otal_detection_loss_scratch_floats(B, K)
+
+
+class AnetDetectionLossFunction(_FusedLossFunction):
+    """The seven terms of the ActivityNet1.3 MultiSegmentLoss (per-sample normalisation): one workgroup per sample + a seven-sum
+    launch.  cls_mode 0 is the OpenTAL recipe, 2 / 3 the closed-set EDL / Softmax baselines; priors are (K,2) = (centre, level);
+    no state.  otal_detection_loss_anet_ev takes the evidence kinds and loss types, and cls_mode 2 with ibm_active."""
+    ENTRIES = {'anet_ex': 'otal_detection_loss_anet_ex', 'anet_ev': 'otal_detection_loss_anet_ev'}
+    TERMS = 7
 
     @staticmethod
-    def backward(ctx, *gs):
-        return DetectionLossFunction.backward(ctx, *gs)[:7] + (None,) * 15
+    def c_args(call, state, B, K, C, G):
+        nlev = len(call.level_bounds)
+        lbs = (ctypes.c_float * (2 * nlev))(*[float(v) for row in call.level_bounds for v in row])
+        args = [B, K, C, G, *_cf(call.clip_length, call.overlap_thresh), lbs, nlev, int(call.ibm_active), *_cf(call.ibm_coeff),
+                int(call.iou_aware), *_cf(call.act_weight, call.act_margin), int(call.cls_mode), *_cf(call.focal_alpha)]
+        if call.entry == 'anet_ev':
+            args += [int(call.evidence), int(call.loss_type)]
+        return args, 8 * B
 
 
-class RPLDetectionLossFunction(torch.autograd.Function):
-    """The five terms of the closed-set MultiSegmentLoss with the RPL / GCPL classification terms (cls_loss.RPLoss) and all
-    their gradients from one launch (csrc/loss.hip: otal_detection_loss_rpl); backward = the shared otal_detection_loss_bwd.
-    conf / prop_conf are the DISTANCE maps (B,K,C) of RPLHeadFunction: the regulariser needs only dist[i][y_i], so the
-    features and the centres get their whole gradient through d conf / d prop_conf."""
-
-    @staticmethod
-    def forward(ctx, loc, conf, prop_loc, prop_conf, center, priors, gt, gvalid, clip_length, overlap, gcpl, temperature,
-                weight_pl, radius):
-        B, K, C = conf.shape
-        G = gt.shape[1]
-        tens = [t.contiguous().float() for t in (loc, conf, prop_loc, prop_conf, center, priors, gt)]
-        L.require_device(*tens)
-        gv = gvalid.contiguous().to(torch.uint8)
-        lib = L.lib()
-        lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
-        lib.otal_detection_loss_scratch_floats.restype = ctypes.c_size_t
-        losses = torch.empty(7, dtype=torch.float32, device=loc.device)
-        grads = torch.empty(lib.otal_detection_loss_grad_floats(B, K, C), dtype=torch.float32, device=loc.device)
-        scratch = torch.empty(lib.otal_detection_loss_scratch_floats(B, K), dtype=torch.float32, device=loc.device)
-        L.check(lib.otal_detection_loss_rpl(*[L.ptr(t) for t in tens], L.ptr(gv), B, K, C, G, ctypes.c_float(clip_length),
-                                            ctypes.c_float(overlap), int(bool(gcpl)), ctypes.c_float(temperature),
-                                            ctypes.c_float(weight_pl), ctypes.c_float(radius), L.ptr(losses), L.ptr(grads),
-                                            L.ptr(scratch), L.stream()), "otal_detection_loss_rpl")
-        ctx.save_for_backward(grads)
-        ctx.dims = (B, K, C)
-        ctx.has_act = False
-        return tuple(losses[i] for i in range(5))
+class RPLDetectionLossFunction(_FusedLossFunction):
+    """The five terms of the closed-set THUMOS14 MultiSegmentLoss with the RPL / GCPL classification terms (cls_loss.RPLoss); no
+    actionness maps, no state.  conf / prop_conf are the DISTANCE maps (B,K,C) of RPLHeadFunction: the regulariser needs only
+    dist[i][y_i], so the features and the centres get their whole gradient through d conf / d prop_conf."""
+    ENTRIES = {'rpl': 'otal_detection_loss_rpl'}
+    TERMS = 5
 
     @staticmethod
-    def backward(ctx, *gs):
-        return DetectionLossFunction.backward(ctx, *gs, None, None)[:5] + (None,) * 9
+    def c_args(call, state, B, K, C, G):
+        args = [B, K, C, G, *_cf(call.clip_length, call.overlap_thresh), int(bool(call.gcpl)),
+                *_cf(call.temperature, call.weight_pl, call.radius)]
+        return args, L.lib().otal_detection_loss_scratch_floats(B, K)
 
 
 # ----------------------------------------------------------------------------- head output tails

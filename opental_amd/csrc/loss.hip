@@ -1164,80 +1164,72 @@ extern "C" size_t otal_detection_loss_grad_floats(int B, int K, int C) {
     return 4 * 2 * A + 2 * A * C + 3 * A;
 }
 
+// ---- host side.  Every extern "C" entry writes its arguments into the kernel's argument struct under their own names and
+// hands it to the one checking-and-launching function of its kernel family.
 namespace {
-// one launch of detection_loss_kernel<., false, RW, GEN>: the staged form when the pass's logits fit the dynamic LDS
-template <int RW, bool GEN = false>
-int launch_detection_loss(const LossArgs& a, bool edl, hipStream_t stream) {
-    // staged logits: EvidenceLoss modes (0, 2) and A * C floats within the dynamic LDS this kernel may add to its ~40 KB of static
-    // arrays (C = 16: up to 1536 anchors, B * 126 anchors for B <= 12); 40 + 96 KB stays inside the 160 KB of a gfx950 compute unit
+// One launch of the single-workgroup kernel: the Staged instance when the pass may stage its logits (`stageable`) and its A * C
+// floats fit the dynamic LDS the kernel may add to its ~40 KB of static arrays (C = 16: up to 1536 anchors, B * 126 anchors for
+// B <= 12; 40 + 96 KB stays inside the 160 KB of a gfx950 compute unit), else the Unstaged instance.
+template <auto Staged, auto Unstaged>
+int launch_staged(const LossArgs& a, bool stageable, hipStream_t stream) {
     const size_t stage = (size_t)a.B * a.K * a.C * sizeof(float);
     constexpr size_t STAGE_MAX = 96 * 1024;
-    static int staged_ok = -1;          // -1: not asked yet; the attribute is set once per process (and per instance)
-    if (edl && stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE")) {
+    // -1: not asked yet.  hipFuncSetAttribute is per function, so the attribute is set once per process and per Staged kernel:
+    // this static belongs to the template's instance, one per pair of kernels
+    static int staged_ok = -1;
+    if (stageable && stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE")) {
         if (staged_ok < 0)
-            staged_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(detection_loss_kernel<true, false, RW, GEN>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAGE_MAX) == hipSuccess ? 1 : 0;
+            staged_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(Staged), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)STAGE_MAX) == hipSuccess ? 1 : 0;
         if (staged_ok == 1) {
-            hipLaunchKernelGGL((detection_loss_kernel<true, false, RW, GEN>), dim3(1), dim3(LT), stage, stream, a);
+            hipLaunchKernelGGL(Staged, dim3(1), dim3(LT), stage, stream, a);
             return otal_launch_status();
         }
         (void)hipGetLastError();
     }
-    hipLaunchKernelGGL((detection_loss_kernel<false, false, RW, GEN>), dim3(1), dim3(LT), 0, stream, a);
+    hipLaunchKernelGGL(Unstaged, dim3(1), dim3(LT), 0, stream, a);
     return otal_launch_status();
 }
 
+// detection_loss_kernel<., false, rw, GEN>; the logits are staged in the EvidenceLoss modes (0, 2)
+template <bool GEN>
+int launch_detection_loss(const LossArgs& a, int rw, hipStream_t stream) {
+    const bool edl = a.cls_mode == 0 || a.cls_mode == 2;
+    switch (rw) {
+        case 1: return launch_staged<detection_loss_kernel<true, false, 1, GEN>, detection_loss_kernel<false, false, 1, GEN>>(a, edl, stream);
+        case 2: return launch_staged<detection_loss_kernel<true, false, 2, GEN>, detection_loss_kernel<false, false, 2, GEN>>(a, edl, stream);
+        case 3: return launch_staged<detection_loss_kernel<true, false, 3, GEN>, detection_loss_kernel<false, false, 3, GEN>>(a, edl, stream);
+        case 4: return launch_staged<detection_loss_kernel<true, false, 4, GEN>, detection_loss_kernel<false, false, 4, GEN>>(a, edl, stream);
+        default: return launch_staged<detection_loss_kernel<true, false, 0, GEN>, detection_loss_kernel<false, false, 0, GEN>>(a, edl, stream);
+    }
+}
+
+// a: the arguments as the entry received them (what an entry does not take is 0)
 // ex: otal_detection_loss_ex (the re-weighting rules of the loss ablations, and IBM over a closed set)
 // gen: otal_detection_loss_ev (evidence / loss_type of csrc/evidence.h, EvidenceLoss modes 0 and 2 only; implies ex)
-int detection_loss_entry(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
-                         const float* center, const float* act, const float* prop_act, const float* priors,
-                         const float* gt, const unsigned char* gvalid, float* weight_accum, int B, int K,
-                         int C, int G, float clip_length, float overlap_thresh, int ibm_active, int num_bins,
-                         float momentum, int iou_aware, int cls_mode, float focal_alpha, int reweight, float rw_gamma,
-                         bool ex, float* losses, float* grads, float* scratch, void* stream, bool gen = false,
-                         int evidence = 0, int loss_type = 0) {
-    const bool closed = cls_mode == 2 || cls_mode == 3;        // closed-set modes: no actionness heads
-    if (!loc || !conf || !prop_loc || !prop_conf || !center || (!closed && (!act || !prop_act)) || !priors || !gt || !gvalid ||
-        !weight_accum || !losses || !grads || !scratch) return OTAL_E_NULL;
-    if (B <= 0 || K <= 0 || C <= 0 || G <= 0) return OTAL_E_SHAPE;
-    if (num_bins <= 0 || num_bins > MAX_BINS || (long)B * K > MAX_A || cls_mode < 0 || cls_mode > 3) return OTAL_E_UNSUPPORTED;
-    if (cls_mode == 2 && ibm_active && !ex) return OTAL_E_UNSUPPORTED;    // closed-set EDL with IBM: otal_detection_loss_ex only
+int detection_loss_entry(LossArgs a, int reweight, bool ex, bool gen, void* stream) {
+    const bool closed = a.cls_mode == 2 || a.cls_mode == 3;    // closed-set modes: no actionness heads
+    if (!a.loc || !a.conf || !a.prop_loc || !a.prop_conf || !a.center || (!closed && (!a.act || !a.prop_act)) || !a.priors ||
+        !a.gt || !a.gvalid || !a.weight_accum || !a.losses || !a.grads || !a.scratch) return OTAL_E_NULL;
+    if (a.B <= 0 || a.K <= 0 || a.C <= 0 || a.G <= 0) return OTAL_E_SHAPE;
+    if (a.num_bins <= 0 || a.num_bins > MAX_BINS || (long)a.B * a.K > MAX_A || a.cls_mode < 0 || a.cls_mode > 3)
+        return OTAL_E_UNSUPPORTED;
+    if (a.cls_mode == 2 && a.ibm_active && !ex) return OTAL_E_UNSUPPORTED;    // closed-set EDL with IBM: otal_detection_loss_ex only
     if (reweight < 0 || reweight > 3) return OTAL_E_UNSUPPORTED;
-    if (reweight != 0 && ((cls_mode != 0 && cls_mode != 2) || ibm_active)) return OTAL_E_UNSUPPORTED;
-    if (reweight == 2 && !(momentum >= 0.f)) return OTAL_E_UNSUPPORTED;
+    if (reweight != 0 && ((a.cls_mode != 0 && a.cls_mode != 2) || a.ibm_active)) return OTAL_E_UNSUPPORTED;
+    if (reweight == 2 && !(a.momentum >= 0.f)) return OTAL_E_UNSUPPORTED;
     if (gen) {
-        if (cls_mode != 0 && cls_mode != 2) return OTAL_E_UNSUPPORTED;           // the focal modes take no evidence
-        if (evidence < 0 || evidence >= otal_ev::EV_KINDS || loss_type < 0 || loss_type >= otal_ev::LOSS_TYPES)
+        if (a.cls_mode != 0 && a.cls_mode != 2) return OTAL_E_UNSUPPORTED;       // the focal modes take no evidence
+        if (a.evidence < 0 || a.evidence >= otal_ev::EV_KINDS || a.loss_type < 0 || a.loss_type >= otal_ev::LOSS_TYPES)
             return OTAL_E_UNSUPPORTED;
         // the reference's mse_loss applies no re-weighting rule (cls_loss.py:193-209): that combination is not this kernel's
-        if (loss_type == otal_ev::LOSS_MSE && (ibm_active || reweight != 0)) return OTAL_E_UNSUPPORTED;
+        if (a.loss_type == otal_ev::LOSS_MSE && (a.ibm_active || reweight != 0)) return OTAL_E_UNSUPPORTED;
     }
-    LossArgs a{};
-    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
-    a.prop_act = prop_act; a.priors = priors; a.gt = gt; a.gvalid = gvalid; a.weight_accum = weight_accum;
-    a.losses = losses; a.grads = grads; a.scratch = scratch;
-    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
-    const bool closed_ibm = cls_mode == 2 && ibm_active;
-    a.ibm_active = (cls_mode == 0 || closed_ibm) ? ibm_active : 0; a.num_bins = num_bins;
-    a.iou_aware = (cls_mode == 0 || cls_mode == 2) ? iou_aware : 0;
-    a.momentum = momentum; a.cls_mode = cls_mode; a.focal_alpha = focal_alpha; a.rw_gamma = rw_gamma;
-    a.evidence = evidence; a.loss_type = loss_type;
-    const bool edl = cls_mode == 0 || cls_mode == 2;
-    if (gen)
-        switch (closed_ibm ? 4 : reweight) {
-            case 1: return launch_detection_loss<1, true>(a, edl, (hipStream_t)stream);
-            case 2: return launch_detection_loss<2, true>(a, edl, (hipStream_t)stream);
-            case 3: return launch_detection_loss<3, true>(a, edl, (hipStream_t)stream);
-            case 4: return launch_detection_loss<4, true>(a, edl, (hipStream_t)stream);
-            default: return launch_detection_loss<0, true>(a, edl, (hipStream_t)stream);
-        }
-    switch (closed_ibm ? 4 : reweight) {
-        case 1: return launch_detection_loss<1>(a, edl, (hipStream_t)stream);
-        case 2: return launch_detection_loss<2>(a, edl, (hipStream_t)stream);
-        case 3: return launch_detection_loss<3>(a, edl, (hipStream_t)stream);
-        case 4: return launch_detection_loss<4>(a, edl, (hipStream_t)stream);
-        default: return launch_detection_loss<0>(a, edl, (hipStream_t)stream);
-    }
+    const bool closed_ibm = a.cls_mode == 2 && a.ibm_active;
+    a.ibm_active = (a.cls_mode == 0 || closed_ibm) ? a.ibm_active : 0;
+    a.iou_aware = (a.cls_mode == 0 || a.cls_mode == 2) ? a.iou_aware : 0;
+    const int rw = closed_ibm ? 4 : reweight;       // RW of the kernel: the rule, or 4 = IBM over every anchor of a closed set
+    return gen ? launch_detection_loss<true>(a, rw, (hipStream_t)stream) : launch_detection_loss<false>(a, rw, (hipStream_t)stream);
 }
 }  // namespace
 
@@ -1247,9 +1239,14 @@ extern "C" int otal_detection_loss(const float* loc, const float* conf, const fl
                                    int C, int G, float clip_length, float overlap_thresh, int ibm_active, int num_bins,
                                    float momentum, int iou_aware, int cls_mode, float focal_alpha, float* losses,
                                    float* grads, float* scratch, void* stream) {
-    return detection_loss_entry(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt, gvalid, weight_accum, B, K, C,
-                                G, clip_length, overlap_thresh, ibm_active, num_bins, momentum, iou_aware, cls_mode, focal_alpha,
-                                0, 0.f, false, losses, grads, scratch, stream);
+    LossArgs a{};
+    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
+    a.prop_act = prop_act; a.priors = priors; a.gt = gt; a.gvalid = gvalid; a.weight_accum = weight_accum;
+    a.losses = losses; a.grads = grads; a.scratch = scratch;
+    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
+    a.ibm_active = ibm_active; a.num_bins = num_bins; a.momentum = momentum; a.iou_aware = iou_aware;
+    a.cls_mode = cls_mode; a.focal_alpha = focal_alpha;
+    return detection_loss_entry(a, 0, false, false, stream);
 }
 
 extern "C" int otal_detection_loss_ex(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
@@ -1258,9 +1255,14 @@ extern "C" int otal_detection_loss_ex(const float* loc, const float* conf, const
                                       int C, int G, float clip_length, float overlap_thresh, int ibm_active, int num_bins,
                                       float momentum, int iou_aware, int cls_mode, float focal_alpha, int reweight,
                                       float rw_gamma, float* losses, float* grads, float* scratch, void* stream) {
-    return detection_loss_entry(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt, gvalid, weight_accum, B, K, C,
-                                G, clip_length, overlap_thresh, ibm_active, num_bins, momentum, iou_aware, cls_mode, focal_alpha,
-                                reweight, rw_gamma, true, losses, grads, scratch, stream);
+    LossArgs a{};
+    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
+    a.prop_act = prop_act; a.priors = priors; a.gt = gt; a.gvalid = gvalid; a.weight_accum = weight_accum;
+    a.losses = losses; a.grads = grads; a.scratch = scratch;
+    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
+    a.ibm_active = ibm_active; a.num_bins = num_bins; a.momentum = momentum; a.iou_aware = iou_aware;
+    a.cls_mode = cls_mode; a.focal_alpha = focal_alpha; a.rw_gamma = rw_gamma;
+    return detection_loss_entry(a, reweight, true, false, stream);
 }
 
 // The other standard EDL settings (model.evidence / training.edl_config.evidence relu | softplus, loss_type digamma | mse;
@@ -1274,9 +1276,14 @@ extern "C" int otal_detection_loss_ev(const float* loc, const float* conf, const
                                       float momentum, int iou_aware, int cls_mode, float focal_alpha, int reweight,
                                       float rw_gamma, int evidence, int loss_type, float* losses, float* grads, float* scratch,
                                       void* stream) {
-    return detection_loss_entry(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors, gt, gvalid, weight_accum, B, K, C,
-                                G, clip_length, overlap_thresh, ibm_active, num_bins, momentum, iou_aware, cls_mode, focal_alpha,
-                                reweight, rw_gamma, true, losses, grads, scratch, stream, true, evidence, loss_type);
+    LossArgs a{};
+    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
+    a.prop_act = prop_act; a.priors = priors; a.gt = gt; a.gvalid = gvalid; a.weight_accum = weight_accum;
+    a.losses = losses; a.grads = grads; a.scratch = scratch;
+    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
+    a.ibm_active = ibm_active; a.num_bins = num_bins; a.momentum = momentum; a.iou_aware = iou_aware;
+    a.cls_mode = cls_mode; a.focal_alpha = focal_alpha; a.rw_gamma = rw_gamma; a.evidence = evidence; a.loss_type = loss_type;
+    return detection_loss_entry(a, reweight, true, true, stream);
 }
 
 // The RPL / GCPL baselines (thumos14_open_rpl.yaml, thumos14_open_gcpl.yaml): the closed-set form of the kernel above with
@@ -1297,70 +1304,44 @@ extern "C" int otal_detection_loss_rpl(const float* loc, const float* conf, cons
     a.cls_mode = 4 + gcpl;              // internal: a closed-set mode (>= 2) that is neither EDL nor focal
     a.focal_alpha = 0.25f;
     a.gcpl = gcpl; a.temperature = temperature; a.weight_pl = weight_pl; a.radius = radius;
-    const size_t stage = (size_t)B * K * C * sizeof(float);
-    constexpr size_t STAGE_MAX = 96 * 1024;
-    static int staged_ok = -1;          // -1: not asked yet; the attribute is set once per process
-    if (stage <= STAGE_MAX && !OTAL_OPT("OTAL_LOSS_NOSTAGE")) {
-        if (staged_ok < 0)
-            staged_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(detection_loss_kernel<true, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAGE_MAX) == hipSuccess ? 1 : 0;
-        if (staged_ok == 1) {
-            hipLaunchKernelGGL((detection_loss_kernel<true, true>), dim3(1), dim3(LT), stage, (hipStream_t)stream, a);
-            return otal_launch_status();
-        }
-        (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL((detection_loss_kernel<false, true>), dim3(1), dim3(LT), 0, (hipStream_t)stream, a);
-    return otal_launch_status();
+    return launch_staged<detection_loss_kernel<true, true>, detection_loss_kernel<false, true>>(a, true, (hipStream_t)stream);
 }
 
-
 namespace {
+// a: the arguments as the entry received them, but for the level table, which is copied into a.lb / a.rb once it is known to
+// be there; a.terms is the entry's scratch.
 // gen: otal_detection_loss_anet_ev (evidence / loss_type of csrc/evidence.h, EvidenceLoss modes 0 and 2 only; mode 2 with IBM)
-int detection_loss_anet_entry(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,
-                              const float* center, const float* act, const float* prop_act, const float* priors2,
-                              const float* gt, const unsigned char* gvalid, int B, int K, int C, int G,
-                              float clip_length, float overlap_thresh, const float* level_bounds, int nlev,
-                              int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
-                              int cls_mode, float focal_alpha, bool gen, int evidence, int loss_type, float* losses,
-                              float* grads, float* scratch, void* stream) {
+int detection_loss_anet_entry(AnetLossArgs a, const float* level_bounds, int cls_mode, bool gen, float* losses, void* stream) {
     const bool closed = cls_mode == 2 || cls_mode == 3;        // closed-set modes: no actionness heads
-    if (!loc || !conf || !prop_loc || !prop_conf || !center || (!closed && (!act || !prop_act)) || !priors2 || !gt ||
-        !gvalid || !level_bounds || !losses || !grads || !scratch) return OTAL_E_NULL;
-    if (B <= 0 || K <= 0 || C <= 0 || G <= 0 || nlev <= 0) return OTAL_E_SHAPE;
-    if (K > MAX_KA || nlev > MAX_LEVELS_A || !(cls_mode == 0 || closed)) return OTAL_E_UNSUPPORTED;
-    if (!gen && cls_mode == 2 && ibm_active) return OTAL_E_UNSUPPORTED;    // closed-set EDL with IBM: otal_detection_loss_anet_ev only
+    if (!a.loc || !a.conf || !a.prop_loc || !a.prop_conf || !a.center || (!closed && (!a.act || !a.prop_act)) || !a.priors ||
+        !a.gt || !a.gvalid || !level_bounds || !losses || !a.grads || !a.terms) return OTAL_E_NULL;
+    if (a.B <= 0 || a.K <= 0 || a.C <= 0 || a.G <= 0 || a.nlev <= 0) return OTAL_E_SHAPE;
+    if (a.K > MAX_KA || a.nlev > MAX_LEVELS_A || !(cls_mode == 0 || closed)) return OTAL_E_UNSUPPORTED;
+    if (!gen && cls_mode == 2 && a.ibm_active) return OTAL_E_UNSUPPORTED;    // closed-set EDL with IBM: otal_detection_loss_anet_ev only
     if (gen) {
         if (cls_mode != 0 && cls_mode != 2) return OTAL_E_UNSUPPORTED;           // the focal mode takes no evidence
-        if (evidence < 0 || evidence >= otal_ev::EV_KINDS || loss_type < 0 || loss_type >= otal_ev::LOSS_TYPES)
+        if (a.evidence < 0 || a.evidence >= otal_ev::EV_KINDS || a.loss_type < 0 || a.loss_type >= otal_ev::LOSS_TYPES)
             return OTAL_E_UNSUPPORTED;
         // the reference's mse_loss applies no re-weighting (anet/cls_loss.py:175-191): that combination is not this kernel's
-        if (loss_type == otal_ev::LOSS_MSE && ibm_active) return OTAL_E_UNSUPPORTED;
+        if (a.loss_type == otal_ev::LOSS_MSE && a.ibm_active) return OTAL_E_UNSUPPORTED;
     }
-    AnetLossArgs a;
-    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
-    a.prop_act = prop_act; a.priors = priors2; a.gt = gt; a.gvalid = gvalid; a.terms = scratch; a.grads = grads;
-    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh;
-    a.ibm_active = (cls_mode == 0 || gen) ? ibm_active : 0; a.iou_aware = cls_mode == 3 ? 0 : iou_aware;
-    a.coeff = ibm_coeff; a.act_weight = act_weight; a.act_margin = act_margin;
-    a.nlev = nlev; a.focal_alpha = focal_alpha;
-    a.evidence = evidence; a.loss_type = loss_type;
     // (exp, log) without closed-set IBM is what the instances without GEN compute: launch those, so that the pair gives the bits
     // of otal_detection_loss_anet_ex by construction and the shipped configs run the code they ran
-    const bool general = gen && (evidence != otal_ev::EV_EXP || loss_type != otal_ev::LOSS_LOG || (cls_mode == 2 && ibm_active));
-    for (int l = 0; l < MAX_LEVELS_A; ++l) { a.lb[l] = l < nlev ? level_bounds[2 * l] : 0.f; a.rb[l] = l < nlev ? level_bounds[2 * l + 1] : 0.f; }
+    const bool general = gen && (a.evidence != otal_ev::EV_EXP || a.loss_type != otal_ev::LOSS_LOG || (cls_mode == 2 && a.ibm_active));
+    a.ibm_active = (cls_mode == 0 || gen) ? a.ibm_active : 0; a.iou_aware = cls_mode == 3 ? 0 : a.iou_aware;
+    for (int l = 0; l < MAX_LEVELS_A; ++l) { a.lb[l] = l < a.nlev ? level_bounds[2 * l] : 0.f; a.rb[l] = l < a.nlev ? level_bounds[2 * l + 1] : 0.f; }
     if (general && cls_mode == 0)
-        hipLaunchKernelGGL((detection_loss_anet_kernel<0, true>), dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((detection_loss_anet_kernel<0, true>), dim3(a.B), dim3(LA), 0, (hipStream_t)stream, a);
     else if (general)
-        hipLaunchKernelGGL((detection_loss_anet_kernel<2, true>), dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((detection_loss_anet_kernel<2, true>), dim3(a.B), dim3(LA), 0, (hipStream_t)stream, a);
     else if (cls_mode == 0)
-        hipLaunchKernelGGL(detection_loss_anet_kernel<0>, dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(detection_loss_anet_kernel<0>, dim3(a.B), dim3(LA), 0, (hipStream_t)stream, a);
     else if (cls_mode == 2)
-        hipLaunchKernelGGL(detection_loss_anet_kernel<2>, dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(detection_loss_anet_kernel<2>, dim3(a.B), dim3(LA), 0, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(detection_loss_anet_kernel<3>, dim3(B), dim3(LA), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(detection_loss_anet_kernel<3>, dim3(a.B), dim3(LA), 0, (hipStream_t)stream, a);
     if (int e = otal_launch_status()) return e;
-    hipLaunchKernelGGL(detection_loss_anet_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scratch, losses, B);
+    hipLaunchKernelGGL(detection_loss_anet_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a.terms, losses, a.B);
     return otal_launch_status();
 }
 }  // namespace
@@ -1372,9 +1353,13 @@ extern "C" int otal_detection_loss_anet_ex(const float* loc, const float* conf, 
                                            int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
                                            int cls_mode, float focal_alpha, float* losses, float* grads, float* scratch,
                                            void* stream) {
-    return detection_loss_anet_entry(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors2, gt, gvalid, B, K, C, G,
-                                     clip_length, overlap_thresh, level_bounds, nlev, ibm_active, ibm_coeff, iou_aware, act_weight,
-                                     act_margin, cls_mode, focal_alpha, false, 0, 0, losses, grads, scratch, stream);
+    AnetLossArgs a{};
+    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
+    a.prop_act = prop_act; a.priors = priors2; a.gt = gt; a.gvalid = gvalid; a.terms = scratch; a.grads = grads;
+    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh; a.nlev = nlev;
+    a.ibm_active = ibm_active; a.coeff = ibm_coeff; a.iou_aware = iou_aware; a.act_weight = act_weight; a.act_margin = act_margin;
+    a.focal_alpha = focal_alpha;
+    return detection_loss_anet_entry(a, level_bounds, cls_mode, false, losses, stream);
 }
 
 // The other standard EDL settings for the ActivityNet1.3 recipe (edl_config.evidence relu | softplus, loss_type digamma | mse;
@@ -1389,9 +1374,13 @@ extern "C" int otal_detection_loss_anet_ev(const float* loc, const float* conf, 
                                            int ibm_active, float ibm_coeff, int iou_aware, float act_weight, float act_margin,
                                            int cls_mode, float focal_alpha, int evidence, int loss_type, float* losses,
                                            float* grads, float* scratch, void* stream) {
-    return detection_loss_anet_entry(loc, conf, prop_loc, prop_conf, center, act, prop_act, priors2, gt, gvalid, B, K, C, G,
-                                     clip_length, overlap_thresh, level_bounds, nlev, ibm_active, ibm_coeff, iou_aware, act_weight,
-                                     act_margin, cls_mode, focal_alpha, true, evidence, loss_type, losses, grads, scratch, stream);
+    AnetLossArgs a{};
+    a.loc = loc; a.conf = conf; a.prop_loc = prop_loc; a.prop_conf = prop_conf; a.center = center; a.act = act;
+    a.prop_act = prop_act; a.priors = priors2; a.gt = gt; a.gvalid = gvalid; a.terms = scratch; a.grads = grads;
+    a.B = B; a.K = K; a.C = C; a.G = G; a.clip = clip_length; a.overlap = overlap_thresh; a.nlev = nlev;
+    a.ibm_active = ibm_active; a.coeff = ibm_coeff; a.iou_aware = iou_aware; a.act_weight = act_weight; a.act_margin = act_margin;
+    a.focal_alpha = focal_alpha; a.evidence = evidence; a.loss_type = loss_type;
+    return detection_loss_anet_entry(a, level_bounds, cls_mode, true, losses, stream);
 }
 
 extern "C" int otal_detection_loss_anet(const float* loc, const float* conf, const float* prop_loc, const float* prop_conf,

@@ -28,7 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..common.input_pipeline import PaddedTargets
-from .cls_loss import ActionnessLoss, EvidenceLoss, FocalLoss_Ori, RPLoss
+from .cls_loss import REWEIGHT, ActionnessLoss, EvidenceLoss, FocalLoss_Ori, RPLoss
 
 _EPS = torch.finfo(torch.float32).eps
 FUSED = True      # single-launch HIP loss for the final recipe and the closed-set baselines (set False to force the torch formulation)
@@ -101,6 +101,15 @@ def as_padded(targets, device):
     return targets
 
 
+def kernel_focal_alpha0(focal):
+    """The focal_alpha of the HIP loss kernels for a FocalLoss_Ori -- its alpha of class 0 -- when it has their form (gamma 2,
+    one alpha for every other class, the two summing to 1), else None.  Read at construction, while alpha is on the host."""
+    al = focal.alpha
+    if focal.gamma == 2 and al.numel() >= 2 and bool((al[1:] == al[1]).all()) and abs(float(al[0]) + float(al[1]) - 1.0) < 1e-6:
+        return float(al[0])
+    return None
+
+
 class MultiSegmentLoss(nn.Module):
     def __init__(self, num_classes, overlap_thresh, negpos_ratio, use_gpu=True, cls_loss_type='focal',
                  edl_config=None, rpl_config=None, os_head=False, act_config=None, size_average=False,
@@ -115,10 +124,7 @@ class MultiSegmentLoss(nn.Module):
         self._focal_alpha0 = None
         if cls_loss_type == 'focal':
             self.cls_loss = FocalLoss_Ori(num_classes, balance_index=0, size_average=size_average, alpha=0.25)
-            al = self.cls_loss.alpha            # still on the host here: decide once whether the HIP kernel's form applies
-            if (self.cls_loss.gamma == 2 and al.numel() >= 2 and bool((al[1:] == al[1]).all())
-                    and abs(float(al[0]) + float(al[1]) - 1.0) < 1e-6):
-                self._focal_alpha0 = float(al[0])
+            self._focal_alpha0 = kernel_focal_alpha0(self.cls_loss)
         elif cls_loss_type == 'edl':
             self.cls_loss = EvidenceLoss(num_classes, edl_config, size_average=size_average)
         elif cls_loss_type == 'rpl':
@@ -165,45 +171,78 @@ class MultiSegmentLoss(nn.Module):
         use the torch formulation."""
         return self._cls_mode(loc) is not None
 
-    def _cls_mode(self, loc):
-        """cls_mode of otal_detection_loss for this criterion, or None when the kernel does not cover it:
-        0 = EDL with actionness (OpenTAL), 1 = focal with actionness (as-shipped dispatch), 2 = closed-set EDL (with IBM it
-        is the noACT ablation), 3 = closed-set focal.  'rpl' is an entry of its own (otal_detection_loss_rpl): 'rpl'.
-        The loss ablations (with_focal / with_ghm / with_ibloss) are modes 0 and 2 with the `reweight` of _reweight(); the
-        evidence function and the loss type of modes 0 and 2 are those of _kinds() (anything but exp / log:
-        otal_detection_loss_ev).  'mse' with a re-weighting rule or IBM configured is not the kernel's: None."""
+    def fused_route(self):
+        """Which HIP entry of csrc/loss.hip this criterion's SETTINGS select at its current epoch -- no tensors are read -- or
+        None where the torch formulation below runs.  -> (entry, cls_mode, kinds, reweight, ibm_active):
+          entry     'plain' (otal_detection_loss), 'ex' (otal_detection_loss_ex: a re-weighting rule in force, or IBM active
+                    over a closed set), 'ev' (otal_detection_loss_ev: any evidence / loss_type but exp / log) or 'rpl'
+                    (otal_detection_loss_rpl);
+          cls_mode  0 = EDL with actionness (OpenTAL), 1 = focal with actionness (as-shipped dispatch), 2 = closed-set EDL (with
+                    IBM it is the noACT ablation), 3 = closed-set focal; 'rpl' with the entry of that name;
+          kinds     None unless 'ev', then (evidence, loss_type) numbered as csrc/evidence.h: _kinds();
+          reweight  cls_loss.REWEIGHT of the rule EvidenceLoss.reweight() picks at this epoch (with_focal / with_ghm / with_ibloss);
+          ibm_active  that rule is the influence-balanced weight.
+        'mse' with a re-weighting rule or IBM configured is not the kernel's (the reference's mse_loss ignores them): None."""
+        from ..common.ops import EVIDENCE, LOSS_TYPE
         cl = self.cls_loss
-        common = (FUSED and loc.is_cuda and loc.dtype == torch.float32 and loc.shape[0] * loc.shape[1] <= 2048
-                  and not self.size_average and not cl.size_average)
-        if self.os_head:
-            common = common and self.act_loss.weight == 0 and not self.act_loss.size_average
-        if not common:
+        if not FUSED or self.size_average or cl.size_average:
+            return None
+        if self.os_head and (self.act_loss.weight != 0 or self.act_loss.size_average):
             return None
         if self.cls_loss_type == 'rpl':
-            return 'rpl' if float(cl.temp) > 0 else None
+            return ('rpl', 'rpl', None, 0, False) if float(cl.temp) > 0 else None
         if self.cls_loss_type == 'focal':       # the as-shipped THUMOS14 dispatch (train.py:27-31, SURVEY H2) / thumos14_softmax.yaml
-            return (1 if self.os_head else 3) if self._focal_alpha0 is not None else None
-        if self.cls_loss_type != 'edl' or cl.num_bins > 64:
-            return None
-        if cl.evidence not in ('exp', 'relu', 'softplus') or cl.loss_type not in ('log', 'digamma', 'mse'):
+            return ('plain', 1 if self.os_head else 3, None, 0, False) if self._focal_alpha0 is not None else None
+        if self.cls_loss_type != 'edl' or cl.num_bins > 64 or cl.evidence not in EVIDENCE or cl.loss_type not in LOSS_TYPE:
             return None
         if cl.loss_type == 'mse' and (cl.with_focal or cl.with_ghm or cl.with_ibloss or cl.with_ibm):
             return None
-        return 0 if self.os_head else 2
+        mode = 0 if self.os_head else 2
+        rule = cl.reweight()
+        ibm, rw = rule == 'ibm', REWEIGHT[rule]
+        kinds = self._kinds()
+        if kinds != (0, 0):
+            return 'ev', mode, kinds, rw, ibm
+        # a re-weighting rule of the loss ablations, or IBM over a closed set (noACT): the extended entry
+        return 'ex' if rw != 0 or (mode == 2 and ibm) else 'plain', mode, None, rw, ibm
+
+    def _route(self, loc):
+        """fused_route() where `loc` is what the kernel takes (a float32 device tensor of at most 2048 anchors), else None."""
+        if not (loc.is_cuda and loc.dtype == torch.float32 and loc.shape[0] * loc.shape[1] <= 2048):
+            return None
+        return self.fused_route()
+
+    def _cls_mode(self, loc):
+        """cls_mode of fused_route() for this tensor, or None where the torch formulation below runs."""
+        route = self._route(loc)
+        return None if route is None else route[1]
 
     def _kinds(self):
         """(evidence, loss_type) of otal_detection_loss_ev for this criterion's EvidenceLoss."""
         from ..common.ops import EVIDENCE, LOSS_TYPE
         return EVIDENCE[self.cls_loss.evidence], LOSS_TYPE[self.cls_loss.loss_type]
 
-    def _reweight(self):
-        """(ibm_active, reweight, rw_gamma, focal_alpha, state) of otal_detection_loss_ex for this call: the rule EvidenceLoss.
-        reweight() picks at the current epoch, and the state tensor it reads and updates (the GHM populations or the IBM EMA)."""
-        from .cls_loss import REWEIGHT
+    def _loss_call(self, route, device):
+        """(ops.LossCall, state) of the launch `route` names: the host scalars of the entry, and the tensor the kernel reads and
+        updates -- the GHM populations or the IBM EMA; one unused float where the mode has neither, None for 'rpl'."""
+        from ..common.ops import LossCall
+        entry, mode, kinds, rw, ibm = route
         cl = self.cls_loss
-        rule = cl.reweight()
-        state = cl.acc_sum if rule == 'ghm' else cl.weight_accum
-        return rule == 'ibm', REWEIGHT[rule], float(cl.gamma), float(cl.focal_alpha), state
+        own = dict(entry=entry, clip_length=float(self.clip_length), overlap_thresh=float(self.overlap_thresh))
+        if mode == 'rpl':
+            return LossCall(gcpl=bool(cl.gcpl), temperature=float(cl.temp), weight_pl=float(cl.weight_pl), radius=float(cl.radius),
+                            **own), None
+        if mode in (1, 3):                      # focal: no EMA, no rule, no IoU calibration
+            if getattr(self, '_no_ibm', None) is None or self._no_ibm.device != device:
+                self._no_ibm = torch.ones(1, dtype=torch.float32, device=device)     # unused EMA slot of the ABI
+            return LossCall(cls_mode=mode, focal_alpha=self._focal_alpha0, **own), self._no_ibm
+        evidence, loss_type = kinds or (0, 0)
+        # (the closed-set mode passes its momentum only with a rule or IBM in force: nothing else reads it)
+        momentum = float(cl.momentum) if (mode == 0 or ibm or rw) else 0.0
+        call = LossCall(cls_mode=mode, focal_alpha=float(cl.focal_alpha), ibm_active=ibm, iou_aware=bool(self.iou_aware),
+                        evidence=evidence, loss_type=loss_type, num_bins=cl.num_bins, momentum=momentum, reweight=rw,
+                        rw_gamma=float(cl.gamma), **own)
+        return call, cl.acc_sum if rw == REWEIGHT['ghm'] else cl.weight_accum
 
     def forward(self, output_dict, targets, pre_locs=None):
         loc, conf = output_dict['loc'], output_dict['conf']
@@ -212,50 +251,18 @@ class MultiSegmentLoss(nn.Module):
         act, prop_act = output_dict.get('act'), output_dict.get('prop_act')
         B, K = loc.shape[0], priors.shape[0]
         C = self.num_classes
-        mode = self._cls_mode(loc)
-        if mode == 'rpl':
-            from ..common.ops import RPLDetectionLossFunction
+        route = self._route(loc)
+        if route is not None:
+            from ..common import ops
             gt, valid = as_padded(targets, loc.device)
-            cl = self.cls_loss
-            out = RPLDetectionLossFunction.apply(
-                loc, conf, prop_loc, prop_conf, center.reshape(B, K), priors[:, 0], gt, valid, float(self.clip_length),
-                float(self.overlap_thresh), bool(cl.gcpl), float(cl.temp), float(cl.weight_pl), float(cl.radius))
-            return out + (None, None)
-        if mode is not None and not self.os_head:
-            from ..common.ops import DetectionLossFunction
-            gt, valid = as_padded(targets, loc.device)
-            cl = self.cls_loss
-            if mode == 3:
-                if getattr(self, '_no_ibm', None) is None or self._no_ibm.device != loc.device:
-                    self._no_ibm = torch.ones(1, dtype=torch.float32, device=loc.device)    # unused EMA slot of the ABI
-                wacc, nb, fa = self._no_ibm, 1, self._focal_alpha0
-                ibm, rw, gamma, mom = False, 0, 0.0, 0.0
-                ev, lt = 0, 0
+            call, state = self._loss_call(route, loc.device)
+            if route[1] == 'rpl':
+                fn, acts = ops.RPLDetectionLossFunction, ()
             else:
-                ibm, rw, gamma, fa, wacc = self._reweight()
-                nb, mom = cl.num_bins, float(cl.momentum) if (ibm or rw) else 0.0
-                ev, lt = self._kinds()
-            out = DetectionLossFunction.apply(
-                loc, conf, prop_loc, prop_conf, center.reshape(B, K), None, None, priors[:, 0], gt, valid, wacc,
-                float(self.clip_length), float(self.overlap_thresh), ibm, nb, mom, bool(self.iou_aware), mode, fa, rw, gamma,
-                ev, lt)
-            return out[:5] + (None, None)
-        if mode is not None:
-            from ..common.ops import DetectionLossFunction
-            gt, valid = as_padded(targets, loc.device)
-            cl = self.cls_loss
-            if self.cls_loss_type == 'focal':
-                if getattr(self, '_no_ibm', None) is None or self._no_ibm.device != loc.device:
-                    self._no_ibm = torch.ones(1, dtype=torch.float32, device=loc.device)    # unused EMA slot of the ABI
-                return DetectionLossFunction.apply(
-                    loc, conf, prop_loc, prop_conf, center.reshape(B, K), act.reshape(B, K), prop_act.reshape(B, K),
-                    priors[:, 0], gt, valid, self._no_ibm, float(self.clip_length), float(self.overlap_thresh),
-                    False, 1, 0.0, False, 1, self._focal_alpha0)
-            ibm, rw, gamma, fa, state = self._reweight()
-            return DetectionLossFunction.apply(
-                loc, conf, prop_loc, prop_conf, center.reshape(B, K), act.reshape(B, K), prop_act.reshape(B, K),
-                priors[:, 0], gt, valid, state, float(self.clip_length), float(self.overlap_thresh),
-                ibm, cl.num_bins, float(cl.momentum), bool(self.iou_aware), 0, fa, rw, gamma, *self._kinds())
+                fn = ops.DetectionLossFunction
+                acts = (act.reshape(B, K), prop_act.reshape(B, K)) if self.os_head else (None, None)
+            out = fn.apply(loc, conf, prop_loc, prop_conf, center.reshape(B, K), *acts, priors[:, 0], gt, valid, state, call)
+            return out if self.os_head else out[:5] + (None, None)
         loc_t, conf_t, prop_loc_t, prop_conf_t, iou_pred = self.match(loc.detach(), priors, targets)
         pos, prop_pos = conf_t > 0, prop_conf_t > 0
         zero = loc.new_zeros(())

@@ -165,6 +165,121 @@ def test_cls_mode_covers_the_nine_pairs_and_refuses_mse_with_a_rule():
         assert E.criterion(None, cfg=dict(E.BASE, evidence='relu', loss_type='digamma', **rule), os_head=True)._cls_mode(Dev) == 0
 
 
+def _thumos_criterion(kind, os_head, cfg=None, epoch=10, **kw):
+    from opental_amd.thumos14.multisegment_loss import MultiSegmentLoss
+    key = dict(edl='edl_config', rpl='rpl_config').get(kind)
+    crit = MultiSegmentLoss(15 if os_head else 16, 0.5, 1.0, cls_loss_type=kind, os_head=os_head,
+                            act_config=kw.pop('act_config', dict(A.ACT)), **({key: dict(cfg)} if key else {}), **kw)
+    if kind == 'edl':
+        crit.cls_loss.epoch = epoch
+    return crit
+
+
+FINAL = dict(A.BASE, **A.IBM)           # thumos14_opental_final.yaml
+PLAIN0 = ('plain', 0, None, 0, False)
+SD = (2, 1)                             # (softplus, digamma) as csrc/evidence.h numbers them
+# (how the criterion is built) -> fused_route(), written out from the branches the dispatch had inside DetectionLossFunction.forward
+# (_ev when the pair is not (exp, log), else _ex with a rule in force or IBM active over a closed set, else the plain entry) and
+# inside MultiSegmentLoss.forward / _cls_mode (the mode, the rule of EvidenceLoss.reweight() at the epoch)
+THUMOS_ROUTES = [
+    (lambda: _thumos_criterion('edl', True, FINAL, 9), PLAIN0),
+    (lambda: _thumos_criterion('edl', True, FINAL, 10), ('plain', 0, None, 0, True)),
+    # the eight ablation variants on both sides of their start epoch (10 in every yaml; focal is ungated)
+    (lambda: A.criterion("focal", epoch=9), ('ex', 0, None, 1, False)),
+    (lambda: A.criterion("focal", epoch=10), ('ex', 0, None, 1, False)),
+    (lambda: A.criterion("ghm", epoch=9), PLAIN0),
+    (lambda: A.criterion("ghm", epoch=10), ('ex', 0, None, 2, False)),
+    (lambda: A.criterion("ghm0", epoch=9), PLAIN0),
+    (lambda: A.criterion("ghm0", epoch=10), ('ex', 0, None, 2, False)),
+    (lambda: A.criterion("ib", epoch=9), PLAIN0),
+    (lambda: A.criterion("ib", epoch=10), ('ex', 0, None, 3, False)),
+    (lambda: A.criterion("hardmib", epoch=9), PLAIN0),
+    (lambda: A.criterion("hardmib", epoch=10), ('plain', 0, None, 0, True)),
+    (lambda: A.criterion("noMIB", epoch=9), PLAIN0),
+    (lambda: A.criterion("noMIB", epoch=10), PLAIN0),
+    (lambda: A.criterion("noIoUC", epoch=9), PLAIN0),
+    (lambda: A.criterion("noIoUC", epoch=10), ('plain', 0, None, 0, True)),
+    (lambda: A.criterion("noACT", epoch=9), ('plain', 2, None, 0, False)),
+    (lambda: A.criterion("noACT", epoch=10), ('ex', 2, None, 0, True)),
+    # the eight pairs other than (exp, log), and the other variants of the evidence fixture
+    (lambda: E.criterion("exp_digamma"), ('ev', 0, (0, 1), 0, False)),
+    (lambda: E.criterion("exp_mse"), ('ev', 0, (0, 2), 0, False)),
+    (lambda: E.criterion("relu_log"), ('ev', 0, (1, 0), 0, False)),
+    (lambda: E.criterion("relu_digamma"), ('ev', 0, (1, 1), 0, False)),
+    (lambda: E.criterion("relu_mse"), ('ev', 0, (1, 2), 0, False)),
+    (lambda: E.criterion("softplus_log"), ('ev', 0, (2, 0), 0, False)),
+    (lambda: E.criterion("softplus_digamma"), ('ev', 0, SD, 0, False)),
+    (lambda: E.criterion("softplus_mse"), ('ev', 0, (2, 2), 0, False)),
+    (lambda: E.criterion("closed_relu_log"), ('ev', 2, (1, 0), 0, False)),
+    (lambda: E.criterion("closed_softplus_digamma"), ('ev', 2, SD, 0, False)),
+    (lambda: E.criterion("closed_exp_mse"), ('ev', 2, (0, 2), 0, False)),
+    (lambda: E.criterion("sd_ibm", epoch=9), ('ev', 0, SD, 0, False)),
+    (lambda: E.criterion("sd_ibm", epoch=10), ('ev', 0, SD, 0, True)),
+    (lambda: E.criterion("sd_focal"), ('ev', 0, SD, 1, False)),
+    (lambda: E.criterion("sd_ghm", epoch=9), ('ev', 0, SD, 0, False)),
+    (lambda: E.criterion("sd_ghm", epoch=10), ('ev', 0, SD, 2, False)),
+    (lambda: E.criterion("sd_ib", epoch=10), ('ev', 0, SD, 3, False)),
+    (lambda: _thumos_criterion('edl', False, dict(E.SD, **E.IBM), 10), ('ev', 2, SD, 0, True)),
+    # mse with a rule or IBM configured: the torch formulation, before the start epoch too
+    (lambda: _thumos_criterion('edl', True, dict(E.BASE, evidence='relu', loss_type='mse', **E.IBM), 3), None),
+    (lambda: _thumos_criterion('edl', False, dict(E.BASE, evidence='exp', loss_type='mse', **E.IBM), 10), None),
+    (lambda: _thumos_criterion('edl', True, dict(E.BASE, evidence='relu', loss_type='mse', with_focal=True), 10), None),
+    (lambda: _thumos_criterion('edl', True, dict(E.BASE, evidence='relu', loss_type='mse', with_ghm=True, num_bins=30, momentum=0.85), 10), None),
+    (lambda: _thumos_criterion('edl', True, dict(E.BASE, evidence='softplus', loss_type='mse', with_ibloss=True), 10), None),
+    (lambda: _thumos_criterion('edl', True, dict(FINAL, num_bins=65), 10), None),          # more bins than the kernel's 64
+    # focal (the as-shipped dispatch and thumos14_softmax.yaml), RPL / GCPL
+    (lambda: _thumos_criterion('focal', True), ('plain', 1, None, 0, False)),
+    (lambda: _thumos_criterion('focal', False), ('plain', 3, None, 0, False)),
+    (lambda: _thumos_criterion('rpl', False, dict(temperature=1, weight_pl=0.1)), ('rpl', 'rpl', None, 0, False)),
+    (lambda: _thumos_criterion('rpl', False, dict(temperature=1, weight_pl=0.1, gcpl=True)), ('rpl', 'rpl', None, 0, False)),
+    (lambda: _thumos_criterion('rpl', False, dict(temperature=0, weight_pl=0.1)), None),
+    (lambda: _thumos_criterion('rpl', False, dict(temperature=-1, weight_pl=0.1, gcpl=True)), None),
+    # size_average, and an actionness rank term with a weight: the torch formulation
+    (lambda: _thumos_criterion('edl', True, FINAL, 10, size_average=True), None),
+    (lambda: _thumos_criterion('focal', False, size_average=True), None),
+    (lambda: _thumos_criterion('edl', True, FINAL, 10, act_config=dict(margin=1.0, weight=0.1)), None),
+    (lambda: _thumos_criterion('focal', True, act_config=dict(margin=1.0, weight=0.1)), None),
+]
+
+
+@pytest.mark.parametrize("make, want", THUMOS_ROUTES, ids=[f"{i:02d}-" + ("torch" if w is None else f"{w[0]}-mode{w[1]}-rw{w[3]}" + "-ibm" * w[4])
+                                                           for i, (_, w) in enumerate(THUMOS_ROUTES)])
+def test_thumos_fused_route_table(make, want):
+    """fused_route() reads the criterion's settings and its epoch only; _cls_mode is that route's mode behind the tensor gate."""
+    from opental_amd.thumos14 import multisegment_loss as M
+    crit = make()
+    assert crit.fused_route() == want
+
+    class Dev:                      # what the tensor gate reads of `loc`
+        is_cuda, dtype, shape = True, torch.float32, (2, 126, 2)
+    class Big(Dev):                 # one anchor past the kernel's 2048
+        shape = (1, 2049, 2)
+    assert crit._cls_mode(Dev) == (None if want is None else want[1]) and crit._fused_ok(Dev) == (want is not None)
+    assert crit._cls_mode(Big) is None and crit._cls_mode(torch.zeros(2, 126, 2)) is None
+    assert crit._cls_mode(torch.zeros(2, 126, 2, dtype=torch.float64)) is None
+    M.FUSED = False
+    try:
+        assert crit.fused_route() is None and crit._cls_mode(Dev) is None      # FUSED = False forces the torch formulation
+    finally:
+        M.FUSED = True
+
+
+def test_a_focal_alpha_that_is_not_the_kernels_form_keeps_the_torch_formulation():
+    """The kernels take FocalLoss_Ori(balance_index 0, gamma 2): alpha for class 0 and 1 - alpha for every other class."""
+    from opental_amd.thumos14.cls_loss import FocalLoss_Ori
+    from opental_amd.thumos14.multisegment_loss import kernel_focal_alpha0
+    assert kernel_focal_alpha0(FocalLoss_Ori(16, balance_index=0, size_average=False, alpha=0.25)) == 0.25
+    others = (FocalLoss_Ori(16, balance_index=3, size_average=False, alpha=0.25),             # alpha[0] + alpha[1] = 1.5
+              FocalLoss_Ori(16, balance_index=0, size_average=False, alpha=0.25, gamma=3),
+              FocalLoss_Ori(16, size_average=False, alpha=[0.25] + [0.75] * 14 + [0.5]))      # not one alpha for the others
+    for os_head in (True, False):
+        crit = _thumos_criterion('focal', os_head)
+        assert crit._focal_alpha0 == 0.25 and crit.fused_route() is not None
+        for focal in others:
+            crit.cls_loss, crit._focal_alpha0 = focal, kernel_focal_alpha0(focal)
+            assert crit._focal_alpha0 is None and crit.fused_route() is None
+
+
 def test_capture_key_holds_the_pair():
     from opental_amd.thumos14.train import DetectorTrainer
     import inspect
