@@ -889,6 +889,30 @@ int otal_eval_match_labeled(const double* pred_seg, const int* pred_label, const
 int otal_average_precision(const int* codes, const int* rank_pos, const int* class_start, const int* gt_count, int N, int K,
                            int nthr, double* ap, void* stream);
 
+/* otal_open_set_curves (csrc/oscurve.hip): AUROC, AUPR, FAR@95 and OSDR of every tIoU threshold from the matched detections
+ * of the split pass, i.e. compute_auc_scores (:459-491) and compute_osdr_scores (:494-510) with the curve functions of
+ * utils_eval, on the device.  The rule is stated in opental_amd/evaluation/table_open.py (open_reference).
+ *   known (nthr, M) fp64    the known-ness of a threshold's matched detections, ascending, equal values by table row;
+ *   flags (nthr, M) int32   bit 0: the matched ground truth is of an unknown class; bit 1: the predicted label equals the
+ *                           ground truth's (ignored with bit 0); negative: an empty slot.  The list of a threshold is the
+ *                           entries before its first empty slot, n <= M of them;
+ *   out (nthr, 4) fp64      AUROC, AUPR, FAR@95, OSDR; every element is written, zeros for an empty list.
+ * Per threshold, with ood = 1.0 - known (descending along the list), unknown the positive kind, P / Q the unknown / known
+ * counts: a tie group ends where the next entry's ood differs; (fps, tps) at the group ends are the curve points
+ * (_binary_clf_curve).  AUPR = sum over the group ends of (recall - previous recall) * tps / (end + 1), recall = tps / P (1.0
+ * where P = 0).  The ROC points are the group ends that roc_curve's drop_intermediate keeps (the first, the last and those
+ * whose second difference of fps or of tps is not 0) after (0, 0); AUROC = sum of (fpr - previous fpr) * (tpr + previous
+ * tpr) / 2.0 over them, 0.0 where P = 0 or Q = 0; FAR@95 = the fpr of the first point with the smallest |tpr - 0.95|, 0.0 where
+ * P = 0, NaN where Q = 0.  OSDR = the trapezoid sum over (1, 1), the cuts 0 .. n-2 (FPR = unknown entries at or behind the cut
+ * / P, 0.0 where P = 0; CCR = correct entries behind the cut / Q, 1.0 where Q = 0), (0, 0).  All in fp64 with IEEE division.
+ * One workgroup of OTAL_AP_TILE threads per threshold walks the list in chunks from the front with carried counts, carried
+ * group ends and a carried best point; the three sums run in one fixed order (inside a wave a butterfly, the waves of a
+ * chunk in order, the chunks in order, the last ROC point last) that depends on OTAL_AP_TILE and n alone: no atomic, no
+ * scratch, the same bits from run to run.  One launch on `stream`, no allocation, no synchronisation.  NULL pointer:
+ * OTAL_E_NULL; M < 0 or nthr < 1: OTAL_E_SHAPE; nthr > 32 or M > OTAL_AP_MAX_CLASS_ROWS: OTAL_E_UNSUPPORTED.  M == 0 writes
+ * zeros.  A refused call writes nothing.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_open_set_curves(const double* known, const int* flags, int M, int nthr, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,9 @@ def lib():
         # otal_average_precision (csrc/ap.hip): codes, rank_pos, class_start, gt_count, N, K, nthr, ap, the stream
         L.otal_average_precision.restype = ctypes.c_int
         L.otal_average_precision.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2
+        # otal_open_set_curves (csrc/oscurve.hip): known, flags, M, nthr, out, the stream
+        L.otal_open_set_curves.restype = ctypes.c_int
+        L.otal_open_set_curves.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2
         _lib = L
     return _lib
 

@@ -1,10 +1,12 @@
 """python -m opental_amd.anet.score_checkpoints <yaml> [--open_set --split N] --gt GT.json --known KNOWN.txt \\
-       [--epochs A B ...] [--tious ...] [--random_init]
+       [--epochs A B ...] [--tious ...] [--random_init] [--open_metrics [--ood_threshold THR]] [--select KEY]
 
 The mAP of every saved epoch of the ActivityNet1.3 recipe on the validation videos, from detection tables on the device
 (common/score_checkpoints.py): the network, video list, batches and thresholds of anet/test.py (`testing`: the validation
 videos that exist on disk, batches of 4), segments clipped to the videos' durations as anet/threshold.py passes them to the
-table, the `validation` subset of the ground truth (whose names carry no "v_"), tIoU 0.5 .. 0.95."""
+table, the `validation` subset of the ground truth (whose names carry no "v_"), tIoU 0.5 .. 0.95.  With --open_set
+--open_metrics also AUROC, AUPR, FAR@95 and OSDR per tIoU (evaluation/table_open.py), the tables' `known` column by
+--ood_scoring; --select KEY names what "best" goes by."""
 import json
 import os
 
@@ -39,14 +41,14 @@ def _batches(config, state):
     return [list(range(i, min(i + BATCH_CLIPS, n))) for i in range(0, n, BATCH_CLIPS)]
 
 
-def _table(net, config, state, positions, dev):
+def _table(net, config, state, positions, dev, scoring='uncertainty'):
     video_list, infos = state
     te, t = config['testing'], config['dataset']['testing']
     part = [video_list[p] for p in positions]
     vids = [T.prepare_data(t['video_mp4_path'], n, t['crop_size'], dev) for n in part]
     rows, counts = T.detect_rows(net, vids, [float(infos[n]['fps']) for n in part], t['clip_length'], te['conf_thresh'],
                                  te['top_k'], te['nms_sigma'], BATCH_CLIPS)
-    return ops.detection_table(rows, counts, [float(infos[n]['duration']) for n in part])
+    return ops.detection_table(rows, counts, [float(infos[n]['duration']) for n in part], scoring=scoring)
 
 
 RECIPE = Recipe('anet', ['validation'], np.linspace(0.5, 0.95, 10), _build, _videos, _batches, _table)

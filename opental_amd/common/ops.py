@@ -2004,6 +2004,31 @@ def average_precision(codes, rank_pos, class_start, gt_count, out=None):
     return out
 
 
+def open_set_curves(known, flags, out=None):
+    """AUROC, AUPR, FAR@95 and OSDR of every tIoU threshold in one launch (otal_open_set_curves, csrc/oscurve.hip; the rule:
+    evaluation/table_open.py).  known (nthr, M) fp64: the known-ness of a threshold's matched detections, ascending, equal
+    values by table row; flags (nthr, M) int32: bit 0 = the matched ground truth is unknown, bit 1 = the predicted label is the
+    ground truth's, negative = an empty slot (a threshold's list ends at its first one); both on the device.
+    -> out (nthr, 4) fp64 = AUROC, AUPR, FAR@95, OSDR, every element written (zeros for an empty list).  `out`: the array to
+    write into instead of allocating it; a refused call leaves it untouched.  No synchronisation."""
+    L.require_device(known, flags)
+    if known.dtype != torch.float64 or flags.dtype != torch.int32:
+        raise RuntimeError("open_set_curves: known in float64, flags in int32")
+    if known.dim() != 2 or flags.shape != known.shape or known.shape[0] < 1:
+        raise RuntimeError("open_set_curves: known (nthr, M), flags (nthr, M), nthr >= 1")
+    nthr, M = known.shape
+    if out is None:
+        out = torch.empty((nthr, 4), dtype=torch.float64, device=known.device)
+    else:
+        L.require_device(out)
+        if tuple(out.shape) != (nthr, 4) or out.dtype != torch.float64:
+            raise RuntimeError("open_set_curves: out must be (nthr, 4) float64")
+    if M == 0:          # an empty tensor has no address to pass; M says that no element of them is read
+        known, flags = known.new_zeros((nthr, 1)), flags.new_zeros((nthr, 1))
+    L.check(L.lib().otal_open_set_curves(L.ptr(known), L.ptr(flags), M, nthr, L.ptr(out), L.stream()), "otal_open_set_curves")
+    return out
+
+
 def detection_table(rows, counts, durations=None, drop_empty=False, scoring='uncertainty', out=None):
     """The Soft-NMS output of softnms_classes as one compact table (otal_detection_table, csrc/dettable.hip; the rule:
     common/det_table.py): rows (V, K, top_k, cols) fp32 with cols 3..5, counts (V, K) int32, durations (V) seconds (a

@@ -1,7 +1,7 @@
 """Which saved epoch is best: the mAP of every `checkpoint-<epoch>.ckpt` under training.checkpoint_path, on the device.
 
     python -m opental_amd.thumos14.score_checkpoints <yaml> [--open_set --split N] --gt GT.json --known KNOWN.txt \\
-           [--epochs A B ...] [--tious ...] [--random_init]
+           [--epochs A B ...] [--tious ...] [--random_init] [--open_metrics [--ood_threshold THR]] [--select KEY]
     python -m opental_amd.anet.score_checkpoints     ... the same, with the ActivityNet defaults
 
 The network is built once; per checkpoint its state dict is loaded, the test videos go through the recipe's device pipeline
@@ -14,6 +14,14 @@ One line is printed per epoch and <checkpoint_path>/checkpoint_map.json holds {e
 "best": epoch}; equal averages go to the earlier epoch, and an epoch already in the file is not scored again.  With
 --random_init the checkpoints' weights are not loaded (every listed epoch is scored with the network's own initialisation: a
 dry run of the pipeline).  One process only; two-stream fusion, the RPL / GCPL heads and OpenMax are not served.
+
+--open_metrics (with --open_set) scores every epoch by AUROC, AUPR, FAR@95 and OSDR per tIoU as well, from the same tables
+(evaluation/table_open.py; their `known` column follows testing.ood_scoring / --ood_scoring), relabelling detections below
+--ood_threshold THR as unknown when it is given.  An epoch's entry gains "AUROC", "AUPR", "FAR95" and "OSDR" lists (NaN written as
+null; "ood_threshold" when one was given) and its line their means; an epoch is skipped only when its entry already holds all
+that is asked for, otherwise it is scored and the entry merged.  --select KEY names what "best" goes by: average_mAP (default),
+AUROC, AUPR, OSDR or FAR95, the mean over the thresholds; FAR95 is best where it is lowest, a NaN mean is never best, equal means
+go to the earlier epoch.  Without these flags the output and the file are what they were without them.
 
 A recipe's module hands `run` a Recipe: how to build its network, list its test videos and detect one batch."""
 import json
@@ -28,6 +36,8 @@ from . import config as C
 from .driver import device_setup, split_flags, write_json
 
 MAP_FILE = 'checkpoint_map.json'
+OPEN_KEYS = ('AUROC', 'AUPR', 'FAR95', 'OSDR')      # an entry's open-set lists, in the order of table_open.KEYS
+SELECT_KEYS = ('average_mAP',) + OPEN_KEYS
 _CKPT = re.compile(r'^checkpoint-(\d+)\.ckpt$')
 
 
@@ -35,7 +45,8 @@ class Recipe(object):
     """dataset: ANETdetection's dataset name (how the class file is read); subset: the ground truth's subsets; tious: the
     default thresholds; build(config, dev) -> the network, randomly initialised, in eval mode;
     videos(config) -> (names as the ground truth spells them, state); batches(config, state) -> lists of positions into names;
-    table(net, config, state, positions, dev) -> the detection table of these videos (video column 0 .. len(positions)-1)."""
+    table(net, config, state, positions, dev, scoring=...) -> the detection table of these videos (video column
+    0 .. len(positions)-1), its `known` column by the out-of-distribution score `scoring`."""
 
     def __init__(self, dataset, subset, tious, build, videos, batches, table):
         self.dataset, self.subset, self.tious = dataset, subset, tious
@@ -69,13 +80,68 @@ def list_checkpoints(checkpoint_path, epochs=None):
     return dict(sorted(found.items()))
 
 
-def best_epoch(scores):
-    """The epoch of the largest average_mAP; equal values go to the earlier epoch.  None without epochs."""
-    best = None
+def select_value(entry, key):
+    """What --select KEY compares: the entry's average_mAP, or the mean of its KEY list over the thresholds (null = NaN),
+    negated for FAR95 so that larger is better throughout.  None where the entry does not hold the key."""
+    if key == 'average_mAP':
+        return entry.get('average_mAP')
+    values = entry.get(key)
+    if values is None:
+        return None
+    mean = float(np.mean([np.nan if v is None else v for v in values])) if len(values) else float('nan')
+    return -mean if key == 'FAR95' else mean
+
+
+def best_epoch(scores, key='average_mAP'):
+    """The epoch of the largest average_mAP (or of the best `key`, select_value); equal values go to the earlier epoch, an
+    epoch without the key or with a NaN mean is never best.  None without such epochs."""
+    best, best_value = None, None
     for e in sorted(int(k) for k in scores if k != 'best'):
-        if best is None or scores[str(e)]['average_mAP'] > scores[str(best)]['average_mAP']:
-            best = e
+        value = select_value(scores[str(e)], key)
+        if value is None or value != value:
+            continue
+        if best is None or value > best_value:
+            best, best_value = e, value
     return best
+
+
+def holds(entry, open_metrics, ood_threshold):
+    """Whether an epoch's entry already holds everything asked for: the mAP, and with `open_metrics` the four lists, scored
+    with this ood_threshold."""
+    if 'mAP' not in entry or 'average_mAP' not in entry:
+        return False
+    return not open_metrics or (all(k in entry for k in OPEN_KEYS) and entry.get('ood_threshold') == ood_threshold)
+
+
+def merge_entry(old, new):
+    """The entry after a scoring: the old one's keys, replaced by the new one's; an ood_threshold only where the new one has it."""
+    return dict({k: v for k, v in (old or {}).items() if k != 'ood_threshold'}, **new)
+
+
+def open_entry(metrics, ood_threshold):
+    """table_open's result as an entry's lists: NaN as None (null in the file)."""
+    from ..evaluation.table_open import KEYS
+    entry = {name: [None if v != v else float(v) for v in metrics[k]] for name, k in zip(OPEN_KEYS, KEYS)}
+    if ood_threshold is not None:
+        entry['ood_threshold'] = ood_threshold
+    return entry
+
+
+def parse_own(argv):
+    """The driver's own arguments: (own, rest).  own['--ood_threshold'] is a float or None."""
+    own, rest = split_flags(argv, ('--random_init', '--open_metrics'),
+                            {'--gt': (1, None), '--known': (1, None), '--ood_threshold': (1, None), '--select': (1, 'average_mAP')})
+    if own['--gt'] is None or own['--known'] is None:
+        raise SystemExit("score_checkpoints: --gt GT.json and --known KNOWN.txt are required")
+    if own['--select'] not in SELECT_KEYS:
+        raise SystemExit("score_checkpoints: --select takes one of %s" % ", ".join(SELECT_KEYS))
+    if own['--open_metrics'] and '--open_set' not in rest:
+        raise SystemExit("score_checkpoints: --open_metrics belongs to the open-set protocol: add --open_set")
+    if not own['--open_metrics'] and (own['--select'] in OPEN_KEYS or own['--ood_threshold'] is not None):
+        raise SystemExit("score_checkpoints: --select %s and --ood_threshold need --open_metrics" % "/".join(OPEN_KEYS))
+    if own['--ood_threshold'] is not None:
+        own['--ood_threshold'] = float(own['--ood_threshold'])
+    return own, rest
 
 
 def read_map(path):
@@ -85,12 +151,14 @@ def read_map(path):
         return {k: v for k, v in json.load(f).items() if k != 'best'}
 
 
-def epoch_tables(recipe, net, config, state, batches, dev):
-    """The detection tables of one pass over the test videos, videos numbered by their position in the recipe's list."""
+def epoch_tables(recipe, net, config, state, batches, dev, scoring=None):
+    """The detection tables of one pass over the test videos, videos numbered by their position in the recipe's list.
+    scoring: the out-of-distribution score behind the tables' `known` column (None: the recipe's default)."""
     tables = []
+    kw = {} if scoring is None else dict(scoring=scoring)
     with torch.no_grad():
         for part in batches:
-            table = recipe.table(net, config, state, part, dev)
+            table = recipe.table(net, config, state, part, dev, **kw)
             table['video'] += part[0]           # a batch holds consecutive videos
             tables.append(table)
     return tables
@@ -102,9 +170,8 @@ def run(recipe, argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     epochs, argv = take_values(argv, '--epochs')
     tious, argv = take_values(argv, '--tious')
-    own, rest = split_flags(argv, ('--random_init',), {'--gt': (1, None), '--known': (1, None)})
-    if own['--gt'] is None or own['--known'] is None:
-        raise SystemExit("score_checkpoints: --gt GT.json and --known KNOWN.txt are required")
+    own, rest = parse_own(argv)
+    open_metrics, ood_threshold, select = own['--open_metrics'], own['--ood_threshold'], own['--select']
     if int(os.environ.get('WORLD_SIZE', 1)) > 1:
         raise SystemExit("score_checkpoints runs in one process (WORLD_SIZE > 1 is not served): start it without torchrun")
     config = C.set_config(C.get_config(rest))
@@ -115,7 +182,7 @@ def run(recipe, argv=None):
     ckpts = list_checkpoints(ckpt_dir, None if epochs is None else [int(e) for e in epochs])
     map_file = os.path.join(ckpt_dir, MAP_FILE)
     scores = read_map(map_file)
-    todo = {e: p for e, p in ckpts.items() if str(e) not in scores}
+    todo = {e: p for e, p in ckpts.items() if str(e) not in scores or not holds(scores[str(e)], open_metrics, ood_threshold)}
     for e in ckpts:
         if e not in todo:
             print(f"epoch {e}: already in {map_file}, skipped")
@@ -129,12 +196,21 @@ def run(recipe, argv=None):
         for e, path in todo.items():
             if not own['--random_init']:
                 net.load_state_dict(torch.load(path, map_location='cpu'))
-            ap = table_ap(epoch_tables(recipe, net, config, state, batches, dev), gt, tious)
+            tables = epoch_tables(recipe, net, config, state, batches, dev,
+                                  config['testing']['ood_scoring'] if open_metrics else None)
+            ap = table_ap(tables, gt, tious)
             mAP = ap.mean(axis=1)
-            scores[str(e)] = {"mAP": mAP.tolist(), "average_mAP": float(mAP.mean())}
-            print(f"epoch {e}: " + " ".join(f"mAP@{t:.2f} {m:.4f}" for t, m in zip(tious, mAP)) + f" average {mAP.mean():.4f}")
-            write_json(map_file, dict(scores, best=best_epoch(scores)))
-    result = dict(scores, best=best_epoch(scores))
+            entry = {"mAP": mAP.tolist(), "average_mAP": float(mAP.mean())}
+            line = f"epoch {e}: " + " ".join(f"mAP@{t:.2f} {m:.4f}" for t, m in zip(tious, mAP)) + f" average {mAP.mean():.4f}"
+            if open_metrics:
+                from ..evaluation.table_open import KEYS, table_open
+                metrics = table_open(tables, gt, tious, ood_threshold)
+                entry.update(open_entry(metrics, ood_threshold))
+                line += "".join(f" {name} {np.mean(metrics[k]):.4f}" for name, k in zip(OPEN_KEYS, KEYS))
+            scores[str(e)] = merge_entry(scores.get(str(e)), entry)
+            print(line)
+            write_json(map_file, dict(scores, best=best_epoch(scores, select)))
+    result = dict(scores, best=best_epoch(scores, select))
     print(f"best epoch: {result['best']} -> {map_file}")
     return map_file, result
 

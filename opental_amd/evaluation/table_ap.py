@@ -117,6 +117,7 @@ class GroundTruth(object):
         self.video_index = dict(video_index)
         self.gt_count = np.bincount(self.cls[self.cls >= 0], minlength=self.n_classes).astype(np.int32)
         self._device = None
+        self._split = None
 
     @classmethod
     def load(cls, ground_truth_filename, cls_idx_detection, subset=('validation',), dataset='thumos14', videos=None):
@@ -159,6 +160,22 @@ class GroundTruth(object):
             self._device = (device, dict(has_gt=up(has_gt), gt_seg=up(seg).reshape(-1, 2), gt_start=up(gt_start),
                                          gt_count=up(self.gt_count)))
         return self._device[1]
+
+    def split_arrays(self, device):
+        """The arrays of the split pass (table_open), uploaded once: has_gt (nvid) bool; gt_seg (M, 2) fp64 and gt_cls (M)
+        int32, ALL rows, the unknown ones (cls = -1) included, sorted by (video, row); gt_start (nvid + 2) int32, their offsets
+        per video (the further group nvid, for the dropped detections, is empty)."""
+        import torch
+        if self._split is None or self._split[0] != device:
+            nvid = self.nvid
+            has_gt = np.zeros(max(nvid, 1), dtype=bool)
+            has_gt[self.video] = True
+            order = np.argsort(self.video, kind='stable')
+            gt_start = np.searchsorted(self.video[order], np.arange(nvid + 2)).astype(np.int32)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            self._split = (device, dict(has_gt=up(has_gt), gt_seg=up(self.seg[order]).reshape(-1, 2),
+                                        gt_cls=up(self.cls[order]), gt_start=up(gt_start)))
+        return self._split[1]
 
 
 def _host_columns(tables):
