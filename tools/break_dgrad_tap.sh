@@ -1,6 +1,6 @@
 #!/bin/bash
 # Shows that the bf16 backward pins (tests/test_bf16_parity_gpu.py::test_bf16_backward_matches_the_operand_rounding_oracle_block_by_block,
-# end to end; tests/test_bf16_layer_pin_gpu.py, every block alone) catch a mis-routed gradient: builds a SECOND library in /tmp whose direct 3x3x3 data-gradient weight pack does not flip
+# end to end; tests/test_bf16_layer_pin_gpu.py, every block alone; tests/test_backbone_tape_gpu.py, element by element on exact inputs) catch a mis-routed gradient: builds a SECOND library in /tmp whose direct 3x3x3 data-gradient weight pack does not flip
 # the temporal taps (-DOTAL_BREAK_DGRAD_TAP: gradient norms barely move, directions do) and runs the test against it through
 # OTAL_LIB_PATH -- it must FAIL; the product library in opental_amd/lib is not touched.   usage (GPU box): tools/break_dgrad_tap.sh
 set -u
