@@ -4,7 +4,9 @@ The product path has NO CPU fallback: if the HIP library is missing or a call fa
 RuntimeError is raised.  torch is used only for device memory and the current HIP stream.
 """
 import ctypes
+import operator
 import os
+import re
 
 import torch
 
@@ -14,7 +16,54 @@ ABI_VERSION = 26
 F32, BF16, F16, F64 = 0, 1, 2, 3
 E_UNSUPPORTED = -7      # OTAL_E_UNSUPPORTED: no kernel for this call's geometry (pair launches: issue the two launches instead)
 
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "opental_hip.h")    # csrc/build.py: -I<repo>/include
+_BY_VALUE = {"int": ctypes.c_int, "float": ctypes.c_float, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t}
+
 _lib = None
+
+
+def _ctype(text, decl, is_param):
+    """One parameter (`const float* const* x`, `int64_t n`) or return type of `decl` as its ctypes type: `const char*` is
+    c_char_p, every other pointer c_void_p (it takes ptr(t), None, ctypes arrays and buffers, cast pointers and raw addresses
+    alike), and by value only what _BY_VALUE lists -- anything else raises instead of passing as ctypes' default int."""
+    words = re.findall(r"\w+|\*", text)
+    if "*" in words:
+        return ctypes.c_char_p if words[:3] == ["const", "char", "*"] and words.count("*") == 1 else ctypes.c_void_p
+    if is_param and len(words) > 1:
+        words = words[:-1]                      # the parameter's name
+    if len(words) != 1 or words[0] not in _BY_VALUE:
+        raise ValueError(f"{decl}: no ctypes mapping for '{text.strip()}'")
+    return _BY_VALUE[words[0]]
+
+
+def signatures(path=HEADER_PATH):
+    """{name: (restype, [argtypes])} of every `ret otal_name(params);` the header declares."""
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} not found: the ctypes signatures are read from the C header")
+    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    text = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    sigs = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(otal_\w+)\s*\(([^()]*)\)\s*;", text):
+        decl = " ".join(f"{ret} {name}({params})".split())
+        params = [] if params.strip() == "void" else params.split(",")
+        sigs[name] = (_ctype(ret, decl, False), [_ctype(p, decl, True) for p in params])
+    return sigs
+
+
+class _Int:
+    """The argtypes entry of an `int` parameter.  c_int.from_param builds an argument object per call (~75 ns each, and the
+    launch wrappers pass plain ints by the dozen); operator.index hands the int itself on (~10 ns), which ctypes passes as a
+    C int as it always has -- and it refuses a float or None just the same (ctypes.ArgumentError)."""
+    from_param = operator.index
+
+
+def declare(cdll):
+    """Set restype and argtypes of every entry point the header declares on a ctypes handle of the library.  This is the only
+    place a prototype is stated on the Python side: call sites pass plain Python numbers and pointers."""
+    for name, (restype, argtypes) in signatures().items():
+        fn = getattr(cdll, name)
+        fn.restype, fn.argtypes = restype, [_Int if t is ctypes.c_int else t for t in argtypes]
+    return cdll
 
 
 def lib():
@@ -25,32 +74,9 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -m opental_amd.csrc.build` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        L.otal_error_string.restype = ctypes.c_char_p
-        L.otal_error_string.argtypes = [ctypes.c_int]
         if L.otal_abi_version() != ABI_VERSION:
             raise RuntimeError("libopental_hip.so ABI version mismatch; rebuild")
-        # otal_eval_match (csrc/eval.hip): five device arrays, ngroups, nthr, out, the non-finite counter, the stream
-        L.otal_eval_match.restype = ctypes.c_int
-        L.otal_eval_match.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3
-        # otal_eval_match_labeled: seven device arrays (labels after each segment array), ngroups, nthr, out, max_tiou, the
-        # counter, the stream
-        L.otal_eval_match_labeled.restype = ctypes.c_int
-        L.otal_eval_match_labeled.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 4
-        # otal_detection_table (csrc/dettable.hip): rows, counts, durations, V, K, top_k, cols, drop_empty, scoring, the six
-        # output arrays, the stream
-        L.otal_detection_table.restype = ctypes.c_int
-        L.otal_detection_table.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 7
-        # otal_anchor_stats (csrc/anchorstats.hip): eight fp32 arrays and gvalid, B, K, C, G, clip_length, overlap_thresh,
-        # os_head, n_known, target, score_bins, grad_bins, the two histograms, label / value / grad, the stream
-        L.otal_anchor_stats.restype = ctypes.c_int
-        L.otal_anchor_stats.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int] * 5 \
-            + [ctypes.c_void_p] * 6
-        # otal_average_precision (csrc/ap.hip): codes, rank_pos, class_start, gt_count, N, K, nthr, ap, the stream
-        L.otal_average_precision.restype = ctypes.c_int
-        L.otal_average_precision.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2
-        # otal_open_set_curves (csrc/oscurve.hip): known, flags, M, nthr, out, the stream
-        L.otal_open_set_curves.restype = ctypes.c_int
-        L.otal_open_set_curves.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2
+        declare(L)
         _lib = L
     return _lib
 

@@ -10,7 +10,6 @@ with their own decode; the proposal dicts, the result-file layout and the known/
 too.  Multi-GPU: shard the video list across ranks (as the reference's unused AFSD/anet/test.py:248-273 sketches); there is
 no collective on this path, `gather_results` collects the dicts afterwards.
 """
-import ctypes
 
 import torch
 
@@ -115,7 +114,7 @@ def decode_clips(output_dict, offsets, fps, clip_length=256, conf_thresh=0.01, o
     t = lambda k: output_dict[k].contiguous()
     head = (L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(output_dict['priors'].contiguous()), L.ptr(t('conf')), L.ptr(t('prop_conf')),
             L.ptr(t('center')), L.ptr(t('act')), L.ptr(t('prop_act')), L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score),
-            L.ptr(unct), L.ptr(actn), L.ptr(flag), n, A, K, ctypes.c_float(clip_length), ctypes.c_float(conf_thresh))
+            L.ptr(unct), L.ptr(actn), L.ptr(flag), n, A, K, clip_length, conf_thresh)
     if evidence == 'exp':
         L.check(L.lib().otal_decode_clips(*head, L.stream()), "otal_decode_clips")
     else:
@@ -137,8 +136,8 @@ def _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, u
     t = lambda k: output_dict[k].contiguous()
     head = (L.ptr(loc), L.ptr(t('prop_loc')), L.ptr(output_dict['priors'].contiguous()), L.ptr(t('conf')), L.ptr(t('prop_conf')),
             L.ptr(t('center')), None, None, L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score),
-            None if unct is None else L.ptr(unct), None, L.ptr(flag), n, A, K, ctypes.c_float(clip_length),
-            ctypes.c_float(conf_thresh), 0 if use_edl else 1, 1)
+            None if unct is None else L.ptr(unct), None, L.ptr(flag), n, A, K, clip_length, conf_thresh,
+            0 if use_edl else 1, 1)
     if use_edl and evidence != 'exp':
         L.check(L.lib().otal_decode_clips_ev(*head, EVIDENCE[evidence], L.stream()), "otal_decode_clips_ev")
     else:
@@ -191,15 +190,13 @@ def softnms_classes(dec, clip_start, top_k=5000, sigma=0.5, score_threshold=0.00
     counts = torch.zeros((V, K), dtype=torch.int32, device=dev)
     index = torch.zeros((V, K, tk), dtype=torch.int32, device=dev)
     lib = L.lib()
-    lib.otal_softnms_scratch_bytes.restype = ctypes.c_size_t
-    nbytes = int(lib.otal_softnms_scratch_bytes(int(n), int(max_clips), int(A), int(K)))   # > 0: a video exceeds the LDS working set
+    nbytes = lib.otal_softnms_scratch_bytes(n, max_clips, A, K)     # > 0: a video exceeds the LDS working set
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     opt = lambda v: None if v is None else L.ptr(v)
     L.check(lib.otal_softnms_classes_ws(L.ptr(dec['seg']), L.ptr(dec['score']), opt(dec.get('unct')),
                                         opt(dec.get('actn')), L.ptr(dec['flag']), L.ptr(cs), V, max_clips, A, K,
-                                        ctypes.c_float(sigma), tk, ctypes.c_float(score_threshold), L.ptr(out),
-                                        L.ptr(counts), L.ptr(index), cols, L.ptr(scratch), ctypes.c_size_t(nbytes), int(n),
-                                        L.stream()), "otal_softnms_classes_ws")
+                                        sigma, tk, score_threshold, L.ptr(out), L.ptr(counts), L.ptr(index), cols,
+                                        L.ptr(scratch), nbytes, n, L.stream()), "otal_softnms_classes_ws")
     return out, counts, index
 
 

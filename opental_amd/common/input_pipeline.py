@@ -6,7 +6,6 @@ fp32 per clip.  Here the host only slices uint8 frames and takes the random deci
 `random` calls as the reference, so a seeded run reproduces it -- and `otal_prepare_clips` writes the normalised
 (B,3,T,Ho,Wo) batch on the GPU from the uint8 upload (4x fewer PCIe bytes).
 """
-import ctypes
 import random
 
 import numpy as np

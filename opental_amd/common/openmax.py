@@ -40,10 +40,6 @@ def feat_view(feature):
     raise RuntimeError(f"feature must be (N, D) or (B, A, D), got {tuple(feature.shape)}")
 
 
-def _i64(v):
-    return ctypes.c_int64(int(v))
-
-
 def compute_eucos_dist(mav, feature, labels=None, family='narrow'):
     """openmax.py:7-9 for many rows: ||mav - f||_2 / 200 + (1 - cos(mav, f)).  mav (K, D) or (D,), feature (N, D) or (B, A, D),
     possibly a strided view; -> (N, K) (all rows against all MAVs), or with int32 `labels` (N) -> (N,), row n against
@@ -63,7 +59,7 @@ def compute_eucos_dist(mav, feature, labels=None, family='narrow'):
         labels = labels.to(torch.int32).contiguous()
         if labels.numel() != N:
             raise RuntimeError("one label per feature row")
-    L.check(getattr(L.lib(), entry)(L.ptr(feature), N, rpb, _i64(sb), _i64(sr), _i64(sc), L.ptr(mav), K, D,
+    L.check(getattr(L.lib(), entry)(L.ptr(feature), N, rpb, sb, sr, sc, L.ptr(mav), K, D,
                                     None if labels is None else L.ptr(labels), L.ptr(out), L.stream()), entry)
     return out
 
@@ -79,7 +75,7 @@ def class_means(feature, labels, num_classes):
         raise RuntimeError("one label per feature row")
     means = torch.empty((num_classes, D), dtype=torch.float32, device=feature.device)
     counts = torch.empty((num_classes,), dtype=torch.int32, device=feature.device)
-    L.check(L.lib().otal_openmax_class_means(L.ptr(feature), N, rpb, _i64(sb), _i64(sr), _i64(sc), L.ptr(labels),
+    L.check(L.lib().otal_openmax_class_means(L.ptr(feature), N, rpb, sb, sr, sc, L.ptr(labels),
                                              num_classes, D, L.ptr(means), L.ptr(counts), L.stream()),
             "otal_openmax_class_means")
     return means, counts
@@ -193,8 +189,8 @@ class OpenMax(nn.Module):
             raise RuntimeError(f"feature dimension {D} != MAV dimension {mav.shape[1]}")
         out = torch.empty((N, K + 1), dtype=torch.float32, device=feature_in.device)
         entry = FAMILIES[self.FAMILY].probs
-        L.check(getattr(L.lib(), entry)(L.ptr(logits), _i64(logits.stride(0)), L.ptr(feature_in), N, rpb, _i64(sb), _i64(sr),
-                                        _i64(sc), L.ptr(mav), L.ptr(wb), K, D, self.rank, L.ptr(out), L.stream()), entry)
+        L.check(getattr(L.lib(), entry)(L.ptr(logits), logits.stride(0), L.ptr(feature_in), N, rpb, sb, sr,
+                                        sc, L.ptr(mav), L.ptr(wb), K, D, self.rank, L.ptr(out), L.stream()), entry)
         return out
 
 
@@ -227,7 +223,7 @@ def decode_clips_openmax(output_dict, offsets, fps, openmax_layer, openmax_prop_
     dev = loc.device
     feat, prop_feat = output_dict['conf_feat'], output_dict['prop_conf_feat'] if refined_feature else None
     D = feat.shape[-1]
-    strides = lambda t: (ctypes.c_int64 * 3)(*[int(s) for s in t.stride()])
+    strides = lambda t: (ctypes.c_int64 * 3)(*t.stride())
     for t in (feat, prop_feat):
         if t is not None and (t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (n, A, D)):
             raise RuntimeError("conf_feat / prop_conf_feat must be (n, A, D) float32 device tensors")
@@ -244,7 +240,7 @@ def decode_clips_openmax(output_dict, offsets, fps, openmax_layer, openmax_prop_
         L.ptr(offs), L.ptr(fpst), L.ptr(feat), None if prop_feat is None else L.ptr(prop_feat), strides(feat),
         None if prop_feat is None else strides(prop_feat), L.ptr(mav), L.ptr(pmav), L.ptr(wb), L.ptr(pwb), L.ptr(seg),
         L.ptr(score), L.ptr(unknown), L.ptr(flag), n, A, C, 1, D, openmax_layer.rank, 1 if refined_feature else 0,
-        ctypes.c_float(clip_length), ctypes.c_float(conf_thresh), L.stream()), entry)
+        clip_length, conf_thresh, L.stream()), entry)
     return dict(seg=seg, score=score, unct=None, actn=None, flag=flag, unknown=unknown)
 
 

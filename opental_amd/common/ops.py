@@ -170,7 +170,7 @@ def _ws_args(device):
     s = STEP
     ws = workspace(device, s.ws_index)
     cur = s.ws_cursor[s.ws_index]
-    return ctypes.c_void_p(ws.data_ptr() + cur), ctypes.c_size_t(min(ws.numel() - cur, WORKSPACE_BYTES))
+    return ctypes.c_void_p(ws.data_ptr() + cur), min(ws.numel() - cur, WORKSPACE_BYTES)
 
 
 def defer_reduces(on):
@@ -205,9 +205,7 @@ def flush_reduces(wait=True):
 def _after_wgrad(device):
     """Advance the workspace cursor past the slabs a deferred reduction still needs; flush when they pile up."""
     s = STEP
-    lib = L.lib()
-    lib.otal_conv_deferred_end.restype = ctypes.c_size_t
-    end = int(lib.otal_conv_deferred_end())
+    end = L.lib().otal_conv_deferred_end()
     if end:
         i = s.ws_index
         s.defer_owner = (i, s.stream)
@@ -622,8 +620,6 @@ class PrologueCache:
         if key in self.entries:
             return self.entries[key]
         lib = L.lib()
-        lib.otal_conv_prologue_bytes.restype = ctypes.c_size_t
-        lib.otal_conv_prologue_desc_bytes.restype = ctypes.c_size_t
         nbytes = lib.otal_conv_prologue_bytes(ga, sa, mode, prec)
         if nbytes == 0:
             self.entries[key] = None
@@ -631,8 +627,7 @@ class PrologueCache:
         dev = w.device if w is not None else torch.device("cuda", torch.cuda.current_device())
         reg = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         desc = ctypes.create_string_buffer(lib.otal_conv_prologue_desc_bytes())
-        rc = lib.otal_conv_prologue(ga, sa, mode, L.ptr(w) if w is not None else None, prec, L.ptr(reg),
-                                    ctypes.c_size_t(nbytes), desc, L.stream())
+        rc = lib.otal_conv_prologue(ga, sa, mode, _opt(w), prec, L.ptr(reg), nbytes, desc, L.stream())
         if rc < 0:
             raise RuntimeError(f"otal_conv_prologue failed: {rc}")
         if rc > 0:                   # fwd / dgrad: needs refreshing whenever the weights change
@@ -657,7 +652,7 @@ class PrologueCache:
             self.total_blocks = starts[-1]
             self.dirty = False
         L.check(L.lib().otal_conv_prologue_batch(len(self.descs), L.ptr(self.dev_descs), L.ptr(self.dev_starts),
-                                                 int(self.total_blocks), L.stream()), "otal_conv_prologue_batch")
+                                                 self.total_blocks, L.stream()), "otal_conv_prologue_batch")
 
 
 def activate_prologues(cache):
@@ -1089,16 +1084,15 @@ def gn_relu_forward_pair(xs, gammas, betas, groups=32, eps=1e-5, relu=True, leve
         st0, st1 = _dest_strides(outs[0], B, C, T), _dest_strides(outs[1], B, C, T)
         if st0 != st1:
             return None
-        rc = L.lib().otal_gn_relu_fwd_pair_to(_pp(*xs), _pp(*gammas), _pp(*betas), _pp(*outs), ctypes.c_int64(st0[0]),
-                                              ctypes.c_int64(st0[1]), _pp(*stats), B, C, T, groups, ctypes.c_float(eps), int(relu),
-                                              nlev, lev, L.stream())
+        rc = L.lib().otal_gn_relu_fwd_pair_to(_pp(*xs), _pp(*gammas), _pp(*betas), _pp(*outs), st0[0], st0[1], _pp(*stats),
+                                              B, C, T, groups, eps, int(relu), nlev, lev, L.stream())
         if rc == L.E_UNSUPPORTED:
             return None
         L.check(rc, "otal_gn_relu_fwd_pair_to")
         return list(zip(outs, stats))
     ys = [torch.empty_like(x) for x in xs]
     rc = L.lib().otal_gn_relu_fwd_pair(_pp(*xs), _pp(*gammas), _pp(*betas), _pp(*ys), _pp(*stats), B, C, T, groups,
-                                       ctypes.c_float(eps), int(relu), nlev, lev, L.stream())
+                                       eps, int(relu), nlev, lev, L.stream())
     if rc == L.E_UNSUPPORTED:
         return None
     L.check(rc, "otal_gn_relu_fwd_pair")
@@ -1129,13 +1123,12 @@ def gn_relu_forward(x, gamma, beta, groups=32, eps=1e-5, relu=True, levels=None,
     stats = torch.empty((B, groups, nlev, 2), dtype=torch.float32, device=x.device)
     if out is not None:
         bs, cs = _dest_strides(out, B, C, T)
-        L.check(L.lib().otal_gn_relu_fwd_to(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(out), ctypes.c_int64(bs), ctypes.c_int64(cs),
-                                            L.ptr(stats), B, C, T, groups, ctypes.c_float(eps), int(relu), nlev, lev, L.stream()),
-                "otal_gn_relu_fwd_to")
+        L.check(L.lib().otal_gn_relu_fwd_to(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(out), bs, cs, L.ptr(stats), B, C, T, groups,
+                                            eps, int(relu), nlev, lev, L.stream()), "otal_gn_relu_fwd_to")
         return out, stats
     y = torch.empty_like(x)
     L.check(L.lib().otal_gn_relu_fwd(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y), L.ptr(stats), B, C, T, groups,
-                                     ctypes.c_float(eps), int(relu), nlev, lev, L.stream()), "otal_gn_relu_fwd")
+                                     eps, int(relu), nlev, lev, L.stream()), "otal_gn_relu_fwd")
     return y, stats
 
 
@@ -1182,7 +1175,7 @@ def gn_relu_backward(dy, x, gamma, beta, stats, groups=32, relu=True, levels=Non
     nlev, lev = _lev_arg(levels)
     dx = torch.empty_like(x)
     partial = torch.empty((B, 3, C), dtype=torch.float32, device=x.device)
-    L.check(L.lib().otal_gn_relu_bwd(L.ptr(dy), ctypes.c_int64(dy.stride(0)), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(stats),
+    L.check(L.lib().otal_gn_relu_bwd(L.ptr(dy), dy.stride(0), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(stats),
                                      L.ptr(dx), L.ptr(partial), B, C, T, groups, int(relu), nlev, lev, L.stream()),
             "otal_gn_relu_bwd")
     return (dx,) + _gn_sums(partial, gamma, beta, bias, C, B)
@@ -1276,8 +1269,7 @@ def maxpool3d_forward(x, k, s, out=None, signbits=False, half_out=False, nonneg=
         lib = L.lib()
         bits = None
         if signbits:
-            lib.otal_maxpool3d_signbits_bytes.restype = ctypes.c_size_t
-            nbytes = int(lib.otal_maxpool3d_signbits_bytes(ga, sa))
+            nbytes = lib.otal_maxpool3d_signbits_bytes(ga, sa)
             if nbytes:
                 bits = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         L.check(lib.otal_maxpool3d_fwd_io(ga, sa, L.ptr(x5), L.ptr(out), L.ptr(arg), _opt(bits), 7 if nonneg else 3, L.stream()),
@@ -1292,8 +1284,7 @@ def maxpool3d_forward(x, k, s, out=None, signbits=False, half_out=False, nonneg=
         _check(x5, "x", torch.bfloat16); _check(out, "y")
         ga, sa = _geom_arrays(g, x5, out)
         lib = L.lib()
-        lib.otal_maxpool3d_signbits_bytes.restype = ctypes.c_size_t
-        nbytes = int(lib.otal_maxpool3d_signbits_bytes(ga, sa))
+        nbytes = lib.otal_maxpool3d_signbits_bytes(ga, sa)
         if not (signbits and nbytes):
             raise RuntimeError("maxpool3d_forward: a bf16 input needs the sign-bit path of the (1,3,3)/(1,2,2) pools")
         bits = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
@@ -1304,8 +1295,7 @@ def maxpool3d_forward(x, k, s, out=None, signbits=False, half_out=False, nonneg=
     ga, sa = _geom_arrays(g, x5, out)
     if signbits:
         lib = L.lib()
-        lib.otal_maxpool3d_signbits_bytes.restype = ctypes.c_size_t
-        nbytes = int(lib.otal_maxpool3d_signbits_bytes(ga, sa))
+        nbytes = lib.otal_maxpool3d_signbits_bytes(ga, sa)
         if nbytes and x5.data_ptr() % 16 == 0 and out.data_ptr() % 8 == 0:
             bits = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
             L.check(lib.otal_maxpool3d_fwd_signbits(ga, sa, L.ptr(x5), L.ptr(out), L.ptr(arg), L.ptr(bits), L.stream()),
@@ -1387,9 +1377,8 @@ def convert_storage(src, dtype, out=None):
         out.copy_(src)
         return out
     (sb, sc), (db, dc) = _bs(s5), _bs(o5)
-    L.check(L.lib().otal_convert_storage(L.ptr(s5), ctypes.c_int64(sb), ctypes.c_int64(sc), L.ptr(o5), ctypes.c_int64(db),
-                                         ctypes.c_int64(dc), int(out.dtype == torch.bfloat16), B, C, T * H * W, L.stream()),
-            "otal_convert_storage")
+    L.check(L.lib().otal_convert_storage(L.ptr(s5), sb, sc, L.ptr(o5), db, dc, int(out.dtype == torch.bfloat16), B, C, T * H * W,
+                                         L.stream()), "otal_convert_storage")
     return out
 
 
@@ -1402,17 +1391,15 @@ def proposal_windows(loc, levels, frame_num):
     seg = torch.empty((B, N, 4), dtype=torch.float32, device=loc.device)
     fseg = torch.empty_like(seg)
     L.check(L.lib().otal_proposal_windows(L.ptr(loc), L.ptr(seg), L.ptr(fseg), B, len(levels) - 1,
-                                          L.int_array(list(levels)), ctypes.c_float(frame_num), L.stream()),
+                                          L.int_array(list(levels)), frame_num, L.stream()),
             "otal_proposal_windows")
     return seg, fseg
 
 
 def adam_flat(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0):
     L.require_device(p, g, m, v)
-    L.check(L.lib().otal_adam_flat(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), ctypes.c_int64(p.numel()),
-                                   ctypes.c_float(lr), ctypes.c_float(beta1), ctypes.c_float(beta2),
-                                   ctypes.c_float(eps), ctypes.c_float(weight_decay), int(step),
-                                   ctypes.c_float(grad_scale), L.stream()), "otal_adam_flat")
+    L.check(L.lib().otal_adam_flat(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), lr, beta1, beta2, eps, weight_decay,
+                                   int(step), grad_scale, L.stream()), "otal_adam_flat")
 
 
 def adam_bias_corrections(step, beta1=0.9, beta2=0.999):
@@ -1426,10 +1413,8 @@ def adam_bias_corrections(step, beta1=0.9, beta2=0.999):
 def adam_flat_dev(p, g, m, v, bias_corr, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0):
     """adam_flat with the bias corrections in a 2-float device tensor (graph-replayable launch)."""
     L.require_device(p, g, m, v, bias_corr)
-    L.check(L.lib().otal_adam_flat_dev(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), ctypes.c_int64(p.numel()),
-                                       ctypes.c_float(lr), ctypes.c_float(beta1), ctypes.c_float(beta2),
-                                       ctypes.c_float(eps), ctypes.c_float(weight_decay), L.ptr(bias_corr),
-                                       ctypes.c_float(grad_scale), L.stream()), "otal_adam_flat_dev")
+    L.check(L.lib().otal_adam_flat_dev(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), lr, beta1, beta2, eps,
+                                       weight_decay, L.ptr(bias_corr), grad_scale, L.stream()), "otal_adam_flat_dev")
 
 
 # ----------------------------------------------------------------------------- fused detection loss
@@ -1464,10 +1449,6 @@ class LossCall(NamedTuple):
     radius: float = 0.0
 
 
-def _cf(*values):
-    return [ctypes.c_float(v) for v in values]
-
-
 class _FusedLossFunction(torch.autograd.Function):
     """What the three Functions below share: every term and every gradient from one launch of csrc/loss.hip in forward; backward
     only scales the stored gradients by the incoming scalars.
@@ -1485,7 +1466,6 @@ class _FusedLossFunction(torch.autograd.Function):
         L.require_device(*[t for t in tens if t is not None])
         gv = gvalid.contiguous().to(torch.uint8)
         lib = L.lib()
-        lib.otal_detection_loss_grad_floats.restype = lib.otal_detection_loss_scratch_floats.restype = ctypes.c_size_t
         args, nscratch = cls.c_args(call, state, B, K, C, G)
         dev = maps[0].device
         losses = torch.empty(7, dtype=torch.float32, device=dev)
@@ -1529,12 +1509,12 @@ class DetectionLossFunction(_FusedLossFunction):
 
     @staticmethod
     def c_args(call, state, B, K, C, G):
-        args = [L.ptr(state), B, K, C, G, *_cf(call.clip_length, call.overlap_thresh), int(call.ibm_active), int(call.num_bins),
-                *_cf(call.momentum), int(call.iou_aware), int(call.cls_mode), *_cf(call.focal_alpha)]
+        args = [L.ptr(state), B, K, C, G, call.clip_length, call.overlap_thresh, int(call.ibm_active), int(call.num_bins),
+                call.momentum, int(call.iou_aware), call.cls_mode, call.focal_alpha]
         if call.entry != 'plain':
-            args += [int(call.reweight), *_cf(call.rw_gamma)]
+            args += [call.reweight, call.rw_gamma]
         if call.entry == 'ev':
-            args += [int(call.evidence), int(call.loss_type)]
+            args += [call.evidence, call.loss_type]
         return args, L.lib().otal_detection_loss_scratch_floats(B, K)
 
 
@@ -1549,10 +1529,10 @@ class AnetDetectionLossFunction(_FusedLossFunction):
     def c_args(call, state, B, K, C, G):
         nlev = len(call.level_bounds)
         lbs = (ctypes.c_float * (2 * nlev))(*[float(v) for row in call.level_bounds for v in row])
-        args = [B, K, C, G, *_cf(call.clip_length, call.overlap_thresh), lbs, nlev, int(call.ibm_active), *_cf(call.ibm_coeff),
-                int(call.iou_aware), *_cf(call.act_weight, call.act_margin), int(call.cls_mode), *_cf(call.focal_alpha)]
+        args = [B, K, C, G, call.clip_length, call.overlap_thresh, lbs, nlev, int(call.ibm_active), call.ibm_coeff,
+                int(call.iou_aware), call.act_weight, call.act_margin, call.cls_mode, call.focal_alpha]
         if call.entry == 'anet_ev':
-            args += [int(call.evidence), int(call.loss_type)]
+            args += [call.evidence, call.loss_type]
         return args, 8 * B
 
 
@@ -1565,8 +1545,8 @@ class RPLDetectionLossFunction(_FusedLossFunction):
 
     @staticmethod
     def c_args(call, state, B, K, C, G):
-        args = [B, K, C, G, *_cf(call.clip_length, call.overlap_thresh), int(bool(call.gcpl)),
-                *_cf(call.temperature, call.weight_pl, call.radius)]
+        args = [B, K, C, G, call.clip_length, call.overlap_thresh, int(call.gcpl),
+                call.temperature, call.weight_pl, call.radius]
         return args, L.lib().otal_detection_loss_scratch_floats(B, K)
 
 
@@ -1855,9 +1835,8 @@ class BoundaryBCEFunction(torch.autograd.Function):
             raise RuntimeError("boundary_bce: mask rows / length do not cover the map")
         terms = torch.empty((B, 2, T), dtype=torch.float32, device=x.device)
         dx = torch.empty((B, C, T), dtype=torch.float32, device=x.device)
-        L.check(L.lib().otal_boundary_bce(L.ptr(x), ctypes.c_int64(x.stride(0)), ctypes.c_int64(x.stride(1)), L.ptr(mask),
-                                          ctypes.c_int64(mask.stride(0)), ctypes.c_int64(mask.stride(1)), int(row0), int(step),
-                                          L.ptr(terms), L.ptr(dx), B, C, T, L.stream()), "otal_boundary_bce")
+        L.check(L.lib().otal_boundary_bce(L.ptr(x), x.stride(0), x.stride(1), L.ptr(mask), mask.stride(0), mask.stride(1),
+                                          int(row0), int(step), L.ptr(terms), L.ptr(dx), B, C, T, L.stream()), "otal_boundary_bce")
         ctx.save_for_backward(dx)
         ctx.x_shape = tuple(x.shape)
         losses = terms.sum(dim=(0, 2)) / float(B * T)
@@ -1891,9 +1870,8 @@ class BoundaryLossesFunction(torch.autograd.Function):
                 raise RuntimeError("boundary losses: mask rows / length do not cover the map")
             t = torch.empty((B, 2, T), dtype=torch.float32, device=x.device)
             dx = torch.empty((B, C, T), dtype=torch.float32, device=x.device)
-            L.check(L.lib().otal_boundary_bce(L.ptr(x), ctypes.c_int64(x.stride(0)), ctypes.c_int64(x.stride(1)), L.ptr(mask),
-                                              ctypes.c_int64(mask.stride(0)), ctypes.c_int64(mask.stride(1)), 0, int(step),
-                                              L.ptr(t), L.ptr(dx), B, C, T, L.stream()), "otal_boundary_bce")
+            L.check(L.lib().otal_boundary_bce(L.ptr(x), x.stride(0), x.stride(1), L.ptr(mask), mask.stride(0), mask.stride(1),
+                                              0, int(step), L.ptr(t), L.ptr(dx), B, C, T, L.stream()), "otal_boundary_bce")
             terms.append(t); dxs.append(dx)
         out = torch.empty(2, dtype=torch.float32, device=xs[0].device)
         wa = (ctypes.c_float * n)(*[float(w) for w in weights])
@@ -2122,7 +2100,5 @@ def anchor_stats(loc, conf, prop_conf, center, act, prop_act, priors, gt, gvalid
     if evidence == 'exp':
         L.check(L.lib().otal_anchor_stats(*head, L.stream()), "otal_anchor_stats")
     else:
-        fn = L.lib().otal_anchor_stats_ev           # otal_anchor_stats's prototype (_lib.py) with the kind in front of the stream
-        fn.argtypes = L.lib().otal_anchor_stats.argtypes[:-1] + [ctypes.c_int, ctypes.c_void_p]
-        L.check(fn(*head, EVIDENCE[evidence], L.stream()), "otal_anchor_stats_ev")
+        L.check(L.lib().otal_anchor_stats_ev(*head, EVIDENCE[evidence], L.stream()), "otal_anchor_stats_ev")
     return res

@@ -7,8 +7,6 @@ to the CPU and loops in Python; here the whole greedy loop runs in one workgroup
 candidates resident in LDS (otal_softnms_classes).  For batches of videos use
 `opental_amd.thumos14.test.detect_batch`, which gathers + suppresses all (video, class) pairs in one launch.
 """
-import ctypes
-
 import torch
 
 from .. import _lib as L
@@ -39,13 +37,11 @@ def softnms_v2(segments, sigma=0.5, top_k=1000, score_threshold=0.001, use_edl=F
     counts = torch.zeros(1, dtype=torch.int32, device=dev)
     idx = torch.empty((1, k), dtype=torch.int32, device=dev)
     lib = L.lib()
-    lib.otal_softnms_scratch_bytes.restype = ctypes.c_size_t
-    nbytes = int(lib.otal_softnms_scratch_bytes(1, 1, n, 1))          # > 0 past ~7600 candidates: global working set
+    nbytes = lib.otal_softnms_scratch_bytes(1, 1, n, 1)               # > 0 past ~7600 candidates: global working set
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     L.check(lib.otal_softnms_classes_ws(L.ptr(se), L.ptr(sc), L.ptr(c3), L.ptr(c4), L.ptr(flag), L.ptr(clip_start),
-                                        1, 1, n, 1, ctypes.c_float(sigma), k, ctypes.c_float(score_threshold),
-                                        L.ptr(out), L.ptr(counts), L.ptr(idx), 5, L.ptr(scratch), ctypes.c_size_t(nbytes), 1,
-                                        L.stream()), "otal_softnms_classes_ws")
+                                        1, 1, n, 1, sigma, k, score_threshold, L.ptr(out), L.ptr(counts), L.ptr(idx), 5,
+                                        L.ptr(scratch), nbytes, 1, L.stream()), "otal_softnms_classes_ws")
     count = int(counts.item())
     rows = out[0, :count]
     if ncol == 3:

@@ -15,7 +15,6 @@ the host:
     Optical-flow frames (`ClipStager(channels=2)`) go through `otal_prepare_clips_ch` and come out as three planes, the
     third all zero, flagged as a zero-plane batch (input_pipeline.mark_zero_plane; common/i3d_backbone.py takes it from there).
 """
-import ctypes
 import math
 import os
 import random

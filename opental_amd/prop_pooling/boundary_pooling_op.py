@@ -97,11 +97,10 @@ def _slice_stride(t, B, C, N):
 
 def bmp_forward_levels_to(input, segments, t_start, n_start, out):
     """bmp_forward_levels writing into `out`, a channel slice of a concatenation buffer."""
-    import ctypes
     L.require_device(input, segments)
     B, C, Tt = input.shape
     N = n_start[-1]
-    L.check(L.lib().otal_bmp_fwd_levels_to(L.ptr(input), L.ptr(segments), L.ptr(out), ctypes.c_int64(_slice_stride(out, B, C, N)),
+    L.check(L.lib().otal_bmp_fwd_levels_to(L.ptr(input), L.ptr(segments), L.ptr(out), _slice_stride(out, B, C, N),
                                            B, C, len(t_start) - 1, L.int_array(t_start), L.int_array(n_start), L.stream()),
             "otal_bmp_fwd_levels_to")
     return out
@@ -109,12 +108,11 @@ def bmp_forward_levels_to(input, segments, t_start, n_start, out):
 
 def bmp_backward_levels_from(grad_output, input, segments, t_start, n_start):
     """bmp_backward_levels reading `grad_output` in place where it is a channel slice of a wider gradient buffer."""
-    import ctypes
     L.require_device(input, segments)
     B, C, _ = input.shape
     N = n_start[-1]
     grad_input = torch.empty_like(input)
-    L.check(L.lib().otal_bmp_bwd_levels_from(L.ptr(grad_output), ctypes.c_int64(_slice_stride(grad_output, B, C, N)), L.ptr(input),
+    L.check(L.lib().otal_bmp_bwd_levels_from(L.ptr(grad_output), _slice_stride(grad_output, B, C, N), L.ptr(input),
                                              L.ptr(segments), L.ptr(grad_input), B, C, len(t_start) - 1, L.int_array(t_start),
                                              L.int_array(n_start), L.stream()), "otal_bmp_bwd_levels_from")
     return grad_input

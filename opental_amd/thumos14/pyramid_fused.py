@@ -49,7 +49,7 @@ def _gn_bwd_raw(dy, c, gamma, beta, stats, groups, levels):
     nlev, lev = ops._lev_arg(levels)
     dc = torch.empty_like(c)
     partial = torch.empty((B, 3, C), dtype=torch.float32, device=c.device)
-    L.check(L.lib().otal_gn_relu_bwd(L.ptr(dy), ctypes.c_int64(dy.stride(0)), L.ptr(c), L.ptr(gamma), L.ptr(beta), L.ptr(stats),
+    L.check(L.lib().otal_gn_relu_bwd(L.ptr(dy), dy.stride(0), L.ptr(c), L.ptr(gamma), L.ptr(beta), L.ptr(stats),
                                      L.ptr(dc), L.ptr(partial), B, C, T, groups, 1, nlev, lev, L.stream()), "otal_gn_relu_bwd")
     return dc, partial
 

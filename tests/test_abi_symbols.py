@@ -21,11 +21,12 @@ def declared_symbols():
 
 @pytest.fixture(scope="module")
 def lib():
+    from opental_amd._lib import declare
     from opental_amd.csrc import build
     path = build.LIB
     if not os.path.exists(path):
         build.build(verbose=False)
-    return ctypes.CDLL(path)
+    return declare(ctypes.CDLL(path))
 
 
 def test_every_declared_symbol_is_exported(lib):
@@ -38,7 +39,6 @@ def test_every_declared_symbol_is_exported(lib):
 def test_abi_version_26_and_error_strings(lib):
     """ABI 26 added otal_layer_last_kernel (include/opental_hip.h)."""
     assert lib.otal_abi_version() == 26
-    lib.otal_error_string.restype = ctypes.c_char_p
     assert b"batch" in lib.otal_error_string(-4)
     assert lib.otal_error_string(0) == b"success"
 
@@ -55,7 +55,6 @@ def test_argument_errors_do_not_launch(lib):
 
 
 def test_set_option_accepts_only_the_listed_switches(lib):
-    lib.otal_get_option.restype = ctypes.c_int
     assert lib.otal_get_option(b"OTAL_LOSS_NOSTAGE", 7) == int(os.environ.get("OTAL_LOSS_NOSTAGE", "0"))
     assert lib.otal_set_option(b"OTAL_LOSS_NOSTAGE", 1) == 0
     try:

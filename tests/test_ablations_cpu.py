@@ -24,7 +24,8 @@ def lib():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    return ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    return declare(ctypes.CDLL(build.LIB))
 
 
 def targets_of(fx):
@@ -89,11 +90,10 @@ def test_ex_entry_exported_and_arguments_checked(lib):
     assert hasattr(lib, "otal_detection_loss_ex")
     assert lib.otal_abi_version() == 26
     one = ctypes.c_void_p(16)     # never dereferenced: argument checks come first
-    f = ctypes.c_float
 
     def ex(cls_mode=0, reweight=0, ibm=0, bins=50, B=1, loc=one, act=one, momentum=0.85):
-        return lib.otal_detection_loss_ex(loc, one, one, one, one, act, act, one, one, one, one, B, 126, 15, 1, f(256.0), f(0.5),
-                                          ibm, bins, f(momentum), 1, cls_mode, f(0.25), reweight, f(2.0), one, one, one, None)
+        return lib.otal_detection_loss_ex(loc, one, one, one, one, act, act, one, one, one, one, B, 126, 15, 1, 256.0, 0.5,
+                                          ibm, bins, momentum, 1, cls_mode, 0.25, reweight, 2.0, one, one, one, None)
     assert ex(loc=None) == -1 and ex(cls_mode=0, reweight=2, act=None) == -1      # OTAL_E_NULL
     assert ex(B=0, reweight=1) == -2                                               # OTAL_E_SHAPE
     assert ex(reweight=4) == -7 and ex(reweight=-1) == -7                          # OTAL_E_UNSUPPORTED
@@ -104,8 +104,8 @@ def test_ex_entry_exported_and_arguments_checked(lib):
     assert ex(reweight=1, B=17) == -7                                               # B * K beyond the single-workgroup kernel
 
     def old(cls_mode, ibm, act=one):
-        return lib.otal_detection_loss(one, one, one, one, one, act, act, one, one, one, one, 1, 126, 16, 1, f(256.0), f(0.5),
-                                       ibm, 50, f(0.99), 1, cls_mode, f(0.25), one, one, one, None)
+        return lib.otal_detection_loss(one, one, one, one, one, act, act, one, one, one, one, 1, 126, 16, 1, 256.0, 0.5,
+                                       ibm, 50, 0.99, 1, cls_mode, 0.25, one, one, one, None)
     assert old(2, 1, act=None) == -7            # the existing entry keeps its contract: closed-set EDL without IBM
 
 
@@ -113,7 +113,6 @@ def test_ex_entry_accepts_ibm_over_a_closed_set(lib):
     """otal_detection_loss_ex(cls_mode 2, ibm_active 1) -- the noACT config -- passes every argument check.  Without a device
     the pointers are placeholders and what comes back is the launch's HIP error, not one of the three argument errors; with a
     device they are real tensors (a launch on placeholders must never reach one) and the call succeeds."""
-    f = ctypes.c_float
     if torch.cuda.is_available():
         dev = torch.device("cuda", 0)
         heads = {k: torch.from_numpy(v).to(dev) for k, v in A.head_outputs(3, 16, False, B=1).items()}
@@ -125,8 +124,8 @@ def test_ex_entry_accepts_ibm_over_a_closed_set(lib):
         assert lib.otal_detection_loss_scratch_floats(1, 126) <= 126 * 12
     else:
         loc = conf = ploc = pconf = cen = pri = gt_ = gv = wacc = losses = grads = scratch = ctypes.c_void_p(16)
-    rc = lib.otal_detection_loss_ex(loc, conf, ploc, pconf, cen, None, None, pri, gt_, gv, wacc, 1, 126, 16, 1, f(256.0), f(0.5),
-                                    1, 50, f(0.99), 1, 2, f(0.25), 0, f(0.0), losses, grads, scratch, None)
+    rc = lib.otal_detection_loss_ex(loc, conf, ploc, pconf, cen, None, None, pri, gt_, gv, wacc, 1, 126, 16, 1, 256.0, 0.5,
+                                    1, 50, 0.99, 1, 2, 0.25, 0, 0.0, losses, grads, scratch, None)
     assert rc not in (-1, -2, -7), rc
     if torch.cuda.is_available():
         torch.cuda.synchronize()

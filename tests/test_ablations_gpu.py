@@ -2,7 +2,6 @@
 tests/golden/ablations.npz (reference values), against the package's torch formulation, the extended entry against the existing
 one bit for bit, run-to-run determinism, and the training driver on a ghm and on the noACT config (lane graphs across the
 start epoch, checkpoint round trip of the loss state)."""
-import ctypes
 import os
 import sys
 
@@ -93,8 +92,6 @@ def _raw(entry, mode, ins, reweight=None, ibm=0, bins=50, momentum=0.99):
     from opental_amd import _lib as L
     lib = L.lib()
     B, K, C = ins["conf"].shape
-    lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
-    lib.otal_detection_loss_scratch_floats.restype = ctypes.c_size_t
     dev = ins["conf"].device
     losses = torch.zeros(7, device=dev)
     grads = torch.zeros(lib.otal_detection_loss_grad_floats(B, K, C), device=dev)
@@ -102,12 +99,11 @@ def _raw(entry, mode, ins, reweight=None, ibm=0, bins=50, momentum=0.99):
     state = torch.linspace(0.5, 1.5, bins, device=dev)
     closed = mode in (2, 3)
     p = lambda k: None if (closed and k in ("act", "prop_act")) else L.ptr(ins[k])
-    f = ctypes.c_float
     args = [p(k) for k in ("loc", "conf", "prop_loc", "prop_conf", "center", "act", "prop_act")] + [
-        L.ptr(ins["priors"]), L.ptr(ins["gt"]), L.ptr(ins["gvalid"]), L.ptr(state), B, K, C, 1, f(256.0), f(0.5), ibm, bins,
-        f(momentum), 1, mode, f(0.25)]
+        L.ptr(ins["priors"]), L.ptr(ins["gt"]), L.ptr(ins["gvalid"]), L.ptr(state), B, K, C, 1, 256.0, 0.5, ibm, bins,
+        momentum, 1, mode, 0.25]
     if reweight is not None:
-        args += [reweight, f(2.0)]
+        args += [reweight, 2.0]
     rc = getattr(lib, entry)(*args, L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream())
     torch.cuda.synchronize()
     assert rc == 0, (entry, mode, rc)

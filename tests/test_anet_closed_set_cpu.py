@@ -136,13 +136,13 @@ def test_loss_ex_argument_checks_do_not_launch():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    lib = ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    lib = declare(ctypes.CDLL(build.LIB))
     p = ctypes.c_void_p(16)                 # never dereferenced: the argument checks come first
-    f = ctypes.c_float
 
     def call(act, cls_mode, ibm_active=0, B=2):
-        return lib.otal_detection_loss_anet_ex(p, p, p, p, p, act, act, p, p, p, B, 189, C, 4, f(768.0), f(0.6), p, 6,
-                                               ibm_active, f(10.0), 0, f(0.1), f(1.0), cls_mode, f(0.25), p, p, p, None)
+        return lib.otal_detection_loss_anet_ex(p, p, p, p, p, act, act, p, p, p, B, 189, C, 4, 768.0, 0.6, p, 6,
+                                               ibm_active, 10.0, 0, 0.1, 1.0, cls_mode, 0.25, p, p, p, None)
     assert call(None, 0) == -1                      # OTAL_E_NULL: the OpenTAL form needs the actionness maps
     assert call(p, 1) == -7 and call(p, 4) == -7 and call(p, -1) == -7        # OTAL_E_UNSUPPORTED
     assert call(None, 2, ibm_active=1) == -7        # closed-set EDL: no influence-balanced weight

@@ -160,9 +160,7 @@ def test_ex_mode_0_is_the_opental_entry_bit_for_bit():
     gt, valid = as_padded(tg, dev)
     gt, gv = gt.contiguous(), valid.contiguous().to(torch.uint8)
     lib = L.lib()
-    lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
     lbs = (ctypes.c_float * 12)(*[float(v) for row in bounds for v in row])
-    f = ctypes.c_float
 
     def run(ex, mode=0, a=act, pa=pact, cf=conf, pcf=pconf):
         Cc = cf.shape[-1]
@@ -172,9 +170,9 @@ def test_ex_mode_0_is_the_opental_entry_bit_for_bit():
         scratch = torch.empty(8 * B, device=dev)
         args = [L.ptr(t["loc"]), L.ptr(cf), L.ptr(t["prop_loc"]), L.ptr(pcf), L.ptr(t["center"]),
                 None if a is None else L.ptr(a), None if pa is None else L.ptr(pa), L.ptr(pri), L.ptr(gt), L.ptr(gv),
-                B, 189, Cc, gt.shape[1], f(768.0), f(0.6), lbs, 6, int(mode == 0), f(10.0), int(mode != 3), f(0.1), f(1.0)]
+                B, 189, Cc, gt.shape[1], 768.0, 0.6, lbs, 6, int(mode == 0), 10.0, int(mode != 3), 0.1, 1.0]
         if ex:
-            rc = lib.otal_detection_loss_anet_ex(*args, mode, f(0.25), L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream())
+            rc = lib.otal_detection_loss_anet_ex(*args, mode, 0.25, L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream())
         else:
             rc = lib.otal_detection_loss_anet(*args, L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream())
         L.check(rc, "loss")

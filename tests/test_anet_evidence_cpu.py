@@ -34,7 +34,8 @@ def lib():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    return ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    return declare(ctypes.CDLL(build.LIB))
 
 
 # ---- 1. the lane-share rows against float64 and against cls_row
@@ -231,12 +232,11 @@ def test_anet_ev_is_declared_and_exported(lib):
 def test_argument_checks_of_anet_ev_do_not_launch(lib):
     """Refusals come before any read or launch: the pointers here are never dereferenced."""
     one = ctypes.c_void_p(16)
-    f = ctypes.c_float
     null, shape, unsupported = -1, -2, -7
 
     def loss(evidence, loss_type, cls_mode=0, ibm=0, K=189, nlev=6, act=one, B=1, lb=one):
-        return lib.otal_detection_loss_anet_ev(one, one, one, one, one, act, act, one, one, one, B, K, 150, 1, f(768.0), f(0.6), lb,
-                                               nlev, ibm, f(10.0), 1, f(0.1), f(1.0), cls_mode, f(0.25), evidence, loss_type, one,
+        return lib.otal_detection_loss_anet_ev(one, one, one, one, one, act, act, one, one, one, B, K, 150, 1, 768.0, 0.6, lb,
+                                               nlev, ibm, 10.0, 1, 0.1, 1.0, cls_mode, 0.25, evidence, loss_type, one,
                                                one, one, None)
     for bad in ((3, 0), (-1, 0), (0, 3), (0, -1)):
         assert loss(*bad) == unsupported, bad
@@ -249,5 +249,5 @@ def test_argument_checks_of_anet_ev_do_not_launch(lib):
     assert loss(1, 1, lb=None) == null and loss(1, 1, cls_mode=2, act=None, lb=None) == null
     assert loss(1, 1, B=0) == shape and loss(1, 1, nlev=0) == shape and loss(1, 1, K=0) == shape
     # otal_detection_loss_anet_ex keeps its refusal of closed-set IBM
-    assert lib.otal_detection_loss_anet_ex(one, one, one, one, one, None, None, one, one, one, 1, 189, 151, 1, f(768.0), f(0.6), one,
-                                           6, 1, f(10.0), 1, f(0.1), f(1.0), 2, f(0.25), one, one, one, None) == unsupported
+    assert lib.otal_detection_loss_anet_ex(one, one, one, one, one, None, None, one, one, one, 1, 189, 151, 1, 768.0, 0.6, one,
+                                           6, 1, 10.0, 1, 0.1, 1.0, 2, 0.25, one, one, one, None) == unsupported

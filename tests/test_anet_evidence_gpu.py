@@ -228,18 +228,16 @@ def _raw(entry, mode, ins, ibm=0, kinds=None, expect=0, K=None):
     from opental_amd.anet.multisegment_loss import bounds
     lib = L.lib()
     B, Kt, C = ins["conf"].shape
-    lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
     dev = ins["conf"].device
     losses = torch.full((7,), float('nan'), device=dev)
     grads = torch.full((lib.otal_detection_loss_grad_floats(B, Kt, C),), float('nan'), device=dev)
     scratch = torch.full((8 * B,), float('nan'), device=dev)
     closed = mode in (2, 3)
     p = lambda k: None if (closed and k in ("act", "prop_act")) else L.ptr(ins[k])
-    f = ctypes.c_float
     lbs = (ctypes.c_float * 12)(*[float(v) for row in bounds for v in row])
     args = [p(k) for k in ("loc", "conf", "prop_loc", "prop_conf", "center", "act", "prop_act")] + [
-        L.ptr(ins["priors"]), L.ptr(ins["gt"]), L.ptr(ins["gvalid"]), B, Kt if K is None else K, C, ins["gt"].shape[1], f(768.0),
-        f(0.6), lbs, 6, ibm, f(10.0), 1, f(0.1), f(1.0), mode, f(0.25)]
+        L.ptr(ins["priors"]), L.ptr(ins["gt"]), L.ptr(ins["gvalid"]), B, Kt if K is None else K, C, ins["gt"].shape[1], 768.0,
+        0.6, lbs, 6, ibm, 10.0, 1, 0.1, 1.0, mode, 0.25]
     if kinds is not None:
         args += list(kinds)
     rc = getattr(lib, entry)(*args, L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream())

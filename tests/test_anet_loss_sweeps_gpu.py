@@ -120,16 +120,14 @@ def test_more_than_1024_anchors_take_the_torch_formulation():
     gt, valid = pad_targets(tg, dev)
     gv = valid.to(torch.uint8).contiguous()
     lib = L.lib()
-    lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
     ng = lib.otal_detection_loss_grad_floats(B, K, C)
     nan = lambda n: torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
     losses, grads, scratch = nan(7), nan(ng), nan(8 * B)
-    f = ctypes.c_float
     lbs = (ctypes.c_float * 12)(*[float(v) for row in M.bounds for v in row])
 
     def call(k):
         return lib.otal_detection_loss_anet_ex(*[L.ptr(t[n].detach()) for n in NAMES], L.ptr(pri), L.ptr(gt.contiguous()), L.ptr(gv), B, k,
-                                               C, gt.shape[1], f(768.0), f(0.6), lbs, 6, 1, f(10.0), 1, f(0.1), f(1.0), 0, f(0.25),
+                                               C, gt.shape[1], 768.0, 0.6, lbs, 6, 1, 10.0, 1, 0.1, 1.0, 0, 0.25,
                                                L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream())
     assert call(1025) == E_UNSUPPORTED
     torch.cuda.synchronize()

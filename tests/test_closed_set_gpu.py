@@ -118,7 +118,6 @@ def test_fused_closed_set_loss_matches_torch_formulation(kind, B):
 
 
 def _decode_ex(out, offsets, fps, score_fn, first_class, act=None, conf_thresh=0.01):
-    import ctypes
     from opental_amd import _lib as L
     t = lambda k: out[k].contiguous()
     n, A, _ = out['loc'].shape
@@ -135,7 +134,7 @@ def _decode_ex(out, offsets, fps, score_fn, first_class, act=None, conf_thresh=0
                                          L.ptr(t('conf')), L.ptr(t('prop_conf')), L.ptr(t('center')),
                                          p(None if act is None else act[0]), p(None if act is None else act[1]),
                                          L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score), L.ptr(unct), L.ptr(actn),
-                                         L.ptr(flag), n, A, K, ctypes.c_float(256.0), ctypes.c_float(conf_thresh),
+                                         L.ptr(flag), n, A, K, 256.0, conf_thresh,
                                          score_fn, first_class, L.stream()), "otal_decode_clips_ex")
     return seg, score, unct, actn, flag
 
@@ -166,7 +165,6 @@ def test_decode_ex_matches_golden(fx, use_edl, fusion):
 
 
 def test_decode_entry_is_the_ex_entry_with_the_opental_head():
-    import ctypes
     from opental_amd import _lib as L
     from opental_amd.thumos14.test import decode_clips
     dev = torch.device("cuda", 0)

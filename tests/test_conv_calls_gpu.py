@@ -132,9 +132,6 @@ def cpu_plan(H, i, precision, switches=()):
 def lib(harness):
     from opental_amd import _lib as L
     lib = L.lib()
-    lib.otal_conv_last_kernel.restype = ctypes.c_char_p
-    lib.otal_conv_prologue_bytes.restype = ctypes.c_size_t
-    lib.otal_conv_prologue_desc_bytes.restype = ctypes.c_size_t
     # the harness reproduces every recorded chain (so the library, with the same defaults, runs it)
     bad = [i for i in range(NROWS) if ">".join(cpu_plan(harness, i, int(Z["precision"][i])))
            != ">".join(kname(s) for s in chain_steps(i))]
@@ -321,18 +318,18 @@ def launch(lib, row, prec, relu=0, prologue=None):
     if mode == 0:
         x = placed(row.x, half_in, ax)
         rc = lib.otal_conv_fwd(ga, sa, L.ptr(x), L.ptr(w), L.ptr(row.scale), L.ptr(row.shift), L.ptr(out), int(relu), prec,
-                               prologue, L.ptr(ws), ctypes.c_size_t(ws.numel()), st)
+                               prologue, L.ptr(ws), ws.numel(), st)
     elif mode == 1:
         dy = placed(row.dy, half_out, ady)
         m = placed(row.mask, half_mask, amask) if row.has_mask else None
         rc = lib.otal_conv_dgrad(ga, sa, L.ptr(dy), L.ptr(w), L.ptr(out), row.acc, L.ptr(m) if m is not None else None,
                                  L.ptr(row.out_scale) if m is not None else None, prec, prologue, L.ptr(ws),
-                                 ctypes.c_size_t(ws.numel()), st)
+                                 ws.numel(), st)
     else:
         x = placed(row.x, half_in, ax)
         dy = placed(row.dy, half_out, ady)
         rc = lib.otal_conv_wgrad(ga, sa, L.ptr(x), L.ptr(dy), L.ptr(out), row.acc, prec, prologue, L.ptr(ws),
-                                 ctypes.c_size_t(ws.numel()), st)
+                                 ws.numel(), st)
     name = lib.otal_conv_last_kernel().decode()
     torch.cuda.synchronize()
     return rc, name, obase, off, o_half, ws
@@ -409,7 +406,7 @@ def test_recorded_call(lib, harness, v):
             w1 = w.clone()
             w.copy_(row.w0)
             nb = lib.otal_conv_prologue((ctypes.c_int * 28)(*row.geom), (ctypes.c_int64 * 4)(*row.strides), row.mode,
-                                        L.ptr(w), prec & 3, L.ptr(region), ctypes.c_size_t(nbytes), desc, L.stream())
+                                        L.ptr(w), prec & 3, L.ptr(region), nbytes, desc, L.stream())
             assert nb > 0, nb
             w.copy_(w1)
             descs = torch.frombuffer(bytearray(desc.raw), dtype=torch.uint8).cuda()

@@ -132,10 +132,9 @@ def test_detection_table_argument_errors_do_not_launch():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    lib = ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    lib = declare(ctypes.CDLL(build.LIB))
     f = lib.otal_detection_table
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 7
     one = ctypes.c_void_p(16)       # never dereferenced: argument checks come first
 
     def call(ptrs=None, V=3, K=5, top_k=7, cols=5, drop_empty=0, scoring=0):

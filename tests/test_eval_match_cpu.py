@@ -132,7 +132,8 @@ def test_eval_match_argument_errors_do_not_launch():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    lib = ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    lib = declare(ctypes.CDLL(build.LIB))
     one = ctypes.c_void_p(16)       # never dereferenced: argument checks come first
     odd = ctypes.c_void_p(24)       # not 16-byte aligned
     f = lib.otal_eval_match

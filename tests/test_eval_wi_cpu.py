@@ -172,7 +172,8 @@ def lib():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    return ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    return declare(ctypes.CDLL(build.LIB))
 
 
 def test_eval_match_labeled_is_exported_and_abi_is_unchanged(lib):

@@ -32,7 +32,8 @@ def lib():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    return ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    return declare(ctypes.CDLL(build.LIB))
 
 
 def _ulp(x, up):
@@ -300,12 +301,11 @@ def test_new_entries_are_declared_and_exported(lib):
 def test_argument_checks_of_the_new_entries(lib):
     """Refusals come before any read or launch: the pointers here are never dereferenced."""
     one = ctypes.c_void_p(16)
-    f = ctypes.c_float
     unsupported = -7
 
     def loss(evidence, loss_type, cls_mode=0, ibm=0, reweight=0, act=one):
-        return lib.otal_detection_loss_ev(one, one, one, one, one, act, act, one, one, one, one, 1, 126, 15, 1, f(256.0), f(0.5),
-                                          ibm, 50, f(0.99), 1, cls_mode, f(0.25), reweight, f(2.0), evidence, loss_type, one, one,
+        return lib.otal_detection_loss_ev(one, one, one, one, one, act, act, one, one, one, one, 1, 126, 15, 1, 256.0, 0.5,
+                                          ibm, 50, 0.99, 1, cls_mode, 0.25, reweight, 2.0, evidence, loss_type, one, one,
                                           one, None)
     for bad in ((3, 0), (-1, 0), (0, 3), (0, -1)):
         assert loss(*bad) == unsupported, bad
@@ -317,11 +317,11 @@ def test_argument_checks_of_the_new_entries(lib):
 
     def decode(evidence, score_fn=0):
         return lib.otal_decode_clips_ev(one, one, one, one, one, one, one, one, one, one, one, one, one, one, one, 1, 126, 15,
-                                        f(256.0), f(0.01), score_fn, 0, evidence, None)
+                                        256.0, 0.01, score_fn, 0, evidence, None)
     assert decode(3) == unsupported and decode(-1) == unsupported and decode(1, score_fn=2) == unsupported
 
     def stats(evidence):
-        return lib.otal_anchor_stats_ev(one, one, one, one, one, one, one, one, one, 1, 126, 15, 1, f(256.0), f(0.5), 1, 15, 0, 100,
+        return lib.otal_anchor_stats_ev(one, one, one, one, one, one, one, one, one, 1, 126, 15, 1, 256.0, 0.5, 1, 15, 0, 100,
                                         100, one, one, None, None, None, evidence, None)
     assert stats(3) == unsupported and stats(-1) == unsupported
     modes = (ctypes.c_int * 1)(5)

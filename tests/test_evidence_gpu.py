@@ -5,7 +5,6 @@ formulation (float32 on the device, float64 on the host for the decision edges),
 for bit, determinism, refusals, and the trainer and the drivers on a (softplus, digamma) configuration.
 
 The head tails take the evidence kind as a mode number (2 exp, 3 relu, 4 softplus): exp through the new route IS mode 2."""
-import ctypes
 import os
 import sys
 
@@ -167,8 +166,6 @@ def _raw(entry, mode, ins, reweight=None, ibm=0, bins=50, momentum=0.99, kinds=N
     from opental_amd import _lib as L
     lib = L.lib()
     B, K, C = ins["conf"].shape
-    lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
-    lib.otal_detection_loss_scratch_floats.restype = ctypes.c_size_t
     dev = ins["conf"].device
     losses = torch.full((7,), SENTINEL, device=dev)
     grads = torch.full((lib.otal_detection_loss_grad_floats(B, K, C),), SENTINEL, device=dev)
@@ -176,12 +173,11 @@ def _raw(entry, mode, ins, reweight=None, ibm=0, bins=50, momentum=0.99, kinds=N
     state = torch.linspace(0.5, 1.5, bins, device=dev)
     closed = mode in (2, 3)
     p = lambda k: None if (closed and k in ("act", "prop_act")) else L.ptr(ins[k])
-    f = ctypes.c_float
     args = [p(k) for k in ("loc", "conf", "prop_loc", "prop_conf", "center", "act", "prop_act")] + [
-        L.ptr(ins["priors"]), L.ptr(ins["gt"]), L.ptr(ins["gvalid"]), L.ptr(state), B, K, C, 1, f(256.0), f(0.5), ibm, bins,
-        f(momentum), 1, mode, f(0.25)]
+        L.ptr(ins["priors"]), L.ptr(ins["gt"]), L.ptr(ins["gvalid"]), L.ptr(state), B, K, C, 1, 256.0, 0.5, ibm, bins,
+        momentum, 1, mode, 0.25]
     if reweight is not None:
-        args += [reweight, f(2.0)]
+        args += [reweight, 2.0]
     if kinds is not None:
         args += list(kinds)
     rc = getattr(lib, entry)(*args, L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream())
@@ -396,8 +392,8 @@ def test_anchor_stats_ev_with_exp_is_the_existing_entry():
     B, K, C = c['conf'].shape
     new = dict(hist_score=torch.zeros_like(old['hist_score']), hist_grad=torch.zeros_like(old['hist_grad']),
                label=torch.zeros_like(old['label']), value=torch.zeros_like(old['value']), grad=torch.zeros_like(old['grad']))
-    rc = L.lib().otal_anchor_stats_ev(*[L.ptr(t) for t in ins], B, K, C, c['gt'].shape[1], ctypes.c_float(CLIP),
-                                      ctypes.c_float(OVERLAP), 1, 15, 4, BINS, BINS,
+    rc = L.lib().otal_anchor_stats_ev(*[L.ptr(t) for t in ins], B, K, C, c['gt'].shape[1], CLIP,
+                                      OVERLAP, 1, 15, 4, BINS, BINS,
                                       *[L.ptr(new[k]) for k in ('hist_score', 'hist_grad', 'label', 'value', 'grad')], 0, L.stream())
     torch.cuda.synchronize()
     assert rc == 0

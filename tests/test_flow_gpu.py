@@ -203,9 +203,7 @@ def test_clip_stager_reproduces_the_reference_flow_clips(golden_dir):
 # ----------------------------------------------------------------------------- 3. Conv3d_1a: zero-plane path vs the generic chain
 def _last_conv_kernel():
     from opental_amd import _lib as L
-    fn = L.lib().otal_conv_last_kernel
-    fn.restype = ctypes.c_char_p
-    return fn().decode()
+    return L.lib().otal_conv_last_kernel().decode()
 
 
 @pytest.fixture(scope="module")

@@ -417,8 +417,8 @@ def test_boundary_bce(lib, C):
         terms, dx = Out((B, 2, T)), Out((B, C, T))
         label = f"boundary_bce B {B} C {C} T {T} step {step} row0 {row0}"
         xp = ctypes.c_void_p(wd.data_ptr() + 4 * (2 * (T + 5) + 3))
-        rc = lib.otal_boundary_bce(xp, ctypes.c_int64((C + 3) * (T + 5)), ctypes.c_int64(T + 5), ctypes.c_void_p(md.data_ptr()),
-                                   ctypes.c_int64(mask.shape[1] * mask.shape[2]), ctypes.c_int64(mask.shape[2]), row0, step, terms.p(), dx.p(),
+        rc = lib.otal_boundary_bce(xp, (C + 3) * (T + 5), T + 5, ctypes.c_void_p(md.data_ptr()),
+                                   mask.shape[1] * mask.shape[2], mask.shape[2], row0, step, terms.p(), dx.p(),
                                    B, C, T, stream())
         assert rc == 0
         torch.cuda.synchronize()
@@ -551,7 +551,7 @@ def test_bmp_levels_inside_a_wider_buffer(lib):
     N, T = ns[-1], ts[-1]
     xd, sd = x.cuda(), seg.cuda()
     wide = Out((B, C + 10, N))
-    rc = lib.otal_bmp_fwd_levels_to(ctypes.c_void_p(xd.data_ptr()), ctypes.c_void_p(sd.data_ptr()), wide.p(c0 * N), ctypes.c_int64((C + 10) * N), B, C, 6,
+    rc = lib.otal_bmp_fwd_levels_to(ctypes.c_void_p(xd.data_ptr()), ctypes.c_void_p(sd.data_ptr()), wide.p(c0 * N), (C + 10) * N, B, C, 6,
                                     IA(ts), IA(ns), stream())
     assert rc == 0
     torch.cuda.synchronize()
@@ -562,7 +562,7 @@ def test_bmp_levels_inside_a_wider_buffer(lib):
     gw = torch.from_numpy(np.random.RandomState(3).randn(B, C + 10, N).astype(np.float32))
     gwd = gw.cuda()
     gin = Out((B, C, T))
-    rc = lib.otal_bmp_bwd_levels_from(ctypes.c_void_p(gwd.data_ptr() + 4 * c0 * N), ctypes.c_int64((C + 10) * N), ctypes.c_void_p(xd.data_ptr()),
+    rc = lib.otal_bmp_bwd_levels_from(ctypes.c_void_p(gwd.data_ptr() + 4 * c0 * N), (C + 10) * N, ctypes.c_void_p(xd.data_ptr()),
                                       ctypes.c_void_p(sd.data_ptr()), gin.p(), B, C, 6, IA(ts), IA(ns), stream())
     assert rc == 0
     torch.cuda.synchronize()
@@ -570,7 +570,7 @@ def test_bmp_levels_inside_a_wider_buffer(lib):
     eq_nan(gin.t.cpu(), H.bmp_bwd(gw, x, seg, ts, ns, c0=c0)[0], "bmp levels_from")
     # a pooled stride below C * N is refused
     wide = Out((B, C + 10, N))
-    assert lib.otal_bmp_fwd_levels_to(ctypes.c_void_p(xd.data_ptr()), ctypes.c_void_p(sd.data_ptr()), wide.p(), ctypes.c_int64(C * N - 1), B, C, 6,
+    assert lib.otal_bmp_fwd_levels_to(ctypes.c_void_p(xd.data_ptr()), ctypes.c_void_p(sd.data_ptr()), wide.p(), C * N - 1, B, C, 6,
                                       IA(ts), IA(ns), stream()) == E_SHAPE
     torch.cuda.synchronize()
     wide.check("bmp levels_to refused", written=False)
@@ -600,8 +600,8 @@ def test_adam(lib, n, offs, wd, step):
     p, g, m, v = buffers()
     for t, o in zip((p, g, m, v), offs):
         assert t.t.data_ptr() % 16 == (o * 4) % 16
-    rc = lib.otal_adam_flat(p.p(), g.p(), m.p(), v.p(), ctypes.c_int64(n), ctypes.c_float(lr), ctypes.c_float(b1), ctypes.c_float(b2),
-                            ctypes.c_float(eps), ctypes.c_float(wd), step, ctypes.c_float(gs), stream())
+    rc = lib.otal_adam_flat(p.p(), g.p(), m.p(), v.p(), n, lr, b1, b2,
+                            eps, wd, step, gs, stream())
     assert rc == 0
     torch.cuda.synchronize()
     (rp, ep), (rm, em), (rv, ev) = H.adam(p0, g0, m0, v0, lr, b1, b2, eps, wd, step, gs)
@@ -614,8 +614,8 @@ def test_adam(lib, n, offs, wd, step):
     # the graph-replayable form, fed the same two floats
     bc = dev(np.asarray(H.adam_bias_corrections(b1, b2, step), dtype=np.float32))
     p2, g2, m2, v2 = buffers()
-    rc = lib.otal_adam_flat_dev(p2.p(), g2.p(), m2.p(), v2.p(), ctypes.c_int64(n), ctypes.c_float(lr), ctypes.c_float(b1), ctypes.c_float(b2),
-                                ctypes.c_float(eps), ctypes.c_float(wd), ctypes.c_void_p(bc.data_ptr()), ctypes.c_float(gs), stream())
+    rc = lib.otal_adam_flat_dev(p2.p(), g2.p(), m2.p(), v2.p(), n, lr, b1, b2,
+                                eps, wd, ctypes.c_void_p(bc.data_ptr()), gs, stream())
     assert rc == 0
     torch.cuda.synchronize()
     for a, b, name in ((p, p2, "p"), (m, m2, "m"), (v, v2, "v")):
@@ -681,7 +681,7 @@ def test_proposal_windows_on_ties_and_floors(lib, lens, B, frames):
     assert B * N > 256 or len(lens) == 1
     ld = dev(loc)
     seg, fseg = Out((B, N, 4)), Out((B, N, 4))
-    assert lib.otal_proposal_windows(ctypes.c_void_p(ld.data_ptr()), seg.p(), fseg.p(), B, len(lens), IA(lev), ctypes.c_float(frames), stream()) == 0
+    assert lib.otal_proposal_windows(ctypes.c_void_p(ld.data_ptr()), seg.p(), fseg.p(), B, len(lens), IA(lev), frames, stream()) == 0
     torch.cuda.synchronize()
     seg.check("proposal windows seg")
     fseg.check("proposal windows frame_seg")

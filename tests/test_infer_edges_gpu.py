@@ -42,7 +42,6 @@ WORST = {}
 def lib():
     from opental_amd import _lib as L
     lb = L.lib()
-    lb.otal_softnms_scratch_bytes.restype = ctypes.c_size_t
     yield lb
     if WORST:
         print("\nlargest observed deviation / tolerance per family:")
@@ -108,8 +107,8 @@ def run_nms(lib, batch, sigma, top_k, thr, out_cols=5, index=True, unct=True, ac
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda")
     rc = lib.otal_softnms_classes_ws(ptr(d["seg"]), ptr(d["score"]), ptr(d["unct"] if unct else None),
                                      ptr(d["actn"] if actn else None), ptr(d["flag"]), ptr(cs), V, max_clips, A, K,
-                                     ctypes.c_float(sigma), top_k, ctypes.c_float(thr), out.p, counts.p, idx.p if index else None,
-                                     out_cols, ptr(scratch), ctypes.c_size_t(nbytes), total, stream())
+                                     sigma, top_k, thr, out.p, counts.p, idx.p if index else None,
+                                     out_cols, ptr(scratch), nbytes, total, stream())
     torch.cuda.synchronize()
     return rc, out, counts, idx
 
@@ -225,8 +224,8 @@ def run_decode(lib, case, entry, unct=True, actn=True, **override):
     prop_act = override.get("prop_act", d.get("prop_act"))
     args = [ptr(d["loc"]), ptr(d["prop_loc"]), ptr(d["priors"]), ptr(d["conf"]), ptr(d["prop_conf"]), ptr(d["center"]), ptr(act),
             ptr(prop_act), ptr(d["offsets"]), ptr(d["fps"]), outs["seg"].p, outs["score"].p, outs["unct"].p if unct else None,
-            outs["actn"].p if actn else None, outs["flag"].p, n, A, override.get("K", K), ctypes.c_float(case["clip_length"]),
-            ctypes.c_float(case["conf_thresh"])]
+            outs["actn"].p if actn else None, outs["flag"].p, n, A, override.get("K", K), case["clip_length"],
+            case["conf_thresh"]]
     fn = [override.get("score_fn", case["score_fn"]), override.get("first_class", case["first_class"])]
     if entry == "plain":
         rc = lib.otal_decode_clips(*args, stream())

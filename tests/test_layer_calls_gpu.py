@@ -181,7 +181,6 @@ def default_library():
     """The loaded library with every option at its table default (restored afterwards)."""
     from opental_amd import _lib as L
     lib = L.lib()
-    lib.otal_layer_last_kernel.restype = ctypes.c_char_p
     saved = [(n, lib.otal_get_option(n.encode(), d)) for n, d in OPTIONS]
     for n, d in OPTIONS:
         L.set_option(n, d)
@@ -452,7 +451,7 @@ def gn_forward_lib(lib, x, gamma, beta, G, eps, nlev, lev):
     B, C, T = x.shape
     y = torch.empty_like(x)
     stats = torch.empty(B, G, max(nlev, 1), 2, device=DEV)
-    L.check(lib.otal_gn_relu_fwd(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y), L.ptr(stats), B, C, T, G, ctypes.c_float(eps), 1,
+    L.check(lib.otal_gn_relu_fwd(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y), L.ptr(stats), B, C, T, G, eps, 1,
                                  nlev, lev, L.stream()), "otal_gn_relu_fwd")
     return y, stats
 
@@ -471,19 +470,18 @@ def run_gn_fwd(lib, label, d, eps, entry, gen):
     stats = [Buf(torch.float32, [B, G, max(nlev, 1), 2], dense([B, G, max(nlev, 1), 2]), 0) for _ in range(n)]
     P = lambda ts: (ctypes.c_void_p * 2)(*[t.data_ptr() for t in ts])
     xs, gs, bs = [p[0] for p in probs], [p[1] for p in probs], [p[2] for p in probs]
-    f = ctypes.c_float(eps)
     st = L.stream()
     if entry == "otal_gn_relu_fwd":
-        rc = lib.otal_gn_relu_fwd(L.ptr(xs[0]), L.ptr(gs[0]), L.ptr(bs[0]), ys[0].ptr(), stats[0].ptr(), B, C, T, G, f, 1, nlev, lev, st)
+        rc = lib.otal_gn_relu_fwd(L.ptr(xs[0]), L.ptr(gs[0]), L.ptr(bs[0]), ys[0].ptr(), stats[0].ptr(), B, C, T, G, eps, 1, nlev, lev, st)
     elif entry == "otal_gn_relu_fwd_to":
-        rc = lib.otal_gn_relu_fwd_to(L.ptr(xs[0]), L.ptr(gs[0]), L.ptr(bs[0]), ys[0].ptr(), ctypes.c_int64(y_bs), ctypes.c_int64(y_cs),
-                                     stats[0].ptr(), B, C, T, G, f, 1, nlev, lev, st)
+        rc = lib.otal_gn_relu_fwd_to(L.ptr(xs[0]), L.ptr(gs[0]), L.ptr(bs[0]), ys[0].ptr(), y_bs, y_cs,
+                                     stats[0].ptr(), B, C, T, G, eps, 1, nlev, lev, st)
     elif entry == "otal_gn_relu_fwd_pair":
-        rc = lib.otal_gn_relu_fwd_pair(P(xs), P(gs), P(bs), P([y.view for y in ys]), P([s.view for s in stats]), B, C, T, G, f, 1,
+        rc = lib.otal_gn_relu_fwd_pair(P(xs), P(gs), P(bs), P([y.view for y in ys]), P([s.view for s in stats]), B, C, T, G, eps, 1,
                                        nlev, lev, st)
     else:
-        rc = lib.otal_gn_relu_fwd_pair_to(P(xs), P(gs), P(bs), P([y.view for y in ys]), ctypes.c_int64(y_bs), ctypes.c_int64(y_cs),
-                                          P([s.view for s in stats]), B, C, T, G, f, 1, nlev, lev, st)
+        rc = lib.otal_gn_relu_fwd_pair_to(P(xs), P(gs), P(bs), P([y.view for y in ys]), y_bs, y_cs,
+                                          P([s.view for s in stats]), B, C, T, G, eps, 1, nlev, lev, st)
     name = name_of(lib)
     torch.cuda.synchronize()
     assert rc == 0, f"{label}: rc {rc}"
@@ -555,7 +553,7 @@ def run_gn_bwd(lib, label, d, entry, variant, gen):
                                        P([p[4] for p in probs]), P([b_.view for b_ in dx]), P([b_.view for b_ in part]), B, C, T, G, 1,
                                        nlev, lev, st)
     else:
-        rc = lib.otal_gn_relu_bwd(dys[0][0].ptr(), ctypes.c_int64(terms[0][0]), L.ptr(probs[0][0]), L.ptr(probs[0][1]),
+        rc = lib.otal_gn_relu_bwd(dys[0][0].ptr(), terms[0][0], L.ptr(probs[0][0]), L.ptr(probs[0][1]),
                                   L.ptr(probs[0][2]), L.ptr(probs[0][4]), dx[0].ptr(), part[0].ptr(), B, C, T, G, 1, nlev, lev, st)
     name = name_of(lib)
     torch.cuda.synchronize()
@@ -618,8 +616,8 @@ def run_convert(lib, label, d, addr, gen):
         src.view.copy_(v)
     else:
         src.view.view(torch.int16).copy_((R.bf16_bits(v) & 0xFFFF).to(torch.int32).to(torch.int16))
-    rc = lib.otal_convert_storage(src.ptr(), ctypes.c_int64(d["src_bs"]), ctypes.c_int64(d["src_cs"]), dst.ptr(),
-                                  ctypes.c_int64(d["dst_bs"]), ctypes.c_int64(d["dst_cs"]), to, B, C, P, L.stream())
+    rc = lib.otal_convert_storage(src.ptr(), d["src_bs"], d["src_cs"], dst.ptr(),
+                                  d["dst_bs"], d["dst_cs"], to, B, C, P, L.stream())
     name = name_of(lib)
     torch.cuda.synchronize()
     assert rc == 0, f"{label}: rc {rc}"
@@ -866,12 +864,12 @@ def test_documented_refusals_write_nothing(lib, harness):
         gam, bet = torch.ones(C, device=DEV), torch.zeros(C, device=DEV)
         y = torch.full_like(x, float("nan"))
         stats = torch.full((1, G, 1, 2), float("nan"), device=DEV)
-        rc = lib.otal_gn_relu_fwd(L.ptr(x), L.ptr(gam), L.ptr(bet), L.ptr(y), L.ptr(stats), 1, C, T, G, ctypes.c_float(1e-5), 1, 1,
+        rc = lib.otal_gn_relu_fwd(L.ptr(x), L.ptr(gam), L.ptr(bet), L.ptr(y), L.ptr(stats), 1, C, T, G, 1e-5, 1, 1,
                                   None, st)
         assert rc == want and name_of(lib) == "", (C, T, G, rc)
         dx = torch.full_like(x, float("nan"))
         part = torch.full((1, 3, C), float("nan"), device=DEV)
-        rc = lib.otal_gn_relu_bwd(L.ptr(x), ctypes.c_int64(0), L.ptr(x), L.ptr(gam), L.ptr(bet), L.ptr(stats), L.ptr(dx), L.ptr(part),
+        rc = lib.otal_gn_relu_bwd(L.ptr(x), 0, L.ptr(x), L.ptr(gam), L.ptr(bet), L.ptr(stats), L.ptr(dx), L.ptr(part),
                                   1, C, T, G, 1, 1, None, st)
         assert rc == want and name_of(lib) == "", (C, T, G, rc)
         torch.cuda.synchronize()

@@ -8,7 +8,6 @@ Each instance (cls_mode 0 with the IBM EMA off and on, 1, 2, 3, RPL, GCPL and th
 compared with the package's torch formulation, modes 0 and 1 also with the CPU oracle, under the bounds those pairings have in
 tests/test_loss_gpu.py, test_closed_set_gpu.py, test_rpl_gpu.py and test_ablations_gpu.py: all sums are normalised by a count,
 so the bounds do not grow with A."""
-import ctypes
 import functools
 import os
 
@@ -223,25 +222,22 @@ def _raw(inst, case=None, inputs=None):
     gt, valid = pad_targets([torch.from_numpy(x).to(dev) for x in targets], dev)
     gt, gv, pri = gt.contiguous(), valid.to(torch.uint8).contiguous(), torch.from_numpy(priors[:, 0].copy()).to(dev)
     lib = L.lib()
-    lib.otal_detection_loss_grad_floats.restype = ctypes.c_size_t
-    lib.otal_detection_loss_scratch_floats.restype = ctypes.c_size_t
     ng, ns = lib.otal_detection_loss_grad_floats(B, K, C), lib.otal_detection_loss_scratch_floats(B, K)
     assert ng == B * K * (2 * C + 11) and ns == B * K * 12
     losses, grads, scratch = _guarded(7, dev), _guarded(ng, dev), _guarded(ns, dev)
     state = torch.linspace(0.5, 1.5, 50, device=dev)
-    f = ctypes.c_float
     tail = [L.ptr(losses), L.ptr(grads), L.ptr(scratch), L.stream()]
     if inst in ("rpl", "gcpl"):
         rc = lib.otal_detection_loss_rpl(*[L.ptr(t[k]) for k in ("loc", "conf", "prop_loc", "prop_conf", "center")], L.ptr(pri),
-                                         L.ptr(gt), L.ptr(gv), B, K, C, gt.shape[1], f(256.0), f(0.5), int(inst == "gcpl"), f(1.0),
-                                         f(0.1), f(0.0), *tail)
+                                         L.ptr(gt), L.ptr(gv), B, K, C, gt.shape[1], 256.0, 0.5, int(inst == "gcpl"), 1.0,
+                                         0.1, 0.0, *tail)
     else:
         mode, ibm = {"mode0_ibm_off": (0, 0), "mode0_ibm_on": (0, 1), "mode1": (1, 0), "mode2": (2, 0), "mode3": (3, 0)}[inst]
         closed = mode >= 2
         p = lambda k: None if (closed and k in ("act", "prop_act")) else L.ptr(t[k])
         rc = lib.otal_detection_loss(*[p(k) for k in ("loc", "conf", "prop_loc", "prop_conf", "center", "act", "prop_act")],
-                                     L.ptr(pri), L.ptr(gt), L.ptr(gv), L.ptr(state), B, K, C, gt.shape[1], f(256.0), f(0.5), ibm, 50,
-                                     f(0.99), int(mode in (0, 2)), mode, f(0.25), *tail)
+                                     L.ptr(pri), L.ptr(gt), L.ptr(gv), L.ptr(state), B, K, C, gt.shape[1], 256.0, 0.5, ibm, 50,
+                                     0.99, int(mode in (0, 2)), mode, 0.25, *tail)
     torch.cuda.synchronize()
     return rc, losses, grads, scratch, state, ng, ns
 

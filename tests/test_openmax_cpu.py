@@ -25,7 +25,8 @@ def lib():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    return ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    return declare(ctypes.CDLL(build.LIB))
 
 
 def fits_of(fx, stage):
@@ -43,8 +44,7 @@ def test_openmax_symbols_are_exported_and_declared(lib):
 
 def test_openmax_argument_errors_do_not_launch(lib):
     one = ctypes.c_void_p(16)           # never dereferenced: argument checks come first
-    i64 = ctypes.c_int64
-    dist = lambda feat, n, rpb, mav, k, d, out: lib.otal_openmax_dist(feat, n, rpb, i64(0), i64(d), i64(1), mav, k, d, None, out, None)
+    dist = lambda feat, n, rpb, mav, k, d, out: lib.otal_openmax_dist(feat, n, rpb, 0, d, 1, mav, k, d, None, out, None)
     assert dist(None, 4, 4, one, 15, 512, one) == -1
     assert dist(one, 4, 4, one, 15, 512, None) == -1
     assert dist(one, 0, 4, one, 15, 512, one) == -2
@@ -53,23 +53,22 @@ def test_openmax_argument_errors_do_not_launch(lib):
     assert dist(one, 4, 4, one, 15, 516, one) == -7             # D beyond the staged row
     assert dist(one, 4, 4, one, 15, 504, one) == -7             # D % 16
     assert dist(one, 4, 4, ctypes.c_void_p(20), 15, 512, one) == -7        # MAVs not 16-byte aligned
-    means = lambda feat, lab, n, k, out, cnt: lib.otal_openmax_class_means(feat, n, n, i64(0), i64(512), i64(1), lab, k, 512, out, cnt, None)
+    means = lambda feat, lab, n, k, out, cnt: lib.otal_openmax_class_means(feat, n, n, 0, 512, 1, lab, k, 512, out, cnt, None)
     assert means(one, None, 4, 15, one, one) == -1
     assert means(one, one, 4, 15, one, None) == -1
     assert means(one, one, 4, 0, one, one) == -2
-    probs = lambda logits, ldl, wb, k, r, out: lib.otal_openmax_probs(logits, i64(ldl), one, 4, 4, i64(0), i64(512), i64(1), one, wb,
+    probs = lambda logits, ldl, wb, k, r, out: lib.otal_openmax_probs(logits, ldl, one, 4, 4, 0, 512, 1, one, wb,
                                                                      k, 512, r, out, None)
     assert probs(None, 15, one, 15, 1, one) == -1
     assert probs(one, 15, None, 15, 1, one) == -1
     assert probs(one, 14, one, 15, 1, one) == -2                # logit rows shorter than K
     assert probs(one, 15, one, 15, 0, one) == -7                # rank outside [1, K]
     assert probs(one, 15, one, 15, 16, one) == -7
-    st = (i64 * 3)(A * 512, 512, 1)
-    f = ctypes.c_float
+    st = (ctypes.c_int64 * 3)(A * 512, 512, 1)
 
     def decode(loc=one, feat=one, prop_feat=None, pst=None, unknown=one, n=2, c=16, first=1, d=512, r=1, refined=0):
         return lib.otal_decode_clips_openmax(loc, one, one, one, one, one, one, one, feat, prop_feat, st, pst, one, one, one, one,
-                                             one, one, unknown, one, n, A, c, first, d, r, refined, f(256.0), f(0.01), None)
+                                             one, one, unknown, one, n, A, c, first, d, r, refined, 256.0, 0.01, None)
     assert decode(loc=None) == -1
     assert decode(feat=None) == -1
     assert decode(unknown=None) == -1
@@ -83,7 +82,7 @@ def test_openmax_argument_errors_do_not_launch(lib):
     assert decode(refined=2, prop_feat=one, pst=st) == -7
     # the softmax / Dirichlet decode keeps refusing a third score function: OpenMax has entries of its own
     assert lib.otal_decode_clips_ex(one, one, one, one, one, one, None, None, one, one, one, one, None, None, one, 2, A, 16,
-                                    f(256.0), f(0.01), 2, 1, None) == -7
+                                    256.0, 0.01, 2, 1, None) == -7
 
 
 def test_weibull_fit_matches_libmr_within_its_stopping_error(fx):

@@ -281,8 +281,8 @@ def test_launches_write_their_whole_output_and_nothing_else(fx, dev, n_rows):
     lab = torch.from_numpy(fx["rows_labels"][:n_rows].astype(np.int32)).to(dev)
     lay = [l.to(dev) for l in layers(fx)]
     mav, wb = lay[0].tensors(dev)
-    i64, lib = ctypes.c_int64, L.lib()
-    view = (n_rows, i64(0), i64(D), i64(1))
+    lib = L.lib()
+    view = (n_rows, 0, D, 1)
     buf, out = guarded(n_rows * K, dev)
     L.check(lib.otal_openmax_dist(L.ptr(f), n_rows, *view, L.ptr(mav), K, D, None, L.ptr(out), L.stream()), "dist")
     check_guard(buf, n_rows * K, "otal_openmax_dist")
@@ -295,7 +295,7 @@ def test_launches_write_their_whole_output_and_nothing_else(fx, dev, n_rows):
     check_guard(buf, K * D, "otal_openmax_class_means")
     check_guard(cbuf, K, "otal_openmax_class_means (counts)")
     buf, out = guarded(n_rows * (K + 1), dev)
-    L.check(lib.otal_openmax_probs(L.ptr(z), i64(K), L.ptr(f), n_rows, *view, L.ptr(mav), L.ptr(wb), K, D, 1, L.ptr(out),
+    L.check(lib.otal_openmax_probs(L.ptr(z), K, L.ptr(f), n_rows, *view, L.ptr(mav), L.ptr(wb), K, D, 1, L.ptr(out),
                                    L.stream()), "probs")
     check_guard(buf, n_rows * (K + 1), "otal_openmax_probs")
 
@@ -316,7 +316,7 @@ def test_decode_launch_writes_its_whole_output_and_nothing_else(fx, dev, refined
         L.ptr(t['loc']), L.ptr(t['prop_loc']), L.ptr(t['priors']), L.ptr(t['conf']), L.ptr(t['prop_conf']), L.ptr(t['center']),
         L.ptr(offs), L.ptr(fps), L.ptr(t['conf_feat']), L.ptr(t['prop_conf_feat']) if refined else None, st, st if refined else None,
         L.ptr(mav), L.ptr(pmav), L.ptr(wb), L.ptr(pwb), L.ptr(bufs['seg'][1]), L.ptr(bufs['score'][1]), L.ptr(bufs['unknown'][1]),
-        L.ptr(bufs['flag'][1]), n, A, K + 1, 1, D, 1, refined, ctypes.c_float(256.0), ctypes.c_float(0.01), L.stream()), "decode")
+        L.ptr(bufs['flag'][1]), n, A, K + 1, 1, D, 1, refined, 256.0, 0.01, L.stream()), "decode")
     for name, (buf, view) in bufs.items():
         check_guard(buf, view.numel(), "otal_decode_clips_openmax " + name)
     assert bool((bufs['flag'][1] <= 1).all())              # every flag byte was written (0 / 1, no sentinel left)

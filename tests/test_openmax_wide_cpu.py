@@ -26,7 +26,8 @@ def lib():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    return ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    return declare(ctypes.CDLL(build.LIB))
 
 
 def test_wide_symbols_are_exported_and_declared(lib):
@@ -42,19 +43,18 @@ def test_wide_symbols_are_exported_and_declared(lib):
 def test_wide_argument_errors_do_not_launch(lib):
     one = ctypes.c_void_p(16)           # never dereferenced: argument checks come first
     odd = ctypes.c_void_p(20)           # not 16-byte aligned
-    i64, f = ctypes.c_int64, ctypes.c_float
 
     def dist(k=150, d=512, mav=one, labels=one, feat=one, out=one, n=4, rpb=4):
-        return lib.otal_openmax_dist_wide(feat, n, rpb, i64(0), i64(d), i64(1), mav, k, d, labels, out, None)
+        return lib.otal_openmax_dist_wide(feat, n, rpb, 0, d, 1, mav, k, d, labels, out, None)
 
     def probs(k=150, d=512, r=1, ldl=None, mav=one, logits=one, wb=one, out=one, n=4):
-        return lib.otal_openmax_probs_wide(logits, i64(k if ldl is None else ldl), one, n, n, i64(0), i64(d), i64(1), mav, wb,
+        return lib.otal_openmax_probs_wide(logits, k if ldl is None else ldl, one, n, n, 0, d, 1, mav, wb,
                                            k, d, r, out, None)
-    st = (i64 * 3)(A * 512, 512, 1)
+    st = (ctypes.c_int64 * 3)(A * 512, 512, 1)
 
     def decode(c=151, first=1, d=512, r=1, refined=0, mav=one, pmav=one, loc=one, prop_feat=None, pst=None, n=2, flag=one):
         return lib.otal_decode_clips_openmax_wide(loc, one, one, one, one, one, one, one, one, prop_feat, st, pst, mav, pmav, one,
-                                                  one, one, one, one, flag, n, A, c, first, d, r, refined, f(768.0), f(0.001),
+                                                  one, one, one, one, flag, n, A, c, first, d, r, refined, 768.0, 0.001,
                                                   None)
     assert dist(k=257) == -7 and probs(k=257) == -7 and decode(c=258) == -7
     assert dist(k=256, mav=odd) == -7                           # 256 classes are inside the limits: only the alignment refuses
@@ -73,8 +73,8 @@ def test_wide_argument_errors_do_not_launch(lib):
     assert dist(n=0) == -2 and dist(rpb=0) == -2 and probs(n=0) == -2 and decode(n=0) == -2
     assert decode(c=1) == -2                                    # nothing left once the background logit is dropped
     # the narrow entries keep their limits
-    assert lib.otal_openmax_dist(one, 4, 4, i64(0), i64(512), i64(1), one, 17, 512, None, one, None) == -7
-    assert lib.otal_openmax_probs(one, i64(17), one, 4, 4, i64(0), i64(512), i64(1), one, one, 17, 512, 1, one, None) == -7
+    assert lib.otal_openmax_dist(one, 4, 4, 0, 512, 1, one, 17, 512, None, one, None) == -7
+    assert lib.otal_openmax_probs(one, 17, one, 4, 4, 0, 512, 1, one, one, 17, 512, 1, one, None) == -7
 
 
 def test_float64_restatement_equals_the_golden(fx):

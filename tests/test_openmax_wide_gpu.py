@@ -298,13 +298,13 @@ def test_launches_write_their_whole_output_and_nothing_else(dev, n_rows, k):
     f, z = up(feats, dev), up(logits, dev)
     lab = up(np.random.RandomState(5).randint(-1, k + 1, n_rows).astype(np.int32), dev)    # some labels outside [0, K)
     mav, wb = layer.tensors(dev)
-    i64, lib = ctypes.c_int64, L.lib()
-    view = (n_rows, i64(0), i64(D), i64(1))
+    lib = L.lib()
+    view = (n_rows, 0, D, 1)
     buf, out = guarded(n_rows, dev)
     L.check(lib.otal_openmax_dist_wide(L.ptr(f), n_rows, *view, L.ptr(mav), k, D, L.ptr(lab), L.ptr(out), L.stream()), "dist")
     check_guard(buf, n_rows, "otal_openmax_dist_wide")
     buf, out = guarded(n_rows * (k + 1), dev)
-    L.check(lib.otal_openmax_probs_wide(L.ptr(z), i64(k), L.ptr(f), n_rows, *view, L.ptr(mav), L.ptr(wb), k, D, 1, L.ptr(out),
+    L.check(lib.otal_openmax_probs_wide(L.ptr(z), k, L.ptr(f), n_rows, *view, L.ptr(mav), L.ptr(wb), k, D, 1, L.ptr(out),
                                         L.stream()), "probs")
     check_guard(buf, n_rows * (k + 1), "otal_openmax_probs_wide")
 
@@ -326,7 +326,7 @@ def test_decode_launch_writes_its_whole_output_and_nothing_else(fx, dev, refined
         L.ptr(t['loc']), L.ptr(t['prop_loc']), L.ptr(pri), L.ptr(t['conf']), L.ptr(t['prop_conf']), L.ptr(t['center']),
         L.ptr(offs), L.ptr(fps), L.ptr(t['conf_feat']), L.ptr(t['prop_conf_feat']) if refined else None, st, st if refined else None,
         L.ptr(mav), L.ptr(pmav), L.ptr(wb), L.ptr(pwb), L.ptr(bufs['seg'][1]), L.ptr(bufs['score'][1]), L.ptr(bufs['unknown'][1]),
-        L.ptr(bufs['flag'][1]), n, A, K + 1, 1, D, 1, refined, ctypes.c_float(768.0), ctypes.c_float(0.001), L.stream()), "decode")
+        L.ptr(bufs['flag'][1]), n, A, K + 1, 1, D, 1, refined, 768.0, 0.001, L.stream()), "decode")
     for name, (buf, view) in bufs.items():
         check_guard(buf, view.numel(), "otal_decode_clips_openmax_wide " + name)
     assert bool((bufs['flag'][1] <= 1).all())              # every flag byte was written (0 / 1, no sentinel left)

@@ -1247,7 +1247,7 @@ def test_deferred_reduction_record_survives_two_issuing_threads():
             try:
                 for r in range(rounds):        # every launch gets its own slab range: the record only keeps pointers
                     rc = lib.otal_conv_wgrad(ga, sa, L.ptr(xs[t]), L.ptr(dys[t]), L.ptr(outs[t][r]), 0, 1, None,
-                                             ctypes.c_void_p(wss[t].data_ptr() + r * (8 << 20)), ctypes.c_size_t(8 << 20),
+                                             ctypes.c_void_p(wss[t].data_ptr() + r * (8 << 20)), 8 << 20,
                                              ctypes.c_void_p(streams[t].cuda_stream))
                     if rc:
                         errs.append(rc)

@@ -27,7 +27,8 @@ def lib():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    return ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    return declare(ctypes.CDLL(build.LIB))
 
 
 def head_outputs(B=2, seed=31):
@@ -94,7 +95,6 @@ def test_symbols_exported_and_arguments_checked(lib):
     assert hasattr(lib, "otal_rpl_head_fwd") and hasattr(lib, "otal_rpl_head_bwd") and hasattr(lib, "otal_detection_loss_rpl")
     assert lib.otal_abi_version() == 26
     one = ctypes.c_void_p(16)     # never dereferenced: argument checks come first
-    f = ctypes.c_float
     fwd = lambda x=one, Cn=16, D=512: lib.otal_rpl_head_fwd(x, one, one, 2, Cn, D, 126, None)
     bwd = lambda g=one, Cn=16, D=512, parts=3: lib.otal_rpl_head_bwd(one, one, g, one, one, 2, Cn, D, 126, parts, None)
     assert fwd(x=None) == -1 and bwd(g=None) == -1                  # OTAL_E_NULL
@@ -104,8 +104,8 @@ def test_symbols_exported_and_arguments_checked(lib):
     assert bwd(parts=0) == -2 and bwd(parts=4) == -2
 
     def loss(loc=one, gcpl=0, B=1):
-        return lib.otal_detection_loss_rpl(loc, one, one, one, one, one, one, one, B, 126, C, 1, f(256.0), f(0.5), gcpl, f(1.0),
-                                           f(0.1), f(0.0), one, one, one, None)
+        return lib.otal_detection_loss_rpl(loc, one, one, one, one, one, one, one, B, 126, C, 1, 256.0, 0.5, gcpl, 1.0,
+                                           0.1, 0.0, one, one, one, None)
     assert loss(loc=None) == -1
     assert loss(gcpl=2) == -7
     assert loss(B=17) == -7                                         # B * K beyond the single-workgroup kernel

@@ -197,7 +197,8 @@ def test_average_precision_argument_errors_do_not_launch():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    lib = ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    lib = declare(ctypes.CDLL(build.LIB))
     one = ctypes.c_void_p(16)       # never dereferenced: argument checks come first
     f = lib.otal_average_precision
     for k in (0, 1, 2, 3, 7):                                               # every pointer argument in turn

@@ -276,13 +276,13 @@ def test_open_set_curves_is_exported_and_its_argument_errors_do_not_launch():
     from opental_amd.csrc import build
     if not os.path.exists(build.LIB):
         build.build(verbose=False)
-    lib = ctypes.CDLL(build.LIB)
+    from opental_amd._lib import declare
+    lib = declare(ctypes.CDLL(build.LIB))
     assert hasattr(lib, 'otal_open_set_curves') and lib.otal_abi_version() == 26
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "opental_hip.h")).read()
     assert "int otal_open_set_curves(const double* known, const int* flags, int M, int nthr, double* out, void* stream);" in header
     one = ctypes.c_void_p(16)       # never dereferenced: argument checks come first
     f = lib.otal_open_set_curves
-    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2
     for k in (0, 1, 4):                                                     # every pointer argument in turn
         args = [one, one, 10, 5, one, None]
         args[k] = None

@@ -33,7 +33,7 @@ from oracle.layer_ref import FIELDS, NINTS  # noqa: E402
 
 def _v(p):
     """A pointer / integer argument as a Python int (0 for NULL)."""
-    if isinstance(p, (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t)):
+    if isinstance(p, ctypes.c_void_p):
         return int(p.value or 0)
     if p is None:
         return 0
@@ -92,7 +92,7 @@ def _gn_fwd(name, a):
     B, C, T, G, eps, relu, nlev, lev = a[k + 1:k + 9]
     first = (lambda p: _arr(p, 1)[0]) if pair else _v
     ints = [B, C, T, G, int(relu), int(pair), y_bs, y_cs, int(nlev)] + _lev(int(nlev), lev)
-    return ints, float(eps.value if isinstance(eps, ctypes.c_float) else eps), [_a(first(x)), _a(first(y)), _a(first(stats)), 0, 0]
+    return ints, float(eps), [_a(first(x)), _a(first(y)), _a(first(stats)), 0, 0]
 
 
 def _gn_bwd(name, a):
