@@ -913,6 +913,34 @@ int otal_average_precision(const int* codes, const int* rank_pos, const int* cla
  * zeros.  A refused call writes nothing.  An additive entry: OTAL_ABI_VERSION is unchanged. */
 int otal_open_set_curves(const double* known, const int* flags, int M, int nthr, double* out, void* stream);
 
+/* otal_wilderness_impact (csrc/wi.hip): the Wilderness Impact of every (class, tIoU threshold) from the codes of
+ * otal_eval_match_labeled, i.e. the tail of compute_wilderness_impact (:694-728) with utils_eval.interpolated_prec_rec
+ * (:20-29), on the device.  The rule is stated in opental_amd/evaluation/table_wi.py (wi_reference, codes_reference).
+ *   codes (nthr, N) int32   out of otal_eval_match_labeled over the positions of the pass order (video by video, table row
+ *                           inside): >= 0 the row of gt_label matched, -1 background, -2 nothing;
+ *   pred_label (N) int32    the label of a position's detection: 1 .. K, 0 = predicted unknown;
+ *   gt_label (M) int32      the ground truths' labels in the rows that codes names: 1 .. K, 0 = unknown;
+ *   n_known, n_unknown      the ground truths of the known classes (Kt >= 1) and of unknown ones (U >= 0), both and their
+ *                           sum below OTAL_WI_MAX_GT = 2^24, where the host rule's float32 counts stop being exact;
+ *   out (nthr, K) fp64      every element is written.
+ * A row's outcome is match.wi_outcome_codes': with lp / lg the two labels, a matched row is tp_u2u (lp == lg == 0), tp_k2k
+ * (lp == lg > 0), fp_u2k (lg == 0 < lp), fp_k2u (lp == 0 < lg) or fp_k2k; a background row is fp_bg2u (lp == 0) or fp_bg2k,
+ * which counts as fp_k2k; code -2 has none.  A code outside -2 .. M - 1 or a label outside 0 .. K has none either and
+ * gt_label is read at no other place than a code inside 0 .. M - 1.  Per (class c, threshold), with A_r / F_r the rows up to
+ * and including r that are tp_k2k or fp_k2k / fp_u2k with lp == c + 1 and U_r those that are tp_u2u (int32):
+ * precision_r = A_r / ((A_r + F_r) + 1e-6), envelope_r = max over j >= r of precision_j, recall_r = Kt / ((Kt + U) - U_r), and
+ * WI = recall_0 * envelope_0 + the sum over the tp_u2u rows r > 0 of (recall_r - Kt / ((Kt + U) - (U_r - 1))) * envelope_r, all
+ * in fp64 with IEEE division.  One workgroup of OTAL_AP_TILE threads per (class, threshold) walks the N rows in chunks from
+ * the back with carried counts and a carried maximum; the sum runs in one fixed order (inside a wave a butterfly, the waves
+ * of a chunk in order, the chunks from the last to the first) that depends on OTAL_AP_TILE and N alone: no atomic, no
+ * scratch, the same bits from run to run.  One launch on `stream`, no allocation, no synchronisation.  NULL pointer:
+ * OTAL_E_NULL; N < 0, M < 0, K < 1, nthr < 1, n_known < 1 or n_unknown < 0: OTAL_E_SHAPE; nthr > 32, N >
+ * OTAL_AP_MAX_CLASS_ROWS or a ground-truth count at or above OTAL_WI_MAX_GT: OTAL_E_UNSUPPORTED.  N == 0 writes zeros.  A
+ * refused call writes nothing.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+#define OTAL_WI_MAX_GT 16777216
+int otal_wilderness_impact(const int* codes, const int* pred_label, const int* gt_label, int n_known, int n_unknown, int N,
+                           int M, int nthr, int K, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

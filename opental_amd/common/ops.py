@@ -1982,6 +1982,40 @@ def average_precision(codes, rank_pos, class_start, gt_count, out=None):
     return out
 
 
+WI_MAX_GT = 2 ** 24                         # OTAL_WI_MAX_GT: where the host rule's float32 ground-truth counts stop being exact
+
+
+def wilderness_impact(codes, pred_label, gt_label, n_known, n_unknown, n_classes, out=None):
+    """The Wilderness Impact of every (class, tIoU threshold) in one launch (otal_wilderness_impact, csrc/wi.hip; the rule:
+    evaluation/table_wi.py).  codes (nthr, N) int32 out of eval_match_labeled over the positions of the pass order, pred_label
+    (N) int32 the positions' labels (1 .. K, 0 = predicted unknown), gt_label (M) int32 the labels of the rows codes names
+    (0 = unknown), all on the device; n_known >= 1 / n_unknown >= 0 the ground truths of known / unknown classes, Python
+    ints; n_classes = K.
+    -> wi (nthr, K) fp64, every element written (zeros for N = 0).  `out`: the array to write into instead of allocating it; a
+    refused call leaves it untouched.  No synchronisation."""
+    L.require_device(codes, pred_label, gt_label)
+    if any(t.dtype != torch.int32 for t in (codes, pred_label, gt_label)):
+        raise RuntimeError("wilderness_impact: codes, pred_label and gt_label in int32")
+    if codes.dim() != 2 or pred_label.dim() != 1 or pred_label.shape[0] != codes.shape[1] or gt_label.dim() != 1 \
+            or codes.shape[0] < 1:
+        raise RuntimeError("wilderness_impact: codes (nthr, N), pred_label (N), gt_label (M), nthr >= 1")
+    nthr, N = codes.shape
+    M, K = gt_label.numel(), int(n_classes)
+    if out is None:
+        out = torch.empty((nthr, max(K, 0)), dtype=torch.float64, device=codes.device)
+    else:
+        L.require_device(out)
+        if tuple(out.shape) != (nthr, K) or out.dtype != torch.float64:
+            raise RuntimeError("wilderness_impact: out must be (nthr, K) float64")
+    if N == 0:          # an empty tensor has no address to pass; N and M say that no element of them is read
+        codes, pred_label = codes.new_zeros((nthr, 1)), pred_label.new_zeros(1)
+    if M == 0:
+        gt_label = gt_label.new_zeros(1)
+    L.check(L.lib().otal_wilderness_impact(L.ptr(codes), L.ptr(pred_label), L.ptr(gt_label), int(n_known), int(n_unknown), N, M,
+                                           nthr, K, L.ptr(out), L.stream()), "otal_wilderness_impact")
+    return out
+
+
 def open_set_curves(known, flags, out=None):
     """AUROC, AUPR, FAR@95 and OSDR of every tIoU threshold in one launch (otal_open_set_curves, csrc/oscurve.hip; the rule:
     evaluation/table_open.py).  known (nthr, M) fp64: the known-ness of a threshold's matched detections, ascending, equal

@@ -1,7 +1,8 @@
 """Which saved epoch is best: the mAP of every `checkpoint-<epoch>.ckpt` under training.checkpoint_path, on the device.
 
     python -m opental_amd.thumos14.score_checkpoints <yaml> [--open_set --split N] --gt GT.json --known KNOWN.txt \\
-           [--epochs A B ...] [--tious ...] [--random_init] [--open_metrics [--ood_threshold THR]] [--select KEY]
+           [--epochs A B ...] [--tious ...] [--random_init] [--select KEY] \\
+           [--open_metrics [--ood_threshold THR | --threshold_from_train [--threshold_videos N]] [--wi]]
     python -m opental_amd.anet.score_checkpoints     ... the same, with the ActivityNet defaults
 
 The network is built once; per checkpoint its state dict is loaded, the test videos go through the recipe's device pipeline
@@ -23,7 +24,18 @@ that is asked for, otherwise it is scored and the entry merged.  --select KEY na
 AUROC, AUPR, OSDR or FAR95, the mean over the thresholds; FAR95 is best where it is lowest, a NaN mean is never best, equal means
 go to the earlier epoch.  Without these flags the output and the file are what they were without them.
 
-A recipe's module hands `run` a Recipe: how to build its network, list its test videos and detect one batch."""
+--threshold_from_train (with --open_metrics, instead of a numeric --ood_threshold) gives every epoch its OWN known / unknown
+operating point, as the protocol does (thumos14/threshold.py, anet/threshold.py): after the state dict is loaded the recipe's
+training videos go through the same device pipeline (Recipe.train_table), each table's known[:n] is kept, and
+det_table.threshold_from_scores over their concatenation -- the known-ness value that 95 % of the detections exceed -- is the
+epoch's ood_threshold for table_open and table_wi.  The entry records it as "ood_threshold" with "ood_threshold_from": "train";
+--threshold_videos N caps the pass at the first N training videos (smoke runs) and is recorded as "threshold_videos": an entry
+made under another cap, or none, does not count as held.  --wi (with one of the two threshold sources) adds the Wilderness
+Impact (evaluation/table_wi.py): "WI", per tIoU the mean over the K classes, NaN as null; the epoch's line gains " WI <mean>"
+and, with --threshold_from_train, " thr <value>".  --select WI is best where it is lowest, as FAR95.
+
+A recipe's module hands `run` a Recipe: how to build its network, list its test videos and detect one batch -- and, for
+--threshold_from_train, how to list its training videos and detect one batch of them."""
 import json
 import os
 import re
@@ -37,7 +49,9 @@ from .driver import device_setup, split_flags, write_json
 
 MAP_FILE = 'checkpoint_map.json'
 OPEN_KEYS = ('AUROC', 'AUPR', 'FAR95', 'OSDR')      # an entry's open-set lists, in the order of table_open.KEYS
-SELECT_KEYS = ('average_mAP',) + OPEN_KEYS
+SELECT_KEYS = ('average_mAP',) + OPEN_KEYS + ('WI',)
+LOWER_IS_BETTER = ('FAR95', 'WI')
+THRESHOLD_KEYS = ('ood_threshold', 'ood_threshold_from', 'threshold_videos', 'WI')     # what a scoring at another threshold stales
 _CKPT = re.compile(r'^checkpoint-(\d+)\.ckpt$')
 
 
@@ -46,11 +60,15 @@ class Recipe(object):
     default thresholds; build(config, dev) -> the network, randomly initialised, in eval mode;
     videos(config) -> (names as the ground truth spells them, state); batches(config, state) -> lists of positions into names;
     table(net, config, state, positions, dev, scoring=...) -> the detection table of these videos (video column
-    0 .. len(positions)-1), its `known` column by the out-of-distribution score `scoring`."""
+    0 .. len(positions)-1), its `known` column by the out-of-distribution score `scoring`.
+    Optional, for --threshold_from_train: train_videos(config) -> (names, state) of the TRAINING split, which `batches` cuts
+    into batches like the test split's; train_table(net, config, state, positions, dev, scoring=...) -> the same table as
+    `table`, over these videos."""
 
-    def __init__(self, dataset, subset, tious, build, videos, batches, table):
+    def __init__(self, dataset, subset, tious, build, videos, batches, table, train_videos=None, train_table=None):
         self.dataset, self.subset, self.tious = dataset, subset, tious
         self.build, self.videos, self.batches, self.table = build, videos, batches, table
+        self.train_videos, self.train_table = train_videos, train_table
 
 
 def take_values(argv, flag):
@@ -82,14 +100,14 @@ def list_checkpoints(checkpoint_path, epochs=None):
 
 def select_value(entry, key):
     """What --select KEY compares: the entry's average_mAP, or the mean of its KEY list over the thresholds (null = NaN),
-    negated for FAR95 so that larger is better throughout.  None where the entry does not hold the key."""
+    negated for FAR95 and WI so that larger is better throughout.  None where the entry does not hold the key."""
     if key == 'average_mAP':
         return entry.get('average_mAP')
     values = entry.get(key)
     if values is None:
         return None
     mean = float(np.mean([np.nan if v is None else v for v in values])) if len(values) else float('nan')
-    return -mean if key == 'FAR95' else mean
+    return -mean if key in LOWER_IS_BETTER else mean
 
 
 def best_epoch(scores, key='average_mAP'):
@@ -105,32 +123,50 @@ def best_epoch(scores, key='average_mAP'):
     return best
 
 
-def holds(entry, open_metrics, ood_threshold):
+def holds(entry, open_metrics, ood_threshold, wi=False, from_train=False, threshold_videos=None):
     """Whether an epoch's entry already holds everything asked for: the mAP, and with `open_metrics` the four lists, scored
-    with this ood_threshold."""
+    with this ood_threshold -- or, with `from_train`, with the epoch's own threshold from the training split under this
+    `threshold_videos` cap; with `wi` the "WI" list too."""
     if 'mAP' not in entry or 'average_mAP' not in entry:
         return False
-    return not open_metrics or (all(k in entry for k in OPEN_KEYS) and entry.get('ood_threshold') == ood_threshold)
+    if not open_metrics:
+        return True
+    if not all(k in entry for k in OPEN_KEYS) or (wi and 'WI' not in entry):
+        return False
+    if from_train:
+        return entry.get('ood_threshold_from') == 'train' and entry.get('ood_threshold') is not None \
+            and entry.get('threshold_videos') == threshold_videos
+    return entry.get('ood_threshold') == ood_threshold and 'ood_threshold_from' not in entry
 
 
 def merge_entry(old, new):
-    """The entry after a scoring: the old one's keys, replaced by the new one's; an ood_threshold only where the new one has it."""
-    return dict({k: v for k, v in (old or {}).items() if k != 'ood_threshold'}, **new)
+    """The entry after a scoring: the old one's keys, replaced by the new one's; an ood_threshold, where it came from and the
+    WI scored at it only where the new one has them."""
+    return dict({k: v for k, v in (old or {}).items() if k not in THRESHOLD_KEYS}, **new)
 
 
-def open_entry(metrics, ood_threshold):
-    """table_open's result as an entry's lists: NaN as None (null in the file)."""
+def open_entry(metrics, ood_threshold, wi=None, from_train=False, threshold_videos=None):
+    """table_open's result as an entry's lists: NaN as None (null in the file).  wi: table_wi's (nthr, K) array, recorded as
+    "WI", its mean over the classes per tIoU; from_train / threshold_videos: where the ood_threshold came from."""
     from ..evaluation.table_open import KEYS
     entry = {name: [None if v != v else float(v) for v in metrics[k]] for name, k in zip(OPEN_KEYS, KEYS)}
     if ood_threshold is not None:
         entry['ood_threshold'] = ood_threshold
+    if from_train:
+        entry['ood_threshold_from'] = 'train'
+        if threshold_videos is not None:
+            entry['threshold_videos'] = threshold_videos
+    if wi is not None:
+        entry['WI'] = [None if v != v else float(v) for v in np.asarray(wi, dtype=np.float64).mean(axis=1)]
     return entry
 
 
 def parse_own(argv):
-    """The driver's own arguments: (own, rest).  own['--ood_threshold'] is a float or None."""
-    own, rest = split_flags(argv, ('--random_init', '--open_metrics'),
-                            {'--gt': (1, None), '--known': (1, None), '--ood_threshold': (1, None), '--select': (1, 'average_mAP')})
+    """The driver's own arguments: (own, rest).  own['--ood_threshold'] is a float or None, own['--threshold_videos'] an int
+    or None."""
+    own, rest = split_flags(argv, ('--random_init', '--open_metrics', '--threshold_from_train', '--wi'),
+                            {'--gt': (1, None), '--known': (1, None), '--ood_threshold': (1, None), '--select': (1, 'average_mAP'),
+                             '--threshold_videos': (1, None)})
     if own['--gt'] is None or own['--known'] is None:
         raise SystemExit("score_checkpoints: --gt GT.json and --known KNOWN.txt are required")
     if own['--select'] not in SELECT_KEYS:
@@ -139,8 +175,22 @@ def parse_own(argv):
         raise SystemExit("score_checkpoints: --open_metrics belongs to the open-set protocol: add --open_set")
     if not own['--open_metrics'] and (own['--select'] in OPEN_KEYS or own['--ood_threshold'] is not None):
         raise SystemExit("score_checkpoints: --select %s and --ood_threshold need --open_metrics" % "/".join(OPEN_KEYS))
+    if not own['--open_metrics'] and (own['--threshold_from_train'] or own['--wi']):
+        raise SystemExit("score_checkpoints: --threshold_from_train and --wi need --open_metrics")
+    if own['--threshold_from_train'] and own['--ood_threshold'] is not None:
+        raise SystemExit("score_checkpoints: --threshold_from_train and a numeric --ood_threshold exclude each other")
+    if own['--threshold_videos'] is not None and not own['--threshold_from_train']:
+        raise SystemExit("score_checkpoints: --threshold_videos caps the pass of --threshold_from_train")
+    if own['--wi'] and not own['--threshold_from_train'] and own['--ood_threshold'] is None:
+        raise SystemExit("score_checkpoints: --wi needs a threshold: --ood_threshold THR or --threshold_from_train")
+    if own['--select'] == 'WI' and not own['--wi']:
+        raise SystemExit("score_checkpoints: --select WI needs --wi")
     if own['--ood_threshold'] is not None:
         own['--ood_threshold'] = float(own['--ood_threshold'])
+    if own['--threshold_videos'] is not None:
+        own['--threshold_videos'] = int(own['--threshold_videos'])
+        if own['--threshold_videos'] < 1:
+            raise SystemExit("score_checkpoints: --threshold_videos takes a positive number of videos")
     return own, rest
 
 
@@ -164,6 +214,26 @@ def epoch_tables(recipe, net, config, state, batches, dev, scoring=None):
     return tables
 
 
+def train_threshold(recipe, net, config, state, batches, dev, scoring=None):
+    """The epoch's own known / unknown operating point: the training videos through Recipe.train_table batch by batch, each
+    table's known[:n] kept (one host read per table), det_table.threshold_from_scores over their concatenation."""
+    from .det_table import threshold_from_scores
+    parts = []
+    kw = {} if scoring is None else dict(scoring=scoring)
+    with torch.no_grad():
+        for part in batches:
+            table = recipe.train_table(net, config, state, part, dev, **kw)
+            parts.append(table['known'][:int(table['n'])].clone())         # the table itself is sized for the upper bound
+    return threshold_from_scores(torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float64))
+
+
+def capped(batches, cap):
+    """The batches over the first `cap` videos only (None: all of them)."""
+    if cap is None:
+        return batches
+    return [part for part in ([p for p in part if p < cap] for part in batches) if part]
+
+
 def run(recipe, argv=None):
     """The driver.  Returns (the path of checkpoint_map.json, its content)."""
     from ..evaluation.table_ap import GroundTruth, table_ap
@@ -172,6 +242,9 @@ def run(recipe, argv=None):
     tious, argv = take_values(argv, '--tious')
     own, rest = parse_own(argv)
     open_metrics, ood_threshold, select = own['--open_metrics'], own['--ood_threshold'], own['--select']
+    from_train, cap, want_wi = own['--threshold_from_train'], own['--threshold_videos'], own['--wi']
+    if from_train and (recipe.train_videos is None or recipe.train_table is None):
+        raise SystemExit("score_checkpoints: this recipe does not list its training videos: --threshold_from_train is not served")
     if int(os.environ.get('WORLD_SIZE', 1)) > 1:
         raise SystemExit("score_checkpoints runs in one process (WORLD_SIZE > 1 is not served): start it without torchrun")
     config = C.set_config(C.get_config(rest))
@@ -182,7 +255,8 @@ def run(recipe, argv=None):
     ckpts = list_checkpoints(ckpt_dir, None if epochs is None else [int(e) for e in epochs])
     map_file = os.path.join(ckpt_dir, MAP_FILE)
     scores = read_map(map_file)
-    todo = {e: p for e, p in ckpts.items() if str(e) not in scores or not holds(scores[str(e)], open_metrics, ood_threshold)}
+    todo = {e: p for e, p in ckpts.items()
+            if str(e) not in scores or not holds(scores[str(e)], open_metrics, ood_threshold, want_wi, from_train, cap)}
     for e in ckpts:
         if e not in todo:
             print(f"epoch {e}: already in {map_file}, skipped")
@@ -193,9 +267,15 @@ def run(recipe, argv=None):
         gt = GroundTruth.load(own['--gt'], own['--known'], subset=recipe.subset, dataset=recipe.dataset, videos=names)
         net = recipe.build(config, dev)
         batches = recipe.batches(config, state)
+        if from_train:
+            _, train_state = recipe.train_videos(config)
+            train_batches = capped(recipe.batches(config, train_state), cap)
         for e, path in todo.items():
             if not own['--random_init']:
                 net.load_state_dict(torch.load(path, map_location='cpu'))
+            if from_train:
+                ood_threshold = train_threshold(recipe, net, config, train_state, train_batches, dev,
+                                                config['testing']['ood_scoring'])
             tables = epoch_tables(recipe, net, config, state, batches, dev,
                                   config['testing']['ood_scoring'] if open_metrics else None)
             ap = table_ap(tables, gt, tious)
@@ -205,8 +285,16 @@ def run(recipe, argv=None):
             if open_metrics:
                 from ..evaluation.table_open import KEYS, table_open
                 metrics = table_open(tables, gt, tious, ood_threshold)
-                entry.update(open_entry(metrics, ood_threshold))
+                wi = None
+                if want_wi:
+                    from ..evaluation.table_wi import table_wi
+                    wi = table_wi(tables, gt, tious, ood_threshold)
+                entry.update(open_entry(metrics, ood_threshold, wi, from_train, cap))
                 line += "".join(f" {name} {np.mean(metrics[k]):.4f}" for name, k in zip(OPEN_KEYS, KEYS))
+                if want_wi:
+                    line += f" WI {wi.mean():.4f}"
+                if from_train:
+                    line += f" thr {ood_threshold:.6f}"
             scores[str(e)] = merge_entry(scores.get(str(e)), entry)
             print(line)
             write_json(map_file, dict(scores, best=best_epoch(scores, select)))
