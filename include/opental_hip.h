@@ -385,6 +385,32 @@ int otal_decode_clips_ev(const float* loc, const float* prop_loc, const float* p
                          const float* offsets, const float* fps, float* seg, float* score, float* unct,
                          float* actn, unsigned char* flag, int nclips, int A, int K, float clip_length,
                          float conf_thresh, int score_fn, int first_class, int evidence, void* stream);
+/* otal_decode_clips_2s: otal_decode_clips_ev for a two-stream run (rgb + flow networks, parse_output test.py:90-108) in one
+ * launch, without the averaged maps ever being written.  loc .. prop_act: the rgb network's raw maps; flow_loc .. flow_prop_act:
+ * the flow network's, same layouts; act / prop_act / flow_act / flow_prop_act are nullable, all four together.  One priors,
+ * offsets, fps for both.  Every map value the decode reads is (rgb + flow) / 2 in fp32, taken in registers as a finished value
+ * (never contracted with the arithmetic that follows), then exactly otal_decode_clips_ev's arithmetic: seg, score, actn and
+ * flag are bit for bit what otal_decode_clips_ev writes on the maps (rgb + flow) / 2.
+ *   conf_sign   +1, or -1 for the GCPL decode: the averaged conf / prop_conf are negated (softmax(-(rgb + flow) / 2)); another
+ *               value: OTAL_E_UNSUPPORTED.
+ *   unct_in, prop_unct_in, flow_unct_in, flow_prop_unct_in: the networks' OWN uncertainty maps (nclips, A), nullable, all four
+ *               together.  Given (the output unct is then required):
+ *               unct = ((unct_in + flow_unct_in) / 2 + (prop_unct_in + flow_prop_unct_in) / 2) / 2, in that association
+ *               (parse_output :105-108, decode_predictions :122), whatever score_fn says; the uncertainty of the averaged logits
+ *               is not computed.  Not given: unct as otal_decode_clips_ev writes it (0 with score_fn 1).
+ * Checks in the order of the neighbouring entries: OTAL_E_NULL (a missing map of either network, a partial set of act or of
+ * uncertainty maps), OTAL_E_SHAPE (nclips, A, K < 1), OTAL_E_UNSUPPORTED (score_fn, first_class), OTAL_E_SHAPE (K - first_class
+ * < 1), OTAL_E_UNSUPPORTED (evidence, then conf_sign); a refused call returns before any launch and writes nothing.  An additive
+ * entry: OTAL_ABI_VERSION is unchanged. */
+int otal_decode_clips_2s(const float* loc, const float* prop_loc, const float* conf, const float* prop_conf,
+                         const float* center, const float* act, const float* prop_act, const float* flow_loc,
+                         const float* flow_prop_loc, const float* flow_conf, const float* flow_prop_conf,
+                         const float* flow_center, const float* flow_act, const float* flow_prop_act,
+                         const float* unct_in, const float* prop_unct_in, const float* flow_unct_in,
+                         const float* flow_prop_unct_in, const float* priors, const float* offsets, const float* fps,
+                         float* seg, float* score, float* unct, float* actn, unsigned char* flag, int nclips, int A, int K,
+                         float clip_length, float conf_thresh, int score_fn, int first_class, int evidence, int conf_sign,
+                         void* stream);
 /* otal_softnms_classes: for every (video, class) gather the flagged candidates of the video's clips
  * [clip_start[v], clip_start[v+1]) in clip-major / anchor-minor order and run softnms_v2
  * (AFSD/common/segment_utils.py:128-162; get_video_detections, test.py:165-200).

@@ -9,7 +9,7 @@ table, the `validation` subset of the ground truth (whose names carry no "v_"), 
 --open_metrics also AUROC, AUPR, FAR@95 and OSDR per tIoU (evaluation/table_open.py), the tables' `known` column by
 --ood_scoring; --select KEY names what "best" goes by.  --threshold_from_train takes each epoch's known / unknown threshold from a
 pass over the training videos (the list and arguments of anet/threshold.py; --threshold_videos N caps it) and --wi adds the
-Wilderness Impact at it (evaluation/table_wi.py)."""
+Wilderness Impact at it (evaluation/table_wi.py).  ActivityNet1.3 has no flow stream in this package: --fusion is refused."""
 import json
 import os
 
@@ -76,6 +76,9 @@ RECIPE = Recipe('anet', ['validation'], np.linspace(0.5, 0.95, 10), _build, _vid
 
 
 def main(argv=None):
+    import sys
+    if '--fusion' in (sys.argv[1:] if argv is None else argv):
+        raise SystemExit("score_checkpoints: ActivityNet1.3 has no flow stream (one rgb network per recipe): --fusion is not served")
     return run(RECIPE, argv)
 
 

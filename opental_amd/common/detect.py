@@ -145,6 +145,84 @@ def _decode_clips_ex(output_dict, loc, offsets, fps, clip_length, conf_thresh, u
     return dict(seg=seg, score=score, unct=unct, actn=None, flag=flag)
 
 
+_MAPS = ('loc', 'prop_loc', 'conf', 'prop_conf', 'center')
+_ACT_MAPS = ('act', 'prop_act')
+_UNCT_MAPS = ('unct', 'prop_unct')
+_PRIORS_FOUND_EQUAL = []    # (a, b, a._version, b._version) of priors tensors compared once; a network hands out ONE priors tensor
+
+
+def _same_priors(a, b):
+    """Whether two networks' priors hold the same values.  Comparing reads the device once (torch.equal), so a pair found equal
+    is remembered by identity and version: the batches of a run after the first do not synchronise with the host."""
+    if a is b:
+        return True
+    for x, y, vx, vy in _PRIORS_FOUND_EQUAL:
+        if x is a and y is b and (vx, vy) == (a._version, b._version):
+            return True
+    if a.shape != b.shape or not torch.equal(a, b):
+        return False
+    del _PRIORS_FOUND_EQUAL[:-7]        # a handful of network pairs at the most
+    _PRIORS_FOUND_EQUAL.append((a, b, a._version, b._version))
+    return True
+
+
+def decode_clips_two_stream(rgb_out, flow_out, offsets, fps, clip_length=256, conf_thresh=0.01, os_head=True, use_edl=True,
+                            evidence='exp', use_gcpl=False):
+    """decode_clips for a two-stream run, from the two networks' RAW outputs in one launch (otal_decode_clips_2s): the kernel
+    reads (rgb + flow) / 2 of every map in registers, so no averaged map is ever written.  Returns the dict of decode_clips:
+    seg, score, actn and flag are bit for bit decode_clips(fuse_outputs(rgb_out, flow_out), ...)'s; unct, with use_edl, is the
+    average of the networks' OWN uncertainty maps ((unct + prop_unct) / 2 of the fused outputs, parse_output test.py:105-108),
+    shaped like them, which both outputs must then carry.  use_gcpl: the averaged distances are negated (rpl_logits on the fused
+    maps).  Device tensors only; the head combinations decode_clips refuses are refused here, and so is a pair of outputs whose
+    map shapes or priors differ."""
+    if use_edl and evidence not in EVIDENCE:
+        raise NotImplementedError(f"evidence {evidence!r}: the decode kernel computes {', '.join(EVIDENCE)} evidence")
+    if os_head and not use_edl:
+        raise NotImplementedError("an actionness head with softmax scores is not a THUMOS14 configuration")
+    if use_gcpl and (os_head or use_edl):
+        raise NotImplementedError("use_gcpl belongs to the closed-set softmax decode of the distance head")
+    keys = _MAPS + (_ACT_MAPS if os_head else ()) + (_UNCT_MAPS if use_edl else ())
+    for k in keys + ('priors',):
+        a, b = rgb_out.get(k), flow_out.get(k)
+        if a is None or b is None:
+            raise RuntimeError(f"decode_clips_two_stream: both networks' outputs must carry '{k}'")
+        if not (a.is_cuda and b.is_cuda) or a.dtype != torch.float32 or b.dtype != torch.float32:
+            raise RuntimeError(f"decode_clips_two_stream decodes fp32 device tensors only ('{k}')")
+        if a.shape != b.shape:
+            raise RuntimeError(f"decode_clips_two_stream: '{k}' is {tuple(a.shape)} for rgb and {tuple(b.shape)} for flow")
+    if not _same_priors(rgb_out['priors'], flow_out['priors']):
+        raise RuntimeError("decode_clips_two_stream: the two networks have different priors")
+    r = {k: rgb_out[k].contiguous() for k in keys}
+    f = {k: flow_out[k].contiguous() for k in keys}
+    n, A, _ = r['loc'].shape
+    K = r['conf'].shape[-1]
+    if r['prop_loc'].shape != (n, A, 2) or r['prop_conf'].shape != (n, A, K) or \
+            any(r[k].numel() != n * A for k in keys if k not in ('loc', 'prop_loc', 'conf', 'prop_conf')):
+        raise RuntimeError("decode_clips_two_stream: the maps are not those of %d clips x %d anchors x %d logits" % (n, A, K))
+    if rgb_out['priors'].numel() != A:
+        raise RuntimeError("decode_clips_two_stream: %d priors for %d anchors" % (rgb_out['priors'].numel(), A))
+    dev = r['loc'].device
+    offs, fpst = clip_scalars(offsets, fps, n, dev)
+    if offs.numel() != n or fpst.numel() != n:
+        raise RuntimeError("decode_clips_two_stream: offsets / fps are not one per clip")
+    first = 0 if os_head else 1
+    seg = torch.empty((n, A, 2), device=dev)
+    score = torch.empty((n, K - first, A), device=dev)
+    unct = torch.empty_like(r['unct']) if use_edl else None
+    actn = torch.empty((n, A), device=dev) if os_head else None
+    flag = torch.empty((n, K - first, A), dtype=torch.uint8, device=dev)
+    opt = lambda d, k: L.ptr(d[k]) if k in d else None
+    out = lambda v: None if v is None else L.ptr(v)
+    L.check(L.lib().otal_decode_clips_2s(
+        *[L.ptr(r[k]) for k in _MAPS], opt(r, 'act'), opt(r, 'prop_act'),
+        *[L.ptr(f[k]) for k in _MAPS], opt(f, 'act'), opt(f, 'prop_act'),
+        opt(r, 'unct'), opt(r, 'prop_unct'), opt(f, 'unct'), opt(f, 'prop_unct'),
+        L.ptr(rgb_out['priors'].contiguous()), L.ptr(offs), L.ptr(fpst), L.ptr(seg), L.ptr(score), out(unct), out(actn),
+        L.ptr(flag), n, A, K, clip_length, conf_thresh, 0 if use_edl else 1, first, EVIDENCE[evidence] if use_edl else 0,
+        -1 if use_gcpl else 1, L.stream()), "otal_decode_clips_2s")
+    return dict(seg=seg, score=score, unct=unct, actn=actn, flag=flag)
+
+
 def decode_predictions(output_dict, idx, offset, sample_fps, clip_length=256, os_head=True, use_edl=True, evidence='exp',
                        use_gcpl=False):
     """Single-clip view with the reference's return values (test.py:112-140):
@@ -258,30 +336,46 @@ def windows_per_pass(batch_clips):
     return max(1, min(int(batch_clips), 32))
 
 
-def forward_windows(net, videos, clips, clip_length, batch_clips, keys, flow_net=None, flow_videos=None, **net_kwargs):
+def forward_windows(net, videos, clips, clip_length, batch_clips, keys, flow_net=None, flow_videos=None, per_stream=False,
+                    **net_kwargs):
     """The network over `clips` (enumerate_windows) in consecutive chunks of `batch_clips` windows -> its output maps named
     in `keys`, concatenated over the chunks ('priors' is the first pass's).  `flow_net` sees the same windows of
-    `flow_videos` and the two networks' raw outputs are averaged per chunk (fuse_outputs).  net_kwargs go to the forward
+    `flow_videos`; the two networks' raw outputs are averaged per chunk (fuse_outputs), or with `per_stream` kept apart and
+    returned as (rgb maps, flow maps) for a decode that reads both (decode_clips_two_stream).  net_kwargs go to the forward
     calls.  The chunking is part of the result: a forward pass of another batch size selects other conv kernels."""
     batch_clips = windows_per_pass(batch_clips)
-    outs = []
+    if per_stream and flow_net is None:
+        raise RuntimeError("forward_windows: per_stream asks for a flow network")
+    outs, flow_outs = [], []
     for i in range(0, len(clips), batch_clips):
         out = net(prepare_windows(videos, clips[i:i + batch_clips], clip_length), **net_kwargs)
         if flow_net is not None:
-            out = fuse_outputs(out, flow_net(prepare_windows(flow_videos, clips[i:i + batch_clips], clip_length), **net_kwargs))
+            flow_out = flow_net(prepare_windows(flow_videos, clips[i:i + batch_clips], clip_length), **net_kwargs)
+            if per_stream:
+                flow_outs.append(flow_out)
+            else:
+                out = fuse_outputs(out, flow_out)
         outs.append(out)
-    return {k: (torch.cat([o[k] for o in outs], 0) if k != 'priors' else outs[0][k]) for k in keys}
+    merge = lambda parts: {k: (torch.cat([o[k] for o in parts], 0) if k != 'priors' else parts[0][k]) for k in keys}
+    return (merge(outs), merge(flow_outs)) if per_stream else merge(outs)
 
 
 @torch.no_grad()
 def detect(net, videos, sample_fps, decode, keys, clip_length=256, stride=128, top_k=5000, nms_sigma=0.5, batch_clips=32,
-           flow_net=None, flow_videos=None, **net_kwargs):
+           flow_net=None, flow_videos=None, decode_two_stream=None, two_stream_decode=True, **net_kwargs):
     """videos: list of uint8 (C,T,96,96) device tensors (already centre-cropped).  Every window through the network
     (enumerate_windows, forward_windows), then decode(merged outputs, offsets, fps) -> the dict of decode_clips, then the
-    Soft-NMS launch.  Returns (rows, counts, index, dec); nothing synchronises with the host."""
+    Soft-NMS launch.  Returns (rows, counts, index, dec); nothing synchronises with the host.
+    With `flow_net` and a `decode_two_stream` callable the two networks' raw maps stay apart and
+    decode_two_stream(rgb maps, flow maps, offsets, fps) decodes them (decode_clips_two_stream: one launch, no averaged
+    copies); two_stream_decode=False, or no such callable, takes the earlier route: fuse_outputs per chunk, then `decode`."""
     clips, offsets, fps, clip_start = enumerate_windows(videos, sample_fps, clip_length, stride)
-    merged = forward_windows(net, videos, clips, clip_length, batch_clips, keys, flow_net, flow_videos, **net_kwargs)
-    dec = decode(merged, offsets, fps)
+    if flow_net is not None and decode_two_stream is not None and two_stream_decode:
+        rgb, flow = forward_windows(net, videos, clips, clip_length, batch_clips, keys, flow_net, flow_videos, True, **net_kwargs)
+        dec = decode_two_stream(rgb, flow, offsets, fps)
+    else:
+        merged = forward_windows(net, videos, clips, clip_length, batch_clips, keys, flow_net, flow_videos, **net_kwargs)
+        dec = decode(merged, offsets, fps)
     return softnms_classes(dec, clip_start, top_k, nms_sigma) + (dec,)
 
 

@@ -2,7 +2,8 @@
 
     python -m opental_amd.thumos14.score_checkpoints <yaml> [--open_set --split N] --gt GT.json --known KNOWN.txt \\
            [--epochs A B ...] [--tious ...] [--random_init] [--select KEY] \\
-           [--open_metrics [--ood_threshold THR | --threshold_from_train [--threshold_videos N]] [--wi]]
+           [--open_metrics [--ood_threshold THR | --threshold_from_train [--threshold_videos N]] [--wi]] \\
+           [--fusion --partner_checkpoint PATH --partner_data DIR [--partner_train_data DIR]]
     python -m opental_amd.anet.score_checkpoints     ... the same, with the ActivityNet defaults
 
 The network is built once; per checkpoint its state dict is loaded, the test videos go through the recipe's device pipeline
@@ -14,7 +15,16 @@ proposal dicts and no result JSON are built; the only reads from the device are 
 One line is printed per epoch and <checkpoint_path>/checkpoint_map.json holds {epoch: {"mAP": [...], "average_mAP": x}, ...,
 "best": epoch}; equal averages go to the earlier epoch, and an epoch already in the file is not scored again.  With
 --random_init the checkpoints' weights are not loaded (every listed epoch is scored with the network's own initialisation: a
-dry run of the pipeline).  One process only; two-stream fusion, the RPL / GCPL heads and OpenMax are not served.
+dry run of the pipeline).  One process only; the RPL / GCPL heads and OpenMax are not served.
+
+--fusion (THUMOS14) scores the listed epochs TOGETHER WITH one fixed checkpoint of the other stream: model.in_channels of the
+yaml says which stream the epochs under training.checkpoint_path are (3: rgb, 2: flow, with the flow yaml), the partner is
+--partner_checkpoint PATH, loaded once into a second network of the other channel count and the same head settings, and its
+videos come from --partner_data DIR (for --threshold_from_train from --partner_train_data DIR; no default is guessed).  Every
+batch goes through the recipe's two-stream pipeline (thumos14.test.detect_batch with flow_net: the two networks' raw maps in
+one decode launch) and everything after the table is what it is single-stream, all flags included.  The results go to
+<checkpoint_path>/checkpoint_map_fusion.json -- checkpoint_map.json is neither read nor written -- and every entry records its
+"partner_checkpoint": an entry made with another partner does not count as held and is scored again.
 
 --open_metrics (with --open_set) scores every epoch by AUROC, AUPR, FAR@95 and OSDR per tIoU as well, from the same tables
 (evaluation/table_open.py; their `known` column follows testing.ood_scoring / --ood_scoring), relabelling detections below
@@ -48,6 +58,8 @@ from . import config as C
 from .driver import device_setup, split_flags, write_json
 
 MAP_FILE = 'checkpoint_map.json'
+FUSION_MAP_FILE = 'checkpoint_map_fusion.json'      # --fusion: its own file, entries tied to their "partner_checkpoint"
+PARTNER_OPTIONS = ('--partner_checkpoint', '--partner_data', '--partner_train_data')
 OPEN_KEYS = ('AUROC', 'AUPR', 'FAR95', 'OSDR')      # an entry's open-set lists, in the order of table_open.KEYS
 SELECT_KEYS = ('average_mAP',) + OPEN_KEYS + ('WI',)
 LOWER_IS_BETTER = ('FAR95', 'WI')
@@ -63,12 +75,25 @@ class Recipe(object):
     0 .. len(positions)-1), its `known` column by the out-of-distribution score `scoring`.
     Optional, for --threshold_from_train: train_videos(config) -> (names, state) of the TRAINING split, which `batches` cuts
     into batches like the test split's; train_table(net, config, state, positions, dev, scoring=...) -> the same table as
-    `table`, over these videos."""
+    `table`, over these videos.
+    Optional, for --fusion: partner_build(config, dev) -> the network of the OTHER stream (the other channel count, the same
+    head settings), randomly initialised, in eval mode; fusion_table(net, partner, partner_data, config, state, positions, dev,
+    scoring=..., train=False) -> the table of the two-stream pipeline over these videos, the partner's read from the directory
+    `partner_data`; train=True: the listed stream's videos are the training split's, as train_table's."""
 
-    def __init__(self, dataset, subset, tious, build, videos, batches, table, train_videos=None, train_table=None):
+    def __init__(self, dataset, subset, tious, build, videos, batches, table, train_videos=None, train_table=None,
+                 partner_build=None, fusion_table=None):
         self.dataset, self.subset, self.tious = dataset, subset, tious
         self.build, self.videos, self.batches, self.table = build, videos, batches, table
         self.train_videos, self.train_table = train_videos, train_table
+        self.partner_build, self.fusion_table = partner_build, fusion_table
+
+    def with_partner(self, partner, partner_data, partner_train_data):
+        """This recipe with `table` / `train_table` made by the two-stream pipeline with the network `partner`."""
+        table = lambda net, *a, **kw: self.fusion_table(net, partner, partner_data, *a, **kw)
+        train_table = lambda net, *a, **kw: self.fusion_table(net, partner, partner_train_data, *a, train=True, **kw)
+        return Recipe(self.dataset, self.subset, self.tious, self.build, self.videos, self.batches, table, self.train_videos,
+                      train_table)
 
 
 def take_values(argv, flag):
@@ -123,11 +148,12 @@ def best_epoch(scores, key='average_mAP'):
     return best
 
 
-def holds(entry, open_metrics, ood_threshold, wi=False, from_train=False, threshold_videos=None):
+def holds(entry, open_metrics, ood_threshold, wi=False, from_train=False, threshold_videos=None, partner=None):
     """Whether an epoch's entry already holds everything asked for: the mAP, and with `open_metrics` the four lists, scored
     with this ood_threshold -- or, with `from_train`, with the epoch's own threshold from the training split under this
-    `threshold_videos` cap; with `wi` the "WI" list too."""
-    if 'mAP' not in entry or 'average_mAP' not in entry:
+    `threshold_videos` cap; with `wi` the "WI" list too.  partner (--fusion): the entry must have been made with this
+    partner checkpoint; without it an entry that names a partner does not count either."""
+    if 'mAP' not in entry or 'average_mAP' not in entry or entry.get('partner_checkpoint') != partner:
         return False
     if not open_metrics:
         return True
@@ -163,10 +189,25 @@ def open_entry(metrics, ood_threshold, wi=None, from_train=False, threshold_vide
 
 def parse_own(argv):
     """The driver's own arguments: (own, rest).  own['--ood_threshold'] is a float or None, own['--threshold_videos'] an int
-    or None."""
+    or None.  --fusion stays in `rest` (the config parser knows it: testing.fusion); with it own holds the PARTNER_OPTIONS."""
     own, rest = split_flags(argv, ('--random_init', '--open_metrics', '--threshold_from_train', '--wi'),
                             {'--gt': (1, None), '--known': (1, None), '--ood_threshold': (1, None), '--select': (1, 'average_mAP'),
-                             '--threshold_videos': (1, None)})
+                             '--threshold_videos': (1, None), **{name: (1, None) for name in PARTNER_OPTIONS}})
+    partner = {name: own.pop(name) for name in PARTNER_OPTIONS}
+    if '--fusion' in rest:
+        for name in PARTNER_OPTIONS[:2]:
+            if partner[name] is None:
+                raise SystemExit("score_checkpoints: --fusion needs %s: the other stream's %s (no default is guessed)"
+                                 % (name, "checkpoint" if name == '--partner_checkpoint' else "test videos"))
+        if own['--threshold_from_train'] and partner['--partner_train_data'] is None:
+            raise SystemExit("score_checkpoints: --fusion with --threshold_from_train needs --partner_train_data: the other "
+                             "stream's training videos (no default is guessed)")
+        own.update(partner)
+    else:
+        given = [name for name in PARTNER_OPTIONS if partner[name] is not None]
+        if given:
+            raise SystemExit("score_checkpoints: %s belong%s to a two-stream run: add --fusion"
+                             % (", ".join(given), "s" if len(given) == 1 else ""))
     if own['--gt'] is None or own['--known'] is None:
         raise SystemExit("score_checkpoints: --gt GT.json and --known KNOWN.txt are required")
     if own['--select'] not in SELECT_KEYS:
@@ -235,7 +276,7 @@ def capped(batches, cap):
 
 
 def run(recipe, argv=None):
-    """The driver.  Returns (the path of checkpoint_map.json, its content)."""
+    """The driver.  Returns (the path of checkpoint_map.json -- checkpoint_map_fusion.json with --fusion --, its content)."""
     from ..evaluation.table_ap import GroundTruth, table_ap
     argv = list(sys.argv[1:] if argv is None else argv)
     epochs, argv = take_values(argv, '--epochs')
@@ -248,15 +289,20 @@ def run(recipe, argv=None):
     if int(os.environ.get('WORLD_SIZE', 1)) > 1:
         raise SystemExit("score_checkpoints runs in one process (WORLD_SIZE > 1 is not served): start it without torchrun")
     config = C.set_config(C.get_config(rest))
-    if config['testing'].get('fusion', False) or config['model'].get('use_rpl', False):
-        raise SystemExit("score_checkpoints: two-stream fusion and the RPL / GCPL heads are not served")
+    fusion = bool(config['testing'].get('fusion', False))
+    if config['model'].get('use_rpl', False):
+        raise SystemExit("score_checkpoints: the RPL / GCPL heads are not served")
+    if fusion and (recipe.partner_build is None or recipe.fusion_table is None):
+        raise SystemExit("score_checkpoints: this recipe has no second stream: --fusion is not served")
+    partner_path = own['--partner_checkpoint'] if fusion else None
     tious = np.asarray(recipe.tious if tious is None else [float(t) for t in tious], dtype=np.float64)
     ckpt_dir = config['training']['checkpoint_path']
     ckpts = list_checkpoints(ckpt_dir, None if epochs is None else [int(e) for e in epochs])
-    map_file = os.path.join(ckpt_dir, MAP_FILE)
+    map_file = os.path.join(ckpt_dir, FUSION_MAP_FILE if fusion else MAP_FILE)
     scores = read_map(map_file)
     todo = {e: p for e, p in ckpts.items()
-            if str(e) not in scores or not holds(scores[str(e)], open_metrics, ood_threshold, want_wi, from_train, cap)}
+            if str(e) not in scores or not holds(scores[str(e)], open_metrics, ood_threshold, want_wi, from_train, cap,
+                                                 partner_path)}
     for e in ckpts:
         if e not in todo:
             print(f"epoch {e}: already in {map_file}, skipped")
@@ -266,6 +312,11 @@ def run(recipe, argv=None):
         names, state = recipe.videos(config)
         gt = GroundTruth.load(own['--gt'], own['--known'], subset=recipe.subset, dataset=recipe.dataset, videos=names)
         net = recipe.build(config, dev)
+        if fusion:
+            partner = recipe.partner_build(config, dev)
+            if not own['--random_init']:
+                partner.load_state_dict(torch.load(partner_path, map_location='cpu'))
+            recipe = recipe.with_partner(partner, own['--partner_data'], own['--partner_train_data'])
         batches = recipe.batches(config, state)
         if from_train:
             _, train_state = recipe.train_videos(config)
@@ -295,7 +346,12 @@ def run(recipe, argv=None):
                     line += f" WI {wi.mean():.4f}"
                 if from_train:
                     line += f" thr {ood_threshold:.6f}"
-            scores[str(e)] = merge_entry(scores.get(str(e)), entry)
+            old = scores.get(str(e))
+            if fusion:
+                entry['partner_checkpoint'] = partner_path
+                if old is not None and old.get('partner_checkpoint') != partner_path:
+                    old = None                  # scored with another partner: nothing of it carries over
+            scores[str(e)] = merge_entry(old, entry)
             print(line)
             write_json(map_file, dict(scores, best=best_epoch(scores, select)))
     result = dict(scores, best=best_epoch(scores, select))

@@ -32,18 +32,25 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v,
 // The late-fusion segment rule of every decode kernel (decode_predictions, AFSD/thumos14/test.py:114-120; anet/test.py:110-115):
 // the refined offsets scale with the coarse width, the segment is clamped to the clip and leaves in seconds.  Anchor i of
 // clip c is row n = c * A + i of loc, prop_loc and seg (n, 2); priors (A) are centres in [0, 1]; offsets and fps are per clip.
-__device__ __forceinline__ void decode_segment(const float* loc, const float* prop_loc, const float* priors,
+// The rule is stated once, on the four map values of the anchor (l0, l1 of loc, p0, p1 of prop_loc): the kernels that read them
+// straight from memory use the pointer form below, the two-stream decode hands in the finished averages of two networks' maps.
+__device__ __forceinline__ void decode_segment(float l0, float l1, float p0, float p1, const float* priors,
                                                const float* offsets, const float* fps, float* seg, size_t n, int i, int c,
                                                float clip_length) {
-    const float l0 = loc[n * 2], l1 = loc[n * 2 + 1];
     const float w = l0 + l1;
-    const float r0 = 0.5f * w * prop_loc[n * 2] + l0;
-    const float r1 = 0.5f * w * prop_loc[n * 2 + 1] + l1;
+    const float r0 = 0.5f * w * p0 + l0;
+    const float r1 = 0.5f * w * p1 + l1;
     const float pc = priors[i] * clip_length;
     const float s0 = fminf(fmaxf(pc - r0, 0.f), clip_length);
     const float s1 = fminf(fmaxf(pc + r1, 0.f), clip_length);
     seg[n * 2] = (s0 + offsets[c]) / fps[c];
     seg[n * 2 + 1] = (s1 + offsets[c]) / fps[c];
+}
+__device__ __forceinline__ void decode_segment(const float* loc, const float* prop_loc, const float* priors,
+                                               const float* offsets, const float* fps, float* seg, size_t n, int i, int c,
+                                               float clip_length) {
+    decode_segment(loc[n * 2], loc[n * 2 + 1], prop_loc[n * 2], prop_loc[n * 2 + 1], priors, offsets, fps, seg, n, i, c,
+                   clip_length);
 }
 
 static inline int otal_launch_status() {

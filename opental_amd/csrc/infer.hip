@@ -5,6 +5,7 @@
 //   otal_decode_clips_ex: the same with the score function (Dirichlet / softmax), the background class and the
 //                         actionness heads chosen by the caller -- the closed-set Softmax and EDL baselines;
 //   otal_decode_clips_ev: the same with the evidence function of the Dirichlet scores (exp / relu / softplus, csrc/evidence.h);
+//   otal_decode_clips_2s: otal_decode_clips_ev on the average of two networks' raw maps (rgb + flow), taken in registers;
 //   otal_softnms_classes: per (video, class) gather of the surviving candidates in the reference's
 //                         order (clip-major, anchor-minor) followed by Gaussian Soft-NMS
 //                         (softnms_v2, AFSD/common/segment_utils.py:128-162) -- one workgroup per
@@ -27,6 +28,32 @@ constexpr int NMS_THREADS = 256;
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// The second network of a two-stream decode (otal_decode_clips_2s), by value in the kernel arguments; empty single-stream.
+//   loc .. prop_act: the flow network's maps, laid out as the rgb network's (act / prop_act NULL with the rgb ones);
+//   unct .. flow_prop_unct: BOTH networks' own uncertainty maps (clip, A), all four or none;
+//   conf_sign: +1, or -1 for the GCPL decode (the averaged conf / prop_conf negated).
+struct FlowMaps {
+    const float *loc, *prop_loc, *conf, *prop_conf, *center, *act, *prop_act;
+    const float *unct, *prop_unct, *flow_unct, *flow_prop_unct;
+    float conf_sign;
+};
+
+// (a + b) / 2 as a FINISHED fp32 value: never contracted with the arithmetic that reads it, whatever -ffp-contract the file is
+// built with (0.5f * w * prop + (a + b) * 0.5f as fma(a + b, 0.5f, 0.5f * w * prop) would round differently from the decode of
+// the averaged map).  Halving is exact, so this is the fp32 sum of the two maps, halved: what (rgb + flow) / 2.0 gives in torch.
+__device__ __forceinline__ float avg2(float a, float b) {
+#pragma clang fp contract(off)
+    const float s = a + b;
+    return s * 0.5f;
+}
+
+// The one loader of the decode kernel's map values: element j of the map, or of the two networks' averaged map.
+template <bool TWO>
+__device__ __forceinline__ float ld_map(const float* a, const float* b, size_t j) {
+    if constexpr (TWO) return avg2(a[j], b[j]);
+    else return a[j];
+}
+
 // one workgroup per clip; A anchors, K logits per anchor.  Outputs: seg (clip,A,2) seconds; score (clip,K-first_class,A);
 // unct (clip,A); actn (clip,A); flag (clip,K-first_class,A) uint8.
 // SOFTMAX false: Dirichlet mean with exp evidence (BDNet.py DirichletLayer); true: softmax, exp(z - max) / sum (nn.Softmax).
@@ -34,55 +61,71 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf
 // no actionness factor and flag = score > conf_thresh.  unct / actn NULL: not written; with SOFTMAX or without act the
 // absent quantity is written as 0.  EV (SOFTMAX false): alpha = evidence(z) + 1 of csrc/evidence.h with the caller's evidence kind;
 // false is the exp code as it was.
-template <bool SOFTMAX, bool EV = false>
+// TWO: every map value is ld_map's average of the map and its FlowMaps partner (conf / prop_conf times conf_sign), and with the
+// four uncertainty maps unct = ((unct + flow_unct) / 2 + (prop_unct + flow_prop_unct) / 2) / 2 instead of the derived value.
+template <bool SOFTMAX, bool EV = false, bool TWO = false>
 __global__ __launch_bounds__(128) void decode_clips_kernel(
         const float* __restrict__ loc, const float* __restrict__ prop_loc, const float* __restrict__ priors,
         const float* __restrict__ conf, const float* __restrict__ prop_conf, const float* __restrict__ center,
         const float* __restrict__ act, const float* __restrict__ prop_act, const float* __restrict__ offsets,
         const float* __restrict__ fps, float* __restrict__ seg, float* __restrict__ score, float* __restrict__ unct,
         float* __restrict__ actn, unsigned char* __restrict__ flag, int A, int K, float clip_length,
-        float conf_thresh, int first_class, int evidence) {
+        float conf_thresh, int first_class, int evidence, const FlowMaps f) {
     const int c = blockIdx.x;
     const int KO = K - first_class;
     const bool has_act = act != nullptr;
     for (int i = threadIdx.x; i < A; i += blockDim.x) {
         const size_t ai = (size_t)c * A + i;
         // decode_predictions (test.py:114-120)
-        decode_segment(loc, prop_loc, priors, offsets, fps, seg, ai, i, c, clip_length);
-        const float* cf = conf + ai * K;
-        const float* pf = prop_conf + ai * K;
+        decode_segment(ld_map<TWO>(loc, f.loc, ai * 2), ld_map<TWO>(loc, f.loc, ai * 2 + 1),
+                       ld_map<TWO>(prop_loc, f.prop_loc, ai * 2), ld_map<TWO>(prop_loc, f.prop_loc, ai * 2 + 1), priors, offsets,
+                       fps, seg, ai, i, c, clip_length);
+        const auto cf = [&](int k) {             // logit k of the anchor's conf row, pf: of its prop_conf row
+            const float z = ld_map<TWO>(conf, f.conf, ai * K + k);
+            if constexpr (TWO) return z * f.conf_sign; else return z;
+        };
+        const auto pf = [&](int k) {
+            const float z = ld_map<TWO>(prop_conf, f.prop_conf, ai * K + k);
+            if constexpr (TWO) return z * f.conf_sign; else return z;
+        };
         float S = 0.f, PS = 0.f, M = 0.f, PM = 0.f;
         if constexpr (SOFTMAX) {
-            M = cf[0]; PM = pf[0];
-            for (int k = 1; k < K; ++k) { M = fmaxf(M, cf[k]); PM = fmaxf(PM, pf[k]); }
-            for (int k = 0; k < K; ++k) { S += expf(cf[k] - M); PS += expf(pf[k] - PM); }
+            M = cf(0); PM = pf(0);
+            for (int k = 1; k < K; ++k) { M = fmaxf(M, cf(k)); PM = fmaxf(PM, pf(k)); }
+            for (int k = 0; k < K; ++k) { S += expf(cf(k) - M); PS += expf(pf(k) - PM); }
         } else if constexpr (EV) {
             for (int k = 0; k < K; ++k) {
-                S += otal_ev::alpha(cf[k], evidence);
-                PS += otal_ev::alpha(pf[k], evidence);
+                S += otal_ev::alpha(cf(k), evidence);
+                PS += otal_ev::alpha(pf(k), evidence);
             }
         } else {
             // Dirichlet mean + uncertainty (BDNet.py:538-561), evidence = exp(clamp(logit, +-10))
             for (int k = 0; k < K; ++k) {
-                S += expf(fminf(fmaxf(cf[k], -10.f), 10.f)) + 1.0f;
-                PS += expf(fminf(fmaxf(pf[k], -10.f), 10.f)) + 1.0f;
+                S += expf(fminf(fmaxf(cf(k), -10.f), 10.f)) + 1.0f;
+                PS += expf(fminf(fmaxf(pf(k), -10.f), 10.f)) + 1.0f;
             }
         }
-        const float an = has_act ? (sigmoidf_(act[ai]) + sigmoidf_(prop_act[ai])) / 2.0f : 0.f;
-        const float ct = sigmoidf_(center[ai]);
-        if (unct) unct[ai] = SOFTMAX ? 0.f : ((float)K / S + (float)K / PS) / 2.0f;
+        const float an =
+            has_act ? (sigmoidf_(ld_map<TWO>(act, f.act, ai)) + sigmoidf_(ld_map<TWO>(prop_act, f.prop_act, ai))) / 2.0f : 0.f;
+        const float ct = sigmoidf_(ld_map<TWO>(center, f.center, ai));
+        bool own_unct = false;          // the networks' own uncertainty maps stand in for the one derived from the logits
+        if constexpr (TWO) own_unct = f.unct != nullptr;
+        if (unct) {
+            if (own_unct) unct[ai] = avg2(avg2(f.unct[ai], f.flow_unct[ai]), avg2(f.prop_unct[ai], f.flow_prop_unct[ai]));
+            else unct[ai] = SOFTMAX ? 0.f : ((float)K / S + (float)K / PS) / 2.0f;
+        }
         if (actn) actn[ai] = an;
         for (int k = first_class; k < K; ++k) {
             float a0, a1;
             if constexpr (SOFTMAX) {
-                a0 = expf(cf[k] - M) / S;
-                a1 = expf(pf[k] - PM) / PS;
+                a0 = expf(cf(k) - M) / S;
+                a1 = expf(pf(k) - PM) / PS;
             } else if constexpr (EV) {
-                a0 = otal_ev::alpha(cf[k], evidence) / S;
-                a1 = otal_ev::alpha(pf[k], evidence) / PS;
+                a0 = otal_ev::alpha(cf(k), evidence) / S;
+                a1 = otal_ev::alpha(pf(k), evidence) / PS;
             } else {
-                a0 = (expf(fminf(fmaxf(cf[k], -10.f), 10.f)) + 1.0f) / S;
-                a1 = (expf(fminf(fmaxf(pf[k], -10.f), 10.f)) + 1.0f) / PS;
+                a0 = (expf(fminf(fmaxf(cf(k), -10.f), 10.f)) + 1.0f) / S;
+                a1 = (expf(fminf(fmaxf(pf(k), -10.f), 10.f)) + 1.0f) / PS;
             }
             const size_t o = ((size_t)c * KO + (k - first_class)) * A + i;
             if (has_act) {
@@ -256,30 +299,54 @@ __global__ __launch_bounds__(NMS_THREADS) void softnms_classes_kernel(
 }  // namespace
 
 namespace {
+template <bool TWO>
+void launch_decode_clips(const float* loc, const float* prop_loc, const float* priors, const float* conf, const float* prop_conf,
+                         const float* center, const float* act, const float* prop_act, const float* offsets, const float* fps,
+                         float* seg, float* score, float* unct, float* actn, unsigned char* flag, int nclips, int A, int K,
+                         float clip_length, float conf_thresh, int score_fn, int first_class, bool ev, int evidence,
+                         const FlowMaps& flow, void* stream) {
+    if (score_fn == 1)
+        hipLaunchKernelGGL((decode_clips_kernel<true, false, TWO>), dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc,
+                           priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
+                           clip_length, conf_thresh, first_class, 0, flow);
+    else if (ev)
+        hipLaunchKernelGGL((decode_clips_kernel<false, true, TWO>), dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc,
+                           priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
+                           clip_length, conf_thresh, first_class, evidence, flow);
+    else if constexpr (!TWO)        // the two-stream entry takes an evidence kind: it has no use for the exp-only instantiation
+        hipLaunchKernelGGL((decode_clips_kernel<false, false, TWO>), dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc,
+                           prop_loc, priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A,
+                           K, clip_length, conf_thresh, first_class, 0, flow);
+}
+
+// two: the second network of otal_decode_clips_2s (with its conf_sign as the caller gave it), NULL for the single-stream entries
 int decode_clips_entry(const float* loc, const float* prop_loc, const float* priors, const float* conf,
                                     const float* prop_conf, const float* center, const float* act,
                                     const float* prop_act, const float* offsets, const float* fps, float* seg,
                                     float* score, float* unct, float* actn, unsigned char* flag, int nclips, int A,
                                     int K, float clip_length, float conf_thresh, int score_fn, int first_class,
-                                    bool ev, int evidence, void* stream) {
+                                    bool ev, int evidence, void* stream, const FlowMaps* two = nullptr, int conf_sign = 1) {
     if (!loc || !prop_loc || !priors || !conf || !prop_conf || !center || (!act) != (!prop_act) || !offsets || !fps ||
         !seg || !score || !flag) return OTAL_E_NULL;
+    if (two) {
+        if (!two->loc || !two->prop_loc || !two->conf || !two->prop_conf || !two->center || (!two->act) != (!act) ||
+            (!two->prop_act) != (!act)) return OTAL_E_NULL;
+        const int given = !!two->unct + !!two->prop_unct + !!two->flow_unct + !!two->flow_prop_unct;
+        if ((given != 0 && given != 4) || (given == 4 && !unct)) return OTAL_E_NULL;
+    }
     if (nclips <= 0 || A <= 0 || K <= 0) return OTAL_E_SHAPE;
     if (score_fn < 0 || score_fn > 1 || first_class < 0 || first_class > 1) return OTAL_E_UNSUPPORTED;
     if (K - first_class <= 0) return OTAL_E_SHAPE;
     if (ev && (evidence < 0 || evidence >= otal_ev::EV_KINDS)) return OTAL_E_UNSUPPORTED;
-    if (score_fn == 1)
-        hipLaunchKernelGGL(decode_clips_kernel<true>, dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc, priors,
-                           conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
-                           clip_length, conf_thresh, first_class, 0);
-    else if (ev)
-        hipLaunchKernelGGL((decode_clips_kernel<false, true>), dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc,
-                           priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
-                           clip_length, conf_thresh, first_class, evidence);
+    if (conf_sign != 1 && conf_sign != -1) return OTAL_E_UNSUPPORTED;
+    if (two)
+        launch_decode_clips<true>(loc, prop_loc, priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct,
+                                  actn, flag, nclips, A, K, clip_length, conf_thresh, score_fn, first_class, ev, evidence, *two,
+                                  stream);
     else
-        hipLaunchKernelGGL(decode_clips_kernel<false>, dim3(nclips), dim3(128), 0, (hipStream_t)stream, loc, prop_loc, priors,
-                           conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn, flag, A, K,
-                           clip_length, conf_thresh, first_class, 0);
+        launch_decode_clips<false>(loc, prop_loc, priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct,
+                                   actn, flag, nclips, A, K, clip_length, conf_thresh, score_fn, first_class, ev, evidence,
+                                   FlowMaps{}, stream);
     return otal_launch_status();
 }
 }  // namespace
@@ -304,6 +371,24 @@ extern "C" int otal_decode_clips_ev(const float* loc, const float* prop_loc, con
                                     int evidence, void* stream) {
     return decode_clips_entry(loc, prop_loc, priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn,
                               flag, nclips, A, K, clip_length, conf_thresh, score_fn, first_class, true, evidence, stream);
+}
+
+// otal_decode_clips_ev for two networks: every map value the decode reads is (rgb + flow) / 2 in fp32, taken in registers (ld_map),
+// so seg, score, actn and flag are bit for bit otal_decode_clips_ev's on the averaged maps; see include/opental_hip.h.
+extern "C" int otal_decode_clips_2s(const float* loc, const float* prop_loc, const float* conf, const float* prop_conf,
+                                    const float* center, const float* act, const float* prop_act, const float* flow_loc,
+                                    const float* flow_prop_loc, const float* flow_conf, const float* flow_prop_conf,
+                                    const float* flow_center, const float* flow_act, const float* flow_prop_act,
+                                    const float* unct_in, const float* prop_unct_in, const float* flow_unct_in,
+                                    const float* flow_prop_unct_in, const float* priors, const float* offsets,
+                                    const float* fps, float* seg, float* score, float* unct, float* actn,
+                                    unsigned char* flag, int nclips, int A, int K, float clip_length, float conf_thresh,
+                                    int score_fn, int first_class, int evidence, int conf_sign, void* stream) {
+    const FlowMaps flow = {flow_loc, flow_prop_loc, flow_conf, flow_prop_conf, flow_center, flow_act, flow_prop_act,
+                           unct_in, prop_unct_in, flow_unct_in, flow_prop_unct_in, (float)conf_sign};
+    return decode_clips_entry(loc, prop_loc, priors, conf, prop_conf, center, act, prop_act, offsets, fps, seg, score, unct, actn,
+                              flag, nclips, A, K, clip_length, conf_thresh, score_fn, first_class, true, evidence, stream, &flow,
+                              conf_sign);
 }
 
 extern "C" int otal_decode_clips(const float* loc, const float* prop_loc, const float* priors, const float* conf,

@@ -10,8 +10,8 @@ imported here under the names it has always had in this module.
 """
 import torch
 
-from ..common.detect import (OOD_SCORES, _decode_clips_ex, decode_clips, decode_predictions, detect, filtering,  # noqa: F401
-                             fuse_outputs, gather_results, get_offsets, get_video_detections, head_mode, ood_threshold,
+from ..common.detect import (OOD_SCORES, _decode_clips_ex, decode_clips, decode_clips_two_stream,  # noqa: F401
+                             decode_predictions, detect, filtering, fuse_outputs, gather_results, get_offsets, get_video_detections, head_mode, ood_threshold,
                              prepare_data, prepare_windows, results_json, rpl_logits, softnms_classes)
 
 
@@ -34,11 +34,14 @@ def rpl_flags(config):
 
 
 def detect_batch(net, videos, sample_fps, clip_length=256, stride=128, conf_thresh=0.01, top_k=5000, nms_sigma=0.5,
-                 batch_clips=32, flow_net=None, flow_videos=None):
+                 batch_clips=32, flow_net=None, flow_videos=None, two_stream_decode=True):
     """videos: list of uint8 (C,T,96,96) device tensors (already centre-cropped).  Returns the
     per-video rows/counts of Soft-NMS.  test.py:203-252 without the JSON dump.
     Two-stream runs (`--fusion`, test.py:227-240 + parse_output :90-108): `flow_net` sees the same windows of
-    `flow_videos` (2-channel optical flow) and the two networks' RAW outputs are averaged before decoding."""
+    `flow_videos` (2-channel optical flow) and the two networks' RAW outputs are averaged before decoding -- inside the decode
+    launch (decode_clips_two_stream: the raw maps of both networks go in, no averaged copy is written).
+    two_stream_decode=False: the earlier route with the same results (torch.equal rows, counts, index and dec) -- fuse_outputs
+    per chunk of windows, decode_clips on the averaged maps, the uncertainty substituted afterwards."""
     if (flow_net is None) != (flow_videos is None):
         raise RuntimeError("detect_batch: flow_net and flow_videos go together")
     os_head, use_edl, evidence = head_mode(net)
@@ -48,16 +51,22 @@ def detect_batch(net, videos, sample_fps, clip_length=256, stride=128, conf_thre
     keys = ('loc', 'conf', 'prop_loc', 'prop_conf', 'center', 'priors') + (('act', 'prop_act') if os_head else ()) + \
         (('unct', 'prop_unct') if flow_net is not None and use_edl else ())
 
+    use_gcpl = bool(getattr(net, 'use_gcpl', False))
+
     def decode(merged, offsets, fps):
         dec = decode_clips(merged, offsets, fps, clip_length, conf_thresh, os_head=os_head, use_edl=use_edl,
-                           evidence=evidence, use_gcpl=bool(getattr(net, 'use_gcpl', False)))
+                           evidence=evidence, use_gcpl=use_gcpl)
         if flow_net is not None and use_edl:
             # the decode kernel derives the uncertainty from the (fused) logits; the reference averages the two networks'
             # OWN uncertainties instead (parse_output :105-108, decode_predictions :122) -- not the same number
             dec['unct'] = ((merged['unct'] + merged['prop_unct']) / 2.0).contiguous()
         return dec
+
+    def decode_two_stream(rgb, flow, offsets, fps):         # the same, from the two networks' raw maps in one launch
+        return decode_clips_two_stream(rgb, flow, offsets, fps, clip_length, conf_thresh, os_head=os_head, use_edl=use_edl,
+                                       evidence=evidence, use_gcpl=use_gcpl)
     return detect(net, videos, sample_fps, decode, keys, clip_length, stride, top_k, nms_sigma, batch_clips, flow_net,
-                  flow_videos)
+                  flow_videos, decode_two_stream, two_stream_decode)
 
 
 def test(net, video_infos, npy_data_path, idx_to_class=None, clip_length=256, stride=128, crop_size=96, conf_thresh=0.01,
