@@ -636,6 +636,25 @@ int otal_adam_flat_dev(float* p, const float* g, float* m, float* v, int64_t n, 
                        float beta2, float eps, float weight_decay, const float* bias_corr, float grad_scale,
                        void* stream);
 
+/* Global L2 norm of the flat gradient and the coefficient torch.nn.utils.clip_grad_norm_ would scale it by, on the device
+ * (the reference's per-step `stats/grad_norm` scalar and its clip line, AFSD/thumos14/train.py:134-141,:248-250):
+ *   out[0] = float( sqrt( sum_i (double)g[i]^2 ) * (double)grad_scale )
+ *   out[1] = max_norm <= 0 ? 1.0f : min(c, 1.0f) with c = (1.0f / (out[0] + 1e-6f)) * max_norm in float32 -- torch's
+ *            `max_norm / (total_norm + 1e-6)` is reciprocal() * max_norm -- and a NaN c kept (torch's clamp keeps it).
+ * fp64 accumulation, a grid and a reduction order that depend on n alone: the same bits on every run and every rank.
+ * Two launches (per-block partial sums, then one block that folds them).  `partials` is a caller-owned workspace of
+ * OTAL_GRAD_NORM_PARTIALS doubles (16 KB), 8-byte aligned, private to the stream while the call is in flight.
+ * Null pointers: OTAL_E_NULL; n <= 0: OTAL_E_SHAPE, both before any launch.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+#define OTAL_GRAD_NORM_PARTIALS 2048
+int otal_grad_norm(const float* g, int64_t n, float grad_scale, float max_norm, double* partials, float* out, void* stream);
+
+/* otal_adam_flat_dev with the gradient clipped by its global norm: norm_coef points at otal_grad_norm's `out`, and the
+ * update uses gi = (g * grad_scale) * norm_coef[1] + weight_decay * p.  With norm_coef[1] == 1.0f the result is
+ * bit-identical to otal_adam_flat_dev.  Return codes as otal_adam_flat_dev.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_adam_flat_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, const float* bias_corr, float grad_scale, const float* norm_coef,
+                        void* stream);
+
 /* MultiSegmentLoss + EvidenceLoss ('log', exp evidence, IBM re-weighting, IoU calibration) + ActionnessLoss (PU BCE,
  * rank weight 0) of the OpenTAL final recipe, forward AND backward in one single-workgroup launch.
  * Replaces AFSD/thumos14/multisegment_loss.py:92-259, cls_loss.py:120-129,:132-168,:212-278,:288-339 and their autograd

@@ -96,7 +96,8 @@ def main(argv=None):
     """python -m opental_amd.anet.train configs/anet_opental.yaml --open_set --split 0 --lw 1 --cw 1 --piou 0.6 [--resume N]
 
     The reference's command line (AFSD/anet/README.md:61; AFSD/common/config.py:10-37) plus --random_init, --save_after N,
-    --max_steps N, --launch lanes|eager as in opental_amd.thumos14.train.  One process per GPU; under torchrun the ranks all-reduce gradients
+    --max_steps N, --log_every N, --launch lanes|eager, --log_grad_norm and --clip_grad_norm X as in opental_amd.thumos14.train
+    (the reference logs `stats/grad_norm` per step and carries the clip line switched off, anet/train.py:126,:234-236).  One process per GPU; under torchrun the ranks all-reduce gradients
     over RCCL (DetectorTrainer).  The epoch loop is thumos14.train.run_one_epoch: same batches-by-permutation sampler,
     ssl branch when the first sample's splice succeeded (`if flags[0]`, anet/train.py:223), device-side loss sums."""
     import os
@@ -106,15 +107,19 @@ def main(argv=None):
     from ..common import config as C
     from ..common import ops
     from ..common.thumos_dataset import ClipStager, max_target_count
-    from ..thumos14.train import run_one_epoch, set_seed
+    from ..thumos14.train import make_step_log, run_one_epoch, set_seed, take_grad_norm_flag
     argv = list(sys.argv[1:] if argv is None else argv)
-    extra = {'random_init': False, 'save_after': 10, 'max_steps': None, 'launch': 'lanes'}
+    extra = {'random_init': False, 'save_after': 10, 'max_steps': None, 'launch': 'lanes', 'log_every': 0,
+             'clip_grad_norm': None, 'log_grad_norm': False}
     rest, i = [], 0
     while i < len(argv):
         a = argv[i]
-        if a == '--random_init':
+        j = take_grad_norm_flag(argv, i, extra)
+        if j is not None:
+            i = j
+        elif a == '--random_init':
             extra['random_init'] = True
-        elif a in ('--save_after', '--max_steps'):
+        elif a in ('--save_after', '--max_steps', '--log_every'):
             extra[a[2:]] = int(argv[i + 1]); i += 1
         elif a == '--launch':
             extra['launch'] = argv[i + 1]; i += 1
@@ -134,7 +139,8 @@ def main(argv=None):
         dist.init_process_group(backend='nccl', device_id=dev)
     ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
     set_seed(tr['random_seed'])
-    net, crit, trainer = build_training(config, dev, extra['random_init'])
+    net, crit, trainer = build_training(config, dev, extra['random_init'], clip_grad_norm=extra['clip_grad_norm'],
+                                        track_grad_norm=extra['log_grad_norm'])
     ds = config['dataset']['training']
     dataset = D.ANET_Dataset(ds['video_info_path'], ds['video_mp4_path'], ds['clip_length'], ds['crop_size'], ds['clip_stride'],
                              channels=config['model']['in_channels'], binary_class=config['dataset']['num_classes'] == 2)
@@ -154,12 +160,15 @@ def main(argv=None):
         print(f"batch size: {tr['batch_size']}  learning rate: {tr['learning_rate']} (backbone x0.1)  weight decay: {tr['weight_decay']}  "
               f"max epoch: {tr['max_epoch']}  cls loss: {crit.cls_loss_type}  clips: {len(dataset)}  ranks: {world}  resume: {tr['resume']}")
     history = []
+    step_log = None
+    if extra['log_every'] > 0 and rank == 0:
+        step_log = make_step_log(extra['log_every'], train_state_path, with_norm=extra['log_grad_norm'])
     for epoch in range(start_epoch, tr['max_epoch'] + 1):
         if crit.cls_loss_type == 'edl':
             crit.cls_loss.epoch = epoch
             crit.cls_loss.total_epoch = tr['max_epoch']
         v = run_one_epoch(epoch, trainer, dataset, stager, tr['batch_size'], rank, world, extra['max_steps'],
-                          log=print if rank == 0 else (lambda *a: None))
+                          log=print if rank == 0 else (lambda *a: None), step_log=step_log)
         history.append(v)
         if epoch > extra['save_after'] and rank == 0:
             trainer.save_model(epoch, checkpoint_path, train_state_path)

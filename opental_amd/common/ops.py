@@ -1417,6 +1417,29 @@ def adam_flat_dev(p, g, m, v, bias_corr, lr, beta1=0.9, beta2=0.999, eps=1e-8, w
                                        weight_decay, L.ptr(bias_corr), grad_scale, L.stream()), "otal_adam_flat_dev")
 
 
+GRAD_NORM_PARTIALS = 2048       # OTAL_GRAD_NORM_PARTIALS of include/opental_hip.h: float64 elements of grad_norm's workspace
+
+
+def grad_norm(g, grad_scale, max_norm, out, partials):
+    """out (2 float32) <- {||g * grad_scale||_2, clip coefficient for max_norm} without leaving the device (the rule:
+    common/grad_clip.py); max_norm None or <= 0: the norm only, coefficient 1.  partials: GRAD_NORM_PARTIALS float64."""
+    L.require_device(g, out, partials)
+    if g.dtype != torch.float32 or out.dtype != torch.float32 or out.numel() < 2 or \
+            partials.dtype != torch.float64 or partials.numel() < GRAD_NORM_PARTIALS:
+        raise RuntimeError("grad_norm: g float32, out 2 float32, partials GRAD_NORM_PARTIALS float64")
+    L.check(L.lib().otal_grad_norm(L.ptr(g), g.numel(), grad_scale, 0.0 if max_norm is None else max_norm,
+                                   L.ptr(partials), L.ptr(out), L.stream()), "otal_grad_norm")
+    return out
+
+
+def adam_flat_clip(p, g, m, v, bias_corr, norm_coef, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0):
+    """adam_flat_dev on the gradient scaled by norm_coef[1], the coefficient grad_norm left in device memory."""
+    L.require_device(p, g, m, v, bias_corr, norm_coef)
+    L.check(L.lib().otal_adam_flat_clip(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), lr, beta1, beta2, eps,
+                                        weight_decay, L.ptr(bias_corr), grad_scale, L.ptr(norm_coef), L.stream()),
+            "otal_adam_flat_clip")
+
+
 # ----------------------------------------------------------------------------- fused detection loss
 EVIDENCE = {'exp': 0, 'relu': 1, 'softplus': 2}         # the evidence kinds and loss types of csrc/evidence.h, by their yaml names
 LOSS_TYPE = {'log': 0, 'digamma': 1, 'mse': 2}

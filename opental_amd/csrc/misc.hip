@@ -46,9 +46,13 @@ __global__ __launch_bounds__(256) void proposal_windows_kernel(const float* __re
 // torch.optim.Adam (L2 weight decay folded into the gradient, reference AFSD/thumos14/train.py:321-323)
 // over ONE flat parameter arena: p, g, m, v are parallel fp32 arrays of n elements.
 // one element of the update (the arithmetic of torch.optim.Adam's single-tensor path, see the header comment above)
+// CLIP: the scaled gradient is multiplied by the global-norm clip coefficient first (torch.nn.utils.clip_grad_norm_ scales
+// .grad before the optimizer reads it); coef == 1.0f leaves every bit as it is without CLIP.
+template <bool CLIP>
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float wd,
-                                         float bc1, float bc2_sqrt, float grad_scale) {
+                                         float bc1, float bc2_sqrt, float grad_scale, float coef) {
     float gi = g * grad_scale;
+    if (CLIP) gi = gi * coef;
     gi = gi + wd * p;
     const float mi = m + (gi - m) * (1.0f - b1);             // lerp form used by torch
     const float vi = v * b2 + (1.0f - b2) * gi * gi;
@@ -60,9 +64,10 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
 // The flat update streams 7 floats per parameter (4 read, 3 written).  One dword per lane and trip kept the kernel at
 // 3.3 TB/s (26 dependent trips of four 4-byte loads per thread); 16-byte accesses: the same values from a quarter of the
 // memory instructions and trips.  `n4` vectors when the four arrays are 16-byte aligned, the tail element-wise.
+template <bool CLIP>
 __device__ __forceinline__ void adam_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                            float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-                                           float bc1, float bc2_sqrt, float grad_scale) {
+                                           float bc1, float bc2_sqrt, float grad_scale, float coef) {
     const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
     const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                        reinterpret_cast<uintptr_t>(v)) & 15) == 0;
@@ -74,15 +79,15 @@ __device__ __forceinline__ void adam_sweep(float* __restrict__ p, const float* _
     for (int64_t i = tid; i < n4; i += nth) {
         float4 pa = p4[i], ma = m4[i], va = v4[i];
         const float4 ga = g4[i];
-        adam_one(pa.x, ga.x, ma.x, va.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale);
-        adam_one(pa.y, ga.y, ma.y, va.y, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale);
-        adam_one(pa.z, ga.z, ma.z, va.z, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale);
-        adam_one(pa.w, ga.w, ma.w, va.w, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale);
+        adam_one<CLIP>(pa.x, ga.x, ma.x, va.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, coef);
+        adam_one<CLIP>(pa.y, ga.y, ma.y, va.y, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, coef);
+        adam_one<CLIP>(pa.z, ga.z, ma.z, va.z, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, coef);
+        adam_one<CLIP>(pa.w, ga.w, ma.w, va.w, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, coef);
         p4[i] = pa; m4[i] = ma; v4[i] = va;
     }
     for (int64_t i = 4 * n4 + tid; i < n; i += nth) {
         float pi = p[i], mi = m[i], vi = v[i];
-        adam_one(pi, g[i], mi, vi, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale);
+        adam_one<CLIP>(pi, g[i], mi, vi, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, coef);
         p[i] = pi; m[i] = mi; v[i] = vi;
     }
 }
@@ -91,7 +96,7 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, c
                                                         float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                         float lr, float b1, float b2, float eps, float wd,
                                                         float bc1, float bc2_sqrt, float grad_scale) {
-    adam_sweep(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale);
+    adam_sweep<false>(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, 1.0f);
 }
 
 // same update with the bias corrections read from device memory: the launch arguments do not change from step
@@ -100,7 +105,79 @@ __global__ __launch_bounds__(256) void adam_flat_dev_kernel(float* __restrict__ 
                                                             float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                             float lr, float b1, float b2, float eps, float wd,
                                                             const float* __restrict__ bias_corr, float grad_scale) {
-    adam_sweep(p, g, m, v, n, lr, b1, b2, eps, wd, bias_corr[0], bias_corr[1], grad_scale);
+    adam_sweep<false>(p, g, m, v, n, lr, b1, b2, eps, wd, bias_corr[0], bias_corr[1], grad_scale, 1.0f);
+}
+
+// ... and with the gradient clipped by its global norm: norm_coef = {norm, coefficient} as grad_norm_finish_kernel left it,
+// read by every thread (one cached dword) -- no host scalar, so the launch replays from a captured graph
+__global__ __launch_bounds__(256) void adam_flat_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                             float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                             float lr, float b1, float b2, float eps, float wd,
+                                                             const float* __restrict__ bias_corr, float grad_scale,
+                                                             const float* __restrict__ norm_coef) {
+    adam_sweep<true>(p, g, m, v, n, lr, b1, b2, eps, wd, bias_corr[0], bias_corr[1], grad_scale, norm_coef[1]);
+}
+
+// Global L2 norm of the flat gradient, in two launches.  Launch 1: every thread accumulates the squares of its elements in
+// fp64 (the product of two floats is exact there), the block folds its 256 sums in a fixed tree and stores ONE double to
+// partials[block]; the kernel reads 4 n bytes and nothing else, so the fp64 adds hide under the loads.  Launch 2 (one
+// block) folds the partials in a fixed order and writes {norm, clip coefficient}.  The grid depends on n alone and no
+// sum depends on arrival order: the same bits on every run and every rank.  Two launches, not a last-block finish: the
+// partials of blocks on other XCDs are only visible to the finishing block through an agent-scope release / acquire pair
+// around an atomic ticket, and the stream order between two kernels gives the same guarantee for ~2 us with nothing to
+// get wrong.  16-byte loads when g is 16-byte aligned, element-wise otherwise (adam_sweep's shape).
+constexpr int GN_BLOCKS = OTAL_GRAD_NORM_PARTIALS;
+
+__device__ __forceinline__ double gn_block_sum(double acc, double* sh) {
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ partials) {
+    __shared__ double sh[256];
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
+    const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+    const int64_t n4 = vec ? n >> 2 : 0;
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
+#pragma unroll 4
+    for (int64_t i = tid; i < n4; i += nth) {
+        const float4 a = g4[i];
+        ax += (double)a.x * (double)a.x; ay += (double)a.y * (double)a.y;
+        az += (double)a.z * (double)a.z; aw += (double)a.w * (double)a.w;
+    }
+    for (int64_t i = 4 * n4 + tid; i < n; i += nth) {
+        const double a = (double)g[i];
+        ax += a * a;
+    }
+    const double total = gn_block_sum((ax + ay) + (az + aw), sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partials, int nblocks, float grad_scale,
+                                                               float max_norm, float* __restrict__ out) {
+    __shared__ double sh[256];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 256) acc += partials[i];
+    const double total = gn_block_sum(acc, sh);
+    if (threadIdx.x == 0) {
+        const float norm = (float)(sqrt(total) * (double)grad_scale);
+        float coef = 1.0f;
+        if (!(max_norm <= 0.0f)) {
+            // torch: `max_norm / (total_norm + 1e-6)` with a Python scalar on the left is Tensor.__rtruediv__, i.e.
+            // reciprocal() * max_norm -- two float32 roundings; then clamp(max=1.0), which keeps a NaN
+            const float c = (1.0f / (norm + 1e-6f)) * max_norm;
+            coef = c >= 1.0f ? 1.0f : c;
+        }
+        out[0] = norm;
+        out[1] = coef;
+    }
 }
 
 
@@ -225,6 +302,31 @@ extern "C" int otal_adam_flat_dev(float* p, const float* g, float* m, float* v, 
     const int blocks = (int)(blocks64 < 4096 ? blocks64 : 4096);
     hipLaunchKernelGGL(adam_flat_dev_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
                        beta2, eps, weight_decay, bias_corr, grad_scale);
+    return otal_launch_status();
+}
+
+extern "C" int otal_adam_flat_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                                   float beta2, float eps, float weight_decay, const float* bias_corr,
+                                   float grad_scale, const float* norm_coef, void* stream) {
+    if (!p || !g || !m || !v || !bias_corr || !norm_coef) return OTAL_E_NULL;
+    if (n <= 0) return OTAL_E_SHAPE;
+    const int64_t blocks64 = (n + 255) / 256;
+    const int blocks = (int)(blocks64 < 4096 ? blocks64 : 4096);
+    hipLaunchKernelGGL(adam_flat_clip_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
+                       beta2, eps, weight_decay, bias_corr, grad_scale, norm_coef);
+    return otal_launch_status();
+}
+
+extern "C" int otal_grad_norm(const float* g, int64_t n, float grad_scale, float max_norm, double* partials, float* out,
+                              void* stream) {
+    if (!g || !partials || !out) return OTAL_E_NULL;
+    if (n <= 0) return OTAL_E_SHAPE;
+    // four elements per thread and trip; the grid is a function of n alone (at most GN_BLOCKS partials)
+    const int64_t blocks64 = (n + 1023) / 1024;
+    const int blocks = (int)(blocks64 < GN_BLOCKS ? blocks64 : GN_BLOCKS);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, partials);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, blocks, grad_scale,
+                       max_norm, out);
     return otal_launch_status();
 }
 

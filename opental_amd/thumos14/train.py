@@ -201,10 +201,21 @@ class FlatArena:
 class DetectorTrainer:
     def __init__(self, net, criterion, loss_weights, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8,
                  process_group=None, bucket_mb=16, distributed=None, force_collectives=False, param_groups=None,
-                 forward_fn=None):
+                 forward_fn=None, clip_grad_norm=None, track_grad_norm=False):
         """`param_groups`: [(parameters, lr), ...] in the order the reference hands them to torch.optim.Adam (the
         ActivityNet recipe trains the backbone at lr/10, anet/train.py:304-312); default one group = net.parameters().
-        `forward_fn`: the recipe's forward_one_epoch (default: this module's, the THUMOS14 one)."""
+        `forward_fn`: the recipe's forward_one_epoch (default: this module's, the THUMOS14 one).
+        `track_grad_norm`: every step leaves `last_grad_norm` = {L2 norm of the averaged flat gradient, clip coefficient}
+        in device memory (ops.grad_norm, one pass over arena.grad behind end_backward; the reference's `stats/grad_norm`,
+        train.py:134-141,:248-250).  `clip_grad_norm` = X > 0: Adam additionally reads the gradient scaled by
+        min(1, X / (norm + 1e-6)) (nn.utils.clip_grad_norm_, the rule: common/grad_clip.py); implies tracking.  Both are
+        plain attributes and part of _capture_key: changing one re-captures.  Neither set: the step is what it was."""
+        self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
+        if self.clip_grad_norm is not None and not self.clip_grad_norm > 0:
+            raise ValueError("clip_grad_norm must be > 0 (None: no clipping)")
+        self.track_grad_norm = bool(track_grad_norm)
+        self.last_grad_norm = None  # 2-float device tensor {norm, coefficient} of the last step, once a step tracked it
+        self._norm_ws = None
         self.net, self.criterion, self.w = net, criterion, dict(loss_weights)
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self._base_lr = lr          # the groups' rates follow `self.lr` proportionally (a scheduler only touches self.lr)
@@ -425,11 +436,16 @@ class DetectorTrainer:
 
     def end_backward(self):
         """Call after cost.backward(): flush the buckets that did not complete (unused parameters), wait for the
-        all-reduces, and leave every .grad aliasing its arena slice."""
+        all-reduces, and leave every .grad aliasing its arena slice.
+
+        With `clip_grad_norm` set the early-Adam branch below is not taken: it updates everything but the stem tail
+        BEFORE the tail's weight gradients exist, and the clip coefficient is a function of the global norm, i.e. of all of
+        them.  Tracking alone keeps early Adam: the norm launch follows the final join, and Adam does not write arena.grad."""
         self._drain(force=True)
         self._adam_left = None
         late = ops.take_late_weights()
-        if late and ops.STEP.lanes is not None and self._capturing and not self.collectives and not self._skipped:
+        if late and ops.STEP.lanes is not None and self._capturing and not self.collectives and not self._skipped \
+                and self.clip_grad_norm is None:
             # lane capture, one process: Adam for everything but the stem tail's weights runs NOW on the main lane -- behind the
             # mark the backbone left on the side lane (ops.late_mark), beside the tail's weight gradients -- and only the
             # tail's parameters wait for the final join (_graph_body)
@@ -492,6 +508,26 @@ class DetectorTrainer:
             end.record()
             self.exposed_events.append((ev, end))
 
+    # ---- the global gradient norm (+ clip coefficient) of the step, on the device
+    def _norm_on(self):
+        return self.clip_grad_norm is not None or self.track_grad_norm
+
+    def _norm_buffers(self):
+        """Allocated outside any capture (a step or capture_step begins here)."""
+        dev = self.arena.flat.device
+        if self._norm_on() and self.last_grad_norm is None:
+            self.last_grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._norm_ws = torch.zeros(ops.GRAD_NORM_PARTIALS, dtype=torch.float64, device=dev)
+        if self.clip_grad_norm is not None and self._bias_corr is None:
+            self._bias_corr = torch.zeros(2, dtype=torch.float32, device=dev)
+
+    def _grad_norm_launch(self):
+        """Behind end_backward() -- side lane joined, all-reduces waited for: arena.grad is final on every rank and holds the
+        SUM over the ranks -- and in front of every Adam launch that reads the coefficient.  grad_scale = 1 / world: the
+        norm of the averaged gradient, from identical bytes on every rank (no collective, replicas stay bit-identical)."""
+        if self._norm_on():
+            ops.grad_norm(self.arena.grad, 1.0 / self.world, self.clip_grad_norm, self.last_grad_norm, self._norm_ws)
+
     # ---- one optimisation step
     def compute_cost(self, clips, targets, scores, ssl_clips=None, ssl_targets=None):
         losses = self.forward_fn(self.net, self.criterion, clips, targets, scores, training=True, ssl=False)
@@ -503,6 +539,7 @@ class DetectorTrainer:
 
     def step(self, clips, targets, scores, ssl_clips=None, ssl_targets=None):
         self._trace("step begin")
+        self._norm_buffers()
         stale = False
         if self._graph is not None and ssl_clips is None:
             if self._graph_key == self._capture_key():
@@ -532,6 +569,7 @@ class DetectorTrainer:
         finally:
             ops.STEP.reset()
         self.step_count += 1
+        self._grad_norm_launch()
         self.optimizer_update()
         result = cost.detach(), _detached(losses)
         if stale:
@@ -586,12 +624,20 @@ class DetectorTrainer:
                    getattr(cl, 'evidence', None), getattr(cl, 'loss_type', None))
         return (float(self.lr), float(self._base_lr), tuple(float(g) for _, _, g in self._group_ranges), float(self.wd),
                 tuple(self.betas), float(self.eps), self.world, bool(self.collectives), ibm,
-                tuple(sorted((k, float(v)) for k, v in self.w.items())))
+                tuple(sorted((k, float(v)) for k, v in self.w.items())),
+                # max_norm is a launch argument of the captured norm launch; with clipping there is no early Adam
+                (self.clip_grad_norm, bool(self.track_grad_norm)))
 
     def optimizer_update(self):
         """Adam (L2 weight decay in the gradient, train.py:321-323) on the flat arena: one launch."""
         a = self.arena
         keep = self._stash_skipped()
+        if self.clip_grad_norm is not None:
+            # the clipped launch reads its bias corrections from device memory, like the coefficient
+            self._set_bias(self.step_count)
+            self._adam_captured(0, a.numel)
+            self._restore_skipped(keep)
+            return
         for lo, hi, g_lr in self._group_ranges:
             g_lr = g_lr * (self.lr / self._base_lr) if self._base_lr else g_lr
             ops.adam_flat(a.flat[lo:hi], a.grad[lo:hi], a.m[lo:hi], a.v[lo:hi], self.step_count, g_lr,
@@ -630,6 +676,7 @@ class DetectorTrainer:
             self.end_backward()
         finally:
             ops.STEP.reset()
+        self._grad_norm_launch()
         keep = self._stash_skipped()
         span = getattr(self, "_adam_left", None) or (0, self.arena.numel)       # (what end_backward's early launches left)
         self._adam_captured(span[0], span[1])
@@ -638,13 +685,19 @@ class DetectorTrainer:
         return cost.detach(), _detached(losses)
 
     def _adam_captured(self, start, stop):
-        """Adam over the arena range [start, stop) (graph-replayable: bias corrections in device memory), group by group."""
+        """Adam over the arena range [start, stop) (graph-replayable: bias corrections in device memory), group by group;
+        with clipping every group reads the same coefficient, last_grad_norm[1]."""
         a = self.arena
         for lo, hi, g_lr in self._group_ranges:
             lo, hi = max(lo, start), min(hi, stop)
             if lo >= hi:
                 continue
             g_lr = g_lr * (self.lr / self._base_lr) if self._base_lr else g_lr
+            if self.clip_grad_norm is not None:
+                ops.adam_flat_clip(a.flat[lo:hi], a.grad[lo:hi], a.m[lo:hi], a.v[lo:hi], self._bias_corr,
+                                   self.last_grad_norm, g_lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                                   grad_scale=1.0 / self.world)
+                continue
             ops.adam_flat_dev(a.flat[lo:hi], a.grad[lo:hi], a.m[lo:hi], a.v[lo:hi], self._bias_corr, g_lr,
                               self.betas[0], self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world)
 
@@ -666,6 +719,7 @@ class DetectorTrainer:
         `warmup` eager steps run first on a side stream (they are real optimisation steps)."""
         dev = clips.device
         self._graph = None
+        self._norm_buffers()
         if lanes:
             return self._capture_lanes(clips, targets, scores, warmup)
         if split:
@@ -853,10 +907,8 @@ class DetectorTrainer:
                 if b in self.stem_buckets:
                     self._issue_allreduce(b)
         self._finish_allreduce()
-        for lo, hi, g_lr in self._group_ranges:
-            g_lr = g_lr * (self.lr / self._base_lr) if self._base_lr else g_lr
-            ops.adam_flat_dev(a.flat[lo:hi], a.grad[lo:hi], a.m[lo:hi], a.v[lo:hi], self._bias_corr, g_lr,
-                              self.betas[0], self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world)
+        self._grad_norm_launch()                    # eager, like Adam: the stem's all-reduces end behind the second graph
+        self._adam_captured(0, a.numel)
         return out
 
     def _copy_inputs(self, static, given):
@@ -1066,8 +1118,8 @@ def loss_dispatch(config, as_shipped=False):
     return 'edl' if tr.get('edl_loss', False) else 'focal'
 
 
-def build_training(config, device, as_shipped=False, random_init=False, dist_group=None):
-    """Model, criterion and trainer from a parsed config (train.py:306-331)."""
+def build_training(config, device, as_shipped=False, random_init=False, dist_group=None, **trainer_kw):
+    """Model, criterion and trainer from a parsed config (train.py:306-331); trainer_kw: further DetectorTrainer arguments."""
     from .BDNet import BDNet, model_cfg_from
     from .multisegment_loss import MultiSegmentLoss
     tr, md = config['training'], config['model']
@@ -1085,7 +1137,7 @@ def build_training(config, device, as_shipped=False, random_init=False, dist_gro
                             clip_length=config['dataset']['training']['clip_length']).to(device)
     weights = dict(lw=tr['lw'], cw=tr['cw'], ctw=tr['ctw'], actw=tr.get('actw', 1.0), ssl=tr['ssl'])
     trainer = DetectorTrainer(net, crit, weights, lr=tr['learning_rate'], weight_decay=tr['weight_decay'],
-                              process_group=dist_group)
+                              process_group=dist_group, **trainer_kw)
     return net, crit, trainer
 
 
@@ -1118,12 +1170,18 @@ class StepLog:
     """Per-step scalars without a host synchronisation (the reference calls .item() ~20 times per step for TensorBoard and
     the progress bar, train.py:255-283): every `every` steps the step's [cost, 7 losses] vector is copied
     to a pinned host slot with ONE asynchronous D2H copy + an event; a slot is read (and handed to `sink`) only once its
-    event has completed, i.e. a few steps later, while the GPU keeps running."""
+    event has completed, i.e. a few steps later, while the GPU keeps running.  `width` 9: the vector carries the step's
+    gradient norm behind the eight (DetectorTrainer.last_grad_norm[0]; `names` gains 'grad_norm')."""
     NAMES = ('total', 'loc', 'conf', 'prop_loc', 'prop_conf', 'IoU', 'start', 'end')
+    EXTRA_NAME = 'grad_norm'
 
-    def __init__(self, every=20, sink=None, slots=4):
+    def __init__(self, every=20, sink=None, slots=4, width=None):
         self.every, self.sink = int(every), sink
-        self._free = [(torch.empty(8, dtype=torch.float32).pin_memory() if torch.cuda.is_available() else torch.empty(8),
+        n = self.width = len(self.NAMES) if width is None else int(width)
+        if n not in (len(self.NAMES), len(self.NAMES) + 1):
+            raise ValueError("StepLog width: 8 (cost + 7 losses) or 9 (+ the gradient norm)")
+        self.names = self.NAMES + ((self.EXTRA_NAME,) if n > len(self.NAMES) else ())
+        self._free = [(torch.empty(n, dtype=torch.float32).pin_memory() if torch.cuda.is_available() else torch.empty(n),
                        torch.cuda.Event() if torch.cuda.is_available() else None) for _ in range(slots)]
         self._inflight = []
         self.records = []
@@ -1154,8 +1212,10 @@ class JsonlSink:
     """A StepLog sink that appends one JSON object per logged step to <dir>/scalars.jsonl -- the scalars the reference hands
     to tensorboardX (Total / loc / conf / prop_loc / prop_conf / IoU / start / end, AFSD/thumos14/train.py:249-268; the
     package is not in this image, and a line-per-step file is what `pandas.read_json(..., lines=True)` or a TensorBoard
-    importer reads).  Call it as sink(step, values); the file is flushed per record (records arrive every N steps)."""
+    importer reads).  Call it as sink(step, values); the file is flushed per record (records arrive every N steps).
+    A ninth value (StepLog(width=9)) is the gradient norm, under the reference's own tag 'stats/grad_norm' (train.py:250)."""
     TAGS = ('Total', 'loc', 'conf', 'prop_loc', 'prop_conf', 'IoU', 'start', 'end')
+    EXTRA_TAG = 'stats/grad_norm'
 
     def __init__(self, directory, filename='scalars.jsonl', echo=None):
         import os
@@ -1168,6 +1228,8 @@ class JsonlSink:
         import json
         rec = {'step': int(step)}
         rec.update({'Train/' + t: float(v) for t, v in zip(self.TAGS, values)})
+        if len(values) > len(self.TAGS):
+            rec[self.EXTRA_TAG] = float(values[len(self.TAGS)])
         self._f.write(json.dumps(rec) + '\n')
         self._f.flush()
         if self.echo is not None:
@@ -1186,7 +1248,8 @@ def run_one_epoch(epoch, trainer, dataset, stager, batch_size, rank=0, world=1, 
     Labels: with a stager built with `max_targets` the batch's targets (any number per sample, train.py:221-224), boundary
     masks and ssl segments cross PCIe as ONE fixed-shape pinned record next to the frames (input_pipeline.LabelRecord), so
     every plain step has the same input shapes and -- `trainer.launch == 'lanes'` -- replays the captured lane graphs, the
-    clip kernel writing straight into the captured step's clip buffer; ssl steps (`flags[0]`) run eagerly beside it."""
+    clip kernel writing straight into the captured step's clip buffer; ssl steps (`flags[0]`) run eagerly beside it.
+    A `step_log` of width 9 also receives the step's gradient norm (a trainer with track_grad_norm / clip_grad_norm)."""
     from ..common import thumos_dataset as D
     dev = trainer.arena.flat.device
     sums, n_iter = None, 0
@@ -1217,7 +1280,12 @@ def run_one_epoch(epoch, trainer, dataset, stager, batch_size, rank=0, world=1, 
         sums = vec if sums is None else sums + vec
         n_iter += 1
         if step_log is not None:
-            step_log.push(trainer.step_count, vec)
+            if step_log.width > vec.numel():
+                if trainer.last_grad_norm is None:
+                    raise RuntimeError("the step log expects a gradient norm, but the trainer does not track it")
+                step_log.push(trainer.step_count, torch.cat([vec, trainer.last_grad_norm[:1]]))
+            else:
+                step_log.push(trainer.step_count, vec)
     if step_log is not None:
         step_log.poll(wait=True)
     mean = sums / n_iter
@@ -1228,6 +1296,34 @@ def run_one_epoch(epoch, trainer, dataset, stager, batch_size, rank=0, world=1, 
     log('Epoch-{} Train Loss: Total - {:.5f}, loc - {:.5f}, conf - {:.5f}, prop_loc - {:.5f}, prop_conf - {:.5f}, '
         'IoU - {:.5f}, start - {:.5f}, end - {:.5f}'.format(epoch, *v))
     return v
+
+
+def take_grad_norm_flag(argv, i, extra):
+    """`--clip_grad_norm X` (X > 0) / `--log_grad_norm` at argv[i]: `extra` updated, -> the index of the flag's last word;
+    any other word -> None.  Clipping implies logging.  Shared by the two training drivers."""
+    a = argv[i]
+    if a == '--log_grad_norm':
+        extra['log_grad_norm'] = True
+        return i
+    if a != '--clip_grad_norm':
+        return None
+    text = argv[i + 1] if i + 1 < len(argv) else None
+    try:
+        x = float(text)
+    except (TypeError, ValueError):
+        x = float('nan')
+    if not 0.0 < x < float('inf'):
+        raise SystemExit(f"--clip_grad_norm takes a finite number > 0 (the maximal global gradient norm), not {text!r}")
+    extra['clip_grad_norm'], extra['log_grad_norm'] = x, True
+    return i + 1
+
+
+def make_step_log(every, directory, with_norm=False):
+    """The drivers' per-step log: a console line AND <directory>/scalars.jsonl (the reference's TensorBoard scalars)."""
+    log = StepLog(every, width=len(StepLog.NAMES) + int(bool(with_norm)))
+    log.sink = JsonlSink(directory, echo=lambda step, v: print(
+        'step {} '.format(step) + ', '.join('{} {:.5f}'.format(n, x) for n, x in zip(log.names, v))))
+    return log
 
 
 def main(argv=None):
@@ -1241,6 +1337,12 @@ def main(argv=None):
       --log_every N           per-step loss line every N steps through asynchronous D2H copies (StepLog; 0 = epoch lines only)
       --launch lanes|eager    lanes (default): plain steps replay captured HIP graphs on two streams (DetectorTrainer.
                               capture_step(lanes=True)) from fixed-shape label records; eager: one launch at a time
+      --log_grad_norm         the step's global gradient norm joins the --log_every records: 'stats/grad_norm' in scalars.jsonl
+                              (the reference's tag, train.py:248-250), `grad_norm x` on the console line; computed on the device
+                              inside the replayed step (DetectorTrainer(track_grad_norm=True))
+      --clip_grad_norm X      X > 0: scale the gradient by min(1, X / (norm + 1e-6)) before Adam (nn.utils.clip_grad_norm_,
+                              which the reference carries switched off, train.py:141); implies --log_grad_norm.  A flag, not
+                              state: nothing of it is saved, and --resume with another X re-captures the step
     A yaml with `model.in_channels: 2` (configs/thumos14_opental_flow.yaml) trains the optical-flow stream on uint8 (T,H,W,2)
     frames: the stager hands out three-plane batches with an all-zero third plane (ClipStager(channels=2)).
     One process per GPU; under torchrun the ranks all-reduce gradients over RCCL (DetectorTrainer)."""
@@ -1250,11 +1352,14 @@ def main(argv=None):
     from ..common import thumos_dataset as D
     argv = list(sys.argv[1:] if argv is None else argv)
     extra = {'as_shipped_dispatch': False, 'random_init': False, 'save_after': 10, 'max_steps': None, 'log_every': 0,
-             'launch': 'lanes'}
+             'launch': 'lanes', 'clip_grad_norm': None, 'log_grad_norm': False}
     rest, i = [], 0
     while i < len(argv):
         a = argv[i]
-        if a in ('--as_shipped_dispatch', '--random_init'):
+        j = take_grad_norm_flag(argv, i, extra)
+        if j is not None:
+            i = j
+        elif a in ('--as_shipped_dispatch', '--random_init'):
             extra[a[2:]] = True
         elif a in ('--save_after', '--max_steps', '--log_every'):
             extra[a[2:]] = int(argv[i + 1]); i += 1
@@ -1278,7 +1383,8 @@ def main(argv=None):
         dist.init_process_group(backend='nccl', device_id=dev)
     ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
     set_seed(tr['random_seed'])
-    net, crit, trainer = build_training(config, dev, extra['as_shipped_dispatch'], extra['random_init'])
+    net, crit, trainer = build_training(config, dev, extra['as_shipped_dispatch'], extra['random_init'],
+                                        clip_grad_norm=extra['clip_grad_norm'], track_grad_norm=extra['log_grad_norm'])
     ds_cfg = config['dataset']['training']
     infos = D.get_video_info(ds_cfg['video_info_path'])
     annos = D.get_video_anno(infos, ds_cfg['video_anno_path'], config['dataset']['class_info_path'])
@@ -1302,8 +1408,7 @@ def main(argv=None):
     step_log = None
     if extra['log_every'] > 0 and rank == 0:
         # per-step scalars: a console line AND <checkpoint_path>/training/scalars.jsonl (the reference's TensorBoard scalars)
-        step_log = StepLog(extra['log_every'], sink=JsonlSink(train_state_path, echo=lambda step, v: print(
-            'step {} '.format(step) + ', '.join('{} {:.5f}'.format(n, x) for n, x in zip(StepLog.NAMES, v)))))
+        step_log = make_step_log(extra['log_every'], train_state_path, with_norm=extra['log_grad_norm'])
     trainer.step_log = step_log
     for epoch in range(start_epoch, tr['max_epoch'] + 1):
         if crit.cls_loss_type == 'edl':
