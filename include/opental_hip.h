@@ -113,8 +113,13 @@ int otal_bmp_bwd_levels(const void* grad_out, const void* in, const float* seg, 
  * strides: 4 int64  x batch stride, x channel stride, y batch stride, y channel stride (elements);
  *          pointers are pre-offset to the first channel, so channel slices of a concat buffer
  *          are read / written in place.
- * ws     : optional split-K workspace (otal_conv_workspace_bytes); a smaller one only lowers the
- *          split factor.  Split-K partials are reduced in a fixed order (deterministic).
+ * ws     : workspace for a launch's tables, weight packs and split-K slabs.  otal_conv_workspace_bytes(geom, mode) is
+ *          the size at which every kernel that may serve the geometry -- fp32 or bf16 operands, fp32- or bf16-stored
+ *          contiguous tensors -- takes all the splits it wants: the largest tables-plus-slabs over the steps of its
+ *          plans, by the functions the launchers themselves use (conv_select.h: conv_launch_shape).  A smaller one lowers
+ *          the split factor (and so changes the fp32 summation order); one too small for a kernel's tables moves the
+ *          launch to the next kernel of its plan or is OTAL_E_UNSUPPORTED.  A pair launch of a 1-D layer takes twice
+ *          the bytes; a strided or misaligned view whose plan differs from the contiguous one may get fewer splits.  Split-K partials are reduced in a fixed order (deterministic).
  * mode   : 0 forward, 1 data gradient, 2 weight gradient.
  * precision: 0 = fp32 operands on v_mfma_f32_32x32x2_f32 (exact fp32, the parity path);
  *            1 = operands rounded to bf16 when staged into LDS, v_mfma_f32_32x32x16_bf16, fp32

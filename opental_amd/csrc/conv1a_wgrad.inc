@@ -220,33 +220,18 @@ __global__ __launch_bounds__(256, 2) void conv1a_wgrad_direct_kernel(const W1aAr
     }
 }
 
-int launch_conv1a_wgrad(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_conv1a_wgrad(ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     const ConvGeom& g = a.g;
     W1aArgs d;
-    d.nblocks = g.B * (g.To / 2) * (g.Ho / 2);
-    // 7 taps x S splits workgroups, two resident per CU (registers): 7 x 73 = 511 of 512 slots
-    // (measured on the b = 8 layer: 36 splits 0.87 ms, 73: 0.81, 109: 0.93, 146: 0.89; the pair-mode kernel: 1.05)
-    int splits = OTAL_OPT("OTAL_W1A_SPLITS") > 0 ? OTAL_OPT("OTAL_W1A_SPLITS") : 73;
-    if (splits > d.nblocks) splits = d.nblocks;
-    const size_t slab1 = (size_t)a.M * a.N * sizeof(float);
-    if (splits > 1 && (!ws || ws_bytes < (size_t)splits * slab1)) {
-        splits = ws ? (int)(ws_bytes / slab1) : 1;
-        if (splits < 2) splits = 1;
-    }
-    d.bps = (d.nblocks + splits - 1) / splits;
-    splits = (d.nblocks + d.bps - 1) / d.bps;
-    a.splits = splits;
-    a.k_per_split = d.bps;
-    a.slab = splits > 1 ? (float*)ws : nullptr;
+    d.nblocks = sh.units;           // 2 x 2 x 48 output blocks, sh.per_split per split (conv_select.h)
+    d.bps = sh.per_split;
     a.src_bytes = (unsigned)gather_extent_bytes(g, MODE_FWD);
     a.dy_bytes = (unsigned)(gather_extent_bytes(g, MODE_DGRAD) >> (a.half ? 1 : 0));
     a.flags &= ~EPI_NPAD8;
-    set_epilogue_extents<MODE_WGRAD>(a);
-    if ((splits > 1 ? a.slab_bytes : a.out_bytes) == 0u) return OTAL_E_UNSUPPORTED;
+    if (!set_splits<MODE_WGRAD>(a, sh, ws)) return OTAL_E_UNSUPPORTED;
     d.c = a;
-    if (a.half) hipLaunchKernelGGL(conv1a_wgrad_direct_kernel<true>, dim3(7, splits), dim3(256), 0, st, d);
-    else hipLaunchKernelGGL(conv1a_wgrad_direct_kernel<false>, dim3(7, splits), dim3(256), 0, st, d);
+    if (a.half) hipLaunchKernelGGL(conv1a_wgrad_direct_kernel<true>, dim3(7, a.splits), dim3(256), 0, st, d);
+    else hipLaunchKernelGGL(conv1a_wgrad_direct_kernel<false>, dim3(7, a.splits), dim3(256), 0, st, d);
     if (int e = otal_launch_status()) return e;
-    if (splits > 1) return launch_splitk_reduce<MODE_WGRAD>(a, st);
-    return 0;
+    return a.splits > 1 ? launch_splitk_reduce<MODE_WGRAD>(a, st) : 0;
 }

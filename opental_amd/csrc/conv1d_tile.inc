@@ -214,57 +214,25 @@ __global__ __launch_bounds__(256) void conv1d_tile_kernel(const ConvArgs a) {
 template <int KT, int MODE>
 static int launch_c1t(const ConvArgs& a, dim3 grid, hipStream_t st) {
     constexpr int lds = 2 * ((64 + 8) * (128 * 2 + 16) + 32 * (KT * 128 * 2 + 16));
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_tile_kernel<KT, MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
-    hipLaunchKernelGGL((conv1d_tile_kernel<KT, MODE>), grid, dim3(256), lds, st, a);
-    return otal_launch_status();
+    return launch_big_lds<conv1d_tile_kernel<KT, MODE>>(lds, grid, 256, st, a);
 }
 
 template <int MODE>
-int launch_conv1d_tile(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_conv1d_tile(ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     // tables + packed weights: the persistent region of the chunked path (same layout), or built here in the workspace
     const int BMsel = choose_bm(a.M, true);
     a.Kp = chunk_kp(a.K);
-    const size_t tb = chunk_tab_bytes(a.K), wb = chunk_wp_bytes(a.M, BMsel, a.K);
-    unsigned short* wp;
-    if (a.pre) {
-        wp = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(const_cast<void*>(a.pre)) + tb);
-    } else {
-        if (!ws || ws_bytes < tb + wb) return OTAL_E_UNSUPPORTED;
-        wp = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(ws) + tb);
-        PrepDesc d;
-        fill_prep_desc<MODE>(d, a, reinterpret_cast<int2*>(ws), wp);
-        launch_prep(d, st);
-        if (int e = otal_launch_status()) return e;
-        ws = reinterpret_cast<char*>(ws) + tb + wb;
-        ws_bytes -= tb + wb;
-    }
+    const size_t wb = chunk_wp_bytes(a.M, BMsel, a.K);
+    int2* ctab;
+    if (int e = chunk_region<MODE>(a, a.pre, ws, ctab, a.wp, st)) return e;
     if (a.pair) {           // the second problem's packed weights: its own persistent region, or built behind the first
-        if (a.pre2) {
-            a.wp2 = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(const_cast<void*>(a.pre2)) + tb);
-        } else {
-            if (!ws || ws_bytes < tb + wb) return OTAL_E_UNSUPPORTED;
-            ConvArgs b = a;
-            b.w = a.w2;
-            unsigned short* wp2 = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(ws) + tb);
-            PrepDesc d;
-            fill_prep_desc<MODE>(d, b, reinterpret_cast<int2*>(ws), wp2);
-            launch_prep(d, st);
-            if (int e = otal_launch_status()) return e;
-            a.wp2 = wp2;
-        }
+        ConvArgs b = a;
+        b.w = a.w2;
+        if (int e = chunk_region<MODE>(b, a.pre2, static_cast<char*>(ws) + sh.second_at, ctab, a.wp2, st)) return e;
     }
-    a.wp = wp;
     a.wp_bytes = (unsigned)wb;
     a.src_bytes = (unsigned)gather_extent_bytes(a.g, MODE);
-    a.splits = 1; a.k_per_split = 0; a.slab = nullptr;
-    set_epilogue_extents<MODE>(a);
-    if (a.out_bytes == 0u) return OTAL_E_UNSUPPORTED;
-    const dim3 grid((a.M + 31) / 32, a.g.B * ((a.g.Ti + 63) / 64), a.pair ? 2 : 1);
+    if (!set_splits<MODE>(a, sh, ws)) return OTAL_E_UNSUPPORTED;
+    const dim3 grid(sh.grid[0], sh.grid[1], sh.grid[2]);
     return a.g.kt == 3 ? launch_c1t<3, MODE>(a, grid, st) : launch_c1t<1, MODE>(a, grid, st);
 }

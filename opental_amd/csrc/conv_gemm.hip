@@ -39,7 +39,7 @@
 namespace otal_conv {
 struct ConvArgs;
 // part 1: one step (conv_select.h: ConvKernel, vector width cw) of a plan for bf16-stored tensors on both sides of the layer
-__attribute__((visibility("hidden"))) int launch_half(int mode, int kernel, int cw, ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st);
+__attribute__((visibility("hidden"))) int launch_half(int mode, int kernel, int cw, ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st);
 }  // namespace otal_conv
 
 namespace {
@@ -2131,6 +2131,30 @@ static void set_epilogue_extents(ConvArgs& a) {
     a.slab_bytes = (a.splits > 1 && slab < (int64_t)0xfffffff0u) ? (unsigned)slab : 0u;
 }
 
+// a kernel with more dynamic LDS than the default limit: raise the limit once (the attribute is per kernel function), launch
+template <auto KERNEL, class Args>
+static int launch_big_lds(int lds, dim3 grid, int threads, hipStream_t st, const Args& d) {
+    static bool configured = false;            // once per instantiation
+    if (!configured) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return (int)e;
+        configured = true;
+    }
+    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, st, d);
+    return otal_launch_status();
+}
+
+// the split fields of a launch as conv_launch_shape() (conv_select.h) cut the workspace, [front][slabs]; then the epilogue's
+// extents: false when what the kernel stores to does not fit 32-bit offsets (the kernels without an element-wise fallback refuse)
+template <int MODE>
+static bool set_splits(ConvArgs& a, const ConvLaunchShape& sh, void* ws) {
+    a.splits = sh.splits;
+    a.k_per_split = sh.per_split;
+    a.slab = sh.splits > 1 ? reinterpret_cast<float*>(static_cast<char*>(ws) + sh.front_bytes) : nullptr;
+    set_epilogue_extents<MODE>(a);
+    return (a.splits > 1 ? a.slab_bytes : a.out_bytes) != 0u;
+}
+
 // =================================================================================================
 // Direct 3x3x3 convolution (bf16 operands; stride 1, SAME, P % 128 == 0, channel count % 16 == 0, W <= 24).
 // The gather kernels above re-fetch every input element 27 times through L1 and are bound by the texture addresser /
@@ -2496,7 +2520,7 @@ __global__ __launch_bounds__(256) void pack_direct_kernel(unsigned* __restrict__
 // conv1a_tile_fwd_kernel (conv1a_tile.hip: 4 x 4 x 48 tiles, persistent workgroups, weights in registers); this kernel
 // serves the rest and is the bit-exact reference of that one (tests/test_ops_gpu.py).
 constexpr int C1_NPL = 9, C1_NR = 9, C1_NC = 104, C1_PITCH = C1_NC * 8;   // bytes per patch row
-constexpr int C1_BNP = C1_TT * C1_TR * C1_WO, C1_NT = C1_BNP * 2, C1_PA = 80, C1_STEPS = 49;
+constexpr int C1_BNP = C1_TT * C1_TR * C1_WO, C1_NT = C1_BNP * 2, C1_PA = 80;
 
 struct Conv1aArgs {
     ConvArgs c;
@@ -2670,32 +2694,26 @@ __global__ __launch_bounds__(C1_NT) void conv1a_direct_fwd_kernel(const Conv1aAr
     store_acc<MODE_FWD, WM, 1, BM>(a, acc, m0, n_wave, 0, 0, lane, 0, reinterpret_cast<float*>(smA[0]));
 }
 
-static inline size_t conv1a_wp_bytes(int M) { return (((size_t)((M + 63) / 64 * 64) * C1_STEPS * 64) + 255) & ~(size_t)255; }
-
-int launch_conv1a_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_conv1a_direct(ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     if (conv1a_tile_eligible(a.g.To, a.g.Ho) && !(a.flags & EPI_ACCUM)) {      // 4 x 4 x 48 tiles (conv1a_tile.hip)
         otal_conv::Conv1aTileArgs t;
         t.x = a.x; t.w = a.w; t.wp = nullptr; t.out = a.out; t.scale = a.scale; t.shift = a.shift;
         t.x_bs = a.g.x_bs; t.x_cs = a.g.x_cs; t.y_bs = a.g.y_bs; t.y_cs = a.g.y_cs;
         t.B = a.g.B; t.Ti = a.g.Ti; t.Hi = a.g.Hi; t.To = a.g.To; t.Ho = a.g.Ho; t.M = a.M;
         t.relu = (a.flags & EPI_RELU) ? 1 : 0; t.half = a.half; t.flags = a.flags;
-        const int e = otal_conv::launch_conv1a_tile(t, ws, ws_bytes, st);
+        const int e = otal_conv::launch_conv1a_tile(t, ws, sh.front_bytes, st);      // (the same pack bytes for both kernels)
         if (e != OTAL_E_UNSUPPORTED) return e;
     }
-    const int tm = (a.M + 63) / 64, Mpad = tm * 64;
-    const size_t wb = conv1a_wp_bytes(a.M);
-    if (!ws || ws_bytes < wb) return OTAL_E_UNSUPPORTED;
+    const int tm = sh.tm, Mpad = tm * 64;
     const int pairs = Mpad * C1_STEPS * 16;
     hipLaunchKernelGGL(pack_conv1a_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, reinterpret_cast<unsigned*>(ws), a.w, a.M, Mpad);
     if (int e = otal_launch_status()) return e;
     Conv1aArgs d;
     a.fd = make_conv_fastdiv(a.g);
-    a.splits = 1; a.k_per_split = 0; a.slab = nullptr;
-    set_epilogue_extents<MODE_FWD>(a);
+    set_splits<MODE_FWD>(a, sh, ws);
     d.c = a;
     d.wp = reinterpret_cast<const unsigned short*>(ws);
-    const dim3 grid(a.g.B * (a.g.To / C1_TT) * (a.g.Ho / C1_TR), tm, 1);
-    hipLaunchKernelGGL(conv1a_direct_fwd_kernel, grid, dim3(C1_NT), 0, st, d);
+    hipLaunchKernelGGL(conv1a_direct_fwd_kernel, dim3(sh.grid[0], sh.grid[1], 1), dim3(C1_NT), 0, st, d);
     return otal_launch_status();
 }
 
@@ -2837,19 +2855,11 @@ __global__ __launch_bounds__(256) void conv_wgrad1d_kernel(const ConvArgs a, int
     }
 }
 
-int launch_wgrad1d(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int nchunks = wgrad1d_chunks(a.g), units = a.g.B * nchunks;
-    // units per workgroup = (sample, chunk) units folded into one split-K slab.  Round 2 (every reduction its own launch behind
-    // its GEMM, one lane): 1 -> 478.4, 2 -> 475.8, 4 -> 465.7 clips/s.  Round 6 (reductions batched on the weight-gradient lane, whose
-    // slab traffic is what these eight launches cost -- 328 MB written, 328 MB read back per step): 1 / 2 / 4 / 8 -> 8.09 / 8.03 /
-    // 8.02 / 8.02 ms.  Four where there are eight units or more (two slabs at b = 8), two from four units on.
-    const int upw = units >= 8 ? 4 : units >= 4 ? 2 : 1;
-    const int splits = (units + upw - 1) / upw;
-    const size_t need = ((size_t)splits * a.M * a.N * sizeof(float) + 255) & ~(size_t)255;
-    if (!ws || ws_bytes < need * (a.pair ? 2 : 1)) return OTAL_E_UNSUPPORTED;
-    a.splits = splits; a.k_per_split = 0; a.slab = reinterpret_cast<float*>(ws);
-    if (a.pair) a.slab2 = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + need);
-    const dim3 grid(splits, a.g.Cin / 64, ((a.g.Cout + 63) / 64) * (a.pair ? 2 : 1));
+int launch_wgrad1d(ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
+    const int nchunks = wgrad1d_chunks(a.g), units = sh.units, upw = sh.per_split;      // units per workgroup: conv_select.h
+    a.splits = sh.splits; a.k_per_split = 0; a.slab = reinterpret_cast<float*>(ws);
+    if (a.pair) a.slab2 = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + sh.second_at);
+    const dim3 grid(sh.grid[0], sh.grid[1], sh.grid[2]);
     if (a.g.kt == 1) hipLaunchKernelGGL(conv_wgrad1d_kernel<1>, grid, dim3(256), 0, st, a, nchunks, units, upw);
     else hipLaunchKernelGGL(conv_wgrad1d_kernel<3>, grid, dim3(256), 0, st, a, nchunks, units, upw);
     if (int e = otal_launch_status()) return e;
@@ -2913,41 +2923,38 @@ static void launch_prep(const PrepDesc& d, hipStream_t st) {
     else hipLaunchKernelGGL((prep_chunks_kernel<MODE_DGRAD>), dim3(prep_blocks(d)), dim3(256), 0, st, d);
 }
 
+// chunk table + packed weights of a launch: the caller's persistent region, or built at `at` (the front of the workspace)
+template <int MODE>
+static int chunk_region(const ConvArgs& a, const void* pre, void* at, int2*& ctab, const unsigned short*& wp, hipStream_t st) {
+    char* base = static_cast<char*>(pre ? const_cast<void*>(pre) : at);
+    unsigned short* pack = reinterpret_cast<unsigned short*>(base + chunk_tab_bytes(a.K));
+    ctab = reinterpret_cast<int2*>(base);
+    wp = pack;
+    if (pre) return 0;
+    PrepDesc d;
+    fill_prep_desc<MODE>(d, a, ctab, pack);
+    launch_prep(d, st);
+    return otal_launch_status();
+}
+
 #if OTAL_CONV_PART == 1
 typedef short v4s16 __attribute__((ext_vector_type(4)));
 #include "conv1x1_stream.inc"
 #endif
 
 template <int MODE, bool H = false>
-int launch_chunked(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_chunked(ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     const int C = MODE == MODE_FWD ? a.g.Cin : a.g.Cout;
     const bool kwv = MODE == MODE_FWD && (C % 8) != 0;
     if (H && (kwv || (a.flags & EPI_ACCUM) || conv_in_positions(a.g) != conv_out_positions(a.g))) return OTAL_E_UNSUPPORTED;
-    if (kwv) a.K = a.g.Cin * a.g.kt * a.g.kh * 8;          // kw padded to 8 taps per (ci, dt, dh) row
+    a.K = sh.K;                                        // (kw-vector mode pads kw to 8 taps)
     const int BMpack = choose_bm(a.M, !kwv);           // the weight pack's row padding (persistent regions are sized by it)
-    int BMsel = BMpack;
-    // bf16 tensors: the 128-row variant needs 247 registers (two workgroups per CU), the 96-row one 105 (four); rows past the
-    // pack's padding read zeros through the buffer bounds check, so a different tile height may run on the same pack
-    if (H && BMsel == 128) BMsel = 96;
-    const int tm = (a.M + BMsel - 1) / BMsel, tn = (a.N + 127) / 128;
+    const int BMsel = sh.bm;                           // (bf16 tensors: 96 rows on the 128-row pack)
     a.Kp = chunk_kp(a.K);
-    const size_t tb = chunk_tab_bytes(a.K), wb = chunk_wp_bytes(a.M, BMpack, a.K);
+    const size_t wb = chunk_wp_bytes(a.M, BMpack, a.K);
     int2* ctab;
-    unsigned short* wp;
-    if (a.pre) {            // tables + packed weights were prepared into a caller-owned region
-        ctab = reinterpret_cast<int2*>(const_cast<void*>(a.pre));
-        wp = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(const_cast<void*>(a.pre)) + tb);
-    } else {
-        if (!ws || ws_bytes < tb + wb) return OTAL_E_UNSUPPORTED;
-        ctab = reinterpret_cast<int2*>(ws);
-        wp = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(ws) + tb);
-        PrepDesc d;
-        fill_prep_desc<MODE>(d, a, ctab, wp);
-        launch_prep(d, st);
-        if (int e = otal_launch_status()) return e;
-        ws = reinterpret_cast<char*>(ws) + tb + wb;
-        ws_bytes -= tb + wb;
-    }
+    const unsigned short* wp;
+    if (int e = chunk_region<MODE>(a, a.pre, ws, ctab, wp, st)) return e;
     a.ctab = ctab; a.wp = wp;
 #if OTAL_CONV_PART == 1
     if constexpr (H) {
@@ -2961,21 +2968,8 @@ int launch_chunked(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     a.src_bytes = (unsigned)gather_extent_bytes(a.g, MODE, H ? 2 : 4);
     a.wp_bytes = (unsigned)wb;
     a.fd = make_conv_fastdiv(a.g);
-    int splits = choose_splits(tm * tn, a.Kp);
-    if (splits > 1) {
-        const size_t need = (size_t)splits * a.M * a.N * sizeof(float);
-        if (ws_bytes < need) {
-            splits = (int)(ws_bytes / ((size_t)a.M * a.N * sizeof(float)));
-            if (splits < 2) splits = 1;
-        }
-    }
-    const int kps = ((a.Kp + splits - 1) / splits + 31) / 32 * 32;
-    splits = (a.Kp + kps - 1) / kps;
-    a.splits = splits;
-    a.k_per_split = kps;
-    a.slab = splits > 1 ? (float*)ws : nullptr;
-    set_epilogue_extents<MODE>(a);
-    const dim3 grid(tn, tm, splits);
+    set_splits<MODE>(a, sh, ws);
+    const dim3 grid(sh.grid[0], sh.grid[1], sh.grid[2]);
     const int cw = chunk_vector_width(a.g);
 #define OTAL_LAUNCH_C(BM_, WM_, WN_)                                                                                   \
     do {                                                                                                               \
@@ -2999,24 +2993,19 @@ int launch_chunked(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     else OTAL_LAUNCH_C(32, 1, 1);
 #undef OTAL_LAUNCH_C
     if (int e = otal_launch_status()) return e;
-    if (splits > 1) {
-        return launch_splitk_reduce<MODE, H>(a, st);
-    }
-    return 0;
+    return a.splits > 1 ? launch_splitk_reduce<MODE, H>(a, st) : 0;
 }
 
 // ---- vector WGRAD: workspace layout [position table][split-K slabs] (eligibility: conv_select.h)
 template <bool H = false>
-int launch_wgrad_vector(ConvArgs& a, int cw, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_wgrad_vector(ConvArgs& a, int cw, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     const bool pair = a.g.sw == 2;
     if (H && pair) return OTAL_E_UNSUPPORTED;
     if (pair) {                                             // columns padded to 8 per (ci, dt, dh) row
-        a.N = a.g.Cin * a.g.kt * a.g.kh * 8;
+        a.N = sh.N;
         a.flags |= EPI_NPAD8;
     }
-    const int BMsel = choose_bm(a.M);
-    const int tm = (a.M + BMsel - 1) / BMsel, tn = (a.N + 127) / 128;
-    const size_t tb = ptab_bytes(a.g, cw);
+    const int BMsel = sh.bm;
     a.fd = make_conv_fastdiv(a.g);
     a.P = conv_out_positions(a.g);
     a.src_bytes = (unsigned)gather_extent_bytes(a.g, MODE_FWD, H ? 2 : 4);
@@ -3025,30 +3014,14 @@ int launch_wgrad_vector(ConvArgs& a, int cw, void* ws, size_t ws_bytes, hipStrea
     if (a.pre) {
         ptab = reinterpret_cast<int2*>(const_cast<void*>(a.pre));      // geometry-only table, built once by the caller
     } else {
-        if (!ws || ws_bytes < tb) return OTAL_E_UNSUPPORTED;
         ptab = reinterpret_cast<int2*>(ws);
         const int ngroups = a.K / cw, npad = ngroups + PTAB_PAD;
         hipLaunchKernelGGL(build_pos_table_kernel, dim3((npad + 255) / 256), dim3(256), 0, st, ptab, a.g, a.fd, cw, ngroups, npad);
         if (int e = otal_launch_status()) return e;
-        ws = reinterpret_cast<char*>(ws) + tb;
-        ws_bytes -= tb;
     }
     a.ptab = ptab;
-    int splits = choose_splits(tm * tn, a.K, 1, true);
-    if (splits > 1) {
-        const size_t need = (size_t)splits * a.M * a.N * sizeof(float);
-        if (ws_bytes < need) {
-            splits = (int)(ws_bytes / ((size_t)a.M * a.N * sizeof(float)));
-            if (splits < 2) splits = 1;
-        }
-    }
-    const int kps = ((a.K + splits - 1) / splits + 31) / 32 * 32;
-    splits = (a.K + kps - 1) / kps;
-    a.splits = splits;
-    a.k_per_split = kps;
-    a.slab = splits > 1 ? (float*)ws : nullptr;
-    set_epilogue_extents<MODE_WGRAD>(a);
-    const dim3 grid(tn, tm, splits);
+    set_splits<MODE_WGRAD>(a, sh, ws);
+    const dim3 grid(sh.grid[0], sh.grid[1], sh.grid[2]);
 #define OTAL_LAUNCH_W(BM_, WM_, WN_)                                                                                   \
     do {                                                                                                               \
         if (cw == 8) hipLaunchKernelGGL((conv_wgrad_bf16v_kernel<BM_, WM_, WN_, 8, false, H>), grid, dim3(NT), 0, st, a);        \
@@ -3071,10 +3044,7 @@ int launch_wgrad_vector(ConvArgs& a, int cw, void* ws, size_t ws_bytes, hipStrea
     else OTAL_LAUNCH_W(32, 1, 1);
 #undef OTAL_LAUNCH_W
     if (int e = otal_launch_status()) return e;
-    if (splits > 1) {
-        return launch_splitk_reduce<MODE_WGRAD>(a, st);
-    }
-    return 0;
+    return a.splits > 1 ? launch_splitk_reduce<MODE_WGRAD>(a, st) : 0;
 }
 
 // ---- direct 3x3x3 path: launch (eligibility, tile height and weight pack size: conv_select.h)
@@ -3083,28 +3053,19 @@ constexpr int direct_lds_bytes() { return 2 * BM * 304 + 2 * (BNP + (H ? 56 : 52
 template <int BM, int MODE, bool XPF2 = false, bool H = false>
 static int launch_direct512(const DirectArgs& d, dim3 grid, hipStream_t st) {
     constexpr int lds = direct_lds_bytes<BM, 512, 48, H>();
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_direct_kernel<BM, MODE, 512, 2, 48, 1, XPF2, H>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
-    hipLaunchKernelGGL((conv3_direct_kernel<BM, MODE, 512, 2, 48, 1, XPF2, H>), grid, dim3(512), lds, st, d);
-    return otal_launch_status();
+    return launch_big_lds<conv3_direct_kernel<BM, MODE, 512, 2, 48, 1, XPF2, H>>(lds, grid, 512, st, d);
 }
 
 template <int MODE, bool H = false>
-int launch_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_direct(ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     if (H && ((a.g.Wi & 1) || (a.flags & EPI_ACCUM))) return OTAL_E_UNSUPPORTED;       // (4-byte aligned loads need an even row length)
     const int C = MODE == MODE_FWD ? a.g.Cin : a.g.Cout;
-    const int BM = direct_bm(a.g, a.M);
-    const int tm = (a.M + BM - 1) / BM, Mpad = tm * BM;
+    const int BM = sh.bm;
+    const int tm = sh.tm, Mpad = tm * BM;
     const size_t wb = direct_wp_bytes(a.g, a.M, C);
     if (a.pre) {            // packed earlier into a caller-owned region (otal_conv_prologue[_batch]): nothing to do per launch
         ws = const_cast<void*>(a.pre);
     } else {
-        if (!ws || ws_bytes < wb) return OTAL_E_UNSUPPORTED;
         const int64_t pairs = (int64_t)Mpad * C * 27 / 2;
         const int blocks = (int)((pairs + 255) / 256 < 2048 ? (pairs + 255) / 256 : 2048);
         hipLaunchKernelGGL((pack_direct_kernel<MODE>), dim3(blocks), dim3(256), 0, st, reinterpret_cast<unsigned*>(ws), a.w,
@@ -3114,14 +3075,13 @@ int launch_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     DirectArgs d;
     a.fd = make_conv_fastdiv(a.g);
     a.src_bytes = (unsigned)gather_extent_bytes(a.g, MODE, H ? 2 : 4);
-    a.splits = 1; a.k_per_split = 0; a.slab = nullptr;
-    set_epilogue_extents<MODE>(a);
+    set_splits<MODE>(a, sh, ws);
     d.c = a;
     d.wp = reinterpret_cast<const unsigned short*>(ws);
     d.C = C; d.Ktot = C * 27; d.wp_bytes = (unsigned)wb;
-    const int bnp = direct_bnp(a.g, a.M);
+    const int bnp = a.N / sh.tn;        // positions per workgroup (direct_bnp)
+    const dim3 grid(sh.grid[0], sh.grid[1], 1);
     if (bnp == 128) {
-        const dim3 grid(a.N / 128, tm, 1);
         if (BM == 96) hipLaunchKernelGGL((conv3_direct_kernel<96, MODE, 128, 1, 48, 1, false, H>), grid, dim3(256), (direct_lds_bytes<96, 128, 48, H>()), st, d);
         else if (BM == 32) hipLaunchKernelGGL((conv3_direct_kernel<32, MODE, 128, 1, 48, 1, false, H>), grid, dim3(256), (direct_lds_bytes<32, 128, 48, H>()), st, d);
         else hipLaunchKernelGGL((conv3_direct_kernel<64, MODE, 128, 1, 48, 1, false, H>), grid, dim3(256), (direct_lds_bytes<64, 128, 48, H>()), st, d);
@@ -3134,14 +3094,12 @@ int launch_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     // Conv3d_2c dgrad 476 -> 558 and the 64-row forward launches +15 %: the load latency was NOT what these tiles wait for
     const int xpf2 = OTAL_OPT("OTAL_CONV_DIRECT_XPF2");
     if (bnp == 512) {           // two position tiles per wave (dynamic LDS: 112 KB)
-        const dim3 grid(a.N / 512, tm, 1);
         if constexpr (MODE == MODE_FWD) {
             if (BM == 96 && (xpf2 & 2)) return launch_direct512<96, MODE, true, H>(d, grid, st);
         }
         if (BM == 96) return launch_direct512<96, MODE, false, H>(d, grid, st);
         return launch_direct512<64, MODE, false, H>(d, grid, st);
     }
-    const dim3 grid(a.N / 256, tm, 1);
     if (BM == 96 && (xpf2 & 1)) hipLaunchKernelGGL((conv3_direct_kernel<96, MODE, 256, 1, 48, 1, true, H>), grid, dim3(512), (direct_lds_bytes<96, 256, 48, H>()), st, d);
     else if (BM == 64 && ((xpf2 & 4) || ((xpf2 & 1) && (int64_t)grid.x * grid.y <= 256))) hipLaunchKernelGGL((conv3_direct_kernel<64, MODE, 256, 1, 48, 1, true, H>), grid, dim3(512), (direct_lds_bytes<64, 256, 48, H>()), st, d);
     else if (BM == 96) hipLaunchKernelGGL((conv3_direct_kernel<96, MODE, 256, 1, 48, 1, false, H>), grid, dim3(512), (direct_lds_bytes<96, 256, 48, H>()), st, d);
@@ -3163,17 +3121,17 @@ int launch_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
 // bf16-stored tensors on BOTH sides of a backbone layer (fwd: x and y; dgrad: dy, dx and the ReLU mask; wgrad: x and dy): the H
 // instantiations of the direct 3x3x3, chunked, direct / wide / vector weight-gradient kernels.
 }  // namespace
-int otal_conv::launch_half(int mode, int kernel, int cw, ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int otal_conv::launch_half(int mode, int kernel, int cw, ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     switch (kernel) {
         case CK_DIRECT:
-            if (mode == MODE_FWD) return launch_direct<MODE_FWD, true>(a, ws, ws_bytes, st);
-            return launch_direct<MODE_DGRAD, true>(a, ws, ws_bytes, st);
+            if (mode == MODE_FWD) return launch_direct<MODE_FWD, true>(a, sh, ws, st);
+            return launch_direct<MODE_DGRAD, true>(a, sh, ws, st);
         case CK_CHUNKED:
-            if (mode == MODE_FWD) return launch_chunked<MODE_FWD, true>(a, ws, ws_bytes, st);
-            return launch_chunked<MODE_DGRAD, true>(a, ws, ws_bytes, st);
-        case CK_WGRAD_DIRECT: return launch_wgrad_direct<true>(a, ws, ws_bytes, st);
-        case CK_WGRAD1X1: return launch_wgrad1x1_wide<true>(a, ws, ws_bytes, st);
-        case CK_WGRAD_VECTOR: return launch_wgrad_vector<true>(a, cw, ws, ws_bytes, st);
+            if (mode == MODE_FWD) return launch_chunked<MODE_FWD, true>(a, sh, ws, st);
+            return launch_chunked<MODE_DGRAD, true>(a, sh, ws, st);
+        case CK_WGRAD_DIRECT: return launch_wgrad_direct<true>(a, sh, ws, st);
+        case CK_WGRAD1X1: return launch_wgrad1x1_wide<true>(a, sh, ws, st);
+        case CK_WGRAD_VECTOR: return launch_wgrad_vector<true>(a, cw, sh, ws, st);
         default: return OTAL_E_UNSUPPORTED;
     }
 }
@@ -3183,38 +3141,28 @@ namespace {
 #if OTAL_CONV_PART == 0
 // the generic tap-table kernel: any geometry (the data gradient packs W^T first when it is given the natural layout)
 template <int MODE>
-int launch_generic(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_generic(ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     if constexpr (MODE == MODE_DGRAD) {
         if (a.w_natural) {          // the generic kernel wants W^T packed (Cin, Cout, kvol): build it at the front of the workspace
             const int kvol = conv_kvol(a.g);
-            const size_t wb = align256((size_t)a.g.Cin * a.g.Cout * kvol * sizeof(float));
-            if (!ws || ws_bytes < wb) return OTAL_E_UNSUPPORTED;
             const int64_t total = (int64_t)a.g.Cout * a.g.Cin * kvol;
             const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
             hipLaunchKernelGGL(pack_wt_kernel, dim3(blocks), dim3(256), 0, st, a.w, reinterpret_cast<float*>(ws), a.g.Cout, a.g.Cin, kvol);
             if (int e = otal_launch_status()) return e;
             a.w = reinterpret_cast<const float*>(ws);
             a.w_natural = 0;
-            ws = reinterpret_cast<char*>(ws) + wb;
-            ws_bytes -= wb;
         }
     }
     a.zero = zero_word_address();
     if (!a.zero) return OTAL_E_UNSUPPORTED;
-    if (MODE != MODE_WGRAD) {       // carve the tap table off the front of the workspace and build it
-        const size_t tb = tab_bytes(a.K);
-        if (!ws || ws_bytes < tb) return OTAL_E_UNSUPPORTED;
-        int2* tab = reinterpret_cast<int2*>(ws);
+    if (MODE != MODE_WGRAD) {       // the tap table, behind the W^T pack where there is one
+        int2* tab = reinterpret_cast<int2*>(static_cast<char*>(ws) + sh.second_at);
         const int Kpad = a.K + (int)TAB_PAD;
         hipLaunchKernelGGL((build_tap_table_kernel<MODE>), dim3((Kpad + 255) / 256), dim3(256), 0, st, tab, a.g, a.K, Kpad);
         if (int e = otal_launch_status()) return e;
         a.tab = tab;
-        ws = reinterpret_cast<char*>(ws) + tb;
-        ws_bytes -= tb;
     }
-    const int BMsel = choose_bm(a.M);
-    const int BN = 128;
-    const int tm = (a.M + BMsel - 1) / BMsel, tn = (a.N + BN - 1) / BN;
+    const int BMsel = sh.bm;
     a.fd = make_conv_fastdiv(a.g);
     if (MODE == MODE_WGRAD) {   // dy rows vectorise along positions when groups of 4 stay inside a sample and aligned
         const int64_t P = conv_out_positions(a.g);
@@ -3222,32 +3170,8 @@ int launch_generic(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     } else {
         a.a_vec4 = (a.K % 4 == 0) && (((uintptr_t)a.w & 15) == 0) && BMsel >= 64;
     }
-    int splits = choose_splits(tm * tn, a.K, a.prec);
-    if (MODE == MODE_WGRAD && a.prec) {
-        // the generic kernel gets the weight gradients of the 1-D pyramid / head layers (126 positions per sample: no vector
-        // path): K = B * 126 positions, a few dozen tiles -- latency-bound K steps, so split down to 4 K steps per split
-        const int ms = 4;      // measured: 8 -> 474.6, 4 -> 478.3, 2 -> 478.0, 1 -> 476.3 clips/s
-        const int tg = 512;
-        const int tiles = tm * tn;
-        int want = (tg + tiles - 1) / tiles, maxs = a.K / (ms * 32);
-        if (maxs < 1) maxs = 1;
-        splits = tiles >= tg * 3 / 4 ? 1 : (want < maxs ? want : maxs);
-        if (splits > 384) splits = 384;
-    }
-    if (splits > 1) {
-        const size_t need = (size_t)splits * a.M * a.N * sizeof(float);
-        if (!ws || ws_bytes < need) {       // shrink to what the workspace allows
-            splits = ws ? (int)(ws_bytes / ((size_t)a.M * a.N * sizeof(float))) : 1;
-            if (splits < 2) splits = 1;
-        }
-    }
-    int kps = ((a.K + splits - 1) / splits + 31) / 32 * 32;      // multiple of both BK values
-    splits = (a.K + kps - 1) / kps;
-    a.splits = splits;
-    a.k_per_split = kps;
-    a.slab = splits > 1 ? (float*)ws : nullptr;
-    set_epilogue_extents<MODE>(a);
-    const dim3 grid(tn, tm, splits);
+    set_splits<MODE>(a, sh, ws);
+    const dim3 grid(sh.grid[0], sh.grid[1], sh.grid[2]);
 #define OTAL_LAUNCH(BM_, WM_, WN_, AV_)                                                                       \
     do {                                                                                                       \
         if (a.prec) hipLaunchKernelGGL((conv_gemm_kernel<BM_, 128, WM_, WN_, MODE, AV_, 1>), grid, dim3(NT), 0, st, a); \
@@ -3260,42 +3184,40 @@ int launch_generic(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     else OTAL_LAUNCH(32, 1, 1, false);
 #undef OTAL_LAUNCH
     if (int e = otal_launch_status()) return e;
-    if (splits > 1) {
-        return launch_splitk_reduce<MODE>(a, st);
-    }
-    return 0;
+    return a.splits > 1 ? launch_splitk_reduce<MODE>(a, st) : 0;
 }
 
 // one step of a plan on fp32-stored tensors (or a bf16-stored output-side tensor: Conv3d_1a's kernels, the direct kernel)
 template <int MODE>
-int launch_kernel(const ConvStep& s, ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_kernel(const ConvStep& s, ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     if constexpr (MODE == MODE_WGRAD) {
         switch (s.kernel) {
-            case CK_CONV1A_WGRAD: return launch_conv1a_wgrad(a, ws, ws_bytes, st);
-            case CK_PROJ_WGRAD: return launch_proj_wgrad(a, st);
-            case CK_WGRAD_DIRECT: return launch_wgrad_direct(a, ws, ws_bytes, st);
-            case CK_WGRAD1X1: return launch_wgrad1x1_wide(a, ws, ws_bytes, st);
-            case CK_WGRAD_VECTOR: return launch_wgrad_vector(a, s.cw, ws, ws_bytes, st);
-            case CK_WGRAD1D: return launch_wgrad1d(a, ws, ws_bytes, st);
+            case CK_CONV1A_WGRAD: return launch_conv1a_wgrad(a, sh, ws, st);
+            case CK_PROJ_WGRAD: return launch_proj_wgrad(a, sh, st);
+            case CK_WGRAD_DIRECT: return launch_wgrad_direct(a, sh, ws, st);
+            case CK_WGRAD1X1: return launch_wgrad1x1_wide(a, sh, ws, st);
+            case CK_WGRAD_VECTOR: return launch_wgrad_vector(a, s.cw, sh, ws, st);
+            case CK_WGRAD1D: return launch_wgrad1d(a, sh, ws, st);
         }
     } else {
         switch (s.kernel) {
-            case CK_PROJ: if constexpr (MODE == MODE_FWD) return launch_proj_fwd(a, ws, ws_bytes, st); break;
-            case CK_CONV1A: if constexpr (MODE == MODE_FWD) return launch_conv1a_direct(a, ws, ws_bytes, st); break;
-            case CK_CONV1D_TILE: return launch_conv1d_tile<MODE>(a, ws, ws_bytes, st);
-            case CK_DIRECT: return launch_direct<MODE>(a, ws, ws_bytes, st);
-            case CK_CHUNKED: return launch_chunked<MODE>(a, ws, ws_bytes, st);
+            case CK_PROJ: if constexpr (MODE == MODE_FWD) return launch_proj_fwd(a, sh, ws, st); break;
+            case CK_CONV1A: if constexpr (MODE == MODE_FWD) return launch_conv1a_direct(a, sh, ws, st); break;
+            case CK_CONV1D_TILE: return launch_conv1d_tile<MODE>(a, sh, ws, st);
+            case CK_DIRECT: return launch_direct<MODE>(a, sh, ws, st);
+            case CK_CHUNKED: return launch_chunked<MODE>(a, sh, ws, st);
         }
     }
-    if (s.kernel == CK_GENERIC) return launch_generic<MODE>(a, ws, ws_bytes, st);
+    if (s.kernel == CK_GENERIC) return launch_generic<MODE>(a, sh, ws, st);
     return OTAL_E_UNSUPPORTED;
 }
 
 // the kernel that served this thread's most recent otal_conv_fwd / _dgrad / _wgrad ("" after a failure): otal_conv_last_kernel()
 thread_local const char* g_last_kernel = "";
 
+// One launch.  pair_kernel: a pair launch has no plan but the one kernel that serves it (and leaves g_last_kernel alone).
 template <int MODE>
-int launch_mode(ConvArgs& a, int precision, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_mode(ConvArgs& a, int precision, void* ws, size_t ws_bytes, hipStream_t st, int pair_kernel = -1) {
     ConvQuery q = {};
     q.g = a.g;
     q.mode = MODE;
@@ -3303,14 +3225,18 @@ int launch_mode(ConvArgs& a, int precision, void* ws, size_t ws_bytes, hipStream
     q.accumulate = (a.flags & EPI_ACCUM) ? 1 : 0;
     q.has_mask = a.emask ? 1 : 0;
     q.x = (uintptr_t)a.x; q.w = (uintptr_t)a.w; q.dy = (uintptr_t)a.dy; q.out = (uintptr_t)a.out; q.mask = (uintptr_t)a.emask;
-    const ConvPlan p = conv_plan(q);
+    q.prologue2 = (uintptr_t)a.pre2; q.pair = a.pair;
+    const ConvPlan p = pair_kernel < 0 ? conv_plan(q) : ConvPlan{1, {{pair_kernel, 0, false}}, conv_step_prologue(pair_kernel)};
     const void* pre = a.pre;
     int e = OTAL_E_UNSUPPORTED;
     for (int i = 0; i < p.n; ++i) {
         const ConvStep& s = p.step[i];
         a.pre = conv_step_prologue(s.kernel) == p.prologue ? pre : nullptr;
-        e = a.xhalf ? otal_conv::launch_half(MODE, s.kernel, s.cw, a, ws, ws_bytes, st) : launch_kernel<MODE>(s, a, ws, ws_bytes, st);
-        if (e == 0) g_last_kernel = conv_kernel_name(s.kernel);
+        q.prologue = (uintptr_t)a.pre;
+        const ConvLaunchShape sh = conv_launch_shape(q, s, ws, ws_bytes);
+        if (sh.refuse) e = OTAL_E_UNSUPPORTED;          // the workspace does not hold the step's tables (or all its slabs)
+        else e = a.xhalf ? otal_conv::launch_half(MODE, s.kernel, s.cw, a, sh, ws, st) : launch_kernel<MODE>(s, a, sh, ws, st);
+        if (e == 0 && pair_kernel < 0) g_last_kernel = conv_kernel_name(s.kernel);
         if (e != OTAL_E_UNSUPPORTED || !s.next) return e;
     }
     return e;
@@ -3323,30 +3249,7 @@ int launch_mode(ConvArgs& a, int precision, void* ws, size_t ws_bytes, hipStream
 extern "C" size_t otal_conv_workspace_bytes(const int* geom, int mode) {
     ConvGeom g;
     if (!geom || fill_geom(g, geom)) return 0;
-    const int kvol = conv_kvol(g);
-    int64_t M, N, K;
-    if (mode == MODE_FWD) { M = g.Cout; N = (int64_t)g.B * conv_out_positions(g); K = (int64_t)g.Cin * kvol; }
-    else if (mode == MODE_DGRAD) { M = g.Cin; N = (int64_t)g.B * conv_in_positions(g); K = (int64_t)g.Cout * kvol; }
-    else {
-        M = g.Cout; N = (int64_t)g.Cin * kvol; K = (int64_t)g.B * conv_out_positions(g);
-        if (g.sw == 2 && g.kw <= 7) N = (int64_t)g.Cin * g.kt * g.kh * 8;      // pair mode pads each kw row to 8 columns
-    }
-    const int BMsel = choose_bm((int)M);
-    const int BN = 128;
-    const int tiles = (int)(((M + BMsel - 1) / BMsel) * ((N + BN - 1) / BN));
-    int s = choose_splits(tiles, (int)K, 0);            // the fp32 rule splits finer: size for it
-    if (mode == MODE_WGRAD) { const int sw = choose_splits(tiles, (int)K, 1, true); if (sw > s) s = sw; }
-    // precision is not an argument here: size for whichever path needs more (generic tap table vs chunk table + packed weights)
-    size_t front = mode == MODE_WGRAD ? ptab_bytes(g, 2) : tab_bytes((int)K);
-    if (mode != MODE_WGRAD) {
-        const int Kc = mode == MODE_FWD && g.Cin * g.kt * g.kh * 8 > K ? g.Cin * g.kt * g.kh * 8 : (int)K;   // kw-vector mode pads kw to 8
-        size_t cf = chunk_tab_bytes(Kc) + chunk_wp_bytes((int)M, BMsel, Kc);
-        if (M % 192 == 0) { const size_t ct = chunk_tab_bytes(Kc) + chunk_wp_bytes((int)M, 192, Kc); if (ct > cf) cf = ct; }
-        if (direct_eligible(g, mode, 1, (int)M)) { const size_t dd = direct_wp_bytes(g, (int)M, mode == MODE_FWD ? g.Cin : g.Cout); if (dd > cf) cf = dd; }
-        if (cf > front) front = cf;
-    }
-    if (mode == MODE_DGRAD) front += align256((size_t)g.Cin * g.Cout * kvol * sizeof(float));    // natural-layout weights on the generic path
-    return front + (s > 1 ? (size_t)(s + 1) * M * N * sizeof(float) : 0);
+    return conv_workspace_bytes(g, mode);
 }
 
 extern "C" int otal_conv_fwd(const int* geom, const int64_t* strides, const float* x, const float* w,
@@ -3440,7 +3343,7 @@ extern "C" int otal_conv_fwd_pair(const int* geom, const int64_t* strides, const
     a.prec = (precision & 1) ? 1 : 0;
     a.pre = prologue ? prologue[0] : nullptr; a.pre2 = prologue ? prologue[1] : nullptr;
     if (!conv1d_tile_eligible(a.g, MODE_FWD, a.prec, a.x, false) || ((uintptr_t)a.x2 & 3)) return OTAL_E_UNSUPPORTED;
-    return launch_conv1d_tile<MODE_FWD>(a, ws, ws_bytes, (hipStream_t)stream);
+    return launch_mode<MODE_FWD>(a, precision, ws, ws_bytes, (hipStream_t)stream, CK_CONV1D_TILE);
 }
 
 extern "C" int otal_conv_dgrad_pair(const int* geom, const int64_t* strides, const float* const* dy, const float* const* w,
@@ -3456,7 +3359,7 @@ extern "C" int otal_conv_dgrad_pair(const int* geom, const int64_t* strides, con
     a.pre = prologue ? prologue[0] : nullptr; a.pre2 = prologue ? prologue[1] : nullptr;
     if (!a.w_natural) return OTAL_E_UNSUPPORTED;            // forward-layout weights only (the prologue re-orders them)
     if (!conv1d_tile_eligible(a.g, MODE_DGRAD, a.prec, a.dy, false) || ((uintptr_t)a.dy2 & 3)) return OTAL_E_UNSUPPORTED;
-    return launch_conv1d_tile<MODE_DGRAD>(a, ws, ws_bytes, (hipStream_t)stream);
+    return launch_mode<MODE_DGRAD>(a, precision, ws, ws_bytes, (hipStream_t)stream, CK_CONV1D_TILE);
 }
 
 extern "C" int otal_conv_wgrad_pair(const int* geom, const int64_t* strides, const float* const* x, const float* const* dy,
@@ -3468,7 +3371,7 @@ extern "C" int otal_conv_wgrad_pair(const int* geom, const int64_t* strides, con
     a.M = a.g.Cout; a.N = a.g.Cin * conv_kvol(a.g); a.K = a.g.B * conv_out_positions(a.g);
     a.prec = (precision & 1) ? 1 : 0;
     if (!wgrad1d_eligible(a.g, a.prec, a.x, a.dy) || !wgrad1d_eligible(a.g, a.prec, a.x2, a.dy2)) return OTAL_E_UNSUPPORTED;
-    return launch_wgrad1d(a, ws, ws_bytes, (hipStream_t)stream);
+    return launch_mode<MODE_WGRAD>(a, precision, ws, ws_bytes, (hipStream_t)stream, CK_WGRAD1D);
 }
 
 // 1 when this geometry has a kernel for the bf16-STORED large operand (precision bit 2): fwd -> y, wgrad / dgrad -> dy.

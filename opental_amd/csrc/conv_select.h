@@ -1,8 +1,11 @@
 // opental_amd/csrc/conv_select.h -- which kernel serves a convolution launch: every predicate the choice reads, the sizes of
-// the tables and weight packs it implies, and conv_plan(), the one place the order of the kernels is written down.
-// Shared by conv_gemm.hip (the launches, the prologue and storage queries), conv1a_tile.hip, and a plain-C++ CPU harness
-// (tests/cpu_conv_select.cpp) that pins the choice per layer of the model.  No HIP types in here.
+// the tables and weight packs it implies, conv_plan(), the one place the order of the kernels is written down, and
+// conv_launch_shape(): the tiles, grid, split-K and cut of the workspace of one step, which the launchers of conv_gemm.hip
+// and its .inc files take from here (conv1x1_stream.inc and conv1a_tile.hip shape their own launches).
+// Shared by conv_gemm.hip (the launches, the prologue, storage and workspace queries), conv1a_tile.hip, and a plain-C++ CPU
+// harness (tests/cpu_conv_select.cpp) that pins choice and shape per layer of the model.  No HIP types in here.
 #pragma once
+#include <initializer_list>
 #include <stddef.h>
 #include <stdint.h>
 #include "conv_index.h"
@@ -15,6 +18,7 @@ enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_WGRAD = 2 };
 // tile constants the predicates read; the kernels take them from here
 constexpr int C1_TT = 2, C1_TR = 2, C1_WO = 48;     // Conv3d_1a direct kernel: output planes x rows x columns per tile
 constexpr int C1T_TT = 4, C1T_TR = 4;               // Conv3d_1a tiled kernel (conv1a_tile.hip): output planes x rows per tile
+constexpr int C1_STEPS = 49;                        // Conv3d_1a, both kernels: (dt, dh) K steps of 64 bytes per packed weight row
 constexpr int W1_TC = 128;                          // 1-D weight gradient: positions per chunk
 constexpr int PJ_HW = 36;                           // projection forward: the 6 x 6 plane the kernel collapses
 constexpr int PW_KS = 32;                           // projection weight gradient: frames per K step
@@ -33,6 +37,7 @@ static inline size_t chunk_wp_bytes(int M, int BM, int K) {      // + one K step
 static inline size_t ptab_bytes(const ConvGeom& g, int cw) {
     return align256(((size_t)g.B * conv_out_positions(g) / cw + PTAB_PAD) * (2 * sizeof(int)));
 }
+static inline size_t conv1a_wp_bytes(int M) { return align256((size_t)((M + 63) / 64 * 64) * C1_STEPS * 64); }
 // extent in bytes of the tensor the gather reads (channel-sliced views: strides come from the caller)
 static inline int64_t gather_extent_bytes(const ConvGeom& g, int mode, int esz = 4) {
     if (mode == MODE_FWD) return esz * ((int64_t)(g.B - 1) * g.x_bs + (int64_t)(g.Cin - 1) * g.x_cs + conv_in_positions(g));
@@ -75,6 +80,87 @@ static inline int choose_splits(int tiles, int K, int prec = 1, bool wgrad = fal
     int s = want < maxs ? want : maxs;
     return s < 1 ? 1 : (s > cap ? cap : s);
 }
+
+// ---- the splits each kernel wants (and the tile counts they follow from)
+// the generic kernel gets the bf16 weight gradients of the 1-D pyramid / head layers (126 positions per sample: no vector
+// path): K = B * 126 positions, a few dozen tiles -- latency-bound K steps, so split down to 4 K steps per split
+static inline int generic_wgrad_splits(int tiles, int K) {
+    const int ms = 4;      // measured: 8 -> 474.6, 4 -> 478.3, 2 -> 478.0, 1 -> 476.3 clips/s
+    const int tg = 512;
+    int want = (tg + tiles - 1) / tiles, maxs = K / (ms * 32);
+    if (maxs < 1) maxs = 1;
+    const int s = tiles >= tg * 3 / 4 ? 1 : (want < maxs ? want : maxs);
+    return s > 384 ? 384 : s;
+}
+// wide 1x1x1 weight gradient, row-block height in 32-row tiles: few row blocks first (each re-reads x), then little padding
+// Row blocks of at most 4 x 32.  Alone, the tallest block that covers M is the fastest (Mixed_3c:
+// <9> 35 us against ~45 for <4>) -- but these launches run on the weight-gradient lane BESIDE the data-gradient lane's
+// kernels, and a 512-thread workgroup at 234 VGPRs (<9>) needs an EMPTY compute unit: it only got one when the main
+// lane's kernel ran out of workgroups (35 us alone, 370 us beside Conv3d_2c's data gradient in the lane timeline), and the
+// backlog surfaced as the step's one-lane tail.  <4> (118 VGPRs, 61 KB of LDS) fits the slot one retiring workgroup of
+// the direct 3x3x3 kernel leaves (8 waves x 104-120 VGPRs, 70 KB).  Step, one box: cap 9 / 5 / 4 / 3 / 2 =
+// 928 / 935 / 939 / 926 / 931 clips/s.
+static inline int wgrad1x1_mt(int M) {
+    const int cand[3] = {4, 3, 2};
+    int mt = 2, best = 1 << 30;
+    for (int i = 0; i < 3; ++i) {
+        const int rb = cand[i] * 32, blocks = (M + rb - 1) / rb;
+        const int cost = blocks * 256 + blocks * rb;
+        if (cost < best) { best = cost; mt = cand[i]; }
+    }
+    return mt;
+}
+// one round of workgroups, >= 8 K steps per split
+static inline int wgrad1x1_splits(int mt, int tiles, int K) {
+    const int wgs = (mt <= 2 ? 2 : 1) * 256;              // the 64-row variant fits twice per CU: twice the loads in flight
+    int splits = tiles >= wgs ? 1 : wgs / tiles;
+    if (splits > K / (8 * 32)) splits = K / (8 * 32) > 0 ? K / (8 * 32) : 1;
+    return splits;
+}
+// direct 3x3x3 weight gradient: tile height, rows per K step, K steps, wanted splits
+// 64-row tiles: a 96-row tile (192 accumulator registers) spills 19 registers on 24-wide planes, and where it fits
+// (12-wide planes) it measured slower (Mixed_3c b1b: 0.505 vs 0.443 ms)
+// The 6x6 and 3x3 planes take 32-row tiles: half the accumulators (116-146 VGPRs instead of ~200: a workgroup that fits
+// beside the other lane's, see wgrad1x1.inc) for twice the workgroups re-reading x.  Step, one box, 32-row tiles on none /
+// 6x6 / 12x12 / both = 942 / 949 / 941 / 938 clips/s -- the five 6x6 layers (Mixed_4b..4f, issued beside the module's data
+// gradients) gain, the 12x12 ones lose more alone than the fit returns, Conv3d_2c's runs in the one-lane tail.
+static inline int wgrad_direct_rows(const ConvGeom& g) { return g.Wi == 24 ? (g.Hi % 8 == 0 ? 8 : 4) : g.Wi; }     // rows per K step
+struct WgradDirectShape { int BM, steps, want; };
+static inline WgradDirectShape wgrad_direct_shape(const ConvGeom& g, int M) {
+    WgradDirectShape d;
+    const bool planes6 = g.Wi == 6, planes3 = g.Wi == 3;
+    d.BM = planes6 || planes3 ? 32 : 64;
+    d.steps = planes3 ? g.B * (g.Ti / 16) : planes6 ? g.B * (g.Ti / 4) : g.B * g.Ti * (g.Hi / wgrad_direct_rows(g));       // ordered (sample, row block, t), t fastest; 6x6: four planes a step, 3x3: sixteen
+    // one 512-thread workgroup per CU is resident (its registers fill the CU): aim at one full round of 256 workgroups,
+    // >= 8 K steps per split, slabs <= the workspace
+    const int tiles = (M + d.BM - 1) / d.BM * ((g.Cin + 31) / 32);
+    int splits = tiles >= 256 ? 1 : 256 / tiles;            // never 257 workgroups: the 257th would wait for a whole round
+    const int target = OTAL_OPT("OTAL_WDIRECT_BLOCKS");
+    if (target > 0) splits = target / tiles > 0 ? target / tiles : 1;
+    const int min_steps = planes3 || planes6 ? 4 : 8;
+    if (splits > d.steps / min_steps) splits = d.steps / min_steps > 0 ? d.steps / min_steps : 1;
+    d.want = splits;
+    return d;
+}
+// Conv3d_1a's weight gradient: 2 x 2 x 48 output blocks, and
+// 7 taps x S splits workgroups, two resident per CU (registers): 7 x 73 = 511 of 512 slots
+// (measured on the b = 8 layer: 36 splits 0.87 ms, 73: 0.81, 109: 0.93, 146: 0.89; the pair-mode kernel: 1.05)
+static inline int conv1a_wgrad_blocks(const ConvGeom& g) { return g.B * (g.To / 2) * (g.Ho / 2); }
+static inline int conv1a_wgrad_splits(int nblocks) {
+    const int splits = OTAL_OPT("OTAL_W1A_SPLITS") > 0 ? OTAL_OPT("OTAL_W1A_SPLITS") : 73;
+    return splits > nblocks ? nblocks : splits;
+}
+// projection forward: split the channels so that ~512 workgroups (two per CU: 78 KB of LDS each) share the 61 MB of weights
+static inline int proj_fwd_splits(int Cin, int tiles) {
+    int splits = (512 + tiles - 1) / tiles;
+    while (splits > 1 && (Cin % (4 * splits) != 0)) --splits;
+    return splits;
+}
+// 1-D weight gradient: units per workgroup = (sample, chunk) units folded into one split-K slab.  Round 2 (every reduction its own launch behind
+// its GEMM, one lane): 1 -> 478.4, 2 -> 475.8, 4 -> 465.7 clips/s.  Round 6 (reductions batched on the weight-gradient lane, whose
+// slab traffic is what these eight launches cost -- 328 MB written, 328 MB read back per step): 1 / 2 / 4 / 8 -> 8.09 / 8.03 /
+// 8.02 / 8.02 ms.  Four where there are eight units or more (two slabs at b = 8), two from four units on.
+static inline int wgrad1d_upw(int units) { return units >= 8 ? 4 : units >= 4 ? 2 : 1; }
 
 // ---- Conv3d_1a (7x7x7, stride 2, 3 input channels): direct forward, its tiled form, the weight gradient
 static inline bool conv1a_half_out_ok(const ConvGeom& g, const void* y) {
@@ -303,6 +389,8 @@ struct ConvQuery {
     int accumulate;
     int has_mask;           // dgrad: a fused ReLU / BN mask
     uintptr_t x, w, dy, out, mask;     // out: fwd y, dgrad dx, wgrad dW
+    uintptr_t prologue, prologue2;     // the caller's persistent region(s) where the step reads one (conv_launch_shape only)
+    int pair;               // a pair launch: two problems of this geometry in one grid (conv_launch_shape only)
 };
 struct ConvStep {
     int kernel;             // ConvKernel
@@ -332,20 +420,6 @@ static inline int conv_prologue_layout(const ConvGeom& g, int mode, int prec) {
     if (direct_eligible(g, mode, prec, mode == MODE_FWD ? g.Cout : g.Cin)) return PRO_DIRECT;
     return chunk_eligible(g, mode, prec) ? PRO_CHUNK : PRO_NONE;
 }
-// bytes of that prologue region (0: none)
-static inline size_t conv_prologue_bytes(const ConvGeom& g, int mode, int prec) {
-    const int layout = conv_prologue_layout(g, mode, prec);
-    const int M = mode == MODE_FWD ? g.Cout : g.Cin;
-    if (layout == PRO_CHUNK) {
-        const bool kwv = mode == MODE_FWD && (g.Cin % 8) != 0;        // kw-vector mode: kw padded to 8 taps
-        const int K = mode == MODE_FWD ? (kwv ? g.Cin * g.kt * g.kh * 8 : g.Cin * conv_kvol(g)) : g.Cout * conv_kvol(g);
-        return chunk_tab_bytes(K) + chunk_wp_bytes(M, choose_bm(M, !kwv), K);
-    }
-    if (layout == PRO_PTAB) return ptab_bytes(g, g.sw == 2 ? 8 : wgrad_vector_width(g, prec));
-    if (layout == PRO_DIRECT) return direct_wp_bytes(g, M, mode == MODE_FWD ? g.Cin : g.Cout);
-    return 0;
-}
-
 // bf16-stored tensors on BOTH sides of a backbone layer (fwd: x and y; dgrad: dy, dx and the ReLU mask; wgrad: x and dy)
 static inline void conv_plan_half(const ConvQuery& q, ConvPlan& p) {
     const ConvGeom& g = q.g;
@@ -369,7 +443,7 @@ static inline void conv_plan_half(const ConvQuery& q, ConvPlan& p) {
     if (cw) add(CK_WGRAD_VECTOR, false, cw);
 }
 
-// The kernels that serve a launch, first to last (the launchers choose tile shapes and splits inside one kernel).
+// The kernels that serve a launch, first to last (tile shapes and splits inside one kernel: conv_launch_shape, below).
 static inline ConvPlan conv_plan(const ConvQuery& q) {
     ConvPlan p = {};
     const ConvGeom& g = q.g;
@@ -421,6 +495,169 @@ static inline int conv_half_storage(const ConvGeom& g, int mode, int precision) 
     for (int i = 0; i < p.n; ++i)
         if (p.step[i].kernel != CK_PROJ) return 1;
     return 0;
+}
+
+// ---- one step's launch: tiles, grid, split-K and the cut of the workspace, [front][slabs]
+}  // namespace
+struct ConvLaunchShape {    // (a type with linkage: conv_gemm.hip hands it across its two translation units)
+    size_t front_bytes;     // tables and packs the launcher builds at the front: tap table, chunk table + weight pack, position
+                            // table, a weight pack (0: nothing, or the caller's prologue region applies)
+    size_t second_at;       // where the launch's second piece starts: the tap table behind the generic data gradient's W^T pack
+                            // (forward-layout weights); a pair launch's second chunk region, or its second problem's slabs
+    int N, K;               // the GEMM as this kernel sees it (kw-vector mode pads K, the weight gradient's pair mode pads N)
+    int bm, tm, tn, grid[3];    // tile height, row and column tiles, the main kernel's grid (Conv3d_1a: the untiled kernel's)
+    int units, splits, per_split;   // what split-K divides (K, padded K, K steps, blocks, (sample, chunk) units, channels) and how
+    size_t slab_bytes;      // all slabs, behind the front
+    bool refuse;            // the workspace is too small for the step: OTAL_E_UNSUPPORTED
+};
+namespace {
+
+// The one carve: take n bytes off what is left of the workspace, or refuse the step.
+static inline size_t shape_take(ConvLaunchShape& s, size_t& left, size_t n) {
+    if (left < n) s.refuse = true; else left -= n;
+    return n;
+}
+// The one split-K rule.  The launch wants `want` splits of `units`, each a multiple of `round` units, one slab of M x N floats
+// per split in the workspace that is left (a null workspace holds nothing): clamp to what fits (fewer than two slabs, or
+// not all of them where a smaller split count would not divide the units: no split), divide the units evenly, drop the
+// splits the rounding left empty.  The splits are the grid's z.
+static inline void fit_splits(ConvLaunchShape& s, int M, int want, int units, int round, const void* ws, size_t ws_bytes, bool all_or_none = false) {
+    const size_t slab1 = (size_t)M * s.N * sizeof(float);
+    if (!ws) ws_bytes = 0;
+    if (want > 1 && ws_bytes < (size_t)want * slab1) want = all_or_none ? 1 : (int)(ws_bytes / slab1);
+    if (want < 2) want = 1;
+    s.units = units;
+    s.per_split = ((units + want - 1) / want + round - 1) / round * round;
+    s.splits = s.grid[2] = (units + s.per_split - 1) / s.per_split;
+    s.slab_bytes = s.splits > 1 ? (size_t)s.splits * slab1 : 0;
+}
+// tile height and column tiles; the grid is (column tiles, row tiles, splits) unless the kernel lays it out otherwise
+static inline int shape_tiles(ConvLaunchShape& s, int M, int bm, int tn) {
+    s.bm = bm; s.tm = (M + bm - 1) / bm; s.tn = tn;
+    s.grid[0] = tn; s.grid[1] = s.tm; s.grid[2] = 1;
+    return s.tm * tn;
+}
+
+// What the launch offers: ws_bytes at ws (null: nothing).  Every step of a plan is offered the whole workspace.  (bf16
+// tensors, 1x1x1 layers: where conv1x1_stream.inc serves, it shapes its own launch; this is the tile kernel behind it.)
+static inline ConvLaunchShape conv_launch_shape(const ConvQuery& q, const ConvStep& step, const void* ws, size_t ws_bytes) {
+    ConvLaunchShape s = {};
+    const ConvGeom& g = q.g;
+    const int mode = q.mode, prec = q.precision & 1, kvol = conv_kvol(g), P = (int)conv_out_positions(g);
+    const int M = mode == MODE_DGRAD ? g.Cin : g.Cout, C = mode == MODE_FWD ? g.Cin : g.Cout;
+    s.N = mode == MODE_FWD ? g.B * P : mode == MODE_DGRAD ? g.B * (int)conv_in_positions(g) : g.Cin * kvol;
+    s.K = mode == MODE_WGRAD ? g.B * P : C * kvol;
+    s.splits = 1;
+    size_t left = ws ? ws_bytes : 0;
+    switch (step.kernel) {
+        case CK_GENERIC: {
+            if (mode == MODE_DGRAD && (q.precision & 2)) s.second_at = align256((size_t)g.Cin * g.Cout * kvol * sizeof(float));
+            s.front_bytes = shape_take(s, left, s.second_at + (mode != MODE_WGRAD ? tab_bytes(s.K) : 0));
+            const int tiles = shape_tiles(s, M, choose_bm(M), (s.N + 127) / 128);
+            fit_splits(s, M, mode == MODE_WGRAD && prec ? generic_wgrad_splits(tiles, s.K) : choose_splits(tiles, s.K, prec), s.K, 32, ws, left);
+            break;
+        }
+        case CK_CHUNKED: case CK_CONV1D_TILE: {
+            const bool kwv = mode == MODE_FWD && (C % 8) != 0, pair = step.kernel == CK_CONV1D_TILE && q.pair;
+            if (kwv) s.K = g.Cin * g.kt * g.kh * 8;         // kw padded to 8 taps per (ci, dt, dh) row
+            const int BMpack = choose_bm(M, !kwv);          // the weight pack's row padding (persistent regions are sized by it)
+            const size_t region = chunk_tab_bytes(s.K) + chunk_wp_bytes(M, BMpack, s.K);
+            s.second_at = q.prologue ? 0 : region;          // (a pair launch builds the second problem's region behind the first)
+            s.front_bytes = shape_take(s, left, s.second_at + (pair && !q.prologue2 ? region : 0));
+            if (step.kernel == CK_CONV1D_TILE) {
+                shape_tiles(s, M, 32, g.B * ((g.Ti + 63) / 64));
+                s.grid[0] = s.tm; s.grid[1] = s.tn; s.grid[2] = pair ? 2 : 1;
+                break;
+            }
+            // bf16 tensors: the 128-row variant needs 247 registers (two workgroups per CU), the 96-row one 105 (four); rows past the
+            // pack's padding read zeros through the buffer bounds check, so a different tile height may run on the same pack
+            const int tiles = shape_tiles(s, M, (q.precision & 8) && BMpack == 128 ? 96 : BMpack, (s.N + 127) / 128);
+            fit_splits(s, M, choose_splits(tiles, chunk_kp(s.K)), chunk_kp(s.K), 32, ws, left);
+            break;
+        }
+        case CK_DIRECT:
+            if (!direct_bnp(g, M)) { s.refuse = true; break; }
+            s.front_bytes = shape_take(s, left, q.prologue ? 0 : direct_wp_bytes(g, M, C));
+            shape_tiles(s, M, direct_bm(g, M), s.N / direct_bnp(g, M));
+            break;
+        case CK_CONV1A:         // the untiled kernel's grid; both kernels pack the weights into the same bytes
+            s.front_bytes = shape_take(s, left, conv1a_wp_bytes(M));
+            shape_tiles(s, M, 64, g.B * (g.To / C1_TT) * (g.Ho / C1_TR));
+            break;
+        case CK_PROJ: {         // a channel split that does not divide Cin is no split: all the wanted slabs, or none
+            const int tiles = shape_tiles(s, M, 64, g.B * ((g.To + 63) / 64));
+            fit_splits(s, M, proj_fwd_splits(g.Cin, tiles), g.Cin, 1, ws, left, true);
+            s.grid[0] = s.splits; s.grid[1] = s.tm; s.grid[2] = s.tn;
+            break;
+        }
+        case CK_CONV1A_WGRAD:
+            fit_splits(s, M, conv1a_wgrad_splits(conv1a_wgrad_blocks(g)), conv1a_wgrad_blocks(g), 1, ws, left);
+            s.grid[0] = 7; s.grid[1] = s.splits; s.grid[2] = 1;
+            break;
+        case CK_PROJ_WGRAD:
+            shape_tiles(s, M, 128, (s.N + 127) / 128);
+            s.grid[0] = 8 * ((s.tn + 7) / 8) * s.tm; s.grid[1] = 1;
+            break;
+        case CK_WGRAD_DIRECT: {
+            const WgradDirectShape d = wgrad_direct_shape(g, M);
+            shape_tiles(s, M, d.BM, (g.Cin + 31) / 32);
+            fit_splits(s, M, d.want, d.steps, 1, ws, left);
+            break;
+        }
+        case CK_WGRAD1X1: {
+            const int tiles = shape_tiles(s, M, wgrad1x1_mt(M) * 32, (s.N + 255) / 256);
+            fit_splits(s, M, wgrad1x1_splits(s.bm / 32, tiles, s.K), s.K, 32, ws, left);
+            break;
+        }
+        case CK_WGRAD_VECTOR: {
+            if (g.sw == 2) s.N = g.Cin * g.kt * g.kh * 8;   // pair mode: columns padded to 8 per (ci, dt, dh) row
+            s.front_bytes = shape_take(s, left, q.prologue ? 0 : ptab_bytes(g, step.cw));
+            const int tiles = shape_tiles(s, M, choose_bm(M), (s.N + 127) / 128);
+            fit_splits(s, M, choose_splits(tiles, s.K, 1, true), s.K, 32, ws, left);
+            break;
+        }
+        case CK_WGRAD1D:        // a workgroup walks wgrad1d_upw() units whatever the workspace: all the slabs (256-byte aligned), or refuse
+            shape_tiles(s, M, 64, g.Cin / 64);
+            s.units = g.B * wgrad1d_chunks(g);
+            s.per_split = wgrad1d_upw(s.units);
+            s.splits = (s.units + s.per_split - 1) / s.per_split;
+            s.second_at = align256((size_t)s.splits * M * s.N * sizeof(float));
+            s.slab_bytes = shape_take(s, left, s.second_at * (q.pair ? 2 : 1));
+            s.grid[0] = s.splits; s.grid[1] = s.tn; s.grid[2] = s.tm * (q.pair ? 2 : 1);
+            break;
+        default: s.refuse = true;
+    }
+    return s;
+}
+
+// bytes of the geometry's prologue region (0: none): the front the kernel of that layout would otherwise build
+static inline size_t conv_prologue_bytes(const ConvGeom& g, int mode, int prec) {
+    const int layout = conv_prologue_layout(g, mode, prec);
+    ConvQuery q = {};
+    q.g = g; q.mode = mode; q.precision = prec;
+    const ConvStep step = {layout == PRO_CHUNK ? CK_CHUNKED : layout == PRO_PTAB ? CK_WGRAD_VECTOR : CK_DIRECT, g.sw == 2 ? 8 : wgrad_vector_width(g, prec), false};
+    return layout == PRO_NONE ? 0 : conv_launch_shape(q, step, &q, ~(size_t)0 >> 1).front_bytes;
+}
+
+// Bytes of workspace with which every kernel of this geometry's plans takes all the splits it wants: the largest front plus
+// slabs over the steps of the plans for contiguous, aligned tensors -- fp32 and bf16 operands, fp32- and bf16-stored
+// tensors, the data gradient from forward-layout weights.  (A pair launch of a 1-D layer takes twice its bytes; a strided
+// or misaligned view whose plan differs from the contiguous one may be served with fewer splits at this size.)
+static inline size_t conv_workspace_bytes(const ConvGeom& geom, int mode) {
+    ConvQuery q = {};
+    q.g = geom; q.mode = mode;
+    q.g.x_cs = conv_in_positions(geom); q.g.x_bs = geom.Cin * q.g.x_cs;
+    q.g.y_cs = conv_out_positions(geom); q.g.y_bs = geom.Cout * q.g.y_cs;
+    size_t need = 0;
+    for (const int precision : {0, 1, 1 | 4, 1 | 4 | 8 | 16}) {
+        q.precision = precision | (mode == MODE_DGRAD ? 2 : 0);
+        const ConvPlan p = conv_plan(q);
+        for (int j = 0; j < p.n; ++j) {
+            const ConvLaunchShape s = conv_launch_shape(q, p.step[j], &q, ~(size_t)0 >> 1);
+            if (s.front_bytes + s.slab_bytes > need) need = s.front_bytes + s.slab_bytes;
+        }
+    }
+    return need;
 }
 
 }  // namespace

@@ -699,92 +699,41 @@ template <int BM, int PW, int PR, bool H>
 static int launch_wd3(const WD3Args& d, dim3 grid, hipStream_t st) {
     constexpr int XB = 4 * (PR + 2) * (PW + 2) * 64, AB = BM * (PR * PW * 2 + 16);
     constexpr int lds = XB + 2 * AB;
-    static bool configured = false;            // once per instantiation (the attribute is per kernel function)
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_direct_kernel<BM, PW, PR, H>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
-    hipLaunchKernelGGL((conv3_wgrad_direct_kernel<BM, PW, PR, H>), grid, dim3(512), lds, st, d);
-    return otal_launch_status();
+    return launch_big_lds<conv3_wgrad_direct_kernel<BM, PW, PR, H>>(lds, grid, 512, st, d);
 }
 
 template <int BM, bool H>
 static int launch_wd6(const WD3Args& d, dim3 grid, hipStream_t st) {
     constexpr int lds = 16 * 4096 + 2 * BM * (144 * 2 + 16);
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_planes6_kernel<BM, H>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
-    hipLaunchKernelGGL((conv3_wgrad_planes6_kernel<BM, H>), grid, dim3(512), lds, st, d);
-    return otal_launch_status();
+    return launch_big_lds<conv3_wgrad_planes6_kernel<BM, H>>(lds, grid, 512, st, d);
 }
 
 template <int BM, bool H>
 static int launch_wd3p(const WD3Args& d, dim3 grid, hipStream_t st) {
     constexpr int lds = 2 * 18 * 25 * 64 + 2 * BM * (144 * 2 + 16);
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_wgrad_planes3_kernel<BM, H>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
-    hipLaunchKernelGGL((conv3_wgrad_planes3_kernel<BM, H>), grid, dim3(512), lds, st, d);
-    return otal_launch_status();
+    return launch_big_lds<conv3_wgrad_planes3_kernel<BM, H>>(lds, grid, 512, st, d);
 }
 
 template <bool H = false>
-int launch_wgrad_direct(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_wgrad_direct(ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     const ConvGeom& g = a.g;
-    // 64-row tiles: a 96-row tile (192 accumulator registers) spills 19 registers on 24-wide planes, and where it fits
-    // (12-wide planes) it measured slower (Mixed_3c b1b: 0.505 vs 0.443 ms)
-    // The 6x6 and 3x3 planes take 32-row tiles: half the accumulators (116-146 VGPRs instead of ~200: a workgroup that fits
-    // beside the other lane's, see wgrad1x1.inc) for twice the workgroups re-reading x.  Step, one box, 32-row tiles on none /
-    // 6x6 / 12x12 / both = 942 / 949 / 941 / 938 clips/s -- the five 6x6 layers (Mixed_4b..4f, issued beside the module's data
-    // gradients) gain, the 12x12 ones lose more alone than the fit returns, Conv3d_2c's runs in the one-lane tail.
     const bool planes6 = g.Wi == 6, planes3 = g.Wi == 3;
-    const int BM = planes6 || planes3 ? 32 : 64;
-    const int tm = (a.M + BM - 1) / BM, tc = (g.Cin + 31) / 32;
+    const int PRr = wgrad_direct_rows(g);      // (tile height, K steps and splits: conv_select.h, wgrad_direct_shape)
     WD3Args d;
-    const int PRr = g.Wi == 24 ? (g.Hi % 8 == 0 ? 8 : 4) : g.Wi;     // rows per K step
     d.HB = g.Hi / PRr;
-    d.steps = planes3 ? g.B * (g.Ti / 16) : planes6 ? g.B * (g.Ti / 4) : g.B * g.Ti * d.HB;       // ordered (sample, row block, t), t fastest; 6x6: four planes a step, 3x3: sixteen
-    // one 512-thread workgroup per CU is resident (its registers fill the CU): aim at one full round of 256 workgroups,
-    // >= 8 K steps per split, slabs <= the workspace
-    const int tiles = tm * tc;
-    int splits = tiles >= 256 ? 1 : 256 / tiles;            // never 257 workgroups: the 257th would wait for a whole round
-    const int target = OTAL_OPT("OTAL_WDIRECT_BLOCKS");
-    if (target > 0) splits = target / tiles > 0 ? target / tiles : 1;
-    const int min_steps = planes3 || planes6 ? 4 : 8;
-    if (splits > d.steps / min_steps) splits = d.steps / min_steps > 0 ? d.steps / min_steps : 1;
-    const size_t slab1 = (size_t)a.M * a.N * sizeof(float);
-    if (splits > 1 && (!ws || ws_bytes < (size_t)splits * slab1)) {
-        splits = ws ? (int)(ws_bytes / slab1) : 1;
-        if (splits < 2) splits = 1;
-    }
-    d.sps = (d.steps + splits - 1) / splits;
-    splits = (d.steps + d.sps - 1) / d.sps;
-    a.splits = splits;
-    a.k_per_split = d.sps;
-    a.slab = splits > 1 ? (float*)ws : nullptr;
+    d.steps = sh.units;
+    d.sps = sh.per_split;
     a.fd = make_conv_fastdiv(g);
     a.src_bytes = (unsigned)gather_extent_bytes(g, MODE_FWD, H ? 2 : 4);
     a.dy_bytes = (unsigned)gather_extent_bytes(g, MODE_DGRAD, H ? 2 : 4);
-    set_epilogue_extents<MODE_WGRAD>(a);
-    if ((splits > 1 ? a.slab_bytes : a.out_bytes) == 0u) return OTAL_E_UNSUPPORTED;      // 32-bit store offsets
+    if (!set_splits<MODE_WGRAD>(a, sh, ws)) return OTAL_E_UNSUPPORTED;      // 32-bit store offsets
     d.c = a;
-    const dim3 grid(tc, tm, splits);
+    const dim3 grid(sh.grid[0], sh.grid[1], sh.grid[2]);
     int e;
     if (planes3) e = launch_wd3p<32, H>(d, grid, st);
     else if (planes6) e = launch_wd6<32, H>(d, grid, st);
     else if (g.Wi == 24) e = PRr == 8 ? launch_wd3<64, 24, 8, H>(d, grid, st) : launch_wd3<64, 24, 4, H>(d, grid, st);
     else e = launch_wd3<64, 12, 12, H>(d, grid, st);    // whole 12x12 planes: 9 k16 steps per barrier (4 rows: 3 steps, 0.44 -> ms)
     if (e) return e;
-    if (splits > 1) return launch_splitk_reduce<MODE_WGRAD>(a, st);
-    return 0;
+    return a.splits > 1 ? launch_splitk_reduce<MODE_WGRAD>(a, st) : 0;
 }

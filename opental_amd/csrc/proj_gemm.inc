@@ -109,25 +109,16 @@ __global__ __launch_bounds__(256) void proj_fwd_kernel(const ConvArgs a, int ci_
     }
 }
 
-int launch_proj_fwd(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_proj_fwd(ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     const ConvGeom& g = a.g;
-    const int tm = (a.M + 63) / 64, nb = g.B * ((g.To + 63) / 64);
-    // split the channels so that ~512 workgroups (two per CU: 78 KB of LDS each) share the 61 MB of weights
-    int splits = (512 + tm * nb - 1) / (tm * nb);
-    while (splits > 1 && (g.Cin % (4 * splits) != 0)) --splits;
-    const size_t slab1 = (size_t)a.M * a.N * sizeof(float);
-    if (splits > 1 && (!ws || ws_bytes < (size_t)splits * slab1)) splits = 1;
-    a.splits = splits;
-    a.k_per_split = 0;
-    a.slab = splits > 1 ? (float*)ws : nullptr;
     a.fd = make_conv_fastdiv(g);
     a.src_bytes = (unsigned)gather_extent_bytes(g, MODE_FWD);
     a.wp_bytes = (unsigned)(4 * (int64_t)g.Cout * g.Cin * PJ_HW);
-    set_epilogue_extents<MODE_FWD>(a);
-    if ((splits > 1 ? a.slab_bytes : a.out_bytes) == 0u) return OTAL_E_UNSUPPORTED;
-    hipLaunchKernelGGL(proj_fwd_kernel, dim3(splits, tm, nb), dim3(256), 0, st, a, g.Cin / splits);
+    if (!set_splits<MODE_FWD>(a, sh, ws)) return OTAL_E_UNSUPPORTED;    // (the channels per split: conv_select.h, proj_fwd_splits)
+    a.k_per_split = 0;
+    hipLaunchKernelGGL(proj_fwd_kernel, dim3(sh.grid[0], sh.grid[1], sh.grid[2]), dim3(256), 0, st, a, sh.per_split);
     if (int e = otal_launch_status()) return e;
-    if (splits > 1) return launch_splitk_reduce<MODE_FWD>(a, st);
+    if (a.splits > 1) return launch_splitk_reduce<MODE_FWD>(a, st);
     return 0;
 }
 
@@ -294,16 +285,14 @@ __global__ __launch_bounds__(256) void proj_wgrad_kernel(const ConvArgs a, int H
         }
 }
 
-int launch_proj_wgrad(ConvArgs& a, hipStream_t st) {
+int launch_proj_wgrad(ConvArgs& a, const ConvLaunchShape& sh, hipStream_t st) {
     const ConvGeom& g = a.g;
     const int HW = g.Hi * g.Wi;
     a.src_bytes = (unsigned)gather_extent_bytes(g, MODE_FWD);
     a.dy_bytes = (unsigned)gather_extent_bytes(g, MODE_DGRAD);
-    a.splits = 1; a.k_per_split = 0; a.slab = nullptr;
-    set_epilogue_extents<MODE_WGRAD>(a);
-    if (a.out_bytes == 0u) return OTAL_E_UNSUPPORTED;
-    const int tilesM = (a.M + 127) / 128, tilesN = (a.N + 127) / 128;
-    const dim3 grid((unsigned)(8 * ((tilesN + 7) / 8) * tilesM));
+    if (!set_splits<MODE_WGRAD>(a, sh, nullptr)) return OTAL_E_UNSUPPORTED;
+    const int tilesM = sh.tm, tilesN = sh.tn;
+    const dim3 grid((unsigned)sh.grid[0]);
     if (HW % 4 == 0) hipLaunchKernelGGL(proj_wgrad_kernel<true>, grid, dim3(256), 0, st, a, HW, tilesM, tilesN);
     else hipLaunchKernelGGL(proj_wgrad_kernel<false>, grid, dim3(256), 0, st, a, HW, tilesM, tilesN);
     return otal_launch_status();

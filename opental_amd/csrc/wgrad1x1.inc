@@ -112,57 +112,19 @@ __global__ __launch_bounds__(512) void wgrad1x1_wide_kernel(const ConvArgs a) {
 template <int MT, bool H>
 static int launch_w1x1(const ConvArgs& a, dim3 grid, hipStream_t st) {
     constexpr int lds = 2 * (MT * 32 + 256) * 80;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1x1_wide_kernel<MT, H>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        configured = true;
-    }
-    hipLaunchKernelGGL((wgrad1x1_wide_kernel<MT, H>), grid, dim3(512), lds, st, a);
-    return otal_launch_status();
+    return launch_big_lds<wgrad1x1_wide_kernel<MT, H>>(lds, grid, 512, st, a);
 }
 
 template <bool H = false>
-int launch_wgrad1x1_wide(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_wgrad1x1_wide(ConvArgs& a, const ConvLaunchShape& sh, void* ws, hipStream_t st) {
     const ConvGeom& g = a.g;
-    // row-block height: few row blocks first (each re-reads x), then little padding
-    // Row blocks of at most 4 x 32.  Alone, the tallest block that covers M is the fastest (Mixed_3c:
-    // <9> 35 us against ~45 for <4>) -- but these launches run on the weight-gradient lane BESIDE the data-gradient lane's
-    // kernels, and a 512-thread workgroup at 234 VGPRs (<9>) needs an EMPTY compute unit: it only got one when the main
-    // lane's kernel ran out of workgroups (35 us alone, 370 us beside Conv3d_2c's data gradient in the lane timeline), and the
-    // backlog surfaced as the step's one-lane tail.  <4> (118 VGPRs, 61 KB of LDS) fits the slot one retiring workgroup of
-    // the direct 3x3x3 kernel leaves (8 waves x 104-120 VGPRs, 70 KB).  Step, one box: cap 9 / 5 / 4 / 3 / 2 =
-    // 928 / 935 / 939 / 926 / 931 clips/s.
-    const int cand[3] = {4, 3, 2};
-    int mt = 2, best = 1 << 30;
-    for (int i = 0; i < 3; ++i) {
-        const int rb = cand[i] * 32, blocks = (a.M + rb - 1) / rb;
-        const int cost = blocks * 256 + blocks * rb;
-        if (cost < best) { best = cost; mt = cand[i]; }
-    }
-    const int tm = (a.M + mt * 32 - 1) / (mt * 32), tn = (a.N + 255) / 256;
+    const int mt = sh.bm / 32;          // row-block height and splits: conv_select.h (wgrad1x1_mt, wgrad1x1_splits)
     a.fd = make_conv_fastdiv(g);
     a.P = conv_out_positions(g);
     a.src_bytes = (unsigned)gather_extent_bytes(g, MODE_FWD, H ? 2 : 4);
     a.dy_bytes = (unsigned)gather_extent_bytes(g, MODE_DGRAD, H ? 2 : 4);
-    // one round of workgroups, >= 8 K steps per split
-    const int wgs = (mt <= 2 ? 2 : 1) * 256;              // the 64-row variant fits twice per CU: twice the loads in flight
-    int splits = tm * tn >= wgs ? 1 : wgs / (tm * tn);
-    if (splits > a.K / (8 * 32)) splits = a.K / (8 * 32) > 0 ? a.K / (8 * 32) : 1;
-    const size_t slab1 = (size_t)a.M * a.N * sizeof(float);
-    if (splits > 1 && (!ws || ws_bytes < (size_t)splits * slab1)) {
-        splits = ws ? (int)(ws_bytes / slab1) : 1;
-        if (splits < 2) splits = 1;
-    }
-    const int kps = ((a.K + splits - 1) / splits + 31) / 32 * 32;
-    splits = (a.K + kps - 1) / kps;
-    a.splits = splits;
-    a.k_per_split = kps;
-    a.slab = splits > 1 ? (float*)ws : nullptr;
-    set_epilogue_extents<MODE_WGRAD>(a);
-    if ((splits > 1 ? a.slab_bytes : a.out_bytes) == 0u) return OTAL_E_UNSUPPORTED;
-    const dim3 grid(tn, tm, splits);
+    if (!set_splits<MODE_WGRAD>(a, sh, ws)) return OTAL_E_UNSUPPORTED;
+    const dim3 grid(sh.grid[0], sh.grid[1], sh.grid[2]);
     int e;
     switch (mt) {
         case 4: e = launch_w1x1<4, H>(a, grid, st); break;
@@ -170,6 +132,5 @@ int launch_wgrad1x1_wide(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t st)
         default: e = launch_w1x1<2, H>(a, grid, st); break;
     }
     if (e) return e;
-    if (splits > 1) return launch_splitk_reduce<MODE_WGRAD>(a, st);
-    return 0;
+    return a.splits > 1 ? launch_splitk_reduce<MODE_WGRAD>(a, st) : 0;
 }

@@ -8,7 +8,9 @@ the one that runs; a step further down a chain is reached by the switches that r
 otal_conv_last_kernel() must name the kernel the CPU harness (tests/cpu_conv_select.cpp) expects.  Variants per row: each
 chain step, the kernel a removal switch leaves, the kernel-internal switches (Conv3d_1a's untiled kernel, the chunked
 1x1x1 without its streaming form), persistent prologues refreshed through otal_conv_prologue_batch, deferred split-K
-reductions, and the fp32 parity path once per geometry.
+reductions, the fp32 parity path once per geometry, and `small-ws` (test_small_workspace): for each head kernel that splits
+K, its recorded row with the smallest output at a workspace of its tables plus 2.5 slabs and at its tables alone
+(conv_launch_shape says who serves and how large those are; bytes of the workspace past the offered size must stay untouched).
 
 Per launch: the output view starts as NaN (or random, for the two accumulating calls) and none may remain; the rest of
 the output buffer (other channels, slack, a guard tail) must keep its sentinel bits; sampled elements (every 32-row x
@@ -31,6 +33,8 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 Z = np.load(os.path.join(HERE, "golden", "conv_calls.npz"))
+SMALL_WS = ("chunked", "conv1a_wgrad", "generic", "proj", "vector", "wgrad1d", "wgrad1x1_wide", "wgrad_direct")    # head kernels that split K
+WS_BYTES = 192 << 20            # ops.WORKSPACE_BYTES
 NROWS = len(Z["mode"])
 MODES = ("fwd", "dgrad", "wgrad")
 C_BOUND = 8.0                   # one constant for every kernel
@@ -125,6 +129,22 @@ def cpu_plan(H, i, precision, switches=()):
         for n, dflt in OPTIONS:
             H.cpu_set_option(n.encode(), dflt)
     return [H.cpu_kernel_name(res[2 + 3 * j]).decode() for j in range(res[0])]
+
+
+def cpu_serving(H, i, precision, ws_bytes):
+    """(kernel name, front bytes, slab bytes, splits) of the first step of row i's plan that a workspace of ws_bytes does
+    not make refuse (conv_launch_shape, options at their defaults)."""
+    ga = (ctypes.c_int * 28)(*[int(v) for v in Z["geom"][i]])
+    sa = (ctypes.c_int64 * 4)(*[int(v) for v in Z["strides"][i]])
+    ad = (ctypes.c_int64 * 5)(*[int(v) for v in Z["addr16"][i]])
+    out = (ctypes.c_int64 * 12)()
+    for step in range(8):
+        n = H.cpu_launch_shape(ga, sa, int(Z["mode"][i]), precision, int(Z["accumulate"][i]), int(Z["has_mask"][i]), ad, step,
+                               ctypes.c_uint64(ws_bytes), out)
+        assert step < n, "no step of the plan serves"
+        if not out[0]:
+            return H.cpu_kernel_name(int(out[10])).decode(), int(out[1]), int(out[2]), int(out[3])
+        assert out[11], "a final step refuses"
 
 
 # ------------------------------------------------------------------------------------------------ library state
@@ -288,15 +308,16 @@ def placed(master, half, addr):
 
 
 # ------------------------------------------------------------------------------------------------ one launch
-def launch(lib, row, prec, relu=0, prologue=None):
-    """Runs row's call with precision `prec`; returns (rc, output base buffer, element offset of the output view, half)."""
+def launch(lib, row, prec, relu=0, prologue=None, ws_bytes=WS_BYTES):
+    """Runs row's call with precision `prec` and ws_bytes of workspace; returns (rc, kernel name, output base buffer, element
+    offset of the output view, half, the workspace buffer: 256 bytes longer than what the call was offered)."""
     from opental_amd import _lib as L
     d, mode = row.d, row.mode
     ax, aw, ady, aout, amask = row.addr
     half_in, half_out, half_mask = bool(prec & 8), bool(prec & 4), bool(prec & 16)
     ga = (ctypes.c_int * 28)(*row.geom)
     sa = (ctypes.c_int64 * 4)(*row.strides)
-    ws = torch.empty(192 << 20, dtype=torch.uint8, device="cuda")            # ops.WORKSPACE_BYTES, fresh per launch
+    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device="cuda")       # fresh per launch
     ws.fill_(0xFF)                                                           # (NaN, were anything to read it unwritten)
     w = placed(row.w, False, aw)
     if prologue is not None:
@@ -318,18 +339,18 @@ def launch(lib, row, prec, relu=0, prologue=None):
     if mode == 0:
         x = placed(row.x, half_in, ax)
         rc = lib.otal_conv_fwd(ga, sa, L.ptr(x), L.ptr(w), L.ptr(row.scale), L.ptr(row.shift), L.ptr(out), int(relu), prec,
-                               prologue, L.ptr(ws), ws.numel(), st)
+                               prologue, L.ptr(ws), ws_bytes, st)
     elif mode == 1:
         dy = placed(row.dy, half_out, ady)
         m = placed(row.mask, half_mask, amask) if row.has_mask else None
         rc = lib.otal_conv_dgrad(ga, sa, L.ptr(dy), L.ptr(w), L.ptr(out), row.acc, L.ptr(m) if m is not None else None,
                                  L.ptr(row.out_scale) if m is not None else None, prec, prologue, L.ptr(ws),
-                                 ws.numel(), st)
+                                 ws_bytes, st)
     else:
         x = placed(row.x, half_in, ax)
         dy = placed(row.dy, half_out, ady)
         rc = lib.otal_conv_wgrad(ga, sa, L.ptr(x), L.ptr(dy), L.ptr(out), row.acc, prec, prologue, L.ptr(ws),
-                                 ws.numel(), st)
+                                 ws_bytes, st)
     name = lib.otal_conv_last_kernel().decode()
     torch.cuda.synchronize()
     return rc, name, obase, off, o_half, ws
@@ -436,3 +457,31 @@ def test_recorded_call(lib, harness, v):
         assert rc == 0, f"launch failed: {rc}"
         assert got == want, f"served by {got!r}, the plan names {want!r}"
         check(row, obase, off, oh, rounded, relu, f"{got}{suffix}:{item_id(v)}" + (":relu" if relu else ""))
+
+
+@pytest.mark.parametrize("kernel", SMALL_WS)
+def test_small_workspace(lib, harness, kernel):
+    """small-ws: the recorded row with the smallest output among those whose head kernel is `kernel` and splits K at 192 MiB,
+    at a workspace of its tables plus 2.5 slabs and at its tables alone."""
+    rows = {}
+    for i in range(NROWS):
+        head, _, _, splits = cpu_serving(harness, i, int(Z["precision"][i]), WS_BYTES)
+        if splits > 1:
+            d = unpack(Z["geom"][i])
+            size = (d["Cout"] * d["B"] * d["To"] * d["Ho"] * d["Wo"], d["Cin"] * d["B"] * d["Ti"] * d["Hi"] * d["Wi"],
+                    d["Cout"] * d["Cin"] * d["kt"] * d["kh"] * d["kw"])[int(Z["mode"][i])]
+            assert head == kname(chain_steps(i)[0])
+            rows.setdefault(head, []).append((size, i))
+    assert set(rows) == set(SMALL_WS), sorted(rows)
+    i = min(rows[kernel])[1]
+    row = get_row(i)
+    head, front, slabs, splits = cpu_serving(harness, i, row.prec, WS_BYTES)
+    slab1 = slabs // splits
+    for ws_bytes in (front + slab1 * 5 // 2, front):
+        want, _, _, want_splits = cpu_serving(harness, i, row.prec, ws_bytes)
+        # 2.5 slabs clamp the split to exactly 2 (proj: all its slabs or none; wgrad1d refuses, generic takes the 2); none: 1
+        assert want_splits == (2 if ws_bytes > front and head != "proj" else 1), (want, want_splits)
+        rc, got, obase, off, oh, ws = launch(lib, row, row.prec, ws_bytes=ws_bytes)
+        assert rc == 0 and got == want, (rc, got, want, ws_bytes)
+        assert bool((ws[ws_bytes:] == 0xFF).all()), f"{got}: wrote past a workspace of {ws_bytes} bytes"
+        check(row, obase, off, oh, bool(row.prec & 1), 0, f"{got}-smallws:{kernel}-row{i}:{ws_bytes}")
