@@ -660,6 +660,22 @@ int otal_adam_flat_clip(float* p, const float* g, float* m, float* v, int64_t n,
                         float eps, float weight_decay, const float* bias_corr, float grad_scale, const float* norm_coef,
                         void* stream);
 
+/* otal_adam_flat_dev / otal_adam_flat_clip with the step's learning-rate multiplier and, optionally, the exponential moving
+ * average of the weights in the same sweep (the rule: opental_amd/common/lr_schedule.py).  step_state points at FOUR device
+ * floats {1 - beta1^t, sqrt(1 - beta2^t), lr multiplier, ema keep factor} the host writes before the launch (4-byte
+ * alignment is enough): a per-step schedule changes no launch argument, so the captured step replays.  The update is the
+ * existing one at the float32 rate lr * step_state[2]; with step_state[2] == 1.0f it is bit-identical to otal_adam_flat_dev
+ * (norm_coef NULL) or otal_adam_flat_clip (norm_coef given).  ema != NULL: a fifth array of n floats,
+ *   ema[i] = fmaf(p'[i] - ema[i], 1.0f - step_state[3], ema[i])   with p' the freshly updated parameter,
+ * 9 floats of traffic per parameter where the update alone moves 7; p, m, v do not depend on its presence.  A keep factor of 1
+ * leaves ema's bits; one of 0 gives fl(fl(p' - ema) + ema), the bits of p' wherever p' - ema is a float32 value (ema within a
+ * factor two of p').  All five arrays 16-byte aligned: 16-byte accesses, else the whole call is element-wise.  ema == NULL:
+ * step_state[3] is not used.  Return codes as otal_adam_flat_dev: OTAL_E_NULL for a NULL among p, g, m, v, step_state, the
+ * shape error for n <= 0, both before any launch.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_adam_flat_sched(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1,
+                         float beta2, float eps, float weight_decay, const float* step_state, float grad_scale,
+                         const float* norm_coef, void* stream);
+
 /* MultiSegmentLoss + EvidenceLoss ('log', exp evidence, IBM re-weighting, IoU calibration) + ActionnessLoss (PU BCE,
  * rank weight 0) of the OpenTAL final recipe, forward AND backward in one single-workgroup launch.
  * Replaces AFSD/thumos14/multisegment_loss.py:92-259, cls_loss.py:120-129,:132-168,:212-278,:288-339 and their autograd

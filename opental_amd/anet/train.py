@@ -96,7 +96,8 @@ def main(argv=None):
     """python -m opental_amd.anet.train configs/anet_opental.yaml --open_set --split 0 --lw 1 --cw 1 --piou 0.6 [--resume N]
 
     The reference's command line (AFSD/anet/README.md:61; AFSD/common/config.py:10-37) plus --random_init, --save_after N,
-    --max_steps N, --log_every N, --launch lanes|eager, --log_grad_norm and --clip_grad_norm X as in opental_amd.thumos14.train
+    --max_steps N, --log_every N, --launch lanes|eager, --log_grad_norm, --clip_grad_norm X, the learning-rate schedule flags
+    (--lr_schedule, --warmup_steps, --min_lr_ratio, --lr_milestones, --lr_gamma) and --ema_decay D as in opental_amd.thumos14.train
     (the reference logs `stats/grad_norm` per step and carries the clip line switched off, anet/train.py:126,:234-236).  One process per GPU; under torchrun the ranks all-reduce gradients
     over RCCL (DetectorTrainer).  The epoch loop is thumos14.train.run_one_epoch: same batches-by-permutation sampler,
     ssl branch when the first sample's splice succeeded (`if flags[0]`, anet/train.py:223), device-side loss sums."""
@@ -107,14 +108,17 @@ def main(argv=None):
     from ..common import config as C
     from ..common import ops
     from ..common.thumos_dataset import ClipStager, max_target_count
-    from ..thumos14.train import make_step_log, run_one_epoch, set_seed, take_grad_norm_flag
+    from ..thumos14.train import (LR_FLAGS, apply_lr_flags, lr_logger, make_step_log, report_ema_resume, run_one_epoch,
+                                  set_seed, take_grad_norm_flag, take_lr_flags)
     argv = list(sys.argv[1:] if argv is None else argv)
     extra = {'random_init': False, 'save_after': 10, 'max_steps': None, 'launch': 'lanes', 'log_every': 0,
-             'clip_grad_norm': None, 'log_grad_norm': False}
+             'clip_grad_norm': None, 'log_grad_norm': False, **LR_FLAGS}
     rest, i = [], 0
     while i < len(argv):
         a = argv[i]
         j = take_grad_norm_flag(argv, i, extra)
+        if j is None:
+            j = take_lr_flags(argv, i, extra)
         if j is not None:
             i = j
         elif a == '--random_init':
@@ -155,14 +159,18 @@ def main(argv=None):
     trainer.launch = extra['launch']
     checkpoint_path = tr['checkpoint_path']
     train_state_path = os.path.join(checkpoint_path, 'training')
+    say = print if rank == 0 else (lambda *a: None)
+    apply_lr_flags(trainer, extra, len(dataset), tr['batch_size'], world, tr['max_epoch'], log=say)     # (both groups scale)
     start_epoch = trainer.resume_training(tr['resume'], checkpoint_path, train_state_path)
+    report_ema_resume(trainer, tr['resume'], log=say)
     if rank == 0:
         print(f"batch size: {tr['batch_size']}  learning rate: {tr['learning_rate']} (backbone x0.1)  weight decay: {tr['weight_decay']}  "
               f"max epoch: {tr['max_epoch']}  cls loss: {crit.cls_loss_type}  clips: {len(dataset)}  ranks: {world}  resume: {tr['resume']}")
     history = []
     step_log = None
     if extra['log_every'] > 0 and rank == 0:
-        step_log = make_step_log(extra['log_every'], train_state_path, with_norm=extra['log_grad_norm'])
+        step_log = make_step_log(extra['log_every'], train_state_path, with_norm=extra['log_grad_norm'],
+                                 lr_of=lr_logger(trainer))
     for epoch in range(start_epoch, tr['max_epoch'] + 1):
         if crit.cls_loss_type == 'edl':
             crit.cls_loss.epoch = epoch

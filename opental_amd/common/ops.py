@@ -1440,6 +1440,19 @@ def adam_flat_clip(p, g, m, v, bias_corr, norm_coef, lr, beta1=0.9, beta2=0.999,
             "otal_adam_flat_clip")
 
 
+def adam_flat_sched(p, g, m, v, step_state, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0, ema=None,
+                    norm_coef=None):
+    """adam_flat_dev at the rate lr * step_state[2], with step_state = {bias corrections, lr multiplier, ema keep factor} in a
+    4-float device tensor (the rule: common/lr_schedule.py).  ema: a fifth flat array that moves toward the new p in the same
+    sweep; norm_coef: grad_norm's `out`, the gradient is clipped as adam_flat_clip clips it."""
+    L.require_device(p, g, m, v, step_state, *[t for t in (ema, norm_coef) if t is not None])
+    if step_state.dtype != torch.float32 or step_state.numel() < 4 or (ema is not None and ema.numel() != p.numel()):
+        raise RuntimeError("adam_flat_sched: step_state 4 float32, ema as long as p")
+    L.check(L.lib().otal_adam_flat_sched(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), None if ema is None else L.ptr(ema), p.numel(),
+                                         lr, beta1, beta2, eps, weight_decay, L.ptr(step_state), grad_scale,
+                                         None if norm_coef is None else L.ptr(norm_coef), L.stream()), "otal_adam_flat_sched")
+
+
 # ----------------------------------------------------------------------------- fused detection loss
 EVIDENCE = {'exp': 0, 'relu': 1, 'softplus': 2}         # the evidence kinds and loss types of csrc/evidence.h, by their yaml names
 LOSS_TYPE = {'log': 0, 'digamma': 1, 'mse': 2}

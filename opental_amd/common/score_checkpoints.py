@@ -1,7 +1,7 @@
 """Which saved epoch is best: the mAP of every `checkpoint-<epoch>.ckpt` under training.checkpoint_path, on the device.
 
     python -m opental_amd.thumos14.score_checkpoints <yaml> [--open_set --split N] --gt GT.json --known KNOWN.txt \\
-           [--epochs A B ...] [--tious ...] [--random_init] [--select KEY] \\
+           [--epochs A B ...] [--tious ...] [--random_init] [--select KEY] [--ema] \\
            [--open_metrics [--ood_threshold THR | --threshold_from_train [--threshold_videos N]] [--wi]] \\
            [--fusion --partner_checkpoint PATH --partner_data DIR [--partner_train_data DIR]]
     python -m opental_amd.anet.score_checkpoints     ... the same, with the ActivityNet defaults
@@ -44,6 +44,10 @@ made under another cap, or none, does not count as held.  --wi (with one of the 
 Impact (evaluation/table_wi.py): "WI", per tIoU the mean over the K classes, NaN as null; the epoch's line gains " WI <mean>"
 and, with --threshold_from_train, " thr <value>".  --select WI is best where it is lowest, as FAR95.
 
+--ema scores the averaged models a run with --ema_decay saved, `checkpoint-ema-<epoch>.ckpt` (the same keys as the weights
+files), in place of the weights: the results go to <checkpoint_path>/checkpoint_map_ema.json (checkpoint_map_fusion_ema.json
+with --fusion) and checkpoint_map.json is neither read nor written.  Every other flag works as before.
+
 A recipe's module hands `run` a Recipe: how to build its network, list its test videos and detect one batch -- and, for
 --threshold_from_train, how to list its training videos and detect one batch of them."""
 import json
@@ -65,6 +69,9 @@ SELECT_KEYS = ('average_mAP',) + OPEN_KEYS + ('WI',)
 LOWER_IS_BETTER = ('FAR95', 'WI')
 THRESHOLD_KEYS = ('ood_threshold', 'ood_threshold_from', 'threshold_videos', 'WI')     # what a scoring at another threshold stales
 _CKPT = re.compile(r'^checkpoint-(\d+)\.ckpt$')
+_EMA_CKPT = re.compile(r'^checkpoint-ema-(\d+)\.ckpt$')         # --ema: the averaged models (DetectorTrainer.save_model)
+EMA_MAP_FILE = 'checkpoint_map_ema.json'
+FUSION_EMA_MAP_FILE = 'checkpoint_map_fusion_ema.json'
 
 
 class Recipe(object):
@@ -107,18 +114,19 @@ def take_values(argv, flag):
     return argv[i + 1:j], argv[:i] + argv[j:]
 
 
-def list_checkpoints(checkpoint_path, epochs=None):
-    """{epoch: path} of the checkpoint-<epoch>.ckpt files of a directory, ascending; `epochs`: only these, all of which
-    must exist."""
+def list_checkpoints(checkpoint_path, epochs=None, ema=False):
+    """{epoch: path} of the checkpoint-<epoch>.ckpt files of a directory (ema: the checkpoint-ema-<epoch>.ckpt ones),
+    ascending; `epochs`: only these, all of which must exist."""
     found = {}
     for f in os.listdir(checkpoint_path) if os.path.isdir(checkpoint_path) else []:
-        m = _CKPT.match(f)
+        m = (_EMA_CKPT if ema else _CKPT).match(f)
         if m:
             found[int(m.group(1))] = os.path.join(checkpoint_path, f)
     if epochs is not None:
         missing = [e for e in epochs if e not in found]
         if missing:
-            raise FileNotFoundError("no checkpoint-<epoch>.ckpt under %s for epoch(s) %s" % (checkpoint_path, missing))
+            raise FileNotFoundError("no checkpoint-%s<epoch>.ckpt under %s for epoch(s) %s"
+                                    % ("ema-" if ema else "", checkpoint_path, missing))
         found = {e: found[e] for e in epochs}
     return dict(sorted(found.items()))
 
@@ -281,6 +289,7 @@ def run(recipe, argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     epochs, argv = take_values(argv, '--epochs')
     tious, argv = take_values(argv, '--tious')
+    ema, argv = '--ema' in argv, [a for a in argv if a != '--ema']     # the averaged models, into a map file of their own
     own, rest = parse_own(argv)
     open_metrics, ood_threshold, select = own['--open_metrics'], own['--ood_threshold'], own['--select']
     from_train, cap, want_wi = own['--threshold_from_train'], own['--threshold_videos'], own['--wi']
@@ -297,8 +306,11 @@ def run(recipe, argv=None):
     partner_path = own['--partner_checkpoint'] if fusion else None
     tious = np.asarray(recipe.tious if tious is None else [float(t) for t in tious], dtype=np.float64)
     ckpt_dir = config['training']['checkpoint_path']
-    ckpts = list_checkpoints(ckpt_dir, None if epochs is None else [int(e) for e in epochs])
-    map_file = os.path.join(ckpt_dir, FUSION_MAP_FILE if fusion else MAP_FILE)
+    ckpts = list_checkpoints(ckpt_dir, None if epochs is None else [int(e) for e in epochs], ema=ema)
+    if ema:
+        map_file = os.path.join(ckpt_dir, FUSION_EMA_MAP_FILE if fusion else EMA_MAP_FILE)
+    else:
+        map_file = os.path.join(ckpt_dir, FUSION_MAP_FILE if fusion else MAP_FILE)
     scores = read_map(map_file)
     todo = {e: p for e, p in ckpts.items()
             if str(e) not in scores or not holds(scores[str(e)], open_metrics, ood_threshold, want_wi, from_train, cap,

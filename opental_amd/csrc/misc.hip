@@ -64,31 +64,49 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
 // The flat update streams 7 floats per parameter (4 read, 3 written).  One dword per lane and trip kept the kernel at
 // 3.3 TB/s (26 dependent trips of four 4-byte loads per thread); 16-byte accesses: the same values from a quarter of the
 // memory instructions and trips.  `n4` vectors when the four arrays are 16-byte aligned, the tail element-wise.
-template <bool CLIP>
+// EMA: `ema` is a fifth parallel array, the exponential moving average of the weights; the new p is still in registers, so
+// ema' = ema + (p' - ema) * (1 - keep) costs one more array read and written (9 floats per parameter) and no pass of its own.
+// The fmaf is written out: its rounding must not depend on the contraction setting.  `drop` = 1.0f - keep, formed once per
+// thread by the caller.  Without EMA the lines compile away and `ema` is never touched (the three kernels below pass nullptr).
+__device__ __forceinline__ float ema_one(float e, float p, float drop) { return fmaf(p - e, drop, e); }
+
+template <bool CLIP, bool EMA = false>
 __device__ __forceinline__ void adam_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                            float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-                                           float bc1, float bc2_sqrt, float grad_scale, float coef) {
+                                           float bc1, float bc2_sqrt, float grad_scale, float coef,
+                                           float* __restrict__ ema = nullptr, float drop = 0.0f) {
     const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
-    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                       reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    uintptr_t addr = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                     reinterpret_cast<uintptr_t>(v);
+    if (EMA) addr |= reinterpret_cast<uintptr_t>(ema);      // one array off alignment: the whole call goes element-wise
+    const bool vec = (addr & 15) == 0;
     const int64_t n4 = vec ? n >> 2 : 0;
     float4* p4 = reinterpret_cast<float4*>(p);
     const float4* g4 = reinterpret_cast<const float4*>(g);
     float4* m4 = reinterpret_cast<float4*>(m);
     float4* v4 = reinterpret_cast<float4*>(v);
+    float4* e4 = reinterpret_cast<float4*>(ema);
     for (int64_t i = tid; i < n4; i += nth) {
         float4 pa = p4[i], ma = m4[i], va = v4[i];
         const float4 ga = g4[i];
+        float4 ea;
+        if (EMA) ea = e4[i];
         adam_one<CLIP>(pa.x, ga.x, ma.x, va.x, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, coef);
         adam_one<CLIP>(pa.y, ga.y, ma.y, va.y, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, coef);
         adam_one<CLIP>(pa.z, ga.z, ma.z, va.z, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, coef);
         adam_one<CLIP>(pa.w, ga.w, ma.w, va.w, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, coef);
         p4[i] = pa; m4[i] = ma; v4[i] = va;
+        if (EMA) {
+            ea.x = ema_one(ea.x, pa.x, drop); ea.y = ema_one(ea.y, pa.y, drop);
+            ea.z = ema_one(ea.z, pa.z, drop); ea.w = ema_one(ea.w, pa.w, drop);
+            e4[i] = ea;
+        }
     }
     for (int64_t i = 4 * n4 + tid; i < n; i += nth) {
         float pi = p[i], mi = m[i], vi = v[i];
         adam_one<CLIP>(pi, g[i], mi, vi, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, coef);
         p[i] = pi; m[i] = mi; v[i] = vi;
+        if (EMA) ema[i] = ema_one(ema[i], pi, drop);
     }
 }
 
@@ -116,6 +134,22 @@ __global__ __launch_bounds__(256) void adam_flat_clip_kernel(float* __restrict__
                                                              const float* __restrict__ bias_corr, float grad_scale,
                                                              const float* __restrict__ norm_coef) {
     adam_sweep<true>(p, g, m, v, n, lr, b1, b2, eps, wd, bias_corr[0], bias_corr[1], grad_scale, norm_coef[1]);
+}
+
+// ... and with the learning-rate schedule and the weight EMA of the step (the rule: common/lr_schedule.py): step_state =
+// {1 - b1^t, sqrt(1 - b2^t), lr multiplier, ema keep factor}, four floats the host writes before each launch or replay, so a
+// per-step warm-up or decay changes no launch argument.  Read as four scalars: nothing is assumed about their alignment.
+// The rate is ONE float32 product per thread, lr * step_state[2]; everything behind it is adam_one as it stands.
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adam_flat_sched_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                              float* __restrict__ m, float* __restrict__ v,
+                                                              float* __restrict__ ema, int64_t n, float lr, float b1, float b2,
+                                                              float eps, float wd, const float* __restrict__ step_state,
+                                                              float grad_scale, const float* __restrict__ norm_coef) {
+    const float rate = lr * step_state[2];
+    const float coef = CLIP ? norm_coef[1] : 1.0f;
+    const float drop = EMA ? 1.0f - step_state[3] : 0.0f;
+    adam_sweep<CLIP, EMA>(p, g, m, v, n, rate, b1, b2, eps, wd, step_state[0], step_state[1], grad_scale, coef, ema, drop);
 }
 
 // Global L2 norm of the flat gradient, in two launches.  Launch 1: every thread accumulates the squares of its elements in
@@ -314,6 +348,25 @@ extern "C" int otal_adam_flat_clip(float* p, const float* g, float* m, float* v,
     const int blocks = (int)(blocks64 < 4096 ? blocks64 : 4096);
     hipLaunchKernelGGL(adam_flat_clip_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
                        beta2, eps, weight_decay, bias_corr, grad_scale, norm_coef);
+    return otal_launch_status();
+}
+
+extern "C" int otal_adam_flat_sched(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, const float* step_state,
+                                    float grad_scale, const float* norm_coef, void* stream) {
+    if (!p || !g || !m || !v || !step_state) return OTAL_E_NULL;
+    if (n <= 0) return OTAL_E_SHAPE;
+    const int64_t blocks64 = (n + 255) / 256;
+    const int blocks = (int)(blocks64 < 4096 ? blocks64 : 4096);
+#define OTAL_SCHED_LAUNCH(CLIP, EMA)                                                                                       \
+    hipLaunchKernelGGL((adam_flat_sched_kernel<CLIP, EMA>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,   \
+                       ema, n, lr, beta1, beta2, eps, weight_decay, step_state, grad_scale, norm_coef)
+    if (norm_coef) {
+        if (ema) OTAL_SCHED_LAUNCH(true, true); else OTAL_SCHED_LAUNCH(true, false);
+    } else {
+        if (ema) OTAL_SCHED_LAUNCH(false, true); else OTAL_SCHED_LAUNCH(false, false);
+    }
+#undef OTAL_SCHED_LAUNCH
     return otal_launch_status();
 }
 

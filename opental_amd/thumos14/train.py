@@ -201,7 +201,7 @@ class FlatArena:
 class DetectorTrainer:
     def __init__(self, net, criterion, loss_weights, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8,
                  process_group=None, bucket_mb=16, distributed=None, force_collectives=False, param_groups=None,
-                 forward_fn=None, clip_grad_norm=None, track_grad_norm=False):
+                 forward_fn=None, clip_grad_norm=None, track_grad_norm=False, lr_schedule=None, ema_decay=None):
         """`param_groups`: [(parameters, lr), ...] in the order the reference hands them to torch.optim.Adam (the
         ActivityNet recipe trains the backbone at lr/10, anet/train.py:304-312); default one group = net.parameters().
         `forward_fn`: the recipe's forward_one_epoch (default: this module's, the THUMOS14 one).
@@ -209,7 +209,16 @@ class DetectorTrainer:
         in device memory (ops.grad_norm, one pass over arena.grad behind end_backward; the reference's `stats/grad_norm`,
         train.py:134-141,:248-250).  `clip_grad_norm` = X > 0: Adam additionally reads the gradient scaled by
         min(1, X / (norm + 1e-6)) (nn.utils.clip_grad_norm_, the rule: common/grad_clip.py); implies tracking.  Both are
-        plain attributes and part of _capture_key: changing one re-captures.  Neither set: the step is what it was."""
+        plain attributes and part of _capture_key: changing one re-captures.  Neither set: the step is what it was.
+        `lr_schedule`: a dict (or an object with these attributes) of common.lr_schedule.multiplier's arguments -- name,
+        total_steps, warmup_steps, min_lr_ratio, milestones, gamma -- : every group's rate is its base rate times the
+        multiplier of the step; `ema_decay` = D in [0, 1): arena.ema follows the weights (ema_state_dict()).  With either,
+        every Adam launch is otal_adam_flat_sched and reads {bias corrections, multiplier, keep factor} from a 4-float device
+        record the host writes before the step: no launch argument changes with the step, so a schedule replays ONE
+        capture.  `self.lr` is then the base rate times the multiplier of the last step (a host float, for logging), and
+        assigning to it sets the base.  Plain attributes too; neither set: the step is what it was."""
+        self.lr_schedule, self.ema_decay = lr_schedule, ema_decay
+        self._sched_args()          # (raises ValueError for arguments the rule refuses)
         self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
         if self.clip_grad_norm is not None and not self.clip_grad_norm > 0:
             raise ValueError("clip_grad_norm must be > 0 (None: no clipping)")
@@ -217,6 +226,7 @@ class DetectorTrainer:
         self.last_grad_norm = None  # 2-float device tensor {norm, coefficient} of the last step, once a step tracked it
         self._norm_ws = None
         self.net, self.criterion, self.w = net, criterion, dict(loss_weights)
+        self.step_count = 0
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self._base_lr = lr          # the groups' rates follow `self.lr` proportionally (a scheduler only touches self.lr)
         self.distributed = dist.is_available() and dist.is_initialized() if distributed is None else distributed
@@ -251,7 +261,6 @@ class DetectorTrainer:
         self._index_of = {p.data_ptr(): i for i, p in enumerate(a.params)}
         self.param_groups = [(list(net.parameters()), lr)] if param_groups is None else [(list(ps), g_lr) for ps, g_lr in param_groups]
         self._group_ranges = self._arena_ranges()
-        self.step_count = 0
         self._pending, self._works = None, []
         lo = self.arena.flat.data_ptr()
         self._prologues = ops.PrologueCache((lo, lo + 4 * self.arena.numel))   # per-layer tables + bf16 weights, refreshed once per step
@@ -276,6 +285,65 @@ class DetectorTrainer:
         self._slots = ops.GradSlots(self.arena.flat, self.arena.grad, self.arena.offsets, [p.numel() for p in self.arena.params])
         for i, p in enumerate(self.arena.params):
             p.register_post_accumulate_grad_hook(self._make_hook(i))
+
+    # ---- the learning-rate schedule and the weight EMA (the rule: common/lr_schedule.py)
+    @property
+    def lr(self):
+        """The rate of the detection-head group: what was assigned, times the schedule's multiplier of the last step run
+        (of step 1 before any) -- a host value, no device read."""
+        if self.lr_schedule is None:
+            return self._lr
+        return self._lr * float(self.lr_multiplier(max(1, self.step_count)))
+
+    @lr.setter
+    def lr(self, value):
+        self._lr = value
+
+    def _sched_args(self):
+        """The schedule's constants as the rule's normalised tuple (None without a schedule); checks ema_decay as well."""
+        from ..common import lr_schedule as S
+        if self.ema_decay is not None:
+            S.ema_keep(self.ema_decay, 1)
+        sch = self.lr_schedule
+        if sch is None:
+            return None
+        get = sch.get if isinstance(sch, dict) else (lambda k, d=None: getattr(sch, k, d))
+        if get('name') is None or get('total_steps') is None:
+            raise ValueError("lr_schedule needs a name and total_steps")
+        return S.check(get('name'), get('total_steps'), get('warmup_steps', 0) or 0, get('min_lr_ratio', 0.0) or 0.0,
+                       tuple(get('milestones', ()) or ()), 0.1 if get('gamma') is None else get('gamma'))
+
+    def lr_multiplier(self, step):
+        """float64 multiplier of the base rates at the 1-based step `step`; 1 without a schedule."""
+        from ..common import lr_schedule as S
+        args = self._sched_args()
+        return 1.0 if args is None else S.multiplier(args[0], step, *args[1:])
+
+    def _sched_on(self):
+        return self.lr_schedule is not None or self.ema_decay is not None
+
+    def _step_record(self, dev):
+        """The device record Adam reads its per-step scalars from: the two bias corrections, and with a schedule or an EMA
+        the multiplier and the keep factor behind them."""
+        return torch.zeros(4 if self._sched_on() else 2, dtype=torch.float32, device=dev)
+
+    def _ema_buffer(self):
+        """arena.ema: the EMA of arena.flat, starting as its copy.  Allocated outside any capture."""
+        a = self.arena
+        if self.ema_decay is not None and getattr(a, 'ema', None) is None:
+            a.ema = a.flat.detach().clone()
+        return getattr(a, 'ema', None) if self.ema_decay is not None else None
+
+    def ema_state_dict(self):
+        """net.state_dict() with every arena parameter replaced by its EMA slice, cloned; frozen BatchNorm tensors and buffers
+        are copied as they are."""
+        ema = self._ema_buffer()
+        if ema is None:
+            raise RuntimeError("ema_state_dict: the trainer keeps no EMA (ema_decay is None)")
+        where = {id(p): off for p, off in zip(self.arena.params, self.arena.offsets)}
+        slices = {name: ema[where[id(p)]:where[id(p)] + p.numel()].view(p.shape)
+                  for name, p in self.net.named_parameters() if id(p) in where}
+        return {k: (slices[k] if k in slices else v).detach().clone() for k, v in self.net.state_dict().items()}
 
     def _arena_ranges(self):
         """[(lo, hi, lr)]: each optimizer group must own ONE contiguous slice of the flat arena (module-aligned groups
@@ -518,8 +586,10 @@ class DetectorTrainer:
         if self._norm_on() and self.last_grad_norm is None:
             self.last_grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
             self._norm_ws = torch.zeros(ops.GRAD_NORM_PARTIALS, dtype=torch.float64, device=dev)
-        if self.clip_grad_norm is not None and self._bias_corr is None:
-            self._bias_corr = torch.zeros(2, dtype=torch.float32, device=dev)
+        want = 4 if self._sched_on() else 2
+        if (self.clip_grad_norm is not None or self._sched_on()) and (self._bias_corr is None or self._bias_corr.numel() != want):
+            self._bias_corr = self._step_record(dev)
+        self._ema_buffer()
 
     def _grad_norm_launch(self):
         """Behind end_backward() -- side lane joined, all-reduces waited for: arena.grad is final on every rank and holds the
@@ -622,24 +692,30 @@ class DetectorTrainer:
                    cl.reweight() if hasattr(cl, 'reweight') else None,
                    # the evidence function and loss type the loss launch is given (otal_detection_loss_ev)
                    getattr(cl, 'evidence', None), getattr(cl, 'loss_type', None))
-        return (float(self.lr), float(self._base_lr), tuple(float(g) for _, _, g in self._group_ranges), float(self.wd),
-                tuple(self.betas), float(self.eps), self.world, bool(self.collectives), ibm,
-                tuple(sorted((k, float(v)) for k, v in self.w.items())),
-                # max_norm is a launch argument of the captured norm launch; with clipping there is no early Adam
-                (self.clip_grad_norm, bool(self.track_grad_norm)))
+        sched = getattr(self, 'lr_schedule', None) is not None or getattr(self, 'ema_decay', None) is not None
+        key = (float(self._lr if sched else self.lr), float(self._base_lr), tuple(float(g) for _, _, g in self._group_ranges),
+               float(self.wd), tuple(self.betas), float(self.eps), self.world, bool(self.collectives), ibm,
+               tuple(sorted((k, float(v)) for k, v in self.w.items())),
+               # max_norm is a launch argument of the captured norm launch; with clipping there is no early Adam
+               (self.clip_grad_norm, bool(self.track_grad_norm)))
+        if sched:
+            # the rate above is the BASE rate: the step's multiplier and keep factor live in the device record, so the
+            # schedule's constants are all a capture depends on (which entry point ran, and on which arrays)
+            key += ((self._sched_args(), self.ema_decay),)
+        return key
 
     def optimizer_update(self):
         """Adam (L2 weight decay in the gradient, train.py:321-323) on the flat arena: one launch."""
         a = self.arena
         keep = self._stash_skipped()
-        if self.clip_grad_norm is not None:
-            # the clipped launch reads its bias corrections from device memory, like the coefficient
+        if self.clip_grad_norm is not None or self._sched_on():
+            # the clipped / scheduled launch reads its bias corrections from device memory, like the coefficient
             self._set_bias(self.step_count)
             self._adam_captured(0, a.numel)
             self._restore_skipped(keep)
             return
         for lo, hi, g_lr in self._group_ranges:
-            g_lr = g_lr * (self.lr / self._base_lr) if self._base_lr else g_lr
+            g_lr = g_lr * (self._lr / self._base_lr) if self._base_lr else g_lr
             ops.adam_flat(a.flat[lo:hi], a.grad[lo:hi], a.m[lo:hi], a.v[lo:hi], self.step_count, g_lr,
                           self.betas[0], self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world)
         self._restore_skipped(keep)
@@ -651,20 +727,27 @@ class DetectorTrainer:
         keep = []
         for i in self._skipped:
             sl = slice(a.offsets[i], a.offsets[i] + a.params[i].numel())
-            keep.append((sl, a.flat[sl].clone(), a.m[sl].clone(), a.v[sl].clone()))
+            keep.append((sl, a.flat[sl].clone(), a.m[sl].clone(), a.v[sl].clone()) +
+                        ((a.ema[sl].clone(),) if self.ema_decay is not None else ()))
         return keep
 
     def _restore_skipped(self, keep):
         a = self.arena
         g = self._used_global if self.collectives else None
-        for (sl, p, m, v), i in zip(keep, self._skipped):
+        for (sl, p, m, v, *e), i in zip(keep, self._skipped):
+            if e:       # the EMA moves toward the value the parameter KEEPS, by the keep factor in the device record (no host sync)
+                moved = e[0] + (p - e[0]) * (1.0 - self._bias_corr[3])
             if g is None:
                 a.flat[sl].copy_(p); a.m[sl].copy_(m); a.v[sl].copy_(v)
+                if e:
+                    a.ema[sl].copy_(moved)
             else:       # device-side decision (no host sync): keep the update where any peer used the parameter
                 unused = g[i] == 0
                 a.flat[sl].copy_(torch.where(unused, p, a.flat[sl]))
                 a.m[sl].copy_(torch.where(unused, m, a.m[sl]))
                 a.v[sl].copy_(torch.where(unused, v, a.v[sl]))
+                if e:
+                    a.ema[sl].copy_(torch.where(unused, moved, a.ema[sl]))
 
     # ---- the same step as ONE HIP graph: ~1500 launches per step are replayed without host involvement
     def _graph_body(self, clips, targets, scores):
@@ -692,7 +775,13 @@ class DetectorTrainer:
             lo, hi = max(lo, start), min(hi, stop)
             if lo >= hi:
                 continue
-            g_lr = g_lr * (self.lr / self._base_lr) if self._base_lr else g_lr
+            g_lr = g_lr * (self._lr / self._base_lr) if self._base_lr else g_lr
+            if self._sched_on():
+                ops.adam_flat_sched(a.flat[lo:hi], a.grad[lo:hi], a.m[lo:hi], a.v[lo:hi], self._bias_corr, g_lr, self.betas[0],
+                                    self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world,
+                                    ema=a.ema[lo:hi] if self.ema_decay is not None else None,
+                                    norm_coef=self.last_grad_norm if self.clip_grad_norm is not None else None)
+                continue
             if self.clip_grad_norm is not None:
                 ops.adam_flat_clip(a.flat[lo:hi], a.grad[lo:hi], a.m[lo:hi], a.v[lo:hi], self._bias_corr,
                                    self.last_grad_norm, g_lr, self.betas[0], self.betas[1], self.eps, self.wd,
@@ -730,7 +819,7 @@ class DetectorTrainer:
             raise RuntimeError("capture_step: a step with RCCL collectives cannot be captured as ONE graph (watchdog event "
                                "query inside stream capture); use split=True (two graphs, collectives between them) or "
                                "eager launches")
-        self._bias_corr = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._bias_corr = self._step_record(dev)
         static = _clone_inputs(clips, targets, scores)
         # (the warm-up steps run on a side stream on purpose: the AccumulateGrad stream-mismatch warning is noise here)
         torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
@@ -766,7 +855,7 @@ class DetectorTrainer:
     def _capture_lanes(self, clips, targets, scores, warmup):
         import gc
         dev = clips.device
-        self._bias_corr = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._bias_corr = self._step_record(dev)
         static = _clone_inputs(clips, targets, scores)
         torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
         cap = ops.capture_stream(dev)
@@ -835,7 +924,7 @@ class DetectorTrainer:
         # forcing one would apply the same batch twice and advance Adam's step count past the reference schedule
         already_split = bool(getattr(model, 'split_backward', False))
         model.split_backward = True
-        self._bias_corr = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._bias_corr = self._step_record(dev)
         static = _clone_inputs(clips, targets, scores)
         torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
         side = ops.capture_stream(dev)
@@ -970,6 +1059,10 @@ class DetectorTrainer:
 
     def _set_bias(self, step):
         bc = ops.adam_bias_corrections(step, self.betas[0], self.betas[1])
+        if self._bias_corr.numel() == 4:
+            from ..common import lr_schedule as S
+            keep = 0.0 if self.ema_decay is None else S.ema_keep(self.ema_decay, step)
+            bc = S.step_state(bc, self.lr_multiplier(step), keep).tolist()
         self._bias_corr.copy_(torch.tensor(bc, dtype=torch.float32), non_blocking=False)
 
     def _replay(self, clips, targets, scores):
@@ -988,7 +1081,8 @@ class DetectorTrainer:
     def optimizer_state_dict(self):
         """The Adam state as `torch.optim.Adam(net.parameters(), ...).state_dict()` would hold it (the reference's
         optimizer, train.py:321-323): per-parameter `step` / `exp_avg` / `exp_avg_sq`, indices in net.parameters() order
-        (frozen parameters are listed in the group but carry no state)."""
+        (frozen parameters are listed in the group but carry no state).  With a schedule a group's 'lr' is its CURRENT rate
+        and 'initial_lr' its base rate (torch.optim.lr_scheduler's convention); the schedule's position is `step`."""
         allp = [p for ps, _ in self.param_groups for p in ps]
         index = {id(p): i for i, p in enumerate(allp)}
         state = {}
@@ -1000,10 +1094,13 @@ class DetectorTrainer:
                                        'exp_avg_sq': self.arena.v[off:off + k].view(p.shape).clone()}
         groups, first = [], 0
         rate = (self.lr / self._base_lr) if self._base_lr else 1.0      # a scheduler moves self.lr; the groups follow
+        base = (self._lr / self._base_lr) if self._base_lr else 1.0
         for ps, g_lr in self.param_groups:
             groups.append({'lr': g_lr * rate, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.wd,
                            'amsgrad': False, 'maximize': False, 'foreach': None, 'capturable': False,
                            'differentiable': False, 'fused': None, 'params': list(range(first, first + len(ps)))})
+            if self.lr_schedule is not None:
+                groups[-1]['initial_lr'] = g_lr * base
             first += len(ps)
         return {'state': state, 'param_groups': groups}
 
@@ -1027,9 +1124,10 @@ class DetectorTrainer:
         if len(sd['param_groups']) != len(self.param_groups):
             raise RuntimeError("optimizer state has a different number of parameter groups")
         g = sd['param_groups'][-1]          # the detection-head group carries the base learning rate
-        self.lr, self.betas, self.eps, self.wd = g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']
-        self.param_groups = [(ps, sg['lr']) for (ps, _), sg in zip(self.param_groups, sd['param_groups'])]
-        self._base_lr = self.lr
+        # ('initial_lr', where a scheduled run saved it, is the base rate; 'lr' is then the rate of the step it was saved at)
+        self.lr, self.betas, self.eps, self.wd = g.get('initial_lr', g['lr']), tuple(g['betas']), g['eps'], g['weight_decay']
+        self.param_groups = [(ps, sg.get('initial_lr', sg['lr'])) for (ps, _), sg in zip(self.param_groups, sd['param_groups'])]
+        self._base_lr = self._lr
         self._group_ranges = self._arena_ranges()
         self._graph = None
 
@@ -1043,6 +1141,9 @@ class DetectorTrainer:
         os.makedirs(checkpoint_path, exist_ok=True); os.makedirs(train_state_path, exist_ok=True)
         model_file = os.path.join(checkpoint_path, 'checkpoint-{}.ckpt'.format(epoch))
         torch.save({k: v.detach().clone() for k, v in self.net.state_dict().items()}, model_file)   # views of the arena: clone
+        if self.ema_decay is not None:
+            # the averaged model, under a name score_checkpoints' `checkpoint-<epoch>.ckpt` does not match: the same 446 keys
+            torch.save(self.ema_state_dict(), os.path.join(checkpoint_path, 'checkpoint-ema-{}.ckpt'.format(epoch)))
         states = [random.getstate(), np.random.get_state(), torch.get_rng_state()]
         if torch.cuda.is_available():
             states.append(torch.cuda.get_rng_state())
@@ -1078,6 +1179,7 @@ class DetectorTrainer:
             st = torch.load(os.path.join(train_state_path, 'checkpoint_{}.ckpt'.format(resume)), map_location='cpu',
                             weights_only=False)
             self.load_optimizer_state_dict(st['optimizer'])
+            self._load_ema(os.path.join(checkpoint_path, 'checkpoint-ema-{}.ckpt'.format(resume)))
             for key in ('weight_accum', 'acc_sum'):
                 if key in st and hasattr(getattr(self.criterion, 'cls_loss', None), key):
                     getattr(self.criterion.cls_loss, key).copy_(st[key])
@@ -1087,6 +1189,24 @@ class DetectorTrainer:
                 if torch.cuda.is_available() and len(states) > 3:
                     torch.cuda.set_rng_state(states[3])
         return start_epoch
+
+    def _load_ema(self, path):
+        """arena.ema from a checkpoint-ema-<epoch>.ckpt; without the file the EMA starts from the (resumed) weights.
+        `ema_restored` says which it was (None: the trainer keeps no EMA)."""
+        import os
+        self.ema_restored = None
+        if self.ema_decay is None:
+            return
+        ema, a = self._ema_buffer(), self.arena
+        self.ema_restored = os.path.exists(path)
+        if not self.ema_restored:
+            ema.copy_(a.flat)
+            return
+        sd = torch.load(path, map_location='cpu')
+        names = {id(p): name for name, p in self.net.named_parameters()}
+        with torch.no_grad():
+            for p, off in zip(a.params, a.offsets):
+                ema[off:off + p.numel()].copy_(sd[names[id(p)]].reshape(-1))
 
     def grad_norm(self):
         """get_grad_norm (train.py:133-140), as a device tensor."""
@@ -1217,12 +1337,15 @@ class JsonlSink:
     TAGS = ('Total', 'loc', 'conf', 'prop_loc', 'prop_conf', 'IoU', 'start', 'end')
     EXTRA_TAG = 'stats/grad_norm'
 
-    def __init__(self, directory, filename='scalars.jsonl', echo=None):
+    LR_TAG = 'stats/lr'
+
+    def __init__(self, directory, filename='scalars.jsonl', echo=None, lr_of=None):
         import os
         os.makedirs(directory, exist_ok=True)
         self.path = os.path.join(directory, filename)
         self._f = open(self.path, 'a')
         self.echo = echo
+        self.lr_of = lr_of          # step -> the learning rate of that step (a scheduled run): a host value under 'stats/lr'
 
     def __call__(self, step, values):
         import json
@@ -1230,6 +1353,8 @@ class JsonlSink:
         rec.update({'Train/' + t: float(v) for t, v in zip(self.TAGS, values)})
         if len(values) > len(self.TAGS):
             rec[self.EXTRA_TAG] = float(values[len(self.TAGS)])
+        if self.lr_of is not None:
+            rec[self.LR_TAG] = float(self.lr_of(step))
         self._f.write(json.dumps(rec) + '\n')
         self._f.flush()
         if self.echo is not None:
@@ -1318,12 +1443,120 @@ def take_grad_norm_flag(argv, i, extra):
     return i + 1
 
 
-def make_step_log(every, directory, with_norm=False):
-    """The drivers' per-step log: a console line AND <directory>/scalars.jsonl (the reference's TensorBoard scalars)."""
+LR_FLAGS = {'lr_schedule': None, 'warmup_steps': 0, 'min_lr_ratio': 0.0, 'lr_milestones': None, 'lr_gamma': 0.1, 'ema_decay': None}
+
+
+def take_lr_flags(argv, i, extra):
+    """`--lr_schedule constant|cosine|multistep`, `--warmup_steps N`, `--min_lr_ratio R`, `--lr_milestones E1 E2 ...` (epochs),
+    `--lr_gamma G`, `--ema_decay D` at argv[i]: `extra` updated (its defaults: LR_FLAGS), -> the index of the flag's last word;
+    any other word -> None.  Shared by the two training drivers; what the flags mean together is lr_schedule_from_flags'."""
+    from ..common import lr_schedule as S
+    a = argv[i]
+    if a not in ('--' + k for k in LR_FLAGS):
+        return None
+    j = i + 1
+    while j < len(argv) and not argv[j].startswith('--') and (a == '--lr_milestones' or j < i + 2):
+        j += 1                                  # one word; the milestones: every word up to the next --option
+    words = argv[i + 1:j]
+
+    def number(kind, ok, what):
+        try:
+            x = kind(words[0]) if len(words) == 1 else None
+        except ValueError:
+            x = None
+        if x is None or not ok(x):
+            raise SystemExit(f"{a} takes {what}, not {' '.join(words)!r}")
+        return x
+
+    if a == '--lr_schedule':
+        if len(words) != 1 or words[0] not in S.NAMES:
+            raise SystemExit(f"--lr_schedule takes one of {', '.join(S.NAMES)}, not {' '.join(words)!r}")
+        extra['lr_schedule'] = words[0]
+    elif a == '--warmup_steps':
+        extra['warmup_steps'] = number(int, lambda x: x >= 0, "a whole number of optimisation steps >= 0")
+    elif a == '--min_lr_ratio':
+        extra['min_lr_ratio'] = number(float, lambda x: 0.0 <= x <= 1.0, "a number in [0, 1] (the cosine's floor, as a share of the rate)")
+    elif a == '--lr_gamma':
+        extra['lr_gamma'] = number(float, lambda x: 0.0 < x < float('inf'), "a finite number > 0 (the factor at each milestone)")
+    elif a == '--ema_decay':
+        extra['ema_decay'] = number(float, lambda x: 0.0 <= x < 1.0, "a number in [0, 1) (the EMA's keep factor)")
+    else:
+        try:
+            ms = [int(w) for w in words]
+        except ValueError:
+            ms = []
+        if not ms or ms[0] < 1 or any(b <= a_ for a_, b in zip(ms, ms[1:])):
+            raise SystemExit(f"--lr_milestones takes increasing epoch numbers >= 1, not {' '.join(words)!r}")
+        extra['lr_milestones'] = ms
+    return j - 1
+
+
+def steps_per_epoch(clips, batch_size, world=1, max_steps=None):
+    """The optimisation steps run_one_epoch makes per epoch on every rank: the full batches of the clip list (drop_last),
+    truncated to a multiple of `world` and dealt out (rank_batches), capped by --max_steps.  Draws from no random stream."""
+    n = (int(clips) // int(batch_size)) // int(world)
+    return n if max_steps is None else min(n, int(max_steps))
+
+
+def lr_schedule_from_flags(extra, max_epoch, per_epoch):
+    """The DetectorTrainer `lr_schedule` dict of a command line (None without --lr_schedule / --warmup_steps):
+    total_steps = max_epoch * per_epoch, the milestones' epochs converted to steps."""
+    from ..common import lr_schedule as S
+    name = extra['lr_schedule']
+    if name is None:
+        if extra['lr_milestones'] is not None:
+            raise SystemExit("--lr_milestones belongs to --lr_schedule multistep")
+        if not extra['warmup_steps']:
+            return None
+        name = 'constant'                       # a warm-up alone: the yaml's rate behind it
+    if (name == 'multistep') != (extra['lr_milestones'] is not None):
+        raise SystemExit("--lr_schedule multistep needs --lr_milestones E1 E2 ... (epochs), and only it takes them")
+    total = int(max_epoch) * int(per_epoch)
+    if total < 1:
+        raise SystemExit("the learning-rate schedule needs at least one optimisation step (max_epoch x steps per epoch is 0)")
+    sch = dict(name=name, total_steps=total, warmup_steps=extra['warmup_steps'], min_lr_ratio=extra['min_lr_ratio'],
+               milestones=tuple(e * int(per_epoch) for e in (extra['lr_milestones'] or ())), gamma=extra['lr_gamma'])
+    try:
+        S.check(**sch)
+    except ValueError as err:
+        raise SystemExit(f"{err} (this run makes {total} steps: {max_epoch} epochs of {per_epoch})")
+    return sch
+
+
+def apply_lr_flags(trainer, extra, clips, batch_size, world, max_epoch, log=print):
+    """Give the trainer the schedule and the EMA decay of the command line (before resume_training: it restores the EMA)."""
+    per_epoch = steps_per_epoch(clips, batch_size, world, extra['max_steps'])
+    trainer.lr_schedule = lr_schedule_from_flags(extra, max_epoch, per_epoch)
+    trainer.ema_decay = extra['ema_decay']
+    if trainer.lr_schedule is not None:
+        s = trainer.lr_schedule
+        log(f"lr schedule: {s['name']}, {s['total_steps']} steps ({per_epoch} per epoch), warm-up {s['warmup_steps']}"
+            + (f", floor {s['min_lr_ratio']}" if s['name'] == 'cosine' else "")
+            + (f", x{s['gamma']} behind steps {list(s['milestones'])}" if s['name'] == 'multistep' else ""))
+    if trainer.ema_decay is not None:
+        log(f"weight EMA: decay {trainer.ema_decay}, saved as checkpoint-ema-<epoch>.ckpt")
+
+
+def report_ema_resume(trainer, resume, log=print):
+    if resume > 0 and getattr(trainer, 'ema_restored', None) is False:
+        log(f"no checkpoint-ema-{resume}.ckpt: the weight EMA starts from the resumed weights")
+
+
+def make_step_log(every, directory, with_norm=False, lr_of=None):
+    """The drivers' per-step log: a console line AND <directory>/scalars.jsonl (the reference's TensorBoard scalars).
+    lr_of: step -> the rate of that step, a host value (a scheduled run): 'stats/lr' in the file, `lr x` on the line."""
     log = StepLog(every, width=len(StepLog.NAMES) + int(bool(with_norm)))
-    log.sink = JsonlSink(directory, echo=lambda step, v: print(
-        'step {} '.format(step) + ', '.join('{} {:.5f}'.format(n, x) for n, x in zip(log.names, v))))
+    log.sink = JsonlSink(directory, lr_of=lr_of, echo=lambda step, v: print(
+        'step {} '.format(step) + ', '.join('{} {:.5f}'.format(n, x) for n, x in zip(log.names, v))
+        + ('' if lr_of is None else ', lr {:.4g}'.format(lr_of(step)))))
     return log
+
+
+def lr_logger(trainer):
+    """step -> base rate x the schedule's multiplier of that step (None without a schedule): no device read."""
+    if trainer.lr_schedule is None:
+        return None
+    return lambda step: float(trainer._lr) * float(trainer.lr_multiplier(step))
 
 
 def main(argv=None):
@@ -1343,6 +1576,16 @@ def main(argv=None):
       --clip_grad_norm X      X > 0: scale the gradient by min(1, X / (norm + 1e-6)) before Adam (nn.utils.clip_grad_norm_,
                               which the reference carries switched off, train.py:141); implies --log_grad_norm.  A flag, not
                               state: nothing of it is saved, and --resume with another X re-captures the step
+      --lr_schedule constant|cosine|multistep, --warmup_steps N, --min_lr_ratio R, --lr_milestones E1 E2 ... (epochs),
+      --lr_gamma G            every group's rate is the yaml's times the multiplier of the step (common/lr_schedule.py): linear
+                              warm-up over N steps, then constant, a cosine down to R x the rate at the run's last step, or
+                              x G behind each milestone epoch.  total_steps = max_epoch x steps per epoch (steps_per_epoch).
+                              The multiplier lives in device memory: the captured step replays at every rate.  --warmup_steps
+                              alone: constant behind the warm-up.  --log_every records gain 'stats/lr', the line `lr x`
+      --ema_decay D           keep an exponential moving average of the weights inside the Adam launch (keep factor
+                              min(D, (1 + t) / (10 + t))); saved as checkpoint-ema-<epoch>.ckpt beside checkpoint-<epoch>.ckpt
+                              (score_checkpoints --ema scores them), resumed from it where it exists.  Flags, not state, like
+                              --clip_grad_norm: the schedule's position is Adam's step count
     A yaml with `model.in_channels: 2` (configs/thumos14_opental_flow.yaml) trains the optical-flow stream on uint8 (T,H,W,2)
     frames: the stager hands out three-plane batches with an all-zero third plane (ClipStager(channels=2)).
     One process per GPU; under torchrun the ranks all-reduce gradients over RCCL (DetectorTrainer)."""
@@ -1352,11 +1595,13 @@ def main(argv=None):
     from ..common import thumos_dataset as D
     argv = list(sys.argv[1:] if argv is None else argv)
     extra = {'as_shipped_dispatch': False, 'random_init': False, 'save_after': 10, 'max_steps': None, 'log_every': 0,
-             'launch': 'lanes', 'clip_grad_norm': None, 'log_grad_norm': False}
+             'launch': 'lanes', 'clip_grad_norm': None, 'log_grad_norm': False, **LR_FLAGS}
     rest, i = [], 0
     while i < len(argv):
         a = argv[i]
         j = take_grad_norm_flag(argv, i, extra)
+        if j is None:
+            j = take_lr_flags(argv, i, extra)
         if j is not None:
             i = j
         elif a in ('--as_shipped_dispatch', '--random_init'):
@@ -1400,7 +1645,10 @@ def main(argv=None):
     trainer.launch = extra['launch']
     checkpoint_path = tr['checkpoint_path']
     train_state_path = os.path.join(checkpoint_path, 'training')
+    say = print if rank == 0 else (lambda *a: None)
+    apply_lr_flags(trainer, extra, len(dataset), tr['batch_size'], world, tr['max_epoch'], log=say)
     start_epoch = trainer.resume_training(tr['resume'], checkpoint_path, train_state_path)
+    report_ema_resume(trainer, tr['resume'], log=say)
     if rank == 0:
         print(f"batch size: {tr['batch_size']}  learning rate: {tr['learning_rate']}  weight decay: {tr['weight_decay']}  "
               f"max epoch: {tr['max_epoch']}  cls loss: {crit.cls_loss_type}  clips: {len(dataset)}  ranks: {world}  resume: {tr['resume']}")
@@ -1408,7 +1656,8 @@ def main(argv=None):
     step_log = None
     if extra['log_every'] > 0 and rank == 0:
         # per-step scalars: a console line AND <checkpoint_path>/training/scalars.jsonl (the reference's TensorBoard scalars)
-        step_log = make_step_log(extra['log_every'], train_state_path, with_norm=extra['log_grad_norm'])
+        step_log = make_step_log(extra['log_every'], train_state_path, with_norm=extra['log_grad_norm'],
+                                 lr_of=lr_logger(trainer))
     trainer.step_log = step_log
     for epoch in range(start_epoch, tr['max_epoch'] + 1):
         if crit.cls_loss_type == 'edl':
