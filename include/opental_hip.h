@@ -676,6 +676,35 @@ int otal_adam_flat_sched(float* p, const float* g, float* m, float* v, float* em
                          float beta2, float eps, float weight_decay, const float* step_state, float grad_scale,
                          const float* norm_coef, void* stream);
 
+/* The non-finite-gradient guard of the training step (the rule: opental_amd/common/step_guard.py): the step is APPLIED iff
+ * norm[0] -- otal_grad_norm's out[0] -- is finite, else SKIPPED, decided on the device so that a replayed step needs no host
+ * round trip.  One launch of one workgroup.  `guard` is a caller-owned device record of OTAL_STEP_GUARD_BYTES bytes, 8-byte
+ * aligned:
+ *   int64 applied; int64 nonfinite; double pow1 (= beta1^applied); double pow2 (= beta2^applied); int32 apply;
+ *   28 bytes reserved, zero.                             (a fresh record: zeros with pow1 = pow2 = 1.0)
+ * applied:  ++applied, pow1 *= (double)beta1, pow2 *= (double)beta2, apply = 1;   skipped:  ++nonfinite, apply = 0.
+ * step_state (4 floats, what otal_adam_flat_guard reads) <- {(float)(1.0 - pow1), (float)sqrt(1.0 - pow2), host_state[2],
+ * host_state[3]} -- the bias corrections of the APPLIED count, by IEEE multiply / subtract / sqrt alone; host_state is the
+ * record the host writes for otal_adam_flat_sched (only its lr multiplier and EMA keep factor are read), NULL: 1.0f and 0.0f.
+ * loss_state != NULL with n_state > 0 (the criterion's cross-step loss state, loss_state_keep then required):
+ *   applied: loss_state_keep[i] = loss_state[i];   skipped: loss_state[i] = loss_state_keep[i]   for i < n_state.
+ * NULL among norm, guard, step_state, or a loss_state (n_state > 0) without loss_state_keep: OTAL_E_NULL; n_state < 0:
+ * OTAL_E_SHAPE; n_state > OTAL_STEP_GATE_MAX_STATE: OTAL_E_UNSUPPORTED (the states in use are 50 and num_bins floats); all
+ * before any launch, a refused call writes nothing.  An additive entry: OTAL_ABI_VERSION is unchanged. */
+#define OTAL_STEP_GUARD_BYTES 64
+#define OTAL_STEP_GATE_MAX_STATE 4096
+int otal_step_gate(const float* norm, void* guard, const float* host_state, float* step_state, float beta1, float beta2,
+                   float* loss_state, float* loss_state_keep, int n_state, void* stream);
+
+/* otal_adam_flat_sched behind the guard: `guard` is the record otal_step_gate left.  guard->apply != 0: every array ends with
+ * the bits otal_adam_flat_sched gives for the same arguments (one body, the same 16-byte and element-wise routes, norm_coef
+ * and ema as there).  guard->apply == 0: every workgroup returns on a branch that is uniform across the grid, having read
+ * that one word: no byte of p, m, v, ema moves.  Return codes as otal_adam_flat_sched, plus OTAL_E_NULL for guard.  An
+ * additive entry: OTAL_ABI_VERSION is unchanged. */
+int otal_adam_flat_guard(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1,
+                         float beta2, float eps, float weight_decay, const float* step_state, float grad_scale,
+                         const float* norm_coef, const void* guard, void* stream);
+
 /* MultiSegmentLoss + EvidenceLoss ('log', exp evidence, IBM re-weighting, IoU calibration) + ActionnessLoss (PU BCE,
  * rank weight 0) of the OpenTAL final recipe, forward AND backward in one single-workgroup launch.
  * Replaces AFSD/thumos14/multisegment_loss.py:92-259, cls_loss.py:120-129,:132-168,:212-278,:288-339 and their autograd

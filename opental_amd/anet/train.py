@@ -97,7 +97,8 @@ def main(argv=None):
 
     The reference's command line (AFSD/anet/README.md:61; AFSD/common/config.py:10-37) plus --random_init, --save_after N,
     --max_steps N, --log_every N, --launch lanes|eager, --log_grad_norm, --clip_grad_norm X, the learning-rate schedule flags
-    (--lr_schedule, --warmup_steps, --min_lr_ratio, --lr_milestones, --lr_gamma) and --ema_decay D as in opental_amd.thumos14.train
+    (--lr_schedule, --warmup_steps, --min_lr_ratio, --lr_milestones, --lr_gamma), --ema_decay D, --skip_nonfinite and
+    --max_nonfinite N as in opental_amd.thumos14.train
     (the reference logs `stats/grad_norm` per step and carries the clip line switched off, anet/train.py:126,:234-236).  One process per GPU; under torchrun the ranks all-reduce gradients
     over RCCL (DetectorTrainer).  The epoch loop is thumos14.train.run_one_epoch: same batches-by-permutation sampler,
     ssl branch when the first sample's splice succeeded (`if flags[0]`, anet/train.py:223), device-side loss sums."""
@@ -108,17 +109,20 @@ def main(argv=None):
     from ..common import config as C
     from ..common import ops
     from ..common.thumos_dataset import ClipStager, max_target_count
-    from ..thumos14.train import (LR_FLAGS, apply_lr_flags, lr_logger, make_step_log, report_ema_resume, run_one_epoch,
-                                  set_seed, take_grad_norm_flag, take_lr_flags)
+    from ..common import step_guard as G
+    from ..thumos14.train import (LR_FLAGS, apply_lr_flags, check_nonfinite_limit, guard_kwargs, guard_log_kwargs, lr_logger,
+                                  make_step_log, report_ema_resume, run_one_epoch, set_seed, take_grad_norm_flag, take_lr_flags)
     argv = list(sys.argv[1:] if argv is None else argv)
     extra = {'random_init': False, 'save_after': 10, 'max_steps': None, 'launch': 'lanes', 'log_every': 0,
-             'clip_grad_norm': None, 'log_grad_norm': False, **LR_FLAGS}
+             'clip_grad_norm': None, 'log_grad_norm': False, **LR_FLAGS, **G.GUARD_FLAGS}
     rest, i = [], 0
     while i < len(argv):
         a = argv[i]
         j = take_grad_norm_flag(argv, i, extra)
         if j is None:
             j = take_lr_flags(argv, i, extra)
+        if j is None:
+            j = G.take_guard_flag(argv, i, extra)
         if j is not None:
             i = j
         elif a == '--random_init':
@@ -130,6 +134,7 @@ def main(argv=None):
         else:
             rest.append(a)
         i += 1
+    G.check_guard_flags(extra)
     config = C.set_config(C.get_config(rest))
     tr = config['training']
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
@@ -144,7 +149,7 @@ def main(argv=None):
     ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
     set_seed(tr['random_seed'])
     net, crit, trainer = build_training(config, dev, extra['random_init'], clip_grad_norm=extra['clip_grad_norm'],
-                                        track_grad_norm=extra['log_grad_norm'])
+                                        track_grad_norm=extra['log_grad_norm'], **guard_kwargs(extra))
     ds = config['dataset']['training']
     dataset = D.ANET_Dataset(ds['video_info_path'], ds['video_mp4_path'], ds['clip_length'], ds['crop_size'], ds['clip_stride'],
                              channels=config['model']['in_channels'], binary_class=config['dataset']['num_classes'] == 2)
@@ -170,7 +175,7 @@ def main(argv=None):
     step_log = None
     if extra['log_every'] > 0 and rank == 0:
         step_log = make_step_log(extra['log_every'], train_state_path, with_norm=extra['log_grad_norm'],
-                                 lr_of=lr_logger(trainer))
+                                 lr_of=lr_logger(trainer), **guard_log_kwargs(extra, world))
     for epoch in range(start_epoch, tr['max_epoch'] + 1):
         if crit.cls_loss_type == 'edl':
             crit.cls_loss.epoch = epoch
@@ -178,6 +183,7 @@ def main(argv=None):
         v = run_one_epoch(epoch, trainer, dataset, stager, tr['batch_size'], rank, world, extra['max_steps'],
                           log=print if rank == 0 else (lambda *a: None), step_log=step_log)
         history.append(v)
+        check_nonfinite_limit(trainer, extra)
         if epoch > extra['save_after'] and rank == 0:
             trainer.save_model(epoch, checkpoint_path, train_state_path)
     if world > 1:

@@ -1453,6 +1453,46 @@ def adam_flat_sched(p, g, m, v, step_state, lr, beta1=0.9, beta2=0.999, eps=1e-8
                                          None if norm_coef is None else L.ptr(norm_coef), L.stream()), "otal_adam_flat_sched")
 
 
+STEP_GUARD_BYTES = 64           # OTAL_STEP_GUARD_BYTES: the guard record (common/step_guard.RECORD), held as 8 int64
+STEP_GATE_MAX_STATE = 4096      # OTAL_STEP_GATE_MAX_STATE
+
+
+def _guard_record(guard, what):
+    if guard.dtype != torch.int64 or guard.numel() * 8 < STEP_GUARD_BYTES or not guard.is_contiguous():
+        raise RuntimeError(what + ": the guard record is 8 contiguous int64 (STEP_GUARD_BYTES)")
+
+
+def step_gate(norm, guard, step_state, beta1=0.9, beta2=0.999, host_state=None, loss_state=None, loss_state_keep=None):
+    """The step's decision, on the device (the rule: common/step_guard.py): norm[0] finite -> applied, else skipped.  guard:
+    the 64-byte record as 8 int64; step_state (4 float32) <- {bias corrections of the applied count, host_state[2:4] or 1, 0};
+    loss_state is copied to loss_state_keep (applied) or put back from it (skipped)."""
+    L.require_device(norm, guard, step_state, *[t for t in (host_state, loss_state, loss_state_keep) if t is not None])
+    _guard_record(guard, "step_gate")
+    n = 0 if loss_state is None else loss_state.numel()
+    if norm.dtype != torch.float32 or step_state.dtype != torch.float32 or step_state.numel() < 4 or \
+            (host_state is not None and (host_state.dtype != torch.float32 or host_state.numel() < 4)):
+        raise RuntimeError("step_gate: norm float32, step_state and host_state 4 float32")
+    if n and (loss_state_keep is None or loss_state.dtype != torch.float32 or loss_state_keep.dtype != torch.float32
+              or loss_state_keep.numel() < n or not loss_state.is_contiguous() or not loss_state_keep.is_contiguous()):
+        raise RuntimeError("step_gate: loss_state needs a contiguous float32 loss_state_keep at least as long")
+    L.check(L.lib().otal_step_gate(L.ptr(norm), L.ptr(guard), None if host_state is None else L.ptr(host_state),
+                                   L.ptr(step_state), beta1, beta2, None if loss_state is None else L.ptr(loss_state),
+                                   None if loss_state_keep is None else L.ptr(loss_state_keep), n, L.stream()), "otal_step_gate")
+
+
+def adam_flat_guard(p, g, m, v, step_state, guard, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0,
+                    ema=None, norm_coef=None):
+    """adam_flat_sched behind step_gate's decision: with guard's apply word 0 the launch moves no byte of p, m, v, ema."""
+    L.require_device(p, g, m, v, step_state, guard, *[t for t in (ema, norm_coef) if t is not None])
+    _guard_record(guard, "adam_flat_guard")
+    if step_state.dtype != torch.float32 or step_state.numel() < 4 or (ema is not None and ema.numel() != p.numel()):
+        raise RuntimeError("adam_flat_guard: step_state 4 float32, ema as long as p")
+    L.check(L.lib().otal_adam_flat_guard(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), None if ema is None else L.ptr(ema), p.numel(),
+                                         lr, beta1, beta2, eps, weight_decay, L.ptr(step_state), grad_scale,
+                                         None if norm_coef is None else L.ptr(norm_coef), L.ptr(guard), L.stream()),
+            "otal_adam_flat_guard")
+
+
 # ----------------------------------------------------------------------------- fused detection loss
 EVIDENCE = {'exp': 0, 'relu': 1, 'softplus': 2}         # the evidence kinds and loss types of csrc/evidence.h, by their yaml names
 LOSS_TYPE = {'log': 0, 'digamma': 1, 'mse': 2}

@@ -141,15 +141,82 @@ __global__ __launch_bounds__(256) void adam_flat_clip_kernel(float* __restrict__
 // per-step warm-up or decay changes no launch argument.  Read as four scalars: nothing is assumed about their alignment.
 // The rate is ONE float32 product per thread, lr * step_state[2]; everything behind it is adam_one as it stands.
 template <bool CLIP, bool EMA>
+__device__ __forceinline__ void adam_sched_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, float* __restrict__ ema, int64_t n, float lr, float b1,
+                                                float b2, float eps, float wd, const float* __restrict__ step_state,
+                                                float grad_scale, const float* __restrict__ norm_coef) {
+    const float rate = lr * step_state[2];
+    const float coef = CLIP ? norm_coef[1] : 1.0f;
+    const float drop = EMA ? 1.0f - step_state[3] : 0.0f;
+    adam_sweep<CLIP, EMA>(p, g, m, v, n, rate, b1, b2, eps, wd, step_state[0], step_state[1], grad_scale, coef, ema, drop);
+}
+
+template <bool CLIP, bool EMA>
 __global__ __launch_bounds__(256) void adam_flat_sched_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                               float* __restrict__ m, float* __restrict__ v,
                                                               float* __restrict__ ema, int64_t n, float lr, float b1, float b2,
                                                               float eps, float wd, const float* __restrict__ step_state,
                                                               float grad_scale, const float* __restrict__ norm_coef) {
-    const float rate = lr * step_state[2];
-    const float coef = CLIP ? norm_coef[1] : 1.0f;
-    const float drop = EMA ? 1.0f - step_state[3] : 0.0f;
-    adam_sweep<CLIP, EMA>(p, g, m, v, n, rate, b1, b2, eps, wd, step_state[0], step_state[1], grad_scale, coef, ema, drop);
+    adam_sched_body<CLIP, EMA>(p, g, m, v, ema, n, lr, b1, b2, eps, wd, step_state, grad_scale, norm_coef);
+}
+
+// The non-finite-gradient guard of the step (the rule: common/step_guard.py).  The record both kernels below share; the
+// header states its layout for callers, who own the 64 bytes.
+struct StepGuard {
+    long long applied, nonfinite;       // steps applied / skipped so far
+    double pow1, pow2;                  // beta1^applied, beta2^applied, by repeated multiplication
+    int apply;                          // the decision of the step in flight: what adam_flat_guard_kernel reads
+    int reserved[7];
+};
+static_assert(sizeof(StepGuard) == OTAL_STEP_GUARD_BYTES, "the guard record is 64 bytes");
+
+// finite: the exponent field is not all ones (a bit test: no floating-point compare to be folded away)
+__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// One workgroup.  Every thread reads norm[0] and takes the same decision; thread 0 advances the record and writes the step
+// record Adam reads; all 256 threads copy the loss state forward (applied) or back (skipped).  The copy depends on norm[0]
+// alone, not on the record, so nothing in here needs a barrier.  1 - pow and sqrt(1 - pow) are IEEE double operations,
+// rounded to float once: the host's recurrence gives the same bits.
+__global__ __launch_bounds__(256) void step_gate_kernel(const float* __restrict__ norm, StepGuard* __restrict__ guard,
+                                                        const float* __restrict__ host_state, float* __restrict__ step_state,
+                                                        float b1, float b2, float* __restrict__ state, float* __restrict__ keep,
+                                                        int n_state) {
+    const bool apply = finite_bits(norm[0]);
+    if (threadIdx.x == 0) {
+        double p1 = guard->pow1, p2 = guard->pow2;
+        if (apply) {
+            p1 = p1 * (double)b1;
+            p2 = p2 * (double)b2;
+            guard->applied = guard->applied + 1;
+            guard->pow1 = p1;
+            guard->pow2 = p2;
+        } else {
+            guard->nonfinite = guard->nonfinite + 1;
+        }
+        guard->apply = apply ? 1 : 0;
+        step_state[0] = (float)(1.0 - p1);
+        step_state[1] = (float)sqrt(1.0 - p2);
+        step_state[2] = host_state ? host_state[2] : 1.0f;
+        step_state[3] = host_state ? host_state[3] : 0.0f;
+    }
+    if (apply) {
+        for (int i = threadIdx.x; i < n_state; i += 256) keep[i] = state[i];
+    } else {
+        for (int i = threadIdx.x; i < n_state; i += 256) state[i] = keep[i];
+    }
+}
+
+// otal_adam_flat_sched's body behind the decision: one cached dword per thread, the same value for the whole grid, so a
+// skipped step's launch ends without touching the arena (44.7 M parameters stay as they are at the cost of an empty launch).
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void adam_flat_guard_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                              float* __restrict__ m, float* __restrict__ v,
+                                                              float* __restrict__ ema, int64_t n, float lr, float b1, float b2,
+                                                              float eps, float wd, const float* __restrict__ step_state,
+                                                              float grad_scale, const float* __restrict__ norm_coef,
+                                                              const StepGuard* __restrict__ guard) {
+    if (guard->apply == 0) return;
+    adam_sched_body<CLIP, EMA>(p, g, m, v, ema, n, lr, b1, b2, eps, wd, step_state, grad_scale, norm_coef);
 }
 
 // Global L2 norm of the flat gradient, in two launches.  Launch 1: every thread accumulates the squares of its elements in
@@ -367,6 +434,38 @@ extern "C" int otal_adam_flat_sched(float* p, const float* g, float* m, float* v
         if (ema) OTAL_SCHED_LAUNCH(false, true); else OTAL_SCHED_LAUNCH(false, false);
     }
 #undef OTAL_SCHED_LAUNCH
+    return otal_launch_status();
+}
+
+extern "C" int otal_step_gate(const float* norm, void* guard, const float* host_state, float* step_state, float beta1,
+                              float beta2, float* loss_state, float* loss_state_keep, int n_state, void* stream) {
+    if (!norm || !guard || !step_state) return OTAL_E_NULL;
+    if (n_state < 0) return OTAL_E_SHAPE;
+    const int n = loss_state ? n_state : 0;         // no state to carry: the keep buffer is not looked at
+    if (n > 0 && !loss_state_keep) return OTAL_E_NULL;
+    if (n_state > OTAL_STEP_GATE_MAX_STATE) return OTAL_E_UNSUPPORTED;
+    hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, norm, static_cast<StepGuard*>(guard),
+                       host_state, step_state, beta1, beta2, loss_state, loss_state_keep, n);
+    return otal_launch_status();
+}
+
+extern "C" int otal_adam_flat_guard(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, const float* step_state,
+                                    float grad_scale, const float* norm_coef, const void* guard, void* stream) {
+    if (!p || !g || !m || !v || !step_state || !guard) return OTAL_E_NULL;
+    if (n <= 0) return OTAL_E_SHAPE;
+    const int64_t blocks64 = (n + 255) / 256;
+    const int blocks = (int)(blocks64 < 4096 ? blocks64 : 4096);
+#define OTAL_GUARD_LAUNCH(CLIP, EMA)                                                                                       \
+    hipLaunchKernelGGL((adam_flat_guard_kernel<CLIP, EMA>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,   \
+                       ema, n, lr, beta1, beta2, eps, weight_decay, step_state, grad_scale, norm_coef,                     \
+                       static_cast<const StepGuard*>(guard))
+    if (norm_coef) {
+        if (ema) OTAL_GUARD_LAUNCH(true, true); else OTAL_GUARD_LAUNCH(true, false);
+    } else {
+        if (ema) OTAL_GUARD_LAUNCH(false, true); else OTAL_GUARD_LAUNCH(false, false);
+    }
+#undef OTAL_GUARD_LAUNCH
     return otal_launch_status();
 }
 

@@ -201,7 +201,8 @@ class FlatArena:
 class DetectorTrainer:
     def __init__(self, net, criterion, loss_weights, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8,
                  process_group=None, bucket_mb=16, distributed=None, force_collectives=False, param_groups=None,
-                 forward_fn=None, clip_grad_norm=None, track_grad_norm=False, lr_schedule=None, ema_decay=None):
+                 forward_fn=None, clip_grad_norm=None, track_grad_norm=False, lr_schedule=None, ema_decay=None,
+                 skip_nonfinite=False):
         """`param_groups`: [(parameters, lr), ...] in the order the reference hands them to torch.optim.Adam (the
         ActivityNet recipe trains the backbone at lr/10, anet/train.py:304-312); default one group = net.parameters().
         `forward_fn`: the recipe's forward_one_epoch (default: this module's, the THUMOS14 one).
@@ -216,7 +217,17 @@ class DetectorTrainer:
         every Adam launch is otal_adam_flat_sched and reads {bias corrections, multiplier, keep factor} from a 4-float device
         record the host writes before the step: no launch argument changes with the step, so a schedule replays ONE
         capture.  `self.lr` is then the base rate times the multiplier of the last step (a host float, for logging), and
-        assigning to it sets the base.  Plain attributes too; neither set: the step is what it was."""
+        assigning to it sets the base.  Plain attributes too; neither set: the step is what it was.
+        `skip_nonfinite`: a step whose gradient norm is not finite is left out, as torch's GradScaler leaves out
+        optimizer.step() (the rule: common/step_guard.py).  One single-workgroup launch behind the norm launch (ops.step_gate)
+        decides on the device, counts, makes Adam's bias corrections for the count of APPLIED steps and rolls the criterion's
+        cross-step loss state back on a skipped step; every Adam launch is otal_adam_flat_guard, which ends at once when the
+        step is skipped.  `step_count` stays "steps run"; guard_counts() reads (applied, nonfinite).  Implies tracking, gives
+        up early Adam like clipping; a plain attribute and part of _capture_key.  Off: the step is what it was."""
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._guard = self._step_dev = self._state_keep = None     # the guard record, the device-made step record, the state copy
+        self._state_keep_of = None  # (address of the state tensor the copy was taken from)
+        self._guard_restore = None  # (applied, nonfinite) a resume read, until the record exists
         self.lr_schedule, self.ema_decay = lr_schedule, ema_decay
         self._sched_args()          # (raises ValueError for arguments the rule refuses)
         self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
@@ -508,12 +519,15 @@ class DetectorTrainer:
 
         With `clip_grad_norm` set the early-Adam branch below is not taken: it updates everything but the stem tail
         BEFORE the tail's weight gradients exist, and the clip coefficient is a function of the global norm, i.e. of all of
-        them.  Tracking alone keeps early Adam: the norm launch follows the final join, and Adam does not write arena.grad."""
+        them.  Tracking alone keeps early Adam: the norm launch follows the final join, and Adam does not write arena.grad.
+        `skip_nonfinite` gives the branch up for the same reason: whether the step is applied at all is a function of the
+        complete gradient (an inf in the tail's weight gradient must stop the update of every other parameter too), so no
+        Adam launch may run before the norm launch and the gate behind it."""
         self._drain(force=True)
         self._adam_left = None
         late = ops.take_late_weights()
         if late and ops.STEP.lanes is not None and self._capturing and not self.collectives and not self._skipped \
-                and self.clip_grad_norm is None:
+                and self.clip_grad_norm is None and not self.skip_nonfinite:
             # lane capture, one process: Adam for everything but the stem tail's weights runs NOW on the main lane -- behind the
             # mark the backbone left on the side lane (ops.late_mark), beside the tail's weight gradients -- and only the
             # tail's parameters wait for the final join (_graph_body)
@@ -578,7 +592,7 @@ class DetectorTrainer:
 
     # ---- the global gradient norm (+ clip coefficient) of the step, on the device
     def _norm_on(self):
-        return self.clip_grad_norm is not None or self.track_grad_norm
+        return self.clip_grad_norm is not None or self.track_grad_norm or self.skip_nonfinite
 
     def _norm_buffers(self):
         """Allocated outside any capture (a step or capture_step begins here)."""
@@ -587,9 +601,56 @@ class DetectorTrainer:
             self.last_grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
             self._norm_ws = torch.zeros(ops.GRAD_NORM_PARTIALS, dtype=torch.float64, device=dev)
         want = 4 if self._sched_on() else 2
-        if (self.clip_grad_norm is not None or self._sched_on()) and (self._bias_corr is None or self._bias_corr.numel() != want):
+        if (self.clip_grad_norm is not None or self._sched_on() or self.skip_nonfinite) \
+                and (self._bias_corr is None or self._bias_corr.numel() != want):
             self._bias_corr = self._step_record(dev)
         self._ema_buffer()
+        if self.skip_nonfinite and self._guard is None:
+            # the guard record (8 int64 = the 64 bytes of common/step_guard.RECORD), the step record the gate makes for Adam,
+            # and the copy of the criterion's cross-step loss state a skipped step is rolled back to
+            applied, nonfinite = self._guard_restore or (self.step_count, 0)
+            self._guard = self._guard_tensor(applied, nonfinite, dev)
+            self._guard_restore = None
+            self._step_dev = torch.zeros(4, dtype=torch.float32, device=dev)
+            self._state_keep, self._state_keep_of = None, None
+        if self.skip_nonfinite:
+            # (the criterion switches state tensors where a re-weighting rule starts: the capture key changes with it, the
+            # eager step that follows passes here, and the copy starts again from the tensor now in force)
+            state = self._ibm_state()
+            ptr = None if state is None else state.data_ptr()
+            if ptr != self._state_keep_of:
+                self._state_keep = None if state is None else state.detach().clone().contiguous()
+                self._state_keep_of = ptr
+
+    # ---- the non-finite-gradient guard (the rule: common/step_guard.py)
+    def _guard_tensor(self, applied, nonfinite, dev):
+        import numpy as np
+        from ..common import step_guard as G
+        rec = G.new_record(applied, nonfinite, self.betas[0], self.betas[1])
+        return torch.from_numpy(np.frombuffer(rec.tobytes(), dtype=np.int64).copy()).to(dev)
+
+    def _step_gate_launch(self):
+        """Behind _grad_norm_launch(), in front of every Adam launch of the step: ONE launch that reads last_grad_norm[0],
+        decides, counts, writes Adam's step record (bias corrections of the applied count; the multiplier and keep factor are
+        copied from the host-written record) and carries the loss state forward or back.  Data parallel: it sits behind
+        _finish_allreduce, i.e. it reads the all-reduced gradient's norm and the rank-averaged loss state -- identical bytes
+        on every rank, the same decision everywhere, no collective."""
+        if not self.skip_nonfinite:
+            return
+        state = self._ibm_state() if self._state_keep is not None else None
+        ops.step_gate(self.last_grad_norm, self._guard, self._step_dev, self.betas[0], self.betas[1],
+                      host_state=self._bias_corr if self._bias_corr.numel() == 4 else None,
+                      loss_state=state, loss_state_keep=self._state_keep)
+
+    def guard_counts(self):
+        """(applied, nonfinite) steps, read from the device record: a host synchronisation -- for where the host already
+        waits (checkpoints, the end of an epoch).  Without the guard every step run was applied."""
+        if not self.skip_nonfinite:
+            return self.step_count, 0
+        if self._guard is None:
+            return tuple(self._guard_restore or (self.step_count, 0))
+        applied, nonfinite = self._guard[:2].tolist()
+        return int(applied), int(nonfinite)
 
     def _grad_norm_launch(self):
         """Behind end_backward() -- side lane joined, all-reduces waited for: arena.grad is final on every rank and holds the
@@ -702,15 +763,19 @@ class DetectorTrainer:
             # the rate above is the BASE rate: the step's multiplier and keep factor live in the device record, so the
             # schedule's constants are all a capture depends on (which entry point ran, and on which arrays)
             key += ((self._sched_args(), self.ema_decay),)
+        if getattr(self, 'skip_nonfinite', False):
+            # another Adam entry, a gate launch, no early Adam: switching the guard re-captures
+            key += (('skip_nonfinite', True),)
         return key
 
     def optimizer_update(self):
         """Adam (L2 weight decay in the gradient, train.py:321-323) on the flat arena: one launch."""
         a = self.arena
         keep = self._stash_skipped()
-        if self.clip_grad_norm is not None or self._sched_on():
-            # the clipped / scheduled launch reads its bias corrections from device memory, like the coefficient
+        if self.clip_grad_norm is not None or self._sched_on() or self.skip_nonfinite:
+            # the clipped / scheduled / guarded launch reads its bias corrections from device memory, like the coefficient
             self._set_bias(self.step_count)
+            self._step_gate_launch()        # (behind the host's record: the gate copies its multiplier and keep factor)
             self._adam_captured(0, a.numel)
             self._restore_skipped(keep)
             return
@@ -737,6 +802,8 @@ class DetectorTrainer:
         for (sl, p, m, v, *e), i in zip(keep, self._skipped):
             if e:       # the EMA moves toward the value the parameter KEEPS, by the keep factor in the device record (no host sync)
                 moved = e[0] + (p - e[0]) * (1.0 - self._bias_corr[3])
+                if self.skip_nonfinite:     # ... unless the step is skipped (the record's apply word, with its zero neighbour)
+                    moved = torch.where(self._guard[4] != 0, moved, e[0])
             if g is None:
                 a.flat[sl].copy_(p); a.m[sl].copy_(m); a.v[sl].copy_(v)
                 if e:
@@ -760,6 +827,7 @@ class DetectorTrainer:
         finally:
             ops.STEP.reset()
         self._grad_norm_launch()
+        self._step_gate_launch()
         keep = self._stash_skipped()
         span = getattr(self, "_adam_left", None) or (0, self.arena.numel)       # (what end_backward's early launches left)
         self._adam_captured(span[0], span[1])
@@ -776,6 +844,13 @@ class DetectorTrainer:
             if lo >= hi:
                 continue
             g_lr = g_lr * (self._lr / self._base_lr) if self._base_lr else g_lr
+            if self.skip_nonfinite:
+                # the device-made record: bias corrections of the APPLIED count; a skipped step's launch moves nothing
+                ops.adam_flat_guard(a.flat[lo:hi], a.grad[lo:hi], a.m[lo:hi], a.v[lo:hi], self._step_dev, self._guard, g_lr,
+                                    self.betas[0], self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world,
+                                    ema=a.ema[lo:hi] if self.ema_decay is not None else None,
+                                    norm_coef=self.last_grad_norm if self.clip_grad_norm is not None else None)
+                continue
             if self._sched_on():
                 ops.adam_flat_sched(a.flat[lo:hi], a.grad[lo:hi], a.m[lo:hi], a.v[lo:hi], self._bias_corr, g_lr, self.betas[0],
                                     self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world,
@@ -997,6 +1072,7 @@ class DetectorTrainer:
                     self._issue_allreduce(b)
         self._finish_allreduce()
         self._grad_norm_launch()                    # eager, like Adam: the stem's all-reduces end behind the second graph
+        self._step_gate_launch()
         self._adam_captured(0, a.numel)
         return out
 
@@ -1082,14 +1158,17 @@ class DetectorTrainer:
         """The Adam state as `torch.optim.Adam(net.parameters(), ...).state_dict()` would hold it (the reference's
         optimizer, train.py:321-323): per-parameter `step` / `exp_avg` / `exp_avg_sq`, indices in net.parameters() order
         (frozen parameters are listed in the group but carry no state).  With a schedule a group's 'lr' is its CURRENT rate
-        and 'initial_lr' its base rate (torch.optim.lr_scheduler's convention); the schedule's position is `step`."""
+        and 'initial_lr' its base rate (torch.optim.lr_scheduler's convention); the schedule's position is `step`.
+        With `skip_nonfinite`, `step` is the count of APPLIED steps -- what torch holds when optimizer.step() was left out
+        for the others (read from the device record: a host synchronisation, as the copies below are)."""
         allp = [p for ps, _ in self.param_groups for p in ps]
         index = {id(p): i for i, p in enumerate(allp)}
         state = {}
+        applied = self.guard_counts()[0]
         if self.step_count > 0:
             for p, off in zip(self.arena.params, self.arena.offsets):
                 k = p.numel()
-                state[index[id(p)]] = {'step': torch.tensor(float(self.step_count)),
+                state[index[id(p)]] = {'step': torch.tensor(float(applied)),
                                        'exp_avg': self.arena.m[off:off + k].view(p.shape).clone(),
                                        'exp_avg_sq': self.arena.v[off:off + k].view(p.shape).clone()}
         groups, first = [], 0
@@ -1153,6 +1232,11 @@ class DetectorTrainer:
             wa = getattr(getattr(self.criterion, 'cls_loss', None), key, None)
             if wa is not None:
                 extra[key] = wa.detach().clone()
+        if self.skip_nonfinite:
+            # the guard's two counts (common/step_guard.py): the optimizer state's `step` is the applied one, their sum is
+            # the number of steps run, which positions the schedule
+            from ..common import step_guard as G
+            extra[G.CHECKPOINT_KEY] = G.checkpoint_entry(*self.guard_counts())
         torch.save(dict({'optimizer': self.optimizer_state_dict(), 'state': states}, **extra), state_file)
         for src, dst in ((model_file, os.path.join(checkpoint_path, 'checkpoint-latest.ckpt')),
                          (state_file, os.path.join(train_state_path, 'checkpoint_latest.ckpt'))):
@@ -1179,6 +1263,7 @@ class DetectorTrainer:
             st = torch.load(os.path.join(train_state_path, 'checkpoint_{}.ckpt'.format(resume)), map_location='cpu',
                             weights_only=False)
             self.load_optimizer_state_dict(st['optimizer'])
+            self._restore_guard(st)
             self._load_ema(os.path.join(checkpoint_path, 'checkpoint-ema-{}.ckpt'.format(resume)))
             for key in ('weight_accum', 'acc_sum'):
                 if key in st and hasattr(getattr(self.criterion, 'cls_loss', None), key):
@@ -1189,6 +1274,18 @@ class DetectorTrainer:
                 if torch.cuda.is_available() and len(states) > 3:
                     torch.cuda.set_rng_state(states[3])
         return start_epoch
+
+    def _restore_guard(self, train_state):
+        """Behind load_optimizer_state_dict (step_count = the saved `step`, i.e. the applied count of a guarded run).  With
+        the guard: step_count = applied + nonfinite, and the device record is rebuilt from the applied count by the rule's
+        recurrence (step_guard.bias_powers) when the next step begins.  A file without the key is an unguarded run's:
+        applied = step, nonfinite = 0.  Without the guard the host's bias corrections follow step_count, which must then
+        stay the applied count."""
+        from ..common import step_guard as G
+        applied, nonfinite = G.counts_from_checkpoint(train_state, self.step_count)
+        self._guard = None                  # (betas and counts may have changed: the record is made again)
+        self._guard_restore = (applied, nonfinite) if self.skip_nonfinite else None
+        self.step_count = applied + nonfinite if self.skip_nonfinite else applied
 
     def _load_ema(self, path):
         """arena.ema from a checkpoint-ema-<epoch>.ckpt; without the file the EMA starts from the (resumed) weights.
@@ -1291,16 +1388,18 @@ class StepLog:
     the progress bar, train.py:255-283): every `every` steps the step's [cost, 7 losses] vector is copied
     to a pinned host slot with ONE asynchronous D2H copy + an event; a slot is read (and handed to `sink`) only once its
     event has completed, i.e. a few steps later, while the GPU keeps running.  `width` 9: the vector carries the step's
-    gradient norm behind the eight (DetectorTrainer.last_grad_norm[0]; `names` gains 'grad_norm')."""
+    gradient norm behind the eight (DetectorTrainer.last_grad_norm[0]; `names` gains 'grad_norm'); `width` 10: behind it the
+    count of steps skipped for a non-finite gradient so far (a guarded trainer's device record; 'nonfinite')."""
     NAMES = ('total', 'loc', 'conf', 'prop_loc', 'prop_conf', 'IoU', 'start', 'end')
     EXTRA_NAME = 'grad_norm'
+    GUARD_NAME = 'nonfinite'
 
     def __init__(self, every=20, sink=None, slots=4, width=None):
         self.every, self.sink = int(every), sink
         n = self.width = len(self.NAMES) if width is None else int(width)
-        if n not in (len(self.NAMES), len(self.NAMES) + 1):
-            raise ValueError("StepLog width: 8 (cost + 7 losses) or 9 (+ the gradient norm)")
-        self.names = self.NAMES + ((self.EXTRA_NAME,) if n > len(self.NAMES) else ())
+        if n not in (len(self.NAMES), len(self.NAMES) + 1, len(self.NAMES) + 2):
+            raise ValueError("StepLog width: 8 (cost + 7 losses), 9 (+ the gradient norm) or 10 (+ the skipped-step count)")
+        self.names = self.NAMES + (self.EXTRA_NAME, self.GUARD_NAME)[:n - len(self.NAMES)]
         self._free = [(torch.empty(n, dtype=torch.float32).pin_memory() if torch.cuda.is_available() else torch.empty(n),
                        torch.cuda.Event() if torch.cuda.is_available() else None) for _ in range(slots)]
         self._inflight = []
@@ -1336,6 +1435,7 @@ class JsonlSink:
     A ninth value (StepLog(width=9)) is the gradient norm, under the reference's own tag 'stats/grad_norm' (train.py:250)."""
     TAGS = ('Total', 'loc', 'conf', 'prop_loc', 'prop_conf', 'IoU', 'start', 'end')
     EXTRA_TAG = 'stats/grad_norm'
+    GUARD_TAG = 'stats/nonfinite_steps'     # a tenth value (StepLog(width=10)): steps skipped so far, a whole number
 
     LR_TAG = 'stats/lr'
 
@@ -1353,6 +1453,8 @@ class JsonlSink:
         rec.update({'Train/' + t: float(v) for t, v in zip(self.TAGS, values)})
         if len(values) > len(self.TAGS):
             rec[self.EXTRA_TAG] = float(values[len(self.TAGS)])
+        if len(values) > len(self.TAGS) + 1:
+            rec[self.GUARD_TAG] = int(values[len(self.TAGS) + 1])
         if self.lr_of is not None:
             rec[self.LR_TAG] = float(self.lr_of(step))
         self._f.write(json.dumps(rec) + '\n')
@@ -1408,7 +1510,12 @@ def run_one_epoch(epoch, trainer, dataset, stager, batch_size, rank=0, world=1, 
             if step_log.width > vec.numel():
                 if trainer.last_grad_norm is None:
                     raise RuntimeError("the step log expects a gradient norm, but the trainer does not track it")
-                step_log.push(trainer.step_count, torch.cat([vec, trainer.last_grad_norm[:1]]))
+                tail = [trainer.last_grad_norm[:1]]
+                if step_log.width > vec.numel() + 1:        # the guard's count of skipped steps rides along, still on the device
+                    if getattr(trainer, '_guard', None) is None:
+                        raise RuntimeError("the step log expects the skipped-step count, but the trainer has no guard")
+                    tail.append(trainer._guard[1:2].to(torch.float32))
+                step_log.push(trainer.step_count, torch.cat([vec] + tail))
             else:
                 step_log.push(trainer.step_count, vec)
     if step_log is not None:
@@ -1542,14 +1649,45 @@ def report_ema_resume(trainer, resume, log=print):
         log(f"no checkpoint-ema-{resume}.ckpt: the weight EMA starts from the resumed weights")
 
 
-def make_step_log(every, directory, with_norm=False, lr_of=None):
+def make_step_log(every, directory, with_norm=False, lr_of=None, with_guard=False, max_nonfinite=None):
     """The drivers' per-step log: a console line AND <directory>/scalars.jsonl (the reference's TensorBoard scalars).
-    lr_of: step -> the rate of that step, a host value (a scheduled run): 'stats/lr' in the file, `lr x` on the line."""
-    log = StepLog(every, width=len(StepLog.NAMES) + int(bool(with_norm)))
-    log.sink = JsonlSink(directory, lr_of=lr_of, echo=lambda step, v: print(
-        'step {} '.format(step) + ', '.join('{} {:.5f}'.format(n, x) for n, x in zip(log.names, v))
-        + ('' if lr_of is None else ', lr {:.4g}'.format(lr_of(step)))))
+    lr_of: step -> the rate of that step, a host value (a scheduled run): 'stats/lr' in the file, `lr x` on the line.
+    with_guard (a trainer with skip_nonfinite; brings the norm along): 'stats/nonfinite_steps' in the file, `nonfinite k` on the
+    line once k > 0; max_nonfinite: the run ends (SystemExit) where a record with a larger count is flushed."""
+    from ..common import step_guard as G
+    n = len(StepLog.NAMES)
+    log = StepLog(every, width=n + (2 if with_guard else int(bool(with_norm))))
+
+    def echo(step, v):
+        shown = list(zip(log.names, v))[:n + 1]
+        print('step {} '.format(step) + ', '.join('{} {:.5f}'.format(k, x) for k, x in shown)
+              + (', nonfinite {}'.format(int(v[n + 1])) if len(v) > n + 1 and v[n + 1] > 0 else '')
+              + ('' if lr_of is None else ', lr {:.4g}'.format(lr_of(step))))
+        if len(v) > n + 1:
+            G.check_limit(v[n + 1], max_nonfinite)
+    log.sink = JsonlSink(directory, lr_of=lr_of, echo=echo)
     return log
+
+
+def guard_kwargs(extra):
+    """The trainer keyword of `--skip_nonfinite`; nothing without the flag, so a plain run builds its trainer as it did."""
+    return {'skip_nonfinite': True} if extra.get('skip_nonfinite') else {}
+
+
+def guard_log_kwargs(extra, world=1):
+    """make_step_log's keywords of the guard flags.  The limit is looked at where a record is flushed only in a one-process
+    run: the log lives on rank 0, and a rank that left alone would leave its peers waiting in a collective; with several
+    ranks the end of the epoch, where all of them hold the same counts, is the place."""
+    if not extra.get('skip_nonfinite'):
+        return {}
+    return {'with_guard': True, 'max_nonfinite': extra.get('max_nonfinite') if world == 1 else None}
+
+
+def check_nonfinite_limit(trainer, extra):
+    """The end of an epoch (the host has just waited for the epoch's means): read the guard's counts, apply --max_nonfinite."""
+    if extra.get('skip_nonfinite') and extra.get('max_nonfinite') is not None:
+        from ..common import step_guard as G
+        G.check_limit(trainer.guard_counts()[1], extra['max_nonfinite'])
 
 
 def lr_logger(trainer):
@@ -1582,6 +1720,14 @@ def main(argv=None):
                               x G behind each milestone epoch.  total_steps = max_epoch x steps per epoch (steps_per_epoch).
                               The multiplier lives in device memory: the captured step replays at every rate.  --warmup_steps
                               alone: constant behind the warm-up.  --log_every records gain 'stats/lr', the line `lr x`
+      --skip_nonfinite        leave out a step whose gradient norm is not finite (an inf or a NaN anywhere in the gradient), as
+                              torch's GradScaler leaves out optimizer.step(): decided on the device inside the replayed step
+                              (DetectorTrainer(skip_nonfinite=True), common/step_guard.py); weights, Adam moments, the EMA and
+                              the criterion's cross-step loss state stay as they were.  Implies --log_grad_norm; --log_every
+                              records gain 'stats/nonfinite_steps', the line `nonfinite k` once k > 0.  The two counts are
+                              saved with the train state and resumed
+      --max_nonfinite N       with --skip_nonfinite: end the run (message, non-zero exit) once more than N steps were skipped;
+                              looked at where a --log_every record is flushed (one process) and at the end of each epoch
       --ema_decay D           keep an exponential moving average of the weights inside the Adam launch (keep factor
                               min(D, (1 + t) / (10 + t))); saved as checkpoint-ema-<epoch>.ckpt beside checkpoint-<epoch>.ckpt
                               (score_checkpoints --ema scores them), resumed from it where it exists.  Flags, not state, like
@@ -1593,15 +1739,18 @@ def main(argv=None):
     import sys
     from ..common import config as C
     from ..common import thumos_dataset as D
+    from ..common import step_guard as G
     argv = list(sys.argv[1:] if argv is None else argv)
     extra = {'as_shipped_dispatch': False, 'random_init': False, 'save_after': 10, 'max_steps': None, 'log_every': 0,
-             'launch': 'lanes', 'clip_grad_norm': None, 'log_grad_norm': False, **LR_FLAGS}
+             'launch': 'lanes', 'clip_grad_norm': None, 'log_grad_norm': False, **LR_FLAGS, **G.GUARD_FLAGS}
     rest, i = [], 0
     while i < len(argv):
         a = argv[i]
         j = take_grad_norm_flag(argv, i, extra)
         if j is None:
             j = take_lr_flags(argv, i, extra)
+        if j is None:
+            j = G.take_guard_flag(argv, i, extra)
         if j is not None:
             i = j
         elif a in ('--as_shipped_dispatch', '--random_init'):
@@ -1615,6 +1764,7 @@ def main(argv=None):
         i += 1
     if extra['launch'] not in ('lanes', 'eager'):
         raise SystemExit("--launch takes lanes or eager")
+    G.check_guard_flags(extra)
     config = C.set_config(C.get_config(rest))
     tr = config['training']
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
@@ -1629,7 +1779,8 @@ def main(argv=None):
     ops.CONV_PRECISION = 1 if os.environ.get('OTAL_DTYPE', 'bf16') == 'bf16' else 0
     set_seed(tr['random_seed'])
     net, crit, trainer = build_training(config, dev, extra['as_shipped_dispatch'], extra['random_init'],
-                                        clip_grad_norm=extra['clip_grad_norm'], track_grad_norm=extra['log_grad_norm'])
+                                        clip_grad_norm=extra['clip_grad_norm'], track_grad_norm=extra['log_grad_norm'],
+                                        **guard_kwargs(extra))
     ds_cfg = config['dataset']['training']
     infos = D.get_video_info(ds_cfg['video_info_path'])
     annos = D.get_video_anno(infos, ds_cfg['video_anno_path'], config['dataset']['class_info_path'])
@@ -1657,7 +1808,7 @@ def main(argv=None):
     if extra['log_every'] > 0 and rank == 0:
         # per-step scalars: a console line AND <checkpoint_path>/training/scalars.jsonl (the reference's TensorBoard scalars)
         step_log = make_step_log(extra['log_every'], train_state_path, with_norm=extra['log_grad_norm'],
-                                 lr_of=lr_logger(trainer))
+                                 lr_of=lr_logger(trainer), **guard_log_kwargs(extra, world))
     trainer.step_log = step_log
     for epoch in range(start_epoch, tr['max_epoch'] + 1):
         if crit.cls_loss_type == 'edl':
@@ -1666,6 +1817,7 @@ def main(argv=None):
         v = run_one_epoch(epoch, trainer, dataset, stager, tr['batch_size'], rank, world, extra['max_steps'],
                           log=print if rank == 0 else (lambda *a: None), step_log=step_log)
         history.append(v)
+        check_nonfinite_limit(trainer, extra)       # (every rank holds the same counts: all of them end here together)
         if epoch > extra['save_after'] and rank == 0:
             trainer.save_model(epoch, checkpoint_path, train_state_path)
     if world > 1:
